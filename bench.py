@@ -2,7 +2,7 @@
 """Headline benchmark: utterances/s of the CNN2D eval forward (BASELINE.json configs[1]: synthetic [256,321,180],
 bf16 storage / fp32 accumulate) on N MI355X GPUs of one node, one process per GPU.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -11,13 +11,20 @@ Inference shards by utterance with no data-path collective (SURVEY.md section 8e
 shards ("scaling": "weak"); the only collectives are the timing barrier and the max-over-ranks of the elapsed time.
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches the torch.distributed.run command above
 itself, as a child process, before anything in this process touches the GPU, and exits with the child's code.
-Rank 0 prints ONE JSON line.  Extra objects on it:
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, pre-conditioning and warm-up,
+exactly --steps timed steps of the bf16 forward, the optional --dump-outputs, and the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step and the configuration).
+  --dump-outputs DIR  after the timed steps, the logits [B, 1] of the last timed step as DIR/logits.npy (float32; rank r > 0
+                      writes DIR/logits_rank<r>.npy).  Inputs and weights are seeded, so two builds compare output for output.
+  --full              everything else, as extra objects on the same line:
   roofline     -- the dominant kernel (block-3 MFMA conv): algorithmic FLOPs per launch / average launch duration
                   measured with HIP events on the launch stream during the timed steps, vs the dense MFMA peak
+  kernel_ms    -- per-kernel HIP-event times of 30 launches directly after the timed steps, plus the in-kernel clock probe
   cpu_baseline -- the CPU restatement of the reference path (oracle/torch_ref.py) timed on this host, rank 0, N=1
   parity_fast  -- the same workload in the split-bf16 parity mode (DFA_PREC_BF16X3: logits within 1e-4 of the reference)
   fp32_parity  -- the same workload in the exact-fp32 parity mode (logits within 1e-4 of the reference)
   train_step   -- BASELINE configs[2] on one GPU with its own roofline object (9,621,849,600 FLOP per utterance)
+  other_models -- CNN1D forward, auto-encoder score, auto-encoder and CNN1D training steps (rank 0, N=1)
   end_to_end   -- features.pkl on the host -> prediction.pkl (unpickle, H2D over PCIe, kernels, D2H, pickle) on the GPU
                   path and (cpu_baseline.end_to_end) on the CPU restatement of src/predict.py, same file; plus the
                   flat-file ingest rate (memmap -> pinned double-buffered H2D -> kernels)
@@ -93,13 +100,20 @@ def parse_args():
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--batch", type=int, default=B_PER_GPU, help="utterances per GPU per step")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write the logits of the last timed step as DIR/logits.npy")
+    p.add_argument("--full", action="store_true", help="also run everything beyond the headline: roofline and per-kernel "
+                   "times, the bf16x3 / fp32 legs, the training step, the other models, the CPU baseline, end to end")
+    # the options below select legs of --full and do nothing without it
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-train", action="store_true", help="skip the training-step leg")
     p.add_argument("--no-other-models", action="store_true", help="skip the CNN1D / auto-encoder legs")
     p.add_argument("--small-batch", action="store_true", help="add the batch 1 / batch 32 latency leg (time-axis split on / off)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the CPU baseline sample")
     p.add_argument("--e2e-utts", type=int, default=512, help="utterances in the end-to-end (features.pkl -> prediction.pkl) legs")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def build_model(torch, device, precision):
@@ -140,19 +154,21 @@ def precondition(torch, ctx, model, x, slot=2, batch=25, tol=0.01, max_batches=4
     return n, prev
 
 
-def timed_steps(torch, dist, model, x, steps, warmup, world, probe_clock=False):
+def timed_steps(torch, dist, model, x, steps, warmup, world, full=False, probe_clock=False):
     """Pre-conditioning (untimed, see precondition), W untimed warm-up steps, then EXACTLY `steps` timed steps between barrier +
-    synchronize on both sides.  Inside the timed region only the dominant kernel (timing slot 2) is bracketed by HIP events on
-    the launch stream; the per-kernel breakdown (every launch bracketed) runs directly AFTER the timed region -- the only host
+    synchronize on both sides.  full: inside the timed region only the dominant kernel (timing slot 2) is bracketed by HIP events
+    on the launch stream; the per-kernel breakdown (every launch bracketed) runs directly AFTER the timed region -- the only host
     work in between is reading back the <= 256 already-completed events of slot 2 -- so both are taken in the same clock state.
+    Without full, no event is recorded and (dt, None, out, None) is returned.
     probe_clock: the breakdown launches also stamp s_memtime / s_memrealtime inside the dominant kernel (dfa_ctx_clock_read)."""
     from dfa_amd import _lib
     ctx = _lib.Context.get(x.device)
     pre_n, _ = precondition(torch, ctx, model, x)
     for _ in range(warmup):
         model(x)
-    ctx.timing_reset()
-    ctx.timing(1 << 2)
+    if full:
+        ctx.timing_reset()
+        ctx.timing(1 << 2)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -163,30 +179,42 @@ def timed_steps(torch, dist, model, x, steps, warmup, world, probe_clock=False):
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    dominant = ctx.timing_read(2)
-    ctx.timing_reset()
-    ctx.timing(True)
-    if probe_clock:
-        ctx.set_option("clock_probe", 1)
-    for _ in range(30):
-        model(x)
-    ctx.timing(False)
-    torch.cuda.synchronize()
-    clock = None
-    if probe_clock:
-        med, lo, hi, n = ctx.clock_read()
-        ctx.set_option("clock_probe", 0)
-        if n:
-            clock = {"ghz": round(med, 3), "min": round(lo, 3), "max": round(hi, 3), "workgroups": n}
-    slots = [ctx.timing_read(s) for s in range(4)]
-    ctx.timing_reset()
-    probe_ms = slots[2][0] / max(slots[2][1], 1)
-    slots[2] = dominant
+    slots = extra = None
+    if full:
+        dominant = ctx.timing_read(2)
+        ctx.timing_reset()
+        ctx.timing(True)
+        if probe_clock:
+            ctx.set_option("clock_probe", 1)
+        for _ in range(30):
+            model(x)
+        ctx.timing(False)
+        torch.cuda.synchronize()
+        clock = None
+        if probe_clock:
+            med, lo, hi, n = ctx.clock_read()
+            ctx.set_option("clock_probe", 0)
+            if n:
+                clock = {"ghz": round(med, 3), "min": round(lo, 3), "max": round(hi, 3), "workgroups": n}
+        slots = [ctx.timing_read(s) for s in range(4)]
+        ctx.timing_reset()
+        probe_ms = slots[2][0] / max(slots[2][1], 1)
+        slots[2] = dominant
+        extra = {"precondition_launches": pre_n, "clock": clock, "probe_kernel_ms": round(probe_ms, 4)}
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=x.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt, slots, out, {"precondition_launches": pre_n, "clock": clock, "probe_kernel_ms": round(probe_ms, 4)}
+    return dt, slots, out, extra
+
+
+def dump_outputs(directory, rank, arrays):
+    """--dump-outputs: each array as <directory>/<name>.npy in float32 (rank r > 0 adds a _rank<r> suffix)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), t.detach().float().cpu().numpy())
 
 
 def host_cores():
@@ -609,22 +637,29 @@ def main():
     B = args.batch
     g = torch.Generator().manual_seed(1234 + rank)
     stored = (torch.randn(B, F, T, generator=g) * 3.2 - 0.07)        # stored layout [B,F,T] (src/dataset.py:52)
-    x32 = stored.to(device).transpose(1, 2)                           # the strided [B,T,F] view the harness feeds
-    x16 = stored.to(device=device, dtype=torch.bfloat16).transpose(1, 2)
+    x16 = stored.to(device=device, dtype=torch.bfloat16).transpose(1, 2)   # the strided [B,T,F] view the harness feeds
+    legs = [("bf16", x16)]
+    if args.full:
+        x32 = stored.to(device).transpose(1, 2)
+        legs += [("bf16x3", x32), ("fp32", x32)]
 
     results = {}
-    for prec, x in (("bf16", x16), ("bf16x3", x32), ("fp32", x32)):
+    for prec, x in legs:
         model = build_model(torch, device, prec)
-        dt, slots, out, extra = timed_steps(torch, dist, model, x, args.steps, args.warmup, world, probe_clock=(prec == "bf16"))
+        dt, slots, out, extra = timed_steps(torch, dist, model, x, args.steps, args.warmup, world, full=args.full,
+                                            probe_clock=(prec == "bf16"))
         if not torch.isfinite(out).all():
             raise SystemExit(f"non-finite logits in {prec} mode")
+        if prec == "bf16" and args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, {"logits": out})
+        results[prec] = {"value": world * B * args.steps / dt, "ms_per_step": dt / args.steps * 1e3}
+        if not args.full:
+            continue
         ms3, n3 = slots[2]
         k_ms = ms3 / max(n3, 1)
         ach = BLOCK3_FLOPS_PER_UTT * B / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
         traffic, traffic_src = pmc_kernel_traffic(PMC_TAGS[prec])
-        results[prec] = {
-            "value": world * B * args.steps / dt,
-            "ms_per_step": dt / args.steps * 1e3,
+        results[prec].update({
             "roofline": {"bound": "mfma", "kernel": BLOCK3_KERNEL[prec] + " (CNN2D block 3, 64->128, +BN+ReLU+mean_T)",
                          "achieved": round(ach, 2), "peak": round(PEAK_TFLOPS[prec], 1), "unit": "TFLOP/s",
                          "frac": round(ach / PEAK_TFLOPS[prec], 4),
@@ -634,7 +669,7 @@ def main():
             "kernel_ms": {name: round(ms / max(n, 1), 4) for name, (ms, n) in
                           zip(("conv1", "block2_mfma_or_fused_blocks12", "block3_mfma", "linear"), slots)},
             "logits_sample": [round(float(v), 6) for v in out[:3, 0].float().cpu()],
-        }
+        })
         if extra["clock"]:
             # the 2500 TFLOP/s peak is quoted at 2.4 GHz; under MFMA load the chip holds less (MI355X_MICROARCH.md, DVFS give-back):
             # clock_ghz is measured INSIDE the dominant kernel (s_memtime / s_memrealtime around its main loop, median over 1024
@@ -648,7 +683,7 @@ def main():
         del model
 
     if rank == 0:
-        r16, r32, rx3 = results["bf16"], results["fp32"], results["bf16x3"]
+        r16 = results["bf16"]
         line = {
             "metric": METRIC, "value": round(r16["value"], 1), "unit": "utterances/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(r16["ms_per_step"], 4),
@@ -658,39 +693,45 @@ def main():
                        "batch_per_gpu": B, "T": T, "F": F, "parallelism": f"utterance-sharded x{world}, no collective"},
             "flops_per_utt": FLOPS_PER_UTT,
             "achieved_tflops_whole_path": round(r16["value"] / world * FLOPS_PER_UTT / 1e12, 2),
-            "roofline": r16["roofline"],
-            "kernel_ms": r16["kernel_ms"],
-            "parity_fast": {"value": round(rx3["value"], 1), "unit": "utterances/s", "dtype": "bf16x3",
-                            "what": "DFA_PREC_BF16X3: hi + lo bf16 operands, three bf16 MFMAs per product, fp32 accumulate; "
-                                    "logits within 1e-4 of the reference and identical EER on the N=2000 set (GPU tests); "
-                                    "roofline peak = bf16 MFMA peak / 3 (algorithmic FLOPs)",
-                            "ms_per_step": round(rx3["ms_per_step"], 4), "roofline": rx3["roofline"],
-                            "kernel_ms": rx3["kernel_ms"],
-                            "max_abs_logit_diff_vs_fp32": round(max(abs(a - b) for a, b in
-                                                                    zip(rx3["logits_sample"], r32["logits_sample"])), 6)},
-            "fp32_parity": {"value": round(r32["value"], 1), "unit": "utterances/s", "dtype": "f32",
-                            "ms_per_step": round(r32["ms_per_step"], 4), "roofline": r32["roofline"],
-                            "kernel_ms": r32["kernel_ms"],
-                            "max_abs_logit_diff_vs_bf16": round(max(abs(a - b) for a, b in
-                                                                    zip(r16["logits_sample"], r32["logits_sample"])), 5)},
         }
-        if world == 1 and args.small_batch:   # opt-in: its B = 1 / 32 launches would mix into the per-kernel averages of a rocprofv3 run
-            line["small_batch"] = small_batch_metric(torch, device)
-    # BASELINE configs[2]: the data-parallel training step runs on EVERY rank (its all-reduce is a collective)
-    train = None if args.no_train else train_step_metric(torch, dist, device, B, world, rank)
+        if args.full:
+            r32, rx3 = results["fp32"], results["bf16x3"]
+            line.update({
+                "roofline": r16["roofline"],
+                "kernel_ms": r16["kernel_ms"],
+                "parity_fast": {"value": round(rx3["value"], 1), "unit": "utterances/s", "dtype": "bf16x3",
+                                "what": "DFA_PREC_BF16X3: hi + lo bf16 operands, three bf16 MFMAs per product, fp32 accumulate; "
+                                        "logits within 1e-4 of the reference and identical EER on the N=2000 set (GPU tests); "
+                                        "roofline peak = bf16 MFMA peak / 3 (algorithmic FLOPs)",
+                                "ms_per_step": round(rx3["ms_per_step"], 4), "roofline": rx3["roofline"],
+                                "kernel_ms": rx3["kernel_ms"],
+                                "max_abs_logit_diff_vs_fp32": round(max(abs(a - b) for a, b in
+                                                                        zip(rx3["logits_sample"], r32["logits_sample"])), 6)},
+                "fp32_parity": {"value": round(r32["value"], 1), "unit": "utterances/s", "dtype": "f32",
+                                "ms_per_step": round(r32["ms_per_step"], 4), "roofline": r32["roofline"],
+                                "kernel_ms": r32["kernel_ms"],
+                                "max_abs_logit_diff_vs_bf16": round(max(abs(a - b) for a, b in
+                                                                        zip(r16["logits_sample"], r32["logits_sample"])), 5)},
+            })
+            if world == 1 and args.small_batch:   # opt-in: its B = 1 / 32 launches would mix into the per-kernel averages of a rocprofv3 run
+                line["small_batch"] = small_batch_metric(torch, device)
+    if args.full:
+        # BASELINE configs[2]: the data-parallel training step runs on EVERY rank (its all-reduce is a collective)
+        train = None if args.no_train else train_step_metric(torch, dist, device, B, world, rank)
+        if rank == 0:
+            if train is not None:
+                line["train_step"] = train
+            if world == 1 and not args.no_other_models:
+                line["other_models"] = other_models_metric(torch, device, B)
+            if world == 1 and not args.no_cpu_baseline:
+                import tempfile
+                line["cpu_baseline"] = cpu_baseline(torch, sd_cpu, args.cpu_seconds)
+                with tempfile.TemporaryDirectory() as tmp:
+                    n_e2e = args.e2e_utts
+                    fpath = write_synthetic_pickle(torch, n_e2e, tmp)
+                    line["cpu_baseline"]["end_to_end"], cpu_pred = cpu_end_to_end(torch, sd_cpu, fpath, n_e2e)
+                    line["end_to_end"] = gpu_end_to_end(torch, device, sd_cpu, fpath, n_e2e, cpu_pred)
     if rank == 0:
-        if train is not None:
-            line["train_step"] = train
-        if world == 1 and not args.no_other_models:
-            line["other_models"] = other_models_metric(torch, device, B)
-        if world == 1 and not args.no_cpu_baseline:
-            import tempfile
-            line["cpu_baseline"] = cpu_baseline(torch, sd_cpu, args.cpu_seconds)
-            with tempfile.TemporaryDirectory() as tmp:
-                n_e2e = args.e2e_utts
-                fpath = write_synthetic_pickle(torch, n_e2e, tmp)
-                line["cpu_baseline"]["end_to_end"], cpu_pred = cpu_end_to_end(torch, sd_cpu, fpath, n_e2e)
-                line["end_to_end"] = gpu_end_to_end(torch, device, sd_cpu, fpath, n_e2e, cpu_pred)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

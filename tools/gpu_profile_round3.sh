@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r03_prof
 mkdir -p $OUT/summary
 echo "== kernel stats: bench"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python3 bench.py --steps 100 --warmup 30 --no-cpu-baseline > $OUT/bench.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python3 bench.py --full --steps 100 --warmup 30 --no-cpu-baseline > $OUT/bench.log 2>&1 || exit 1
 grep '^{' $OUT/bench.log > $OUT/summary/r03_bench_under_rocprof.json.log
 declare -A TARGET=( [train_step]=tools/gpu_prof_train.py [cnn1d_fwd]=tools/gpu_prof_cnn1d.py [cnn1d_train_step]=tools/gpu_prof_cnn1d_train.py \
                     [cae_score]=tools/gpu_prof_cae.py [cae_train_step]=tools/gpu_prof_cae_train.py [fwd]=tools/gpu_prof_fwd.py )
