@@ -199,20 +199,24 @@ class Context:
         check(self.handle, self.lib.dfa_ctx_timing_read(self.handle, slot, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
-    # ---- synchronised BatchNorm --------------------------------------------------------------------------------
-    BN_SYNC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
+    def clock_read(self):
+        """(median, min, max GHz, workgroups) of the last bf16 CNN2D block-3 launch run with set_option("clock_probe", 1)."""
+        med, lo, hi, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        check(self.handle, self.lib.dfa_ctx_clock_read(self.handle, C.byref(med), C.byref(lo), C.byref(hi), C.byref(n)))
+        return med.value, lo.value, hi.value, n.value
 
-    def set_bn_sync(self, process_group=None, enable=True):
-        """Synchronised BatchNorm for data-parallel CNN2D training (dfa_ctx_set_bn_sync): every BatchNorm layer's per-channel
-        sums are added over the ranks of `process_group` between their reduction and their use, so N ranks x B utterances
-        behave like one rank x N*B.  enable=False (or a world of 1) restores local statistics."""
+
+class BnSync:
+    """Synchronised BatchNorm for data-parallel training (dfa_ctx_set_bn_sync): while armed on the device's context, every
+    BatchNorm layer's per-channel sums are added over the ranks of `process_group` between their reduction and their use, so
+    N ranks x B utterances behave like one rank x N*B.  Built once per trainer (sync buffer and callback); the hook is global
+    to the context and must stay the same across a forward / backward pair, so its owner arms it around exactly that pair."""
+    FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
+
+    def __init__(self, device, process_group=None):
         import torch.distributed as dist
-        world = dist.get_world_size(process_group) if (enable and dist.is_available() and dist.is_initialized()) else 1
-        if not enable or world == 1:
-            check(self.handle, self.lib.dfa_ctx_set_bn_sync(self.handle, None, None, 1, None, 0))
-            self._bn_sync = None
-            return
-        buf = torch.zeros(1024, dtype=torch.float32, device=self.device)
+        self.ctx = Context.get(device)
+        buf = self.buf = torch.zeros(1024, dtype=torch.float32, device=self.ctx.device)
 
         def hook(_user, _buf, count):
             try:       # in place, ordered after the work already on the current (= the context's) stream
@@ -220,16 +224,15 @@ class Context:
                 return 0
             except Exception:   # noqa: BLE001 -- reported through the C ABI's error path
                 return -1
-        cb = self.BN_SYNC_FN(hook)
-        self._bn_sync = (buf, cb, hook)                 # keep the tensor and the callback object alive
-        check(self.handle, self.lib.dfa_ctx_set_bn_sync(self.handle, C.cast(cb, C.c_void_p), None, world,
-                                                        C.c_void_p(buf.data_ptr()), buf.numel()))
+        self._fn = self.FN(hook)                        # keeps the callback alive as long as the hook object
+        self._armed = (C.cast(self._fn, C.c_void_p), None, dist.get_world_size(process_group), C.c_void_p(buf.data_ptr()),
+                       buf.numel())
 
-    def clock_read(self):
-        """(median, min, max GHz, workgroups) of the last bf16 CNN2D block-3 launch run with set_option("clock_probe", 1)."""
-        med, lo, hi, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
-        check(self.handle, self.lib.dfa_ctx_clock_read(self.handle, C.byref(med), C.byref(lo), C.byref(hi), C.byref(n)))
-        return med.value, lo.value, hi.value, n.value
+    def arm(self):
+        check(self.ctx.handle, self.ctx.lib.dfa_ctx_set_bn_sync(self.ctx.handle, *self._armed))
+
+    def disarm(self):
+        check(self.ctx.handle, self.ctx.lib.dfa_ctx_set_bn_sync(self.ctx.handle, None, None, 1, None, 0))
 
 
 def x_dtype_code(t: torch.Tensor) -> int:

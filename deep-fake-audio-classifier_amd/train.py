@@ -207,7 +207,7 @@ def main(argv=None):
     flat_mode = args.native or world > 1          # one flat parameter / gradient buffer, one all-reduce per step
     trainer = None
     if flat_mode:
-        from .training.train_step import FlatTrainer, NativeTrainer
+        from .training.train_step import NativeTrainer
         # all-C-ABI step for both classifiers: 464,644-byte (CNN2D) / 195,204-byte (CNN1D) flat gradient, one all-reduce
         trainer = NativeTrainer(model, lr=args.lr, weight_decay=weight_decay, label_smoothing=args.label_smoothing,
                                 sync_bn=bool(getattr(args, "sync_bn", False)) and world > 1)
@@ -250,11 +250,7 @@ def main(argv=None):
                 else:
                     resident = False
             batcher = resident.epoch(idx) if resident else IndexedFlatBatcher(feats, labels, idx, args.batch_size, device=device)
-            if isinstance(trainer, FlatTrainer):
-                train_loss = train_one_epoch(model, batcher, criterion, trainer, device=device, augment_fn=augment_fn,
-                                             swap_tf=args.swap_tf)
-            else:
-                train_loss = train_one_epoch_native(trainer, batcher, augment_fn, args.swap_tf)
+            train_loss = train_one_epoch_native(trainer, batcher, augment_fn, args.swap_tf)
             train_loss = dfa_dist.mean_scalar(train_loss, device)
             # BatchNorm running statistics come from rank-local batches: average them so that every rank evaluates (and
             # rank 0 checkpoints) the same model

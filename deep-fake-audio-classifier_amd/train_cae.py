@@ -20,13 +20,14 @@ from .dataloaders import train_shard_indices
 from .dataset_cae import BonafideDataset, FeatureNormalizer, build_normalizer, fit_normalizer_sharded
 from .model_cae import ConvAutoencoder
 from .training import save_checkpoint
+from .training.train_step import CaeNativeTrainer, FlatTrainer
 
 
 def train_one_epoch(model, dataloader, criterion, optimizer, device="cuda"):
     """Mean reconstruction loss over the epoch (src/train_cae.py:58-82); the loss stays on the device until the end."""
     model.train()
     total, count = None, 0
-    native = hasattr(optimizer, "flat_g") and hasattr(optimizer, "step") and type(optimizer).__name__ == "CaeNativeTrainer"
+    native = isinstance(optimizer, CaeNativeTrainer)
     for x in dataloader:
         x = x.to(device, non_blocking=True)
         if native:                       # the whole step on the C ABI (criterion is MSELoss(recon, x) by construction)
@@ -199,7 +200,6 @@ def main(argv=None):
     if world > 1 or args.trainer == "native":
         # src/train_cae.py:58-82 on every rank's shard: one flat 2,246,532-byte gradient all-reduce per step (world > 1), fused
         # AdamW, equal step counts on every rank
-        from .training.train_step import CaeNativeTrainer, FlatTrainer
         Trainer = CaeNativeTrainer if args.trainer == "native" else FlatTrainer
         kw = {"sync_bn": True} if (args.sync_bn and world > 1 and args.trainer == "native") else {}
         optimizer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, **kw)

@@ -1,22 +1,32 @@
-"""Train-mode path of the HIP models.
+"""Train-mode path of the HIP models (CNN2D, CNN1D, ConvAutoencoder), one bridge for all three.
 
 Two ways to use it:
   * drop-in (reference semantics, src/train.py:71-76): `logits = model(x); loss = criterion(logits, y);
-    optimizer.zero_grad(); loss.backward(); optimizer.step()` -- `model(x)` in train mode goes through
-    `Cnn2dTrainFunction`, a torch.autograd.Function whose forward/backward are the C-ABI calls
-    dfa_cnn2d_forward_train / dfa_cnn2d_backward; any torch criterion and optimizer work unchanged.
-  * native (`NativeTrainer`): forward, BCE-with-smoothing, backward, ONE all-reduce of the flat gradient buffer
+    optimizer.zero_grad(); loss.backward(); optimizer.step()` -- `model(x)` in train mode goes through `TrainFunction`, a
+    torch.autograd.Function whose forward/backward are the C-ABI calls dfa_<kind>_forward_train / dfa_<kind>_backward; any
+    torch criterion and optimizer work unchanged.
+  * native (`NativeTrainer`, `CaeNativeTrainer`): forward, loss, backward, ONE all-reduce of the flat gradient buffer
     (RCCL over xGMI when torch.distributed is initialised with backend "nccl") and the fused AdamW kernel,
     with no autograd graph and no per-parameter optimizer loop.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
 from .. import _lib
-from .._params import tensors_signature
+
+KINDS = {"CNN2D": "cnn2d", "CNN1D": "cnn1d", "ConvAutoencoder": "cae"}      # model class -> C-ABI prefix / context slot
+
+# what a raw backward needs from its forward: the context, the workspace that holds the saved activations, the forward's
+# generation on the context's slot and its batch key (B, T, F, precision, x dtype)
+TrainState = namedtuple("TrainState", "ctx ws gen key")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _train_ws(model, ctx, nbytes):
@@ -28,33 +38,24 @@ def _train_ws(model, ctx, nbytes):
     return ws
 
 
-def _bind_cnn2d(model, ctx):
-    """dfa_cnn2d_set_params with the CURRENT tensors (the kernels read weights and update running stats in place)."""
+def _bind(model, ctx, kind):
+    """dfa_<kind>_set_params with the CURRENT tensors (the kernels read weights and update running stats in place)."""
     ts = model._abi_tensors()
     for t in ts:
         if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("CNN2D parameters must be contiguous float32 tensors on the GPU (model.to('cuda'))")
+            raise RuntimeError(f"{type(model).__name__} parameters must be contiguous float32 tensors on the GPU (model.to('cuda'))")
     sig = (ctx.index, tuple(t.data_ptr() for t in ts))
-    stale = ctx.owner_changed("cnn2d", model)
-    if getattr(model, "_bound", None) != sig or stale:
-        arr = _lib.ptr_array([t.detach() for t in ts])
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn2d_set_params(ctx.handle, arr, len(ts), model.in_features,
-                                                            model.base_channels))
+    if ctx.owner_changed(kind, model) or getattr(model, "_bound", None) != sig:
+        dims = (model.base_channels,) if kind == "cae" else (model.in_features, model.base_channels)
+        _lib.check(ctx.handle, getattr(ctx.lib, f"dfa_{kind}_set_params")(ctx.handle, _lib.ptr_array([t.detach() for t in ts]),
+                                                                            len(ts), *dims))
         model._bound = sig
     model._prepared = None   # eval-mode folded images are stale after any training step
 
 
-def _grad_sink(model):
-    """FlatTrainer's gradient views when every parameter's .grad still IS its view of the flat buffer: the C-ABI backward then
-    writes the gradients straight into the all-reduce payload (it writes, never accumulates) and autograd gets no tensors to
-    add -- no per-parameter allocation, no add kernels, no memset.  None = plain autograd semantics (fresh tensors returned)."""
-    sink = model.__dict__.get("_flat_grad_sink")
-    if sink is None:
-        return None
-    for p, g in zip(model.parameters(), sink):
-        if p.grad is None or p.grad.data_ptr() != g.data_ptr():
-            return None
-    return sink
+def _batch_key(model, kind, x):
+    B, T, F = x.shape
+    return B, T, F, (None if kind == "cnn1d" else _lib.PRECISIONS[model.precision]), x.dtype
 
 
 def _next_dropout_offset(model, n_elems):
@@ -63,228 +64,135 @@ def _next_dropout_offset(model, n_elems):
     return off
 
 
-def cnn2d_forward_train_raw(model, x, update_running_stats=True):
-    """Run dfa_cnn2d_forward_train; returns (logits[B,1], ctx, workspace).  Stamps model._train_gen."""
+def forward_train_raw(model, x, want=("recon", "latent")):
+    """One train-mode forward (dfa_<kind>_forward_train: batch statistics, running statistics updated, dropout in the
+    classifiers); returns (outputs, TrainState).  outputs: (logits[B,1],) for the classifiers; for the auto-encoder the
+    tensors named in `want` out of recon[B,T,F], latent[B,8C,T/16,F/16] and the per-sample mse[B], in that order."""
+    kind = KINDS[type(model).__name__]
     if x.device.type != "cuda":
-        raise RuntimeError("dfa_amd.CNN2D runs on the GPU only: move the input with .to('cuda')")
-    B, T, F = x.shape
+        raise RuntimeError(f"dfa_amd.{type(model).__name__} runs on the GPU only: move the input with .to('cuda')")
+    if kind == "cnn1d" and x.dtype != torch.float32:
+        raise ValueError(f"CNN1D takes float32 input, got {x.dtype}")
+    key = _batch_key(model, kind, x)
+    B, T, F, prec, _ = key
     ctx = _lib.Context.get(x.device)
+    lib, h = ctx.lib, ctx.handle
     with torch.cuda.device(ctx.index):
         ctx.use_current_stream()
-        _bind_cnn2d(model, ctx)
-        prec = _lib.PRECISIONS[model.precision]
-        nbytes = ctx.lib.dfa_cnn2d_train_workspace_bytes(ctx.handle, B, T, F, prec)
+        _bind(model, ctx, kind)
+        nbytes = getattr(lib, f"dfa_{kind}_train_workspace_bytes")(h, B, T, F, *(() if prec is None else (prec,)))
         if nbytes == 0:
-            raise ValueError(f"bad training shape (B={B}, T={T}, F={F})")
+            raise ValueError(f"bad {type(model).__name__} training shape (B={B}, T={T}, F={F})"
+                             + (": need T >= 16 and F = 16k+4" if kind == "cae" else ""))
         ws = _train_ws(model, ctx, nbytes)
-        logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
-        seed = getattr(model, "_drop_seed", None)
-        if seed is None:
-            seed = model._drop_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        offset = _next_dropout_offset(model, B * (T // 2) * F * 32)
-        sb, st, sf = x.stride()
-        code = ctx.lib.dfa_cnn2d_forward_train(
-            ctx.handle, C.c_void_p(x.data_ptr()), _lib.x_dtype_code(x), B, T, F, sb, st, sf, prec,
-            float(model.dropout), seed, offset, 0.1, int(update_running_stats), C.c_void_p(logits.data_ptr()), None,
-            C.c_void_p(ws.data_ptr()), ws.numel())
-        _lib.check(ctx.handle, code)
-        model._train_gen = ctx.next_train_gen("cnn2d")
-        model._train_shape = (B, T, F, prec, x.dtype)
-        if update_running_stats:      # one multi-tensor launch instead of three
-            torch._foreach_add_([model.conv[i].num_batches_tracked for i in model._BN_IDX], 1)
-    return logits, ctx, ws
+        if kind == "cae":
+            shapes = {"recon": (B, T, F), "latent": (B, 8 * model.base_channels, T // 16, F // 16), "mse": (B,)}
+            made = {n: torch.empty(shapes[n], dtype=torch.float32, device=x.device) for n in want}
+            outs = tuple(made.values())
+            args = (prec, 0.1, 1, *(_ptr(made.get(n)) for n in shapes))
+            bns = [model.encoder[bi] for _, bi in model._ENC] + [model.decoder[bi] for _, bi in model._DEC if bi is not None]
+        else:
+            outs = (torch.empty((B, 1), dtype=torch.float32, device=x.device),)
+            seed = getattr(model, "_drop_seed", None)
+            if seed is None:
+                seed = model._drop_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+            offset = _next_dropout_offset(model, B * (T // 2) * F * 32 if kind == "cnn2d" else B * 64 * T)
+            args = (float(model.dropout), seed, offset, 0.1, 1, _ptr(outs[0]))
+            args = (prec, *args, None) if kind == "cnn2d" else args
+            bns = [model.conv[i] for i in model._BN_IDX]
+        _lib.check(h, getattr(lib, f"dfa_{kind}_forward_train")(h, _ptr(x), _lib.x_dtype_code(x), B, T, F, *x.stride(), *args,
+                                                                 _ptr(ws), ws.numel()))
+        torch._foreach_add_([bn.num_batches_tracked for bn in bns], 1)      # one multi-tensor launch
+    st = TrainState(ctx, ws, ctx.next_train_gen(kind), key)
+    model.__dict__["_train_last"] = (st.gen, key)        # for the per-model entry points below (no Module.__setattr__)
+    return outs, st
+
+
+def backward_raw(model, x, dout, grads, st):
+    """dfa_<kind>_backward of the forward that returned `st`, on that forward's batch x: WRITES (never adds) every parameter
+    gradient into `grads` (one tensor per parameter, e.g. views of one flat buffer).  dout: dlogits[B,1] for the classifiers;
+    for the auto-encoder drecon[B,T,F], or None when the loss is MSELoss(recon, x) (src/train_cae.py:67-68): its gradient is
+    then formed inside the decoder's last backward kernel."""
+    kind = KINDS[type(model).__name__]
+    ctx = st.ctx
+    ctx.check_train_gen(kind, st.gen, model)
+    if _batch_key(model, kind, x) != st.key:
+        raise RuntimeError("backward called with a batch shape / precision / dtype other than its forward's")
+    B, T, F = x.shape
+    with torch.cuda.device(ctx.index):
+        ctx.use_current_stream()
+        _lib.check(ctx.handle, getattr(ctx.lib, f"dfa_{kind}_backward")(
+            ctx.handle, _ptr(x), _lib.x_dtype_code(x), B, T, F, *x.stride(), _ptr(dout), _lib.ptr_array(grads), len(grads),
+            _ptr(st.ws), st.ws.numel()))
+
+
+# The per-model raw entry points other code calls (same arguments and returns as before the bridge was shared): thin
+# forms of the pair above; the batch key (and CNN2D's default generation) come from the model's latest forward.
+def cnn2d_forward_train_raw(model, x):
+    """(logits[B,1], ctx, workspace)"""
+    (logits,), st = forward_train_raw(model, x)
+    return logits, st.ctx, st.ws
 
 
 def cnn2d_backward_raw(model, x, dlogits, grad_tensors, ctx, ws, gen=None):
-    B, T, F = x.shape
-    ctx.check_train_gen("cnn2d", model._train_gen if gen is None else gen, model)
-    if (B, T, F, _lib.PRECISIONS[model.precision], x.dtype) != getattr(model, "_train_shape", None):
-        raise RuntimeError("backward called with a batch shape / precision / dtype other than its forward's")
-    with torch.cuda.device(ctx.index):
-        ctx.use_current_stream()
-        arr = _lib.ptr_array(grad_tensors)
-        sb, st, sf = x.stride()
-        code = ctx.lib.dfa_cnn2d_backward(ctx.handle, C.c_void_p(x.data_ptr()), _lib.x_dtype_code(x), B, T, F, sb, st,
-                                          sf, C.c_void_p(dlogits.data_ptr()), arr, len(grad_tensors),
-                                          C.c_void_p(ws.data_ptr()), ws.numel())
-        _lib.check(ctx.handle, code)
+    last_gen, key = model._train_last
+    backward_raw(model, x, dlogits, grad_tensors, TrainState(ctx, ws, last_gen if gen is None else gen, key))
 
 
-class Cnn2dTrainFunction(torch.autograd.Function):
+def cae_forward_train_raw(model, x, want_recon=True, want_latent=True, want_mse=False):
+    """(recon | None, latent | None, mse[B] | None, ctx, workspace, generation)"""
+    names = [n for n, w in (("recon", want_recon), ("latent", want_latent), ("mse", want_mse)) if w]
+    outs, st = forward_train_raw(model, x, want=names)
+    got = dict(zip(names, outs))
+    return got.get("recon"), got.get("latent"), got.get("mse"), st.ctx, st.ws, st.gen
+
+
+def cae_backward_raw(model, x, drecon, grad_tensors, ctx, ws, gen):
+    backward_raw(model, x, drecon, grad_tensors, TrainState(ctx, ws, gen, model._train_last[1]))
+
+
+def _grad_dest(model):
+    """(where the C backward writes each gradient, what autograd receives for it).  A parameter whose .grad is still its view
+    of a FlatTrainer's flat buffer is written in place and autograd gets None: nothing is allocated, added or memset.  Any
+    other parameter gets a fresh tensor that autograd accumulates as usual, so every .grad ends as plain autograd's."""
+    params = list(model.parameters())
+    views = model.__dict__.get("_flat_grad_sink") or [None] * len(params)
+    fresh = [torch.empty_like(p) if v is None or p.grad is None or p.grad.data_ptr() != v.data_ptr() else None
+             for p, v in zip(params, views)]
+    return [v if g is None else g for g, v in zip(fresh, views)], fresh
+
+
+class TrainFunction(torch.autograd.Function):
+    """model(x) in train mode.  The auto-encoder returns (reconstruction, latent): the gradient flows through the
+    reconstruction (src/train_cae.py:67-71 uses MSELoss(recon, x)), the latent map is returned for inspection only."""
+
     @staticmethod
     def forward(fctx, x, model, *params):
-        logits, ctx, ws = cnn2d_forward_train_raw(model, x)
-        fctx.model, fctx.x, fctx.ctx, fctx.ws, fctx.gen = model, x, ctx, ws, model._train_gen
-        return logits
+        outs, st = forward_train_raw(model, x)
+        fctx.model, fctx.x, fctx.st = model, x, st
+        if len(outs) == 1:
+            return outs[0]
+        fctx.mark_non_differentiable(*outs[1:])
+        return outs
 
     @staticmethod
-    def backward(fctx, dlogits):
-        model = fctx.model
-        grads = [torch.empty_like(p) for p in model.parameters()]
-        cnn2d_backward_raw(model, fctx.x, dlogits.contiguous().float(), grads, fctx.ctx, fctx.ws, fctx.gen)
-        return (None, None, *grads)
+    def backward(fctx, dout, *_):
+        dest, fresh = _grad_dest(fctx.model)
+        backward_raw(fctx.model, fctx.x, dout.contiguous().float(), dest, fctx.st)
+        return (None, None, *fresh)
+
+
+def train_forward(model, x):
+    return TrainFunction.apply(x, model, *model.parameters())
 
 
 def cnn2d_train_forward(model, x, return_embedding=False):
     if return_embedding:
         raise NotImplementedError("return_embedding=True is an eval-mode feature (src/embedding_anomaly.py:61)")
-    return Cnn2dTrainFunction.apply(x, model, *model.parameters())
+    return train_forward(model, x)
 
 
-def _bind_cnn1d(model, ctx):
-    ts = model._abi_tensors()
-    for t in ts:
-        if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("CNN1D parameters must be contiguous float32 tensors on the GPU (model.to('cuda'))")
-    sig = (ctx.index, tuple(t.data_ptr() for t in ts))
-    stale = ctx.owner_changed("cnn1d", model)
-    if getattr(model, "_bound", None) != sig or stale:
-        arr = _lib.ptr_array([t.detach() for t in ts])
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn1d_set_params(ctx.handle, arr, len(ts), model.in_features,
-                                                            model.base_channels))
-        model._bound = sig
-    model._prepared = None
-
-
-def cnn1d_forward_train_raw(model, x):
-    """Run dfa_cnn1d_forward_train; returns (logits[B,1], ctx, workspace, generation)."""
-    if x.device.type != "cuda":
-        raise RuntimeError("dfa_amd.CNN1D runs on the GPU only: move the input with .to('cuda')")
-    if x.dtype != torch.float32:
-        raise ValueError(f"CNN1D takes float32 input, got {x.dtype}")
-    B, T, F = x.shape
-    ctx = _lib.Context.get(x.device)
-    with torch.cuda.device(ctx.index):
-        ctx.use_current_stream()
-        _bind_cnn1d(model, ctx)
-        nbytes = ctx.lib.dfa_cnn1d_train_workspace_bytes(ctx.handle, B, T, F)
-        ws = _train_ws(model, ctx, nbytes)
-        logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
-        seed = getattr(model, "_drop_seed", None)
-        if seed is None:
-            seed = model._drop_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        offset = _next_dropout_offset(model, B * 64 * T)
-        sb, st, sf = x.stride()
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn1d_forward_train(
-            ctx.handle, C.c_void_p(x.data_ptr()), _lib.DTYPE_F32, B, T, F, sb, st, sf, float(model.dropout), seed,
-            offset, 0.1, 1, C.c_void_p(logits.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel()))
-        torch._foreach_add_([model.conv[i].num_batches_tracked for i in model._BN_IDX], 1)
-    return logits, ctx, ws, ctx.next_train_gen("cnn1d")
-
-
-def cnn1d_backward_raw(model, x, dlogits, grad_tensors, ctx, ws, gen):
-    """dfa_cnn1d_backward with the 14 gradients WRITTEN into grad_tensors (e.g. views of one flat buffer)."""
-    ctx.check_train_gen("cnn1d", gen, model)
-    B, T, F = x.shape
-    with torch.cuda.device(ctx.index):
-        ctx.use_current_stream()
-        sb, st, sf = x.stride()
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn1d_backward(
-            ctx.handle, C.c_void_p(x.data_ptr()), _lib.DTYPE_F32, B, T, F, sb, st, sf, C.c_void_p(dlogits.data_ptr()),
-            _lib.ptr_array(grad_tensors), len(grad_tensors), C.c_void_p(ws.data_ptr()), ws.numel()))
-
-
-class Cnn1dTrainFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(fctx, x, model, *params):
-        logits, ctx, ws, gen = cnn1d_forward_train_raw(model, x)
-        fctx.model, fctx.x, fctx.ctx, fctx.ws, fctx.gen = model, x, ctx, ws, gen
-        return logits
-
-    @staticmethod
-    def backward(fctx, dlogits):
-        model = fctx.model
-        sink = _grad_sink(model)
-        grads = sink if sink is not None else [torch.empty_like(p) for p in model.parameters()]
-        cnn1d_backward_raw(model, fctx.x, dlogits.contiguous().float(), grads, fctx.ctx, fctx.ws, fctx.gen)
-        return (None, None, *([None] * len(grads) if sink is not None else grads))
-
-
-def cnn1d_train_forward(model, x):
-    return Cnn1dTrainFunction.apply(x, model, *model.parameters())
-
-
-def _bind_cae(model, ctx):
-    ts = model._abi_tensors()
-    for t in ts:
-        if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("ConvAutoencoder parameters must be contiguous float32 tensors on the GPU")
-    sig = (ctx.index, tuple(t.data_ptr() for t in ts))
-    stale = ctx.owner_changed("cae", model)
-    if getattr(model, "_bound", None) != sig or stale:
-        arr = _lib.ptr_array([t.detach() for t in ts])
-        _lib.check(ctx.handle, ctx.lib.dfa_cae_set_params(ctx.handle, arr, len(ts), model.base_channels))
-        model._bound = sig
-    model._prepared = None
-
-
-def cae_forward_train_raw(model, x, want_recon=True, want_latent=True, want_mse=False):
-    """Run dfa_cae_forward_train; returns (recon | None, latent | None, mse[B] | None, ctx, workspace, generation)."""
-    if x.device.type != "cuda":
-        raise RuntimeError("dfa_amd.ConvAutoencoder runs on the GPU only: move the input with .to('cuda')")
-    B, T, F = x.shape
-    ctx = _lib.Context.get(x.device)
-    with torch.cuda.device(ctx.index):
-        ctx.use_current_stream()
-        _bind_cae(model, ctx)
-        prec = _lib.PRECISIONS[model.precision]
-        nbytes = ctx.lib.dfa_cae_train_workspace_bytes(ctx.handle, B, T, F, prec)
-        if nbytes == 0:
-            raise ValueError(f"bad auto-encoder training shape (B={B}, T={T}, F={F}): need T >= 16 and F = 16k+4")
-        ws = _train_ws(model, ctx, nbytes)
-        recon = torch.empty((B, T, F), dtype=torch.float32, device=x.device) if want_recon else None
-        latent = torch.empty((B, 8 * model.base_channels, T // 16, F // 16), dtype=torch.float32, device=x.device) \
-            if want_latent else None
-        mse = torch.empty(B, dtype=torch.float32, device=x.device) if want_mse else None
-        sb, st, sf = x.stride()
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(ctx.handle, ctx.lib.dfa_cae_forward_train(
-            ctx.handle, C.c_void_p(x.data_ptr()), _lib.x_dtype_code(x), B, T, F, sb, st, sf, prec, 0.1, 1,
-            ptr(recon), ptr(latent), ptr(mse), C.c_void_p(ws.data_ptr()), ws.numel()))
-        bns = [model.encoder[bi].num_batches_tracked for _, bi in model._ENC]
-        bns += [model.decoder[bi].num_batches_tracked for _, bi in model._DEC if bi is not None]
-        torch._foreach_add_(bns, 1)
-    return recon, latent, mse, ctx, ws, ctx.next_train_gen("cae")
-
-
-def cae_backward_raw(model, x, drecon, grad_tensors, ctx, ws, gen):
-    """dfa_cae_backward with the 30 gradients WRITTEN into grad_tensors.  drecon = None: the loss is MSELoss(recon, x)
-    (src/train_cae.py:67-68) and its gradient is formed inside the decoder's last backward kernel."""
-    ctx.check_train_gen("cae", gen, model)
-    B, T, F = x.shape
-    with torch.cuda.device(ctx.index):
-        ctx.use_current_stream()
-        sb, st, sf = x.stride()
-        _lib.check(ctx.handle, ctx.lib.dfa_cae_backward(
-            ctx.handle, C.c_void_p(x.data_ptr()), _lib.x_dtype_code(x), B, T, F, sb, st, sf,
-            C.c_void_p(drecon.data_ptr()) if drecon is not None else None, _lib.ptr_array(grad_tensors), len(grad_tensors),
-            C.c_void_p(ws.data_ptr()), ws.numel()))
-
-
-class CaeTrainFunction(torch.autograd.Function):
-    """(reconstruction, latent) = ConvAutoencoder(x) in train mode; the gradient flows through the reconstruction
-    (src/train_cae.py:67-71 uses MSELoss(recon, x)); the latent map is returned for inspection only."""
-
-    @staticmethod
-    def forward(fctx, x, model, *params):
-        recon, latent, _, ctx, ws, gen = cae_forward_train_raw(model, x)
-        fctx.model, fctx.x, fctx.ctx, fctx.ws, fctx.gen = model, x, ctx, ws, gen
-        fctx.mark_non_differentiable(latent)
-        return recon, latent
-
-    @staticmethod
-    def backward(fctx, drecon, _dlatent):
-        model = fctx.model
-        sink = _grad_sink(model)
-        grads = sink if sink is not None else [torch.empty_like(p) for p in model.parameters()]
-        cae_backward_raw(model, fctx.x, drecon.contiguous().float(), grads, fctx.ctx, fctx.ws, fctx.gen)
-        return (None, None, *([None] * len(grads) if sink is not None else grads))
-
-
-def cae_train_forward(model, x):
-    return CaeTrainFunction.apply(x, model, *model.parameters())
+cnn1d_train_forward = cae_train_forward = train_forward
 
 
 class _FlatAdamW:
@@ -381,18 +289,20 @@ class _FlatAdamW:
 
 
 class FlatTrainer(_FlatAdamW):
-    """Optimizer-shaped data-parallel engine for ANY dfa_amd model used through the autograd bridge (CNN1D with BCE,
-    the auto-encoder with MSELoss, src/train_cae.py:58-82): `zero_grad(); loss.backward(); step()`.  Every parameter's
-    .grad is a view of the flat gradient buffer, so autograd accumulates straight into the all-reduce payload."""
+    """Optimizer-shaped data-parallel engine for any dfa_amd model used through the autograd bridge (CNN2D / CNN1D with any
+    criterion, the auto-encoder with MSELoss, src/train_cae.py:58-82): `zero_grad(); loss.backward(); step()`.  Every
+    parameter's .grad is a view of the flat gradient buffer, and the bridge's backward writes those gradients straight into
+    the all-reduce payload (_grad_dest)."""
 
     def __init__(self, model, **kw):
         super().__init__(model, **kw)
         for p, g in zip(model.parameters(), self.grad_views):
             p.grad = g
-        model.__dict__["_flat_grad_sink"] = self.grad_views     # CNN1D / auto-encoder bridges write into the views directly
+        model.__dict__["_flat_grad_sink"] = self.grad_views
 
     def zero_grad(self, set_to_none: bool = False):
-        """Re-attach the views; no memset: the dfa_*_backward calls WRITE every gradient (one backward per step on this path)."""
+        """Re-attach the views; no memset: the dfa_*_backward calls WRITE every gradient whose .grad is its view, and a
+        detached one gets a fresh tensor (one backward per step on this path)."""
         for p, g in zip(self.model.parameters(), self.grad_views):
             if p.grad is None or p.grad.data_ptr() != g.data_ptr():
                 p.grad = g
@@ -404,7 +314,10 @@ class FlatTrainer(_FlatAdamW):
 class NativeTrainer(_FlatAdamW):
     """Whole classifier training step on the C ABI: forward_train -> BCE(smoothed) -> backward (gradients written straight
     into the views of the flat buffer) -> all-reduce -> fused AdamW, with no autograd graph (src/train.py:71-76).
-    CNN2D and CNN1D (chosen by the model's class)."""
+    CNN2D and CNN1D (chosen by the model's class).
+    sync_bn (world > 1): BatchNorm statistics over the GLOBAL batch (two 2C-float all-reduces per layer and step through the
+    C ABI's hook, armed for this trainer's forward / backward only): N ranks x B then train like one rank x N*B; the default
+    is DistributedDataParallel's local statistics."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, label_smoothing=0.0,
                  process_group=None, sync_bn=False):
@@ -412,34 +325,31 @@ class NativeTrainer(_FlatAdamW):
             raise ValueError("--label-smoothing must be in [0, 0.5)")          # src/train.py:308-309
         super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, process_group=process_group)
         self.label_smoothing = label_smoothing
-        # sync_bn (world > 1): BatchNorm statistics over the GLOBAL batch (two 2C-float all-reduces per layer and step through the
-        # C ABI's hook): N ranks x B then train like one rank x N*B; the default is DistributedDataParallel's local statistics
-        self.sync_bn = bool(sync_bn)
-        _lib.Context.get(self.flat_p.device).set_bn_sync(process_group, enable=self.sync_bn)
+        self.bn_sync = _lib.BnSync(self.flat_p.device, process_group) if sync_bn and self.world > 1 else None
         self.loss_buf = torch.zeros(1, dtype=torch.float32, device=self.flat_p.device)
         self.dlogits = None
-        self.kind = "cnn1d" if type(model).__name__ == "CNN1D" else "cnn2d"
+        self.kind = KINDS[type(model).__name__]
 
     def step(self, x, y):
         """One optimisation step on batch (x[B,T,F], y[B]); returns the (device) loss scalar of this rank's batch."""
         model = self.model
         model.train()
-        if self.kind == "cnn1d":
-            logits, ctx, ws, gen = cnn1d_forward_train_raw(model, x)
-        else:
-            logits, ctx, ws = cnn2d_forward_train_raw(model, x)
-        B = x.shape[0]
-        if self.dlogits is None or self.dlogits.numel() != B:
-            self.dlogits = torch.empty(B, dtype=torch.float32, device=x.device)
-        y = y.to(device=x.device, dtype=torch.float32).contiguous()
-        with torch.cuda.device(ctx.index):
-            _lib.check(ctx.handle, ctx.lib.dfa_bce_smooth_fwd_bwd(
-                ctx.handle, C.c_void_p(logits.data_ptr()), C.c_void_p(y.data_ptr()), float(self.label_smoothing), B,
-                C.c_void_p(self.loss_buf.data_ptr()), C.c_void_p(self.dlogits.data_ptr())))
-        if self.kind == "cnn1d":
-            cnn1d_backward_raw(model, x, self.dlogits, self.grad_views, ctx, ws, gen)
-        else:
-            cnn2d_backward_raw(model, x, self.dlogits, self.grad_views, ctx, ws)
+        if self.bn_sync is not None:
+            self.bn_sync.arm()
+        try:
+            (logits,), st = forward_train_raw(model, x)
+            B = x.shape[0]
+            if self.dlogits is None or self.dlogits.numel() != B:
+                self.dlogits = torch.empty(B, dtype=torch.float32, device=x.device)
+            y = y.to(device=x.device, dtype=torch.float32).contiguous()
+            ctx = st.ctx
+            with torch.cuda.device(ctx.index):
+                _lib.check(ctx.handle, ctx.lib.dfa_bce_smooth_fwd_bwd(
+                    ctx.handle, _ptr(logits), _ptr(y), float(self.label_smoothing), B, _ptr(self.loss_buf), _ptr(self.dlogits)))
+            backward_raw(model, x, self.dlogits, self.grad_views, st)
+        finally:
+            if self.bn_sync is not None:
+                self.bn_sync.disarm()
         self._exchange_and_update()
         return self.loss_buf
 
@@ -448,19 +358,25 @@ class CaeNativeTrainer(_FlatAdamW):
     """Whole auto-encoder training step on the C ABI (src/train_cae.py:58-82: recon = model(x); MSELoss(recon, x); backward;
     AdamW): forward_train writes only the per-sample MSE, the backward forms 2 (recon - x) / N inside its first kernel
     (dfa_cae_backward with drecon = NULL) and writes the 30 gradients straight into the flat buffer, then ONE 2,246,532-byte
-    all-reduce and the fused AdamW.  No reconstruction, no loss gradient, no autograd graph and no torch elementwise kernel."""
+    all-reduce and the fused AdamW.  No reconstruction, no loss gradient, no autograd graph and no torch elementwise kernel.
+    sync_bn: as NativeTrainer's."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4, process_group=None, sync_bn=False):
         super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, process_group=process_group)
-        self.sync_bn = bool(sync_bn)      # BatchNorm statistics over the global batch (NativeTrainer's docstring)
-        _lib.Context.get(self.flat_p.device).set_bn_sync(process_group, enable=self.sync_bn)
+        self.bn_sync = _lib.BnSync(self.flat_p.device, process_group) if sync_bn and self.world > 1 else None
 
     def step(self, x):
         """One optimisation step on the (z-scored) batch x[B,T,F]; returns the device scalar MSELoss(recon, x) of this rank."""
         model = self.model
         model.train()
-        _, _, mse, ctx, ws, gen = cae_forward_train_raw(model, x, want_recon=False, want_latent=False, want_mse=True)
-        cae_backward_raw(model, x, None, self.grad_views, ctx, ws, gen)
+        if self.bn_sync is not None:
+            self.bn_sync.arm()
+        try:
+            (mse,), st = forward_train_raw(model, x, want=("mse",))
+            backward_raw(model, x, None, self.grad_views, st)
+        finally:
+            if self.bn_sync is not None:
+                self.bn_sync.disarm()
         self._exchange_and_update()
         return mse.mean()          # every sample has T*F elements: the mean of the per-sample MSEs is nn.MSELoss's mean
 

@@ -93,21 +93,25 @@ def test_rccl_branch_single_rank_group():
             dist.destroy_process_group()
 
 
-def _syncbn_make(which, prec, dev, sync):
-    """(model, trainer, step(x, y) -> loss) for one of the three model families, dropout off, same seed everywhere"""
-    from dfa_amd.training.train_step import CaeNativeTrainer, NativeTrainer
+def _syncbn_model(which, prec, dev):
     torch.manual_seed(0)
     if which == "cae":
         from dfa_amd.model_cae import ConvAutoencoder
-        model = ConvAutoencoder(precision=prec).to(dev)
-        tr = CaeNativeTrainer(model, lr=1e-4, weight_decay=1e-4, sync_bn=sync)
-        return model, tr, (lambda x, y: tr.step(x))
+        return ConvAutoencoder(precision=prec).to(dev)
     if which == "cnn1d":
         from dfa_amd.model_cnn1d import CNN1D
-        model = CNN1D(in_features=180, dropout=0.0).to(dev)
-    else:
-        from dfa_amd.model import CNN2D
-        model = CNN2D(in_features=180, dropout=0.0, precision=prec).to(dev)
+        return CNN1D(in_features=180, dropout=0.0).to(dev)
+    from dfa_amd.model import CNN2D
+    return CNN2D(in_features=180, dropout=0.0, precision=prec).to(dev)
+
+
+def _syncbn_make(which, prec, dev, sync):
+    """(model, trainer, step(x, y) -> loss) for one of the three model families, dropout off, same seed everywhere"""
+    from dfa_amd.training.train_step import CaeNativeTrainer, NativeTrainer
+    model = _syncbn_model(which, prec, dev)
+    if which == "cae":
+        tr = CaeNativeTrainer(model, lr=1e-4, weight_decay=1e-4, sync_bn=sync)
+        return model, tr, (lambda x, y: tr.step(x))
     tr = NativeTrainer(model, lr=1e-3, weight_decay=0.01, label_smoothing=0.05, sync_bn=sync)
     return model, tr, (lambda x, y: tr.step(x, y))
 
@@ -116,18 +120,35 @@ def _syncbn_worker(rank, world, port, tmp, which, prec, sync):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK="0", DFA_DIST_BACKEND="gloo")
+    import time
     import torch.distributed as dist
+    import torch.nn.functional as Fn
     import dfa_amd  # noqa: F401
     from dfa_amd import distributed as D
     dev = torch.device("cuda", 0)
     D.init(device=dev)
     x, y = _syncbn_batch(which)
     per = x.shape[0] // world
+    xs, ys = x[rank * per:(rank + 1) * per].to(dev), y[rank * per:(rank + 1) * per].to(dev)
     model, tr, step = _syncbn_make(which, prec, dev, sync)
-    loss = step(x[rank * per:(rank + 1) * per].to(dev), y[rank * per:(rank + 1) * per].to(dev))
+    if sync:      # the hook is the synced trainer's own: a live unsynced trainer of another model on the same device leaves it be
+        other = _syncbn_make("cnn2d" if which == "cnn1d" else "cnn1d", "fp32", dev, False)      # noqa: F841
+    loss = step(xs, ys)
     torch.cuda.synchronize()
     out = {"flat_g": tr.flat_g.detach().cpu() / world, "loss": float(loss),
            "stats": {k: v.detach().cpu().clone() for k, v in model.state_dict().items() if "running" in k}}
+    if sync:
+        # ... armed for that trainer's steps only: one autograd-bridge train step of a separate model keeps rank-local statistics
+        bridge = _syncbn_model(which, prec, dev).train()
+        o = bridge(xs)
+        (Fn.mse_loss(o[0], xs.float()) if which == "cae" else Fn.binary_cross_entropy_with_logits(o.view(-1), ys)).backward()
+        torch.cuda.synchronize()
+        out["bridge_stats"] = {k: v.detach().cpu().clone() for k, v in bridge.state_dict().items() if "running" in k}
+        t0 = time.perf_counter()
+        for _ in range(1000):
+            tr.bn_sync.arm()
+            tr.bn_sync.disarm()
+        out["arm_disarm_us"] = (time.perf_counter() - t0) * 1e3           # host cost of one arm + disarm pair
     torch.save(out, os.path.join(tmp, f"syncbn_{which}_{prec}_{int(sync)}_{rank}.pt"))
     dist.barrier()
     dist.destroy_process_group()
@@ -175,4 +196,9 @@ def test_sync_bn_two_ranks_train_like_one_rank_with_the_whole_batch(tmp_path, wh
     c0 = torch.load(os.path.join(tmp, f"syncbn_{which}_{prec}_0_0.pt"))
     worst = max(float((c0["stats"][k] - v).abs().max()) / max(1.0, float(v.abs().max())) for k, v in want_stats.items())
     assert worst > 1e-3, worst
-    print(f"sync_bn {which} {prec}: averaged gradient vs whole-batch gradient, relative L2 {rel:.2e}; control stats mismatch {worst:.2e}")
+    # the autograd bridge of another model, after the synced step: the ranks' statistics stay their own halves'
+    b0, b1 = r0["bridge_stats"], r1["bridge_stats"]
+    apart = max(float((b0[k] - b1[k]).abs().max()) / max(1.0, float(b1[k].abs().max())) for k in b1)
+    assert apart > 1e-3, apart
+    print(f"sync_bn {which} {prec}: averaged gradient vs whole-batch gradient, relative L2 {rel:.2e}; control stats mismatch {worst:.2e}; "
+          f"bridge stats apart {apart:.2e}; arm + disarm {r0['arm_disarm_us']:.2f} us")

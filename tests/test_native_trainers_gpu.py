@@ -131,7 +131,9 @@ def test_cnn1d_native_trainer_matches_reference(golden):
 
 def test_flat_trainer_bridge_writes_gradients_straight_into_the_flat_buffer(golden):
     """FlatTrainer + autograd bridge (arbitrary torch loss): the C-ABI backward writes into the flat views, autograd receives no
-    per-parameter tensors to add; gradients equal the plain-autograd ones bit for bit; a detached .grad falls back cleanly."""
+    per-parameter tensors to add; gradients equal the plain-autograd ones bit for bit; a detached .grad (set to None, or replaced
+    by a foreign zero tensor) falls back cleanly: that parameter gets a fresh tensor autograd accumulates, every other is still
+    written into its view, and every .grad is still plain autograd's."""
     from dfa_amd.training.train_step import FlatTrainer
     _, g = golden("cae_train")
     x = torch.from_numpy(g["ls0.x"]).to("cuda")
@@ -148,12 +150,79 @@ def test_flat_trainer_bridge_writes_gradients_straight_into_the_flat_buffer(gold
         assert p.grad.data_ptr() == gv.data_ptr(), n
         assert torch.equal(p.grad, q.grad), n
     tr.step()
-    # a parameter whose .grad was replaced: the bridge returns fresh tensors and autograd accumulates as usual
-    first = next(m.parameters())
-    first.grad = None
-    r3, _ = m(x)
-    torch.nn.MSELoss()(r3, x).backward()
-    assert first.grad is not None and torch.isfinite(first.grad).all()
+    for detach in (lambda p: None, torch.zeros_like):
+        plain.load_state_dict(m.state_dict())                # same parameters and BatchNorm buffers
+        plain.zero_grad(set_to_none=True)
+        r, _ = plain(x)
+        torch.nn.MSELoss()(r, x).backward()
+        tr.flat_g.fill_(123.0)
+        tr.zero_grad()
+        first = next(m.parameters())
+        first.grad = detach(first)
+        r3, _ = m(x)
+        torch.nn.MSELoss()(r3, x).backward()
+        for i, ((n, p), q, gv) in enumerate(zip(m.named_parameters(), plain.parameters(), tr.grad_views)):
+            assert torch.equal(p.grad, q.grad), n
+            assert i == 0 or p.grad.data_ptr() == gv.data_ptr(), n
+
+
+def _bridge_case(which, prec):
+    """(model, x, y) with dropout off: the same seeds give the same model and batch on every call"""
+    torch.manual_seed(0)
+    if which == "cae":
+        from dfa_amd.model_cae import ConvAutoencoder
+        model = ConvAutoencoder(precision=prec)
+    elif which == "cnn1d":
+        from dfa_amd.model_cnn1d import CNN1D
+        model = CNN1D(in_features=180, dropout=0.0)
+    else:
+        from dfa_amd.model import CNN2D
+        model = CNN2D(in_features=180, dropout=0.0, precision=prec)
+    g = torch.Generator().manual_seed(7)
+    B, T = 4, (96 if which == "cae" else 66)
+    x = (torch.randn(B, 180, T, generator=g) * 3.0).to("cuda").transpose(1, 2)
+    y = (torch.rand(B, generator=g) > 0.5).float().to("cuda")
+    return model.to("cuda").train(), (x.to(torch.bfloat16) if prec == "bf16" else x), y
+
+
+def _bridge_loss(model, x, y):
+    out = model(x)
+    if isinstance(out, tuple):                               # auto-encoder: (reconstruction, latent)
+        return torch.nn.functional.mse_loss(out[0], x.float())
+    return torch.nn.functional.binary_cross_entropy_with_logits(out.view(-1), y)
+
+
+@pytest.mark.parametrize("which,prec", [("cnn2d", "fp32"), ("cnn2d", "bf16"), ("cnn1d", "fp32"), ("cae", "fp32")])
+def test_flat_trainer_gradients_equal_plain_autograd_for_every_model(which, prec):
+    """FlatTrainer over the autograd bridge of each model: `zero_grad(); loss.backward(); step()` twice, with the flat gradient
+    buffer full of stale values before each step (zero_grad does not memset it).  In both steps every .grad equals, bit for
+    bit, what the plain bridge (no FlatTrainer) computes for the same parameters, BatchNorm buffers and batch."""
+    from dfa_amd.training.train_step import FlatTrainer
+    plain, x, y = _bridge_case(which, prec)
+    m, _, _ = _bridge_case(which, prec)
+    tr = FlatTrainer(m, lr=1e-3, weight_decay=0.01)
+    for step in range(2):
+        plain.load_state_dict(m.state_dict())
+        plain.zero_grad(set_to_none=True)
+        _bridge_loss(plain, x, y).backward()
+        tr.flat_g.fill_(123.0)
+        tr.zero_grad()
+        _bridge_loss(m, x, y).backward()
+        for (n, p), q in zip(m.named_parameters(), plain.parameters()):
+            assert torch.equal(p.grad, q.grad), (step, n)
+        tr.step()
+
+
+def test_raw_backward_on_another_batch_shape_than_its_forward_raises():
+    """A raw backward reads the activations its forward saved for ITS batch: CNN1D and the auto-encoder refuse another batch
+    shape before any kernel runs, as CNN2D does."""
+    from dfa_amd.training.train_step import backward_raw, forward_train_raw
+    for which in ("cnn1d", "cae"):
+        m, x, _ = _bridge_case(which, "fp32")
+        outs, st = forward_train_raw(m, x)
+        grads = [torch.empty_like(p) for p in m.parameters()]
+        with pytest.raises(RuntimeError, match="batch shape"):
+            backward_raw(m, x[:2], torch.ones_like(outs[0][:2]), grads, st)
 
 
 @pytest.mark.parametrize("option", ["cae_dgrad_mfma", "conv1_mfma", "dgrad_m16", "cae_conv_stats", "cae_bwd_fold", "cae_enc4_wide"])
