@@ -229,6 +229,7 @@ int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "cnn1d_fused") == 0) { ctx->cnn1d_fused = value < 0 ? 0 : (value > 2 ? 1 : value); return DFA_OK; }
   if (strcmp(name, "block3_m16") == 0) { ctx->block3_m16 = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "fuse_conv1") == 0) { ctx->fuse_conv1 = value ? 1 : 0; return DFA_OK; }
+  if (strcmp(name, "fuse_blocks123") == 0) { ctx->fuse_blocks123 = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "lds_pipe") == 0) { ctx->lds_pipe = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "conv_dma") == 0) { ctx->conv_dma = value < 0 ? -1 : value; return DFA_OK; }
   return fail(ctx, DFA_E_UNSUPPORTED, "unknown option '%s'", name);
@@ -401,7 +402,20 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   // every workgroup would walk the whole time axis alone, so the axis is split into segments that separate workgroups walk
   // (blocks 1+2: disjoint output rows; block 3: partial means per segment, added up by the classifier kernel).
   const int nstrips30 = (F + 29) / 30;     // conv12_fused, conv3_m16 and conv_split own 30 columns per strip (conv3x3_mfma 32)
-  if (fused12) {
+  const int niter3 = (pl.H2 + 1) / 2;
+  const int chunk3 = 6 * std::max(2, (niter3 + 6 * kMaxSeg - 1) / (6 * kMaxSeg));   // canonical chunks: depend on T only (12 iterations = 24 rows for T = 321), <= kMaxSeg of them
+  // Blocks 1-3 + time mean as ONE kernel (conv123_fused.hip, timing slot 2; slot 1 reports nothing) wherever neither kernel of
+  // the two-kernel path would split the time axis: same chunked time mean, bit-identical logits and embeddings
+  // (B * strips >= 512 also where a short T would not split: small batches keep the two-kernel path and its a2 in the workspace)
+  const bool fused123 = fused12 && ctx->block3_m16 && ctx->fuse_blocks123 && ctx->time_split <= 0 && B * nstrips30 >= 512 &&
+                        seg_iters_for((pl.H1 + 3) / 4, B * nstrips30, 512, 6, ctx->time_split) == 0 &&
+                        seg_iters_for(niter3, B * nstrips30, 512, chunk3, ctx->time_split) == 0;
+  if (fused123) {
+    ScopedSlot ts(ctx, 2);
+    DFA_HIP_CHECK(ctx, launch_conv123_fused(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
+                                            m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
+                                            s, ctx->lds_pipe));
+  } else if (fused12) {
     ScopedSlot ts(ctx, 1);
     const int seg12 = seg_iters_for((pl.H1 + 3) / 4, B * nstrips30, 512, 6, ctx->time_split);
     DFA_HIP_CHECK(ctx, launch_conv12_fused(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, a2,
@@ -419,13 +433,11 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
     if (prec == DFA_PREC_BF16X3) DFA_HIP_CHECK(ctx, launch_cnn2d_block2_split(a, s, ctx->lds_pipe));
     else DFA_HIP_CHECK(ctx, launch_cnn2d_block2(prec, a, s, ctx->conv_dma, ctx->lds_pipe));
   }
-  {
+  if (!fused123) {
     ScopedSlot ts(ctx, 2);
     ConvArgs a{};
     a.in = a2; a.wpack = m.c3.wpack; a.bias = m.c3.bias; a.out = nullptr; a.emb = emb;
     a.B = B; a.H = pl.H2; a.W = F; a.COUT = 128; a.inv_h = 1.0f / (float)pl.H2; a.relu = 1; a.zero_page = ctx->zero_page;
-    const int niter3 = (pl.H2 + 1) / 2;
-    const int chunk3 = 6 * std::max(2, (niter3 + 6 * kMaxSeg - 1) / (6 * kMaxSeg));   // canonical chunks: depend on T only (12 iterations = 24 rows for T = 321), <= kMaxSeg of them
     if (prec == DFA_PREC_BF16X3) {
       a.chunk_iters = chunk3;
       a.seg_iters = seg_iters_for(niter3, B * nstrips30, 256, chunk3, ctx->time_split);

@@ -73,6 +73,9 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *                   compiler-scheduled twins (bit-identical results)
  *   "fuse_conv1"    1 (default) = CNN2D bf16 mode on bf16 features runs blocks 1+2 as one kernel, 0 = two kernels
  *   "block3_m16"    1 (default) = CNN2D bf16 block 3 on v_mfma_f32_16x16x32_bf16, 0 = the 32x32x16 kernel
+ *   "fuse_blocks123" 1 (default) = CNN2D bf16 eval forward with fuse_conv1 and block3_m16 set runs blocks 1-3 + the time
+ *                   mean as ONE kernel (a2 stays in LDS) wherever neither old kernel would split the time axis (B * strips >= 512,
+ *                   no forced time_split); 0 = the two-kernel path.  Bit-identical results either way
  *   "time_split"    -1 (default) = CNN2D eval forward splits the time axis over workgroups when the batch alone cannot fill
  *                   the chip (B * strips below the resident-workgroup count, e.g. the reference's predict batch of 32), 0 =
  *                   never, n > 0 = force n segments (at most 4).  Logits and embeddings are bit-identical for every setting and
