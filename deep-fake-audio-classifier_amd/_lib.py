@@ -78,6 +78,10 @@ SYMBOLS = [
     ("dfa_mse_fwd_bwd", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                   C.c_int64, C.c_void_p, C.c_void_p]),
     ("dfa_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dfa_ragged_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dfa_cnn2d_forward_ragged", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t]),
     ("dfa_dominant_kernel", C.c_char_p, [C.c_int, C.c_int]),
     ("dfa_ctx_timing_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("dfa_ctx_timing_reset", C.c_int, [C.c_void_p]),
@@ -248,3 +252,26 @@ def ptr_array(tensors):
     for i, t in enumerate(tensors):
         arr[i] = t.data_ptr()
     return arr
+
+
+def host_lengths(lengths, B: int, T_max: int, min_len: int):
+    """Per-utterance frame counts of a ragged batch (list, numpy array or int tensor on any device) -> a contiguous host
+    int32 numpy array, checked against the batch: one length per row, each in [min_len, T_max]."""
+    import numpy as np
+
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_floating_point() or lengths.is_complex():
+            raise ValueError(f"lengths must be integers, got a {lengths.dtype} tensor")
+        lengths = lengths.detach().cpu().numpy()
+    arr = np.asarray(lengths)
+    if arr.ndim != 1:
+        raise ValueError(f"lengths must be one-dimensional, got shape {arr.shape}")
+    if arr.size and not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"lengths must be integers, got dtype {arr.dtype}")
+    if arr.shape[0] != B:
+        raise ValueError(f"got {arr.shape[0]} lengths for a batch of {B}")
+    bad = np.nonzero((arr < min_len) | (arr > T_max))[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"lengths[{i}]={int(arr[i])} is outside [{min_len}, T_max={T_max}]")
+    return np.ascontiguousarray(arr, dtype=np.int32)

@@ -58,6 +58,9 @@ int seg_iters_for(int niter, int nwg, int slots, int period, int forced) {
   return seg >= niter ? 0 : seg;
 }
 
+// canonical chunk of block 3's time mean (iterations of 2 rows, a multiple of 6): depends on H2 only, <= kMaxSeg chunks
+int chunk3_for(int niter3) { return 6 * std::max(2, (niter3 + 6 * kMaxSeg - 1) / (6 * kMaxSeg)); }
+
 struct Cnn1dPlan {
   size_t h1_off, h2_off, pooled_off, total;
 };
@@ -159,6 +162,9 @@ int dfa_ctx_destroy(dfa_ctx* ctx) {
   if (ctx->clock_buf) (void)hipFree(ctx->clock_buf);
   if (ctx->mse_partial) (void)hipFree(ctx->mse_partial);
   if (ctx->aug_keep) (void)hipFree(ctx->aug_keep);
+  for (auto e : ctx->ragged_done)
+    if (e) (void)hipEventSynchronize(e), (void)hipEventDestroy(e);
+  if (ctx->ragged_host) (void)hipHostFree(ctx->ragged_host);
   for (auto& t : ctx->slots) {
     for (auto e : t.start) (void)hipEventDestroy(e);
     for (auto e : t.stop) (void)hipEventDestroy(e);
@@ -403,7 +409,7 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   // (blocks 1+2: disjoint output rows; block 3: partial means per segment, added up by the classifier kernel).
   const int nstrips30 = (F + 29) / 30;     // conv12_fused, conv3_m16 and conv_split own 30 columns per strip (conv3x3_mfma 32)
   const int niter3 = (pl.H2 + 1) / 2;
-  const int chunk3 = 6 * std::max(2, (niter3 + 6 * kMaxSeg - 1) / (6 * kMaxSeg));   // canonical chunks: depend on T only (12 iterations = 24 rows for T = 321), <= kMaxSeg of them
+  const int chunk3 = chunk3_for(niter3);   // canonical chunks: depend on T only (12 iterations = 24 rows for T = 321), <= kMaxSeg of them
   // Blocks 1-3 + time mean as ONE kernel (conv123_fused.hip, timing slot 2; slot 1 reports nothing) wherever neither kernel of
   // the two-kernel path would split the time axis: same chunked time mean, bit-identical logits and embeddings
   // (B * strips >= 512 also where a short T would not split: small batches keep the two-kernel path and its a2 in the workspace)
@@ -465,6 +471,122 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
     if (nseg3 > 1) {   // chunk slabs 1 .. nseg3 of the workspace region -> the embedding (slab 0 of the region, or the caller's buffer)
       const size_t n = (size_t)B * 128 * F;
       DFA_HIP_CHECK(ctx, launch_emb_reduce((const float*)(ws + pl.emb_off) + n, nseg3, n, n, 1.0f / (float)pl.H2, emb, s));
+    }
+    DFA_HIP_CHECK(ctx, launch_linear(emb, m.p[18], m.p[19], logits, B, 128 * F, s));
+  }
+  return DFA_OK;
+}
+
+// Ragged batches: the uniform plan at T_max plus the ragged table (conv3x3_mfma.h: RaggedTab, 4 * B int32 words) behind it
+size_t dfa_ragged_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T_max, int F, int precision) {
+  if (B < 1 || T_max < 1 || F < 1) return 0;
+  if (model == DFA_MODEL_CNN2D) return plan_cnn2d(B, T_max, F, precision, ctx ? ctx->time_split : -1).total + align_up((size_t)4 * B * 4, 256);
+  return 0;
+}
+
+int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b, int64_t stride_t,
+                             int64_t stride_f, const int32_t* lengths, float* logits, float* embedding, void* workspace,
+                             size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn2d_forward_ragged");
+  if (!ctx) return DFA_E_NULL_PTR;
+  Cnn2dState& m = ctx->cnn2d;
+  if (m.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn2d_prepare has not been called since the last set_params");
+  if (!x || !logits || !workspace || !lengths) return fail(ctx, DFA_E_NULL_PTR, "x, lengths, logits and workspace must be non-null");
+  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
+  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
+  if (F != m.in_features)
+    return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d of the classifier (src/model.py:31)", F, m.in_features);
+  if (T_max < 4) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: two (2,1) average pools need T >= 4", T_max);
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] < 4 || lengths[b] > T_max)
+      return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [4, T_max=%d]", b, (int)lengths[b], T_max);
+  const int prec = m.prepared_prec;
+  if (prec != DFA_PREC_BF16)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward has kernels for precision bf16 only (prepared: %d)", prec);
+  if (!ctx->fuse_conv1 || !ctx->block3_m16)   // the uniform forward would run other kernels: no bit-identity promise there
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward needs the default options fuse_conv1=1 and block3_m16=1");
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward cannot be captured into a graph: its lengths are copied per call");
+  const Cnn2dPlan pl = plan_cnn2d(B, T_max, F, prec, ctx->time_split);
+  const size_t tab_off = pl.total, need = pl.total + align_up((size_t)4 * B * 4, 256);
+  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
+  if (embedding && ((uintptr_t)embedding & 15) != 0)
+    return fail(ctx, DFA_E_BAD_SHAPE, "embedding must be 16-byte aligned (got %p)", (void*)embedding);
+  // the ragged table (conv3x3_mfma.h: RaggedTab) in the next pinned staging slot
+  const size_t words = (size_t)4 * B;
+  if (words > ctx->ragged_cap) {
+    for (auto& e : ctx->ragged_done)
+      if (e) DFA_HIP_CHECK(ctx, hipEventSynchronize(e));
+    if (ctx->ragged_host) DFA_HIP_CHECK(ctx, hipHostFree(ctx->ragged_host));
+    ctx->ragged_host = nullptr;
+    ctx->ragged_cap = 0;
+    const size_t cap = std::max(words, (size_t)4 * 256);
+    DFA_HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->ragged_host, dfa_ctx::kRaggedSlots * cap * sizeof(int32_t), hipHostMallocDefault));
+    ctx->ragged_cap = cap;
+  }
+  const int slot = ctx->ragged_slot;
+  ctx->ragged_slot = (slot + 1) % dfa_ctx::kRaggedSlots;
+  if (!ctx->ragged_done[slot]) DFA_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ragged_done[slot], hipEventDisableTiming));
+  else DFA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ragged_done[slot]));   // its previous copy has been read
+  int32_t* tab = ctx->ragged_host + slot * ctx->ragged_cap;
+  int nseg3 = 1;
+  for (int b = 0; b < B; ++b) {
+    const int h2 = lengths[b] / 4, niter3 = (h2 + 1) / 2, chunk = chunk3_for(niter3);
+    const float inv_h = 1.0f / (float)h2;
+    tab[b] = lengths[b];
+    memcpy(&tab[2 * B + b], &inv_h, 4);
+    tab[3 * B + b] = chunk;
+    nseg3 = std::max(nseg3, (niter3 + chunk - 1) / chunk);
+  }
+  // dispatch order: the kernels' XCD remap gives each of the 8 XCDs one contiguous range of workgroup slots, so the utterances,
+  // sorted longest first, are dealt round-robin over 8 contiguous groups (sorted rank k -> group k % 8, place k / 8 in it).
+  // Every XCD then gets about the same work, and inside its range the long utterances start first.
+  std::vector<int> sorted(B);
+  for (int b = 0; b < B; ++b) sorted[b] = b;
+  std::stable_sort(sorted.begin(), sorted.end(), [&](int i, int j) { return lengths[i] > lengths[j]; });
+  {
+    int group_start[9] = {0};
+    for (int g = 0; g < 8; ++g) group_start[g + 1] = group_start[g] + (B - g + 7) / 8;   // ranks k < B with k % 8 == g
+    for (int k = 0; k < B; ++k) tab[B + group_start[k % 8] + k / 8] = sorted[k];
+  }
+  char* ws = (char*)workspace;
+  const int* dtab = (const int*)(ws + tab_off);
+  hipStream_t s = ctx->stream;
+  DFA_HIP_CHECK(ctx, hipMemcpyAsync(ws + tab_off, tab, words * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  DFA_HIP_CHECK(ctx, hipEventRecord(ctx->ragged_done[slot], s));
+  const RaggedTab rt{dtab, B};
+  void* a2 = ws + pl.a2_off;
+  float* emb = embedding ? embedding : (float*)(ws + pl.emb_off);
+  const int nstrips30 = (F + 29) / 30;
+  {   // blocks 1 + 2 (timing slot 1): segments of the longest utterance's trip count, the shorter ones leave their late ones
+    ScopedSlot ts(ctx, 1);
+    const int seg12 = seg_iters_for((pl.H1 + 3) / 4, B * nstrips30, 512, 6, ctx->time_split);
+    DFA_HIP_CHECK(ctx, launch_conv12_ragged(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, a2,
+                                            B, T_max, F, dtab, s, ctx->lds_pipe, seg12));
+  }
+  // block 3 + time mean (slot 2): split as the uniform plan would (its chunk slabs exist then), one workgroup per chunk
+  const bool split3 = ctx->time_split > 0 || (ctx->time_split < 0 && (size_t)B * ((F + 31) / 32) < 512);
+  {
+    ScopedSlot ts(ctx, 2);
+    ConvArgs a{};
+    a.in = a2; a.wpack = m.c3_m16; a.bias = m.c3.bias; a.out = nullptr; a.emb = emb;
+    a.B = B; a.H = pl.H2; a.W = F; a.COUT = 128; a.relu = 1; a.zero_page = ctx->zero_page;
+    a.chunk_iters = 1;                 // (the kernel takes each utterance's own chunk from the table)
+    if (split3) {
+      a.seg_iters = 1;
+      a.emb_seg_stride = (size_t)B * 128 * F;
+      a.emb = (float*)(ws + pl.emb_off) + a.emb_seg_stride;
+    }
+    DFA_HIP_CHECK(ctx, launch_cnn2d_block3_m16_ragged(a, rt, nseg3, s, ctx->lds_pipe));
+  }
+  {
+    ScopedSlot ts(ctx, 3);
+    if (split3) {
+      const size_t n = (size_t)B * 128 * F;
+      DFA_HIP_CHECK(ctx, launch_emb_reduce_ragged((const float*)(ws + pl.emb_off) + n, n, 128 * F, dtab, B, emb, s));
     }
     DFA_HIP_CHECK(ctx, launch_linear(emb, m.p[18], m.p[19], logits, B, 128 * F, s));
   }

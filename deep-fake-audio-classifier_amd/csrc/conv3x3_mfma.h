@@ -127,6 +127,15 @@ struct ConvArgs {
   long long* clock_stamps;
 };
 
+// Variable-length batches (dfa_cnn2d_forward_ragged): a device table of 4 * B int32 words, copied from the host with each
+// call.  [0, B): length T_b of utterance b; [B, 2B): dispatch order, workgroup slot u -> utterance (longest first);
+// [2B, 3B): 1 / H2_b as float bits; [3B, 4B): number of canonical time-mean chunks of block 3.  A ragged kernel reads its
+// utterance's words once per workgroup (wave-uniform).
+struct RaggedTab {
+  const int* tab;
+  int B;
+};
+
 // chunk swizzle as a function of the pixel slot (column) only
 template <int PB>
 __device__ __forceinline__ int lds_swz(int slot) {

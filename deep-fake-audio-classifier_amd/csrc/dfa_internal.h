@@ -147,6 +147,13 @@ struct dfa_ctx {
   float* aug_keep = nullptr;        // device copy of the armed augmentation's keep mask (dfa_cnn2d_set_train_augment copies keep_f)
   int aug_keep_cap = 0, aug_keep_slot = 0;
   float* mse_partial = nullptr;     // device, kMseBlocks floats: block sums of dfa_mse_fwd_bwd (allocated on first use)
+  // ragged forwards: pinned host staging of the per-call table (RaggedTab), kRaggedSlots slots used in turn; a slot is rewritten
+  // only after the event recorded behind its last copy has completed
+  static constexpr int kRaggedSlots = 4;
+  int32_t* ragged_host = nullptr;   // kRaggedSlots x ragged_cap words
+  size_t ragged_cap = 0;
+  int ragged_slot = 0;
+  hipEvent_t ragged_done[kRaggedSlots] = {};
   int conv_dma = -1;           // conv input staging: 1 = global_load_lds (LDS-DMA), 0 = through registers, -1 = per-kernel default
   dfa::Cnn2dState cnn2d;
   dfa::Cnn1dState cnn1d;
@@ -224,6 +231,7 @@ hipError_t launch_conv1(const void* x, int x_dtype, int64_t sb, int64_t st, int6
 hipError_t launch_linear(const float* emb, const float* w, const float* bias, float* logits, int B, int K,
                          hipStream_t s);
 hipError_t launch_emb_reduce(const float* parts, int nparts, size_t stride, size_t n, float inv_h, float* out, hipStream_t s);
+hipError_t launch_emb_reduce_ragged(const float* parts, size_t stride, int per_b, const int* tab, int B, float* out, hipStream_t s);
 // conv1d.hip
 hipError_t launch_fold_conv1d(const float* w, const float* b, const float* g, const float* beta, const float* mean,
                               const float* var, float* wf, float* bf, int cin, int cout, hipStream_t s);
@@ -382,6 +390,7 @@ hipError_t launch_pack_conv3x3_dgrad_m16(const float* w, int cin, int cout, uint
 hipError_t launch_train_dgrad3_m16(const ConvArgs& a, hipStream_t s, int pipe = 1);
 hipError_t launch_train_dgrad2_m16(const ConvArgs& a, hipStream_t s, int pipe = 1);
 hipError_t launch_cnn2d_block3_m16(const ConvArgs& a, hipStream_t s, int pipe = 1);
+hipError_t launch_cnn2d_block3_m16_ragged(const ConvArgs& a, const RaggedTab& rt, int nseg, hipStream_t s, int pipe = 1);
 hipError_t launch_reduce_wgrad_record(const float* partial, int nparts, int stride, int cin, int cout, int cin_total,
                                       int ci_off, int co_off, float* dw, float* db, hipStream_t s, int perm = 0);
 void set_train_conv_variant(int v);
@@ -391,6 +400,9 @@ hipError_t launch_pack_conv1_mfma(const float* w1, const float* b1, uint4* c1pac
 hipError_t launch_conv12_fused(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack, const float* c1bias,
                                const uint4* wpack2, const float* bias2, void* a2, int B, int T, int F, hipStream_t s, int pipe = 1,
                                int seg_iters = 0);
+hipError_t launch_conv12_ragged(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
+                                const float* c1bias, const uint4* wpack2, const float* bias2, void* a2, int B, int T_max,
+                                int F, const int* tab, hipStream_t s, int pipe = 1, int seg_iters = 0);
 hipError_t launch_conv123_fused(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
                                 const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
                                 const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,

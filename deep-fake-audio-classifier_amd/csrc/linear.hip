@@ -61,4 +61,28 @@ hipError_t launch_emb_reduce(const float* parts, int nparts, size_t stride, size
   return hipGetLastError();
 }
 
+// Ragged batch (dfa_cnn2d_forward_ragged): as emb_reduce_kernel, with utterance b's own number of chunk slabs and 1/H2_b
+// from the ragged table (conv3x3_mfma.h: RaggedTab).  per_b = 128 * F floats per utterance, a multiple of 4.
+__global__ __launch_bounds__(256) void emb_reduce_ragged_kernel(const float* __restrict__ parts, size_t stride, int per_b,
+                                                                const int* __restrict__ tab, int B, float* __restrict__ out) {
+  const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= (size_t)B * per_b) return;
+  const int b = (int)(i / per_b);
+  const int niter = (tab[b] / 4 + 1) / 2, chunk = tab[3 * B + b];
+  const int nparts = (niter + chunk - 1) / chunk;
+  const float inv_h = __int_as_float(tab[2 * B + b]);
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int k = 0; k < nparts; ++k) {
+    const float4 p = *reinterpret_cast<const float4*>(parts + (size_t)k * stride + i);
+    v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
+  }
+  *reinterpret_cast<float4*>(out + i) = make_float4(v.x * inv_h, v.y * inv_h, v.z * inv_h, v.w * inv_h);
+}
+
+hipError_t launch_emb_reduce_ragged(const float* parts, size_t stride, int per_b, const int* tab, int B, float* out, hipStream_t s) {
+  const size_t nthreads = ((size_t)B * per_b + 3) / 4;
+  hipLaunchKernelGGL(emb_reduce_ragged_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, parts, stride, per_b, tab, B, out);
+  return hipGetLastError();
+}
+
 }  // namespace dfa

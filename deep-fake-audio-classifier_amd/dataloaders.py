@@ -304,3 +304,53 @@ def open_flat(features_path: str, labels_path: str | None, cache_dir: str, rank:
             dist.barrier()
     ff = ingest.FlatFeatures(prefix)
     return ff.tensor(), ff.labels, ff.uttids
+
+
+class RaggedBatcher:
+    """Iterate (features, labels, lengths) over a list of per-utterance [F, T_i] tensors of unequal lengths (the layout a
+    features.pkl holds), for `model(features, lengths=lengths)`.
+
+    features: [b, T_pad, F] on `device`, the transposed view of a [b, F, T_pad] batch zero-padded to the batch's longest
+    utterance (T_pad rounded up so every stored row is a multiple of 16 bytes), staged in pinned memory when `device` is a GPU;
+    labels: [b] on `device` or None; lengths: int32 [b] on the CPU.  rank/world shard the utterances contiguously like
+    FlatBatcher.  Each utterance's output is independent of its batch companions, so a shard is walked in order of length
+    (longest first) to cut padding; `restore` puts per-batch outputs back in input order.
+    """
+
+    def __init__(self, features, labels=None, batch_size: int = 32, device="cuda", rank: int = 0, world: int = 1,
+                 dtype: torch.dtype | None = None):
+        n = len(features)
+        per = -(-n // world)
+        self.lo, self.hi = min(rank * per, n), min((rank + 1) * per, n)
+        self.features, self.labels = features, labels
+        self.batch_size, self.device, self.dtype = batch_size, torch.device(device), dtype
+        F = {int(f.shape[0]) for f in features[self.lo:self.hi]}
+        if len(F) > 1:
+            raise ValueError(f"ragged utterances must share the feature dimension, got {sorted(F)}")
+        lens = np.array([int(f.shape[-1]) for f in features[self.lo:self.hi]], dtype=np.int64)
+        self.order = self.lo + np.argsort(-lens, kind="stable")          # longest first, ties in input order
+        self.batches = [self.order[i:i + batch_size] for i in range(0, len(self.order), batch_size)]
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        pin = self.device.type == "cuda"
+        for idx in self.batches:
+            utts = [torch.as_tensor(self.features[i]) for i in idx]
+            dtype = self.dtype or utts[0].dtype
+            lengths = torch.tensor([u.shape[-1] for u in utts], dtype=torch.int32)
+            align = max(1, 16 // torch.empty(0, dtype=dtype).element_size())
+            t_pad = -(-int(lengths.max()) // align) * align
+            host = torch.zeros((len(idx), utts[0].shape[0], t_pad), dtype=dtype, pin_memory=pin)
+            for j, u in enumerate(utts):
+                host[j, :, :u.shape[-1]] = u
+            x = host.to(self.device, non_blocking=True).transpose(1, 2)
+            y = None if self.labels is None else torch.as_tensor(np.asarray(self.labels)[idx]).to(self.device)
+            yield x, y, lengths
+
+    def restore(self, outputs):
+        """Per-batch outputs (first dimension = the batch's utterances, in iteration order) -> one tensor in input order."""
+        cat = torch.cat(list(outputs))
+        inv = torch.from_numpy(np.argsort(np.concatenate(self.batches) - self.lo, kind="stable")).to(cat.device)
+        return cat[inv]

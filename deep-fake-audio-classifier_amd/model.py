@@ -85,13 +85,45 @@ class CNN2D(nn.Module):
         self._prepared = sig
 
     # ---- forward -----------------------------------------------------------------------------------------------
-    def forward(self, x, return_embedding=False):
+    def forward(self, x, return_embedding=False, lengths=None):
+        """lengths: None (every utterance spans all T frames: the reference's call), or the per-utterance frame counts of a
+        ragged batch padded to T (a list, numpy array or int tensor): utterance b is scored as x[b:b+1, :lengths[b]] alone
+        would be, and its padding rows are never read.  Ragged batches run in bf16 precision, eval mode only."""
         if x.dim() != 3:
             raise ValueError(f"CNN2D expects x of shape (B, T, F), got {tuple(x.shape)}")
         if self.training:
+            if lengths is not None:
+                raise NotImplementedError("ragged batches (lengths=...) are eval-only: batch-norm statistics over a "
+                                          "variable-length batch have no reference definition")
             from .training import cnn2d_train_forward  # train-mode path (batch-stat BN, dropout, autograd)
             return cnn2d_train_forward(self, x, return_embedding)
+        if lengths is not None:
+            return self._ragged_forward(x, return_embedding, _lib.host_lengths(lengths, x.shape[0], x.shape[1], 4))
         return self._eval_forward(x, return_embedding)
+
+    def _ragged_forward(self, x, return_embedding, lengths):
+        if x.device.type != "cuda":
+            raise RuntimeError("dfa_amd.CNN2D runs on the GPU only: move the input with .to('cuda')")
+        B, T, F = x.shape
+        ctx = _lib.Context.get(x.device)
+        with torch.cuda.device(ctx.index):
+            ctx.use_current_stream()
+            self._ensure_prepared(ctx)
+            prec = _lib.PRECISIONS[self.precision]
+            nbytes = ctx.lib.dfa_ragged_workspace_bytes(ctx.handle, _lib.MODEL_CNN2D, B, T, F, prec)
+            ws = ctx.workspace(nbytes)
+            logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
+            emb = torch.empty((B, 4 * self.base_channels * F), dtype=torch.float32, device=x.device) \
+                if return_embedding else None
+            sb, st, sf = x.stride()
+            code = ctx.lib.dfa_cnn2d_forward_ragged(
+                ctx.handle, C.c_void_p(x.data_ptr()), _lib.x_dtype_code(x), B, T, F, sb, st, sf,
+                C.c_void_p(lengths.ctypes.data), C.c_void_p(logits.data_ptr()),
+                C.c_void_p(emb.data_ptr() if emb is not None else None), C.c_void_p(ws.data_ptr()), ws.numel())
+            _lib.check(ctx.handle, code)
+        if return_embedding:
+            return logits, emb
+        return logits
 
     def _eval_forward(self, x, return_embedding):
         if x.device.type != "cuda":

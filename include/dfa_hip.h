@@ -154,6 +154,19 @@ int dfa_cnn2d_prepare(dfa_ctx* ctx, int precision);
 int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
                       int64_t stride_t, int64_t stride_f, float* logits, float* embedding,
                       void* workspace, size_t workspace_bytes);
+/* eval-mode forward of a variable-length (ragged) batch: utterance b is x[b, :lengths[b], :] and gets exactly the logit
+ * (and embedding) dfa_cnn2d_forward gives x[b:b+1, :lengths[b], :] alone, bit for bit.  Replaces scoring a file of
+ * uncropped utterances one at a time (src/predict.py:97-110 at --batch-size 1; src/dataloaders.py:63-75).
+ *   x: the padded [B, T_max, F] strided view as above; rows t >= lengths[b] are never read (may be uninitialised);
+ *   lengths: HOST int32[B], 4 <= lengths[b] <= T_max (else DFA_E_BAD_SHAPE naming the index); validated here and copied
+ *      into the workspace on the context's stream;
+ *   workspace: device, >= dfa_ragged_workspace_bytes(ctx, DFA_MODEL_CNN2D, B, T_max, F, precision) bytes.
+ * Precision bf16 only in this version (blocks 1+2 and block 3 + time mean as two kernels, then the classifier).  A context
+ * prepared for fp32 or bf16x3, one with fuse_conv1 = 0 or block3_m16 = 0, or a capturing stream returns DFA_E_UNSUPPORTED
+ * (the lengths are copied per call, so the forward cannot be replayed from a graph). */
+int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,
+                             int64_t stride_t, int64_t stride_f, const int32_t* lengths, float* logits,
+                             float* embedding, void* workspace, size_t workspace_bytes);
 
 /* ---- CNN2D training step (replaces, for src/train.py:71-76, torch autograd over src/model.py:13-39) ------------ */
 size_t dfa_cnn2d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, int precision);
@@ -294,6 +307,8 @@ int dfa_mse_fwd_bwd(dfa_ctx* ctx, const float* recon, const void* x, int x_dtype
 
 /* ---- shared ------------------------------------------------------------------------------------ */
 size_t dfa_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T, int F, int precision);
+/* workspace of dfa_cnn2d_forward_ragged for B utterances padded to T_max frames (0 for a model without a ragged forward) */
+size_t dfa_ragged_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T_max, int F, int precision);
 /* names of the device kernels a forward launches, for profile post-processing ("" when unknown) */
 const char* dfa_dominant_kernel(int model, int precision);
 /* ---- per-kernel timing (HIP events recorded on the context's stream around every launch) -------------
