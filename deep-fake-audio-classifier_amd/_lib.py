@@ -82,6 +82,11 @@ SYMBOLS = [
     ("dfa_cnn2d_forward_ragged", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                            C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_size_t]),
+    ("dfa_cnn1d_forward_ragged", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("dfa_cnn1d_ragged_segments", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.c_int]),
+    ("dfa_cnn1d_ragged_lds_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("dfa_dominant_kernel", C.c_char_p, [C.c_int, C.c_int]),
     ("dfa_ctx_timing_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("dfa_ctx_timing_reset", C.c_int, [C.c_void_p]),

@@ -112,6 +112,44 @@ CaePlan plan_cae(int B, int T, int F, int prec) {
 
 }  // namespace
 
+// The per-call table of a ragged forward, staged and sent: takes the next of the context's pinned slots (waiting for the copy
+// that last read it; the staging grows when a batch needs more words), fills [0, B) with the lengths and [B, 2B) with the
+// dispatch order, lets `fill_rest` write the model's own words behind them, and copies `words` words to `dst` (device) on the
+// context's stream.  Dispatch order: the kernels' XCD remap gives each of the 8 XCDs one contiguous range of workgroup slots,
+// so the utterances, sorted longest first, are dealt round-robin over 8 contiguous groups (sorted rank k -> group k % 8, place
+// k / 8 in it).  Every XCD then gets about the same work, and inside its range the long utterances start first.
+template <typename Fill>
+static int stage_ragged_table(dfa_ctx* ctx, const int32_t* lengths, int B, size_t words, void* dst, Fill fill_rest) {
+  if (words > ctx->ragged_cap) {
+    for (auto& e : ctx->ragged_done)
+      if (e) DFA_HIP_CHECK(ctx, hipEventSynchronize(e));
+    if (ctx->ragged_host) DFA_HIP_CHECK(ctx, hipHostFree(ctx->ragged_host));
+    ctx->ragged_host = nullptr;
+    ctx->ragged_cap = 0;
+    const size_t cap = std::max(words, (size_t)4 * 256);
+    DFA_HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->ragged_host, dfa_ctx::kRaggedSlots * cap * sizeof(int32_t), hipHostMallocDefault));
+    ctx->ragged_cap = cap;
+  }
+  const int slot = ctx->ragged_slot;
+  ctx->ragged_slot = (slot + 1) % dfa_ctx::kRaggedSlots;
+  if (!ctx->ragged_done[slot]) DFA_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ragged_done[slot], hipEventDisableTiming));
+  else DFA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ragged_done[slot]));   // its previous copy has been read
+  int32_t* tab = ctx->ragged_host + slot * ctx->ragged_cap;
+  for (int b = 0; b < B; ++b) tab[b] = lengths[b];
+  fill_rest(tab);
+  std::vector<int> sorted(B);
+  for (int b = 0; b < B; ++b) sorted[b] = b;
+  std::stable_sort(sorted.begin(), sorted.end(), [&](int i, int j) { return lengths[i] > lengths[j]; });
+  {
+    int group_start[9] = {0};
+    for (int g = 0; g < 8; ++g) group_start[g + 1] = group_start[g] + (B - g + 7) / 8;   // ranks k < B with k % 8 == g
+    for (int k = 0; k < B; ++k) tab[B + group_start[k % 8] + k / 8] = sorted[k];
+  }
+  DFA_HIP_CHECK(ctx, hipMemcpyAsync(dst, tab, words * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  DFA_HIP_CHECK(ctx, hipEventRecord(ctx->ragged_done[slot], ctx->stream));
+  return DFA_OK;
+}
+
 extern "C" {
 
 int dfa_version(void) { return DFA_VERSION; }
@@ -477,10 +515,12 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   return DFA_OK;
 }
 
-// Ragged batches: the uniform plan at T_max plus the ragged table (conv3x3_mfma.h: RaggedTab, 4 * B int32 words) behind it
+// Ragged batches.  CNN2D: the uniform plan at T_max plus the ragged table (conv3x3_mfma.h: RaggedTab, 4 * B int32 words) behind
+// it.  CNN1D: the table alone (2 * B words: lengths and dispatch order) -- its one kernel keeps every activation in LDS.
 size_t dfa_ragged_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T_max, int F, int precision) {
   if (B < 1 || T_max < 1 || F < 1) return 0;
   if (model == DFA_MODEL_CNN2D) return plan_cnn2d(B, T_max, F, precision, ctx ? ctx->time_split : -1).total + align_up((size_t)4 * B * 4, 256);
+  if (model == DFA_MODEL_CNN1D) return align_up((size_t)2 * B * 4, 256);
   return 0;
 }
 
@@ -515,48 +555,24 @@ int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
   if (embedding && ((uintptr_t)embedding & 15) != 0)
     return fail(ctx, DFA_E_BAD_SHAPE, "embedding must be 16-byte aligned (got %p)", (void*)embedding);
-  // the ragged table (conv3x3_mfma.h: RaggedTab) in the next pinned staging slot
+  // the ragged table (conv3x3_mfma.h: RaggedTab) through the next pinned staging slot
   const size_t words = (size_t)4 * B;
-  if (words > ctx->ragged_cap) {
-    for (auto& e : ctx->ragged_done)
-      if (e) DFA_HIP_CHECK(ctx, hipEventSynchronize(e));
-    if (ctx->ragged_host) DFA_HIP_CHECK(ctx, hipHostFree(ctx->ragged_host));
-    ctx->ragged_host = nullptr;
-    ctx->ragged_cap = 0;
-    const size_t cap = std::max(words, (size_t)4 * 256);
-    DFA_HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->ragged_host, dfa_ctx::kRaggedSlots * cap * sizeof(int32_t), hipHostMallocDefault));
-    ctx->ragged_cap = cap;
-  }
-  const int slot = ctx->ragged_slot;
-  ctx->ragged_slot = (slot + 1) % dfa_ctx::kRaggedSlots;
-  if (!ctx->ragged_done[slot]) DFA_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ragged_done[slot], hipEventDisableTiming));
-  else DFA_HIP_CHECK(ctx, hipEventSynchronize(ctx->ragged_done[slot]));   // its previous copy has been read
-  int32_t* tab = ctx->ragged_host + slot * ctx->ragged_cap;
   int nseg3 = 1;
-  for (int b = 0; b < B; ++b) {
-    const int h2 = lengths[b] / 4, niter3 = (h2 + 1) / 2, chunk = chunk3_for(niter3);
-    const float inv_h = 1.0f / (float)h2;
-    tab[b] = lengths[b];
-    memcpy(&tab[2 * B + b], &inv_h, 4);
-    tab[3 * B + b] = chunk;
-    nseg3 = std::max(nseg3, (niter3 + chunk - 1) / chunk);
-  }
-  // dispatch order: the kernels' XCD remap gives each of the 8 XCDs one contiguous range of workgroup slots, so the utterances,
-  // sorted longest first, are dealt round-robin over 8 contiguous groups (sorted rank k -> group k % 8, place k / 8 in it).
-  // Every XCD then gets about the same work, and inside its range the long utterances start first.
-  std::vector<int> sorted(B);
-  for (int b = 0; b < B; ++b) sorted[b] = b;
-  std::stable_sort(sorted.begin(), sorted.end(), [&](int i, int j) { return lengths[i] > lengths[j]; });
-  {
-    int group_start[9] = {0};
-    for (int g = 0; g < 8; ++g) group_start[g + 1] = group_start[g] + (B - g + 7) / 8;   // ranks k < B with k % 8 == g
-    for (int k = 0; k < B; ++k) tab[B + group_start[k % 8] + k / 8] = sorted[k];
-  }
   char* ws = (char*)workspace;
   const int* dtab = (const int*)(ws + tab_off);
   hipStream_t s = ctx->stream;
-  DFA_HIP_CHECK(ctx, hipMemcpyAsync(ws + tab_off, tab, words * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  DFA_HIP_CHECK(ctx, hipEventRecord(ctx->ragged_done[slot], s));
+  {
+    const int rc = stage_ragged_table(ctx, lengths, B, words, ws + tab_off, [&](int32_t* tab) {
+      for (int b = 0; b < B; ++b) {
+        const int h2 = lengths[b] / 4, niter3 = (h2 + 1) / 2, chunk = chunk3_for(niter3);
+        const float inv_h = 1.0f / (float)h2;
+        memcpy(&tab[2 * B + b], &inv_h, 4);
+        tab[3 * B + b] = chunk;
+        nseg3 = std::max(nseg3, (niter3 + chunk - 1) / chunk);
+      }
+    });
+    if (rc != DFA_OK) return rc;
+  }
   const RaggedTab rt{dtab, B};
   void* a2 = ws + pl.a2_off;
   float* emb = embedding ? embedding : (float*)(ws + pl.emb_off);
@@ -675,6 +691,70 @@ int dfa_cnn1d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   { ScopedSlot ts(ctx, 7);
     DFA_HIP_CHECK(ctx, launch_linear(pooled, m.p[18], m.p[19], logits, B, 128, s)); }
   return DFA_OK;
+}
+
+// Ragged CNN1D batch: ONE launch of cnn1d_ragged_x3_kernel (cnn1d_fused_x3.hip), workgroup i = utterance order[i] of the
+// table.  No activation ever leaves LDS, so the workspace is the table alone; an utterance longer than one LDS window is
+// walked in time segments inside its workgroup, so lengths[b] has no upper bound but T_max.
+int dfa_cnn1d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b, int64_t stride_t,
+                             int64_t stride_f, const int32_t* lengths, float* logits, void* workspace, size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_forward_ragged");
+  if (!ctx) return DFA_E_NULL_PTR;
+  Cnn1dState& m = ctx->cnn1d;
+  if (!m.prepared) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_prepare has not been called since the last set_params");
+  if (!x || !logits || !workspace || !lengths) return fail(ctx, DFA_E_NULL_PTR, "x, lengths, logits and workspace must be non-null");
+  if (x_dtype != DFA_DTYPE_F32) return fail(ctx, DFA_E_BAD_DTYPE, "cnn1d takes float32 input (got dtype %d)", x_dtype);
+  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
+  if (F != m.in_features)
+    return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d of the first Conv1d (src/model_cnn1d.py:17)", F, m.in_features);
+  if (T_max < 3) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: the ragged cnn1d kernel needs T >= 3", T_max);
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] < 3 || lengths[b] > T_max)
+      return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [3, T_max=%d]", b, (int)lengths[b], T_max);
+  // layout: the stored channel-major batch [B][F][T_pad] seen as [B, T_max, F] -- frames contiguous, 16-byte aligned rows
+  if (stride_t != 1)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward takes the channel-major storage only: stride_t=%lld, needs 1", (long long)stride_t);
+  if ((F & 3) != 0) return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs F %% 4 == 0 (got F=%d)", F);
+  if ((stride_f & 3) != 0 || stride_f < T_max)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs stride_f %% 4 == 0 and stride_f >= T_max=%d (got stride_f=%lld)", T_max,
+                (long long)stride_f);
+  if ((stride_b & 3) != 0 || stride_b < 0)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs a non-negative stride_b %% 4 == 0 (got stride_b=%lld)", (long long)stride_b);
+  if (((uintptr_t)x & 15) != 0) return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs x 16-byte aligned (got %p)", x);
+  if ((int64_t)F * stride_f >= ((int64_t)1 << 31))   // (the kernel addresses an utterance's elements with 32-bit offsets)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs F * stride_f < 2^31 (got %d * %lld)", F, (long long)stride_f);
+  if (ctx->cnn1d_fused != 1)   // the uniform forward would run other kernels: no bit-identity promise there
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs the default option cnn1d_fused=1 (got %d)", ctx->cnn1d_fused);
+  if (cnn1d_ragged_segments(3, F, nullptr, nullptr, nullptr, nullptr, 0) < 1)
+    return fail(ctx, DFA_E_UNSUPPORTED, "F=%d: the layer-1 weights leave no LDS for a time window", F);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward cannot be captured into a graph: its lengths are copied per call");
+  const size_t words = (size_t)2 * B, need = align_up(words * 4, 256);
+  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
+  {
+    const int rc = stage_ragged_table(ctx, lengths, B, words, workspace, [](int32_t*) {});
+    if (rc != DFA_OK) return rc;
+  }
+  ScopedSlot ts(ctx, 4);
+  DFA_HIP_CHECK(ctx, launch_cnn1d_ragged_x3((const float*)x, stride_b, stride_f, (const int*)workspace, m.wx[0], m.b[0], m.wx[1], m.b[1], m.wx[2],
+                                            m.b[2], m.p[18], m.p[19], logits, B, T_max, F, ctx->stream,
+                                            ctx->clock_probe ? ctx->clock_buf : nullptr));
+  return DFA_OK;
+}
+
+// the time segments the ragged cnn1d kernel walks for an utterance of T frames (a function of T and F only): window
+// [starts[i], starts[i] + lens[i]) and the layer-3 frames [owned_lo[i], owned_hi[i]) it adds to the mean; fills up to cap
+// entries of each non-null array and returns the number of segments (0: T < 3, or F leaves no LDS for a window)
+int dfa_cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap) {
+  return cnn1d_ragged_segments(T, F, starts, lens, owned_lo, owned_hi, cap);
+}
+// dynamic LDS of the ragged cnn1d launch for a batch padded to T_max (the layout of the largest window)
+size_t dfa_cnn1d_ragged_lds_bytes(int T_max, int F) {
+  if (T_max < 3 || cnn1d_ragged_segments(3, F, nullptr, nullptr, nullptr, nullptr, 0) < 1) return 0;
+  return cnn1d_ragged_lds_bytes(T_max, F);
 }
 
 /* ------------------------------------------------------------------------------------------------ CAE */

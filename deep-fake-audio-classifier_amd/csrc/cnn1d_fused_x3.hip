@@ -17,6 +17,9 @@
 // LDS: two fp32 slabs + two split images + layer-1 weights during layer 1 (156.5 KB at T = 321), then h1 and h2 over the same space.
 // Takes the reference's storage only (x[b][f][t] contiguous, 16-byte aligned, F % 4 == 0, 3 <= T <= 347 at F = 180: the LDS budget); anything else runs
 // cnn1d_fused.hip / the three-launch path (api.hip).
+// A variable-length batch padded to its longest utterance runs cnn1d_ragged_x3_kernel (dfa_cnn1d_forward_ragged): the same body
+// (cnn1d_x3_body.h) with the utterance's own length from a device table, rows read at the batch's pitch, and utterances longer
+// than one LDS window walked in time segments inside their workgroup.
 #include "dfa_internal.h"
 #include "conv3x3_mfma.h"
 #include "rng.h"
@@ -151,262 +154,77 @@ __device__ __forceinline__ void store_split(const f32x16_t& acc, const float* bi
   for (int g = 0; g < 4; ++g) store_split_g<COUT>(acc, bias, co0, img, t, T, h, g);
 }
 
-__global__ __launch_bounds__(512) void cnn1d_fused_x3_kernel(Cnn1dX3Args a) {
-  using namespace c1x;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int col = lane & 31, h = lane >> 5;
-  const int b = blockIdx.x;
-  const int T = a.T, NT = a.NT;
-  const int nslots = 32 * NT + 2;
-  float* const slab0 = (float*)smem;                      // two slabs of slab_floats floats: [4 pad][16 x T][4 pad]
-  char* const h1S = smem;                                 // region A again, after layer 1: [nslots][128 B]
-  char* const w1S = smem + a.offB;                        // region B: layer-1 A fragments [3][nks1][2][64] x 16 B ...
-  char* const h2S = smem + a.offH2;                       // h2 [nslots][256 B]: behind h1, over the (then dead) slab / weight regions
-  float* const red = (float*)(smem + a.offH2 + nslots * 256);
-  const bool stamp = a.stamps != nullptr && tid == 0 && b < 128;
-  if (stamp) { a.stamps[8 * b] = __builtin_amdgcn_s_memtime(); a.stamps[8 * b + 5] = __builtin_amdgcn_s_memrealtime(); }
-
-  // ------------------------------------------------------------------------------------------------ layer 1: F -> 32
-  // A slab (16 channels x T frames, fp32, contiguous) goes global -> registers -> LDS as it is (F buffers), is then SPLIT ONCE
-  // into a pixel image S[slot = frame + 1][hi: 16 ch bf16 | lo: 16 ch bf16] (64 bytes per frame, the chunk swizzle of the
-  // h1 / h2 images; halo slots and the slots beyond T stay zero), and the tiles read their three taps from that image as two
-  // ds_read_b128 each.  The first version split x[c][t-1..t+1] per lane and tap -- every element three times, plus six masks per
-  // tile -- and layer 1 was bound by that vector work (51 k of the kernel's 86 k cycles for 13.8 k cycles of matrix-pipe time).
-  // Pipeline per trip s (one barrier): compute slab s from S[s & 1] | split slab s + 1: F[(s+1) & 1] -> S[(s+1) & 1] | park slab
-  // s + 2 (registers) in F[s & 1] | request slab s + 4.
-  const int nks1 = a.nks1;
-  f32x16_t acc1[MAXT1];
-  {
-    const float4* xg = (const float4*)(a.x + (size_t)b * a.F * T);
-    const int SL = a.slab_floats;
-    char* const S0 = smem + a.offS;                          // two split images of nslots x 64 bytes
-    const int SB = nslots * 64;
-    constexpr int NLD = 3;                                   // 16 T / 4 float4 per slab <= 1536 = 3 x 512
-    float4 xrA[NLD], xrB[NLD];                                // even / odd slabs in flight
-    const int nreal = (a.F + 15) / 16;                        // slabs that exist (nks1 may be one more: a zero slab)
-    auto slab_n4 = [&](int s) { return max(0, min(16, a.F - 16 * s)) * T / 4; };
-    auto slab_load = [&](int s, float4 (&xr)[NLD]) {          // unconditional, clamped index (a conditional load is an exec branch
-      const int sc = min(s, nreal - 1), n4 = slab_n4(sc);    //  and hipcc's vmcnt bookkeeping across a branch is conservative)
-      const float4* src = xg + (size_t)4 * sc * T;
-#pragma unroll
-      for (int k = 0; k < NLD; ++k) xr[k] = src[min(k * NTH + tid, n4 - 1)];
-    };
-    auto slab_park = [&](int s, const float4 (&xr)[NLD]) {    // registers -> F[s & 1]; channels a short / padded slab lacks become zeros
-      float* dst = slab0 + (s & 1) * SL + 4;
-      const int n4 = slab_n4(s);
-#pragma unroll
-      for (int k = 0; k < NLD; ++k) {
-        const int i = k * NTH + tid;
-        const unsigned m = i < n4 ? 0xffffffffu : 0u;
-        const float4 v = xr[k];
-        if (i < 4 * T)
-          *(uint4*)(dst + 4 * i) = make_uint4(__float_as_uint(v.x) & m, __float_as_uint(v.y) & m, __float_as_uint(v.z) & m, __float_as_uint(v.w) & m);
-      }
-    };
-    auto slab_split = [&](int s) {                            // F[s & 1] -> S[s & 1]: item = (frame t, channel octet g), lanes run along t
-      const float* fb = slab0 + (s & 1) * SL + 4;
-      char* sb = S0 + (s & 1) * SB;
-      // 2 T <= 768 items: one per thread, the remaining 2 T - 512 go to the waves that own ONE frame tile (waves NT - 8 ...: the
-      // first NT - 8 waves carry two tiles per trip and would otherwise also carry two items -- every trip ends in a barrier)
-      const int t2 = tid - 64 * max(0, NT - NW);
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int it = pass == 0 ? tid : (t2 >= 0 ? NTH + t2 : 2 * T);
-        if (it < 2 * T) {
-          const int g = it >= T ? 1 : 0, t = it - g * T;
-          float v[8];
-#pragma unroll
-          for (int c = 0; c < 8; ++c) v[c] = fb[(8 * g + c) * T + t];
-          uint4 hi, lo;
-          split8(v, hi, lo);
-          const int slot = t + 1, sw = lds_swz<64>(slot);
-          *(uint4*)(sb + slot * 64 + ((g ^ sw) << 4)) = hi;
-          *(uint4*)(sb + slot * 64 + (((2 + g) ^ sw) << 4)) = lo;
-        }
-      }
-    };
-    slab_load(0, xrA);
-    slab_load(1, xrB);
-    // layer-1 A fragments -> LDS (contiguous copy); the never-written slots of both split images (0 and T + 1 ...) -> zero
-    {
-      const int n = 3 * nks1 * 2 * 64;
-      for (int i = tid; i < n; i += NTH) *(uint4*)(w1S + (size_t)i * 16) = a.w1[i];
-      const int nz = (nslots - T) * 4;                        // 16-byte chunks of the zero slots, per image
-      for (int i = tid; i < 2 * nz; i += NTH) {
-        const int img = i >= nz, q = i - img * nz, zs = q >> 2;
-        const int slot = zs == 0 ? 0 : T + zs;
-        *(uint4*)(S0 + img * SB + slot * 64 + (q & 3) * 16) = make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
-    slab_park(0, xrA);
-    slab_load(2, xrA);
-    __syncthreads();
-    slab_split(0);
-    slab_park(1, xrB);
-    slab_load(3, xrB);
-    __syncthreads();
-
-    const int nmine = (NT - wave + NW - 1) / NW;
-#pragma unroll
-    for (int j = 0; j < MAXT1; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc1[j][r] = 0.f;
-    auto trip = [&](int s, float4 (&xr)[NLD]) {               // xr: the register set of this trip's parity (holds slab s + 2)
-      const char* sb = S0 + (s & 1) * SB;
-      uint4 wh[3], wl[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        wh[k] = *(const uint4*)(w1S + ((size_t)((k * nks1 + s) * 2) * 64 + lane) * 16);
-        wl[k] = *(const uint4*)(w1S + ((size_t)((k * nks1 + s) * 2 + 1) * 64 + lane) * 16);
-      }
-      uint4 xh[MAXT1][3], xl[MAXT1][3];
-#pragma unroll
-      for (int j = 0; j < MAXT1; ++j)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int slot = min(TW * (wave + NW * j) + col + k, nslots - 1);      // (tiles this wave does not have: clamped, unused)
-          const int sw = lds_swz<64>(slot);
-          xh[j][k] = *(const uint4*)(sb + slot * 64 + ((h ^ sw) << 4));
-          xl[j][k] = *(const uint4*)(sb + slot * 64 + (((2 + h) ^ sw) << 4));
-        }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < MAXT1; ++j)
-        if (j < nmine) {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            acc1[j] = mma_bf16(wh[k], xh[j][k], acc1[j]);
-            acc1[j] = mma_bf16(wl[k], xh[j][k], acc1[j]);
-            acc1[j] = mma_bf16(wh[k], xl[j][k], acc1[j]);
-          }
-        }
-      __builtin_amdgcn_sched_barrier(0);
-      slab_split(s + 1);                                      // (past the last slab: a stale buffer into an image nobody reads)
-      slab_park(s + 2, xr);
-      slab_load(s + 4, xr);                                   // (clamped: past the end it re-reads the last slab, never parked as data)
-      __syncthreads();
-    };
-    for (int s = 0; s < nks1; s += 2) {                       // nks1 is even
-      trip(s, xrA);
-      trip(s + 1, xrB);
-    }
-  }
-  if (stamp) a.stamps[8 * b + 1] = __builtin_amdgcn_s_memtime();
-  // (the barrier that closed the loop: every wave is done with the slabs and the layer-1 weights)
-  {
-    // h1 halo: slot 0 (frame -1); frames >= T are written as zeros by the epilogue below, slot 32 NT + 1 here
-    if (tid < 16) *(uint4*)(h1S + (tid < 8 ? 0 : (nslots - 1) * 128) + (tid & 7) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    const int nmine = (NT - wave + NW - 1) / NW;
-#pragma unroll
-    for (int j = 0; j < MAXT1; ++j)
-      if (j < nmine) store_split<32>(acc1[j], a.b1, 0, h1S, TW * (wave + NW * j) + col, T, h);
-  }
-  // hi / lo weight fragments of layer 2 (this wave's 32 output channels): requested in front of the barrier
-  uint4 w2h[6], w2l[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    w2h[i] = a.w2[((size_t)((wave & 1) * 6 + i) * 2) * 64 + lane];
-    w2l[i] = a.w2[((size_t)((wave & 1) * 6 + i) * 2 + 1) * 64 + lane];
-  }
-  __syncthreads();
-
-  // ------------------------------------------------------------------------------------------------ layer 2: 32 -> 64
-  {
-    const int m = wave & 1, par = wave >> 1;                 // 32 of the 64 channels; tiles par, par + 4, par + 8
-    constexpr int ST = NW / 2;
-    if (tid < 32) *(uint4*)(h2S + (tid < 16 ? 0 : (nslots - 1) * 256) + (tid & 15) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    // tile i's bias + ReLU + split + store rides on tile i + 1's steps (one 4-channel group per step)
-    f32x16_t accA, accB;
-    int tile = par;
-    if (tile < NT) {
-      split_gemm<32>(w2h, w2l, h1S, TW * tile, col, h, accA, [](int) {});
-      for (tile += ST; tile + ST < NT; tile += 2 * ST) {
-        split_gemm<32>(w2h, w2l, h1S, TW * tile, col, h, accB,
-                       [&](int i) { if (i >= 1 && i < 5) store_split_g<64>(accA, a.b2, 32 * m, h2S, TW * (tile - ST) + col, T, h, i - 1); });
-        split_gemm<32>(w2h, w2l, h1S, TW * (tile + ST), col, h, accA,
-                       [&](int i) { if (i >= 1 && i < 5) store_split_g<64>(accB, a.b2, 32 * m, h2S, TW * tile + col, T, h, i - 1); });
-      }
-      if (tile < NT) {
-        split_gemm<32>(w2h, w2l, h1S, TW * tile, col, h, accB,
-                       [&](int i) { if (i >= 1 && i < 5) store_split_g<64>(accA, a.b2, 32 * m, h2S, TW * (tile - ST) + col, T, h, i - 1); });
-        store_split<64>(accB, a.b2, 32 * m, h2S, TW * tile + col, T, h);
-      } else {
-        store_split<64>(accA, a.b2, 32 * m, h2S, TW * (tile - ST) + col, T, h);
-      }
-    }
-  }
-  // layer 3's fragments (32 of the 128 channels per wave; two waves share a channel tile and split its frame tiles)
-  uint4 w3h[12], w3l[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    w3h[i] = a.w3[((size_t)((wave & 3) * 12 + i) * 2) * 64 + lane];
-    w3l[i] = a.w3[((size_t)((wave & 3) * 12 + i) * 2 + 1) * 64 + lane];
-  }
-  __syncthreads();
-  if (stamp) a.stamps[8 * b + 2] = __builtin_amdgcn_s_memtime();
-
-  // ------------------------------------------------------------------------------------------------ layer 3: 64 -> 128, frame mean, classifier
-  {
-    const int m = wave & 3, par = wave >> 2;                 // tiles par, par + 2, ...
-    float bias[16], sum[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      bias[r] = a.b3[32 * m + (r & 3) + 8 * (r >> 2) + 4 * h];
-      sum[r] = 0.f;
-    }
-    auto add_regs = [&](const f32x16_t& v, int tile, int r0) {       // two accumulator registers per step
-      const bool inside = TW * tile + col < T;
-#pragma unroll
-      for (int r = r0; r < r0 + 2; ++r) sum[r] += inside ? fmaxf(v[r] + bias[r], 0.f) : 0.f;
-    };
-    f32x16_t accA, accB;
-    int tile = par;
-    if (tile < NT) {
-      split_gemm<64>(w3h, w3l, h2S, TW * tile, col, h, accA, [](int) {});
-      for (tile += 2; tile + 2 < NT; tile += 4) {
-        split_gemm<64>(w3h, w3l, h2S, TW * tile, col, h, accB, [&](int i) { if (i >= 2 && i < 10) add_regs(accA, tile - 2, 2 * (i - 2)); });
-        split_gemm<64>(w3h, w3l, h2S, TW * (tile + 2), col, h, accA, [&](int i) { if (i >= 2 && i < 10) add_regs(accB, tile, 2 * (i - 2)); });
-      }
-      if (tile < NT) {
-        split_gemm<64>(w3h, w3l, h2S, TW * tile, col, h, accB, [&](int i) { if (i >= 2 && i < 10) add_regs(accA, tile - 2, 2 * (i - 2)); });
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) add_regs(accB, tile, r);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) add_regs(accA, tile - 2, r);
-      }
-    }
-    float part = 0.f;
-    const float inv_t = 1.0f / (float)T;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float s = sum[r];
-#pragma unroll
-      for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      part = fmaf(s * inv_t, a.cw[32 * m + (r & 3) + 8 * (r >> 2) + 4 * h], part);
-    }
-    part += __shfl_xor(part, 32, 64);
-    if (lane == 0) red[wave] = part;
-  }
-  __syncthreads();
-  if (stamp) { a.stamps[8 * b + 3] = __builtin_amdgcn_s_memtime(); a.stamps[8 * b + 6] = __builtin_amdgcn_s_memrealtime(); }
-  if (tid == 0) a.logits[b] = (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) + a.cb[0];
-}
-
-static void cnn1d_x3_layout(int T, int F, int* offB, int* total, int* slab_floats, int* offS = nullptr, int* offH2 = nullptr) {
-  const int NT = (T + 31) / 32, nslots = 32 * NT + 2, nks1 = cnn1d_x3_nks(F);
-  const int SL = 16 * T + 8;
+// LDS layout of one utterance (uniform kernel) or one time window (ragged kernel) of T frames.  ragged: a slab's rows sit at a
+// pitch of T rounded up to 4 floats (rows of the padded batch are loaded 16 bytes at a time), otherwise at T (contiguous slab).
+// Host and device: the ragged kernel asks it per segment, its launch for the largest window.
+__host__ __device__ inline int cnn1d_x3_nks_hd(int cin) { const int n = (cin + 15) / 16; return (cin == 32 || cin == 64) ? n : (n + 1) & ~1; }
+__host__ __device__ inline void cnn1d_x3_layout(int T, int F, int ragged, int* offB, int* total, int* slab_floats, int* offS = nullptr,
+                                                int* offH2 = nullptr) {
+  const int NT = (T + 31) / 32, nslots = 32 * NT + 2, nks1 = cnn1d_x3_nks_hd(F);
+  const int SL = 16 * (ragged ? (T + 3) & ~3 : T) + 8;
   const int oS = (2 * SL * 4 + 255) / 256 * 256;                       // two fp32 slabs
   const int oB = (oS + 2 * nslots * 64 + 255) / 256 * 256;             // two split images
   const int oH2 = (nslots * 128 + 255) / 256 * 256;                    // h1, then h2
+  const int l1 = oB + 3 * nks1 * 2 * 64 * 16, l23 = oH2 + nslots * 256 + 64;
   *offB = oB;
-  *total = std::max(oB + 3 * nks1 * 2 * 64 * 16, oH2 + nslots * 256 + 64);
+  *total = l1 > l23 ? l1 : l23;
   *slab_floats = SL;
   if (offS) *offS = oS;
   if (offH2) *offH2 = oH2;
 }
+
+// ---- the segment plan of the ragged kernel: a function of the utterance's length T, the feature count F (through wcap and
+// seg_step) and nothing else, so an utterance's logit does not depend on its batch.
+//   wcap     = the longest window whose layout fits the 160 KiB of a workgroup (cnn1d_ragged_wcap);
+//   seg_step = the frames a segment owns when T > wcap: the largest multiple of 4 with seg_step + 7 <= wcap.
+// T <= wcap: one segment, window = owned = [0, T) -- the uniform kernel's work.  Otherwise segment i owns
+// [i seg_step, min(T, (i + 1) seg_step)) and its window runs from 4 frames before (a multiple of 4: the 16-byte row loads stay
+// aligned; layer 3 needs 3) to 3 frames behind the owned range, both clipped to [0, T).
+__host__ __device__ inline int cnn1d_ragged_nseg(int T, int seg_step, int wcap) { return T <= wcap ? 1 : (T + seg_step - 1) / seg_step; }
+// -> window start w0 and length W in the utterance, owned frames [olo, ohi) in WINDOW coordinates
+__host__ __device__ inline void cnn1d_ragged_segment(int T, int seg_step, int wcap, int seg, int* w0, int* W, int* olo, int* ohi) {
+  if (T <= wcap) { *w0 = 0; *W = T; *olo = 0; *ohi = T; return; }
+  const int lo = seg * seg_step, hi = lo + seg_step < T ? lo + seg_step : T;
+  const int ws = lo >= 4 ? lo - 4 : 0, we = hi + 3 < T ? hi + 3 : T;
+  *w0 = ws; *W = we - ws; *olo = lo - ws; *ohi = hi - ws;
+}
+int cnn1d_ragged_wcap(int F) {
+  int w = 0;
+  for (int T = 3; T <= 384 && (T + 31) / 32 <= c1x::NW * c1x::MAXT1; ++T) {   // (a slab's 16 rows of ceil(T / 4) float4 fit the 3 x 512 loads of a trip)
+    int offB, total, sl;
+    cnn1d_x3_layout(T, F, 1, &offB, &total, &sl);
+    if (total <= 160 * 1024) w = T;      // (the layout grows with T)
+  }
+  return w;
+}
+int cnn1d_ragged_seg_step(int F) { return (cnn1d_ragged_wcap(F) - 7) & ~3; }
+
+// what the ragged form takes beside Cnn1dX3Args (whose x is then the padded batch and whose T / NT / LDS offsets are unused)
+struct Cnn1dRaggedArgs {
+  RaggedTab rt;                // [0, B): lengths, [B, 2B): dispatch order (conv3x3_mfma.h)
+  long long stride_b;          // floats between utterances (a multiple of 4)
+  int stride_f;                // floats between the rows of an utterance (a multiple of 4, >= T_max)
+  int seg_step, wcap;          // the segment plan's two constants (functions of F)
+};
+
+#define DFA_KERNEL_BODY_SCOPE   // the kernel bodies below include cnn1d_x3_body.h
+__global__ __launch_bounds__(512) void cnn1d_fused_x3_kernel(Cnn1dX3Args a) {
+#define C1X_RAGGED 0
+#include "cnn1d_x3_body.h"
+#undef C1X_RAGGED
+}
+
+// Variable-length batch (dfa_cnn1d_forward_ragged): workgroup i scores utterance order[i] of the ragged table, of its own
+// length T_b, from rows at the pitch of the batch padded to T_max.  The arithmetic is the uniform kernel's; an utterance that
+// fits one window takes exactly its path, a longer one is walked in segments (cnn1d_x3_body.h).
+__global__ __launch_bounds__(512) void cnn1d_ragged_x3_kernel(Cnn1dX3Args a, Cnn1dRaggedArgs rg) {
+#define C1X_RAGGED 1
+#include "cnn1d_x3_body.h"
+#undef C1X_RAGGED
+}
+#undef DFA_KERNEL_BODY_SCOPE
+
+
 // x must be the contiguous [B][F][T] storage (element (b, t, f) at b F T + f T + t), 16-byte aligned
 // ---- one Conv1d(k = 3, pad 1) layer of the TRAINING step on the matrix cores (src/train.py:71-76 through
 // src/model_cnn1d.py:17-34): z[b][co][t] = bias[co] + sum_{ci, k} W[co][ci][k] in[b][ci][t + k - 1], channel-major fp32 in and
@@ -741,7 +559,7 @@ bool cnn1d_fused_x3_supports(const void* x, int64_t sb, int64_t st, int64_t sf, 
   if (T < 3 || T > 384 || (T + 31) / 32 > c1x::NW * c1x::MAXT1 || F < 1 || (F & 3)) return false;
   if (st != 1 || sf != T || sb != (int64_t)F * T || ((uintptr_t)x & 15)) return false;
   int offB, total, sl;
-  cnn1d_x3_layout(T, F, &offB, &total, &sl);
+  cnn1d_x3_layout(T, F, 0, &offB, &total, &sl);
   return total <= 160 * 1024;
 }
 
@@ -752,10 +570,49 @@ hipError_t launch_cnn1d_fused_x3(const float* x, const void* w1, const float* b1
   a.x = x; a.w1 = (const uint4*)w1; a.w2 = (const uint4*)w2; a.w3 = (const uint4*)w3; a.b1 = b1; a.b2 = b2; a.b3 = b3; a.cw = cw; a.cb = cb;
   a.logits = logits; a.T = T; a.F = F; a.NT = (T + 31) / 32; a.nks1 = cnn1d_x3_nks(F); a.stamps = stamps;
   int total;
-  cnn1d_x3_layout(T, F, &a.offB, &total, &a.slab_floats, &a.offS, &a.offH2);
+  cnn1d_x3_layout(T, F, 0, &a.offB, &total, &a.slab_floats, &a.offS, &a.offH2);
   hipError_t e = hipFuncSetAttribute((const void*)cnn1d_fused_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(cnn1d_fused_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a);
+  return hipGetLastError();
+}
+
+// ---- ragged launch: x = the padded batch (element (b, f, t) at b stride_b + f stride_f + t), tab = the device table
+size_t cnn1d_ragged_lds_bytes(int T_max, int F) {
+  int offB, total, sl;
+  cnn1d_x3_layout(std::min(T_max, cnn1d_ragged_wcap(F)), F, 1, &offB, &total, &sl);
+  return (size_t)total;
+}
+// the plan as the kernel walks it (tests, tools): fills up to cap entries, returns the number of segments
+int cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap) {
+  const int wcap = cnn1d_ragged_wcap(F), step = cnn1d_ragged_seg_step(F);
+  if (T < 3 || wcap < 11 || step < 4) return 0;
+  const int n = cnn1d_ragged_nseg(T, step, wcap);
+  for (int i = 0; i < n && i < cap; ++i) {
+    int w0, W, lo, hi;
+    cnn1d_ragged_segment(T, step, wcap, i, &w0, &W, &lo, &hi);
+    if (starts) starts[i] = w0;
+    if (lens) lens[i] = W;
+    if (owned_lo) owned_lo[i] = w0 + lo;
+    if (owned_hi) owned_hi[i] = w0 + hi;
+  }
+  return n;
+}
+hipError_t launch_cnn1d_ragged_x3(const float* x, int64_t stride_b, int64_t stride_f, const int* tab, const void* w1, const float* b1,
+                                  const void* w2, const float* b2, const void* w3, const float* b3, const float* cw, const float* cb,
+                                  float* logits, int B, int T_max, int F, hipStream_t s, long long* stamps) {
+  Cnn1dX3Args a{};
+  a.x = x; a.w1 = (const uint4*)w1; a.w2 = (const uint4*)w2; a.w3 = (const uint4*)w3; a.b1 = b1; a.b2 = b2; a.b3 = b3; a.cw = cw; a.cb = cb;
+  a.logits = logits; a.F = F; a.nks1 = cnn1d_x3_nks(F); a.stamps = stamps;
+  Cnn1dRaggedArgs rg{};
+  rg.rt = RaggedTab{tab, B};
+  rg.stride_b = stride_b; rg.stride_f = (int)stride_f;
+  rg.wcap = cnn1d_ragged_wcap(F); rg.seg_step = cnn1d_ragged_seg_step(F);
+  if (rg.wcap < 11 || rg.seg_step < 4) return hipErrorInvalidValue;
+  const size_t total = cnn1d_ragged_lds_bytes(T_max, F);
+  hipError_t e = hipFuncSetAttribute((const void*)cnn1d_ragged_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(cnn1d_ragged_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a, rg);
   return hipGetLastError();
 }
 

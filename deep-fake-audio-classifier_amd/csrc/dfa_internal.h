@@ -263,6 +263,13 @@ int cnn1d_x3_nks(int cin);
 size_t cnn1d_x3_pack_bytes(int cin, int cout);
 hipError_t launch_pack_cnn1d_x3(const float* wf, void* wx, int cin, int cout, hipStream_t s);
 bool cnn1d_fused_x3_supports(const void* x, int64_t sb, int64_t st, int64_t sf, int T, int F);
+// ragged form (cnn1d_ragged_x3_kernel): x = the batch padded to T_max, element (b, f, t) at b stride_b + f stride_f + t;
+// tab = device table, [0, B) lengths, [B, 2B) dispatch order
+hipError_t launch_cnn1d_ragged_x3(const float* x, int64_t stride_b, int64_t stride_f, const int* tab, const void* w1, const float* b1,
+                                  const void* w2, const float* b2, const void* w3, const float* b3, const float* cw, const float* cb,
+                                  float* logits, int B, int T_max, int F, hipStream_t s, long long* stamps);
+size_t cnn1d_ragged_lds_bytes(int T_max, int F);
+int cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap);
 hipError_t launch_cnn1d_fused_x3(const float* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
                                  const float* b3, const float* cw, const float* cb, float* logits, int B, int T, int F, hipStream_t s,
                                  long long* stamps = nullptr);

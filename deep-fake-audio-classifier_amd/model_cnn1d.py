@@ -57,12 +57,21 @@ class CNN1D(nn.Module):
         _lib.check(ctx.handle, ctx.lib.dfa_cnn1d_prepare(ctx.handle))
         self._prepared = sig
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """lengths: None (every utterance spans all T frames: the reference's call), or the per-utterance frame counts of a
+        ragged batch padded to T (a list, numpy array or int tensor, each in [3, T]): utterance b is scored from
+        x[b, :lengths[b]] alone, in one kernel launch for the whole batch, whatever its length; its padding is never used.
+        Eval mode only."""
         if x.dim() != 3:
             raise ValueError(f"CNN1D expects x of shape (B, T, F), got {tuple(x.shape)}")
         if self.training:
+            if lengths is not None:
+                raise NotImplementedError("ragged batches (lengths=...) are eval-only: batch-norm statistics over a "
+                                          "variable-length batch have no reference definition")
             from .training import cnn1d_train_forward
             return cnn1d_train_forward(self, x)
+        if lengths is not None:
+            return self._ragged_forward(x, _lib.host_lengths(lengths, x.shape[0], x.shape[1], 3))
         if x.device.type != "cuda":
             raise RuntimeError("dfa_amd.CNN1D runs on the GPU only: move the input with .to('cuda')")
         if x.dtype != torch.float32:
@@ -78,6 +87,35 @@ class CNN1D(nn.Module):
             sb, st, sf = x.stride()
             code = ctx.lib.dfa_cnn1d_forward(ctx.handle, C.c_void_p(x.data_ptr()), _lib.DTYPE_F32, B, T, F, sb, st, sf,
                                              C.c_void_p(logits.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel())
+            _lib.check(ctx.handle, code)
+        return logits
+
+    def _ragged_forward(self, x, lengths):
+        """x: float32 [B, T, F] on the GPU.  The kernel reads the stored channel-major layout -- the transposed view of a
+        [B, F, T_pad] batch with T_pad % 4 == 0, what dataloaders.RaggedBatcher yields -- in place.  A tensor in any other
+        layout (a contiguous [B, T, F], a pitch that is not a multiple of 4, a misaligned base) is first copied into such a
+        zero-padded channel-major batch on the GPU; the result is the same."""
+        if x.device.type != "cuda":
+            raise RuntimeError("dfa_amd.CNN1D runs on the GPU only: move the input with .to('cuda')")
+        if x.dtype != torch.float32:
+            raise ValueError(f"CNN1D takes float32 input, got {x.dtype}")
+        B, T, F = x.shape
+        sb, st, sf = x.stride()
+        if B and not (st == 1 and sf % 4 == 0 and sf >= T and sb % 4 == 0 and sb >= 0 and x.data_ptr() % 16 == 0):
+            stored = torch.zeros((B, F, -(-T // 4) * 4), dtype=torch.float32, device=x.device)
+            stored[:, :, :T] = x.transpose(1, 2)
+            x = stored.transpose(1, 2)[:, :T]
+            sb, st, sf = x.stride()
+        ctx = _lib.Context.get(x.device)
+        with torch.cuda.device(ctx.index):
+            ctx.use_current_stream()
+            self._ensure_prepared(ctx)
+            nbytes = ctx.lib.dfa_ragged_workspace_bytes(ctx.handle, _lib.MODEL_CNN1D, B, T, F, _lib.PREC_F32)
+            ws = ctx.workspace(nbytes)
+            logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
+            code = ctx.lib.dfa_cnn1d_forward_ragged(
+                ctx.handle, C.c_void_p(x.data_ptr()), _lib.DTYPE_F32, B, T, F, sb, st, sf,
+                C.c_void_p(lengths.ctypes.data), C.c_void_p(logits.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel())
             _lib.check(ctx.handle, code)
         return logits
 

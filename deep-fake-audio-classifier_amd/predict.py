@@ -47,6 +47,44 @@ def predict_scores(model, features: torch.Tensor, batch_size: int = 32, device="
     return torch.cat(outs) if outs else torch.empty(0, device=device)
 
 
+def check_ragged_args(model: str, precision: str, swap_tf: bool = True) -> None:
+    """Can a features.pkl whose utterances differ in length be scored with these arguments?  Raises ValueError when not:
+    cnn1d scores ragged files as it is; cnn2d has ragged kernels for --precision bf16 only; and the stored [F, T_i] layout
+    is the only ragged layout, so --no-swap-tf is refused.  Pure: touches neither the GPU nor the file."""
+    if not swap_tf:
+        raise ValueError("features.pkl holds utterances of unequal lengths: --no-swap-tf is not supported for such a file "
+                         "(the stored [F, T] layout is the only ragged layout)")
+    if model == "cnn2d" and precision != "bf16":
+        raise ValueError(f"features.pkl holds utterances of unequal lengths: --model cnn2d scores such a file with "
+                         f"--precision bf16 only (got --precision {precision}); --model cnn1d takes any length")
+    if model not in ("cnn2d", "cnn1d"):
+        raise ValueError(f"unknown model {model!r} (choices: cnn2d, cnn1d)")
+
+
+@torch.no_grad()
+def predict_scores_ragged(model, feature_list, batch_size: int = 32, device="cuda", apply_sigmoid: bool = True,
+                          input_dtype=None, rank: int = 0, world: int = 1, return_embedding: bool = False):
+    """Scores for a list of per-utterance [F, T_i] tensors of unequal lengths, in input order, as one GPU tensor: batches
+    padded to their longest utterance (dataloaders.RaggedBatcher, longest first) through `model(x, lengths=...)`.
+    return_embedding (cnn2d): also the [N, 128*F] embeddings, as a host tensor."""
+    from .dataloaders import RaggedBatcher
+    model.eval()
+    batcher = RaggedBatcher(feature_list, None, batch_size, device=device, rank=rank, world=world, dtype=input_dtype)
+    outs, embs = [], []
+    for x, _, lengths in batcher:
+        if return_embedding:
+            logits, e = model(x, return_embedding=True, lengths=lengths)
+            embs.append(e.cpu())
+        else:
+            logits = model(x, lengths=lengths)
+        logits = logits.squeeze(-1)
+        outs.append(torch.sigmoid(logits) if apply_sigmoid else logits)
+    scores = batcher.restore(outs) if outs else torch.empty(0, device=device)
+    if return_embedding:
+        return scores, (batcher.restore(embs) if embs else torch.empty(0, 0))
+    return scores
+
+
 @torch.no_grad()
 def extract_embeddings(model, features: torch.Tensor, batch_size: int = 256, device="cuda", swap_tf: bool = True,
                        rank: int = 0, world: int = 1, input_dtype=None):
@@ -146,12 +184,28 @@ def main(argv=None):
     args = parse_args(argv)
     device = args.device or "cuda"
     apply_sigmoid = False if args.no_apply_sigmoid else args.apply_sigmoid
-    model = build_model(args.model, args.in_features, args.dropout, args.precision).to(device)
-    load_weights(model, args.checkpoint, device)
-    model.eval()
     features_df = pd.read_pickle(args.features)
     if "uttid" not in features_df.columns:
         raise ValueError("features.pkl must contain 'uttid'")
+    ragged = len({tuple(f.shape) for f in features_df["features"]}) > 1      # utterances of unequal lengths
+    if ragged:
+        check_ragged_args(args.model, args.precision, args.swap_tf)
+    model = build_model(args.model, args.in_features, args.dropout, args.precision).to(device)
+    load_weights(model, args.checkpoint, device)
+    model.eval()
+    if ragged:
+        feature_list = [f.float() for f in features_df["features"]]
+        scores = predict_scores_ragged(model, feature_list, batch_size=args.batch_size, device=device,
+                                       apply_sigmoid=apply_sigmoid)
+        write_predictions(features_df["uttid"].values, scores.cpu().tolist(), args.out)
+        if args.embeddings_out:
+            if args.model != "cnn2d":
+                raise ValueError("extract_embeddings needs the CNN2D model (the 1D CNN has no [128*F] embedding)")
+            logits, emb = predict_scores_ragged(model, feature_list, batch_size=max(args.batch_size, 256), device=device,
+                                                apply_sigmoid=False, return_embedding=True)
+            torch.save({"uttid": list(features_df["uttid"].values), "embeddings": emb, "logits": logits.cpu()},
+                       args.embeddings_out)
+        return
     feats = torch.stack([f.float() for f in features_df["features"]]) if len(features_df) else torch.empty(0, 180, 321)
     scores = predict_scores(model, feats, batch_size=args.batch_size, device=device, apply_sigmoid=apply_sigmoid,
                             swap_tf=args.swap_tf)

@@ -168,6 +168,31 @@ int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
                              int64_t stride_t, int64_t stride_f, const int32_t* lengths, float* logits,
                              float* embedding, void* workspace, size_t workspace_bytes);
 
+/* eval-mode CNN1D forward of a variable-length (ragged) batch in ONE kernel launch: utterance b is x[b, :lengths[b], :].
+ *   x: float32, the padded batch in the stored channel-major layout -- [B][F][T_pad] storage seen as [B, T_max, F]:
+ *      stride_t == 1, stride_f % 4 == 0, stride_f >= T_max, stride_b % 4 == 0, base 16-byte aligned, F % 4 == 0
+ *      (what dataloaders.RaggedBatcher yields); any other layout or a bf16 x returns DFA_E_UNSUPPORTED / DFA_E_BAD_DTYPE.
+ *      Of row f of utterance b only the floats [0, 4 * ceil(lengths[b] / 4)) are read, and those at t >= lengths[b] are
+ *      masked before use: padding may be uninitialised, NaN or Inf;
+ *   lengths: HOST int32[B], 3 <= lengths[b] <= T_max (else DFA_E_BAD_SHAPE naming the index), no other upper bound:
+ *      an utterance longer than one LDS window (348 frames at F = 180) is walked in time segments by its workgroup;
+ *   logits: device float[B];
+ *   workspace: device, 256-byte aligned, >= dfa_ragged_workspace_bytes(ctx, DFA_MODEL_CNN1D, B, T_max, F, DFA_PREC_F32)
+ *      bytes: the per-call table only, no activation leaves the chip.
+ * The arithmetic is that of the split-bf16 kernel of dfa_cnn1d_forward (fp32-grade, 1e-4 of the fp32 reference).  An
+ * utterance that fits one window gets, bit for bit, the logit dfa_cnn1d_forward gives its own contiguous [F][T_b] tensor;
+ * for every length the logit depends on the utterance alone, not on its batch, its position in it or T_max.
+ * Option cnn1d_fused != 1 or a capturing stream returns DFA_E_UNSUPPORTED (the lengths are copied per call). */
+int dfa_cnn1d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,
+                             int64_t stride_t, int64_t stride_f, const int32_t* lengths, float* logits,
+                             void* workspace, size_t workspace_bytes);
+/* the time segments dfa_cnn1d_forward_ragged walks for an utterance of T frames, a function of T and F only: segment i loads
+ * the window [starts[i], starts[i] + lens[i]) and adds the layer-3 frames [owned_lo[i], owned_hi[i]) to the frame mean.
+ * Fills up to cap entries of each non-NULL array; returns the number of segments (0 when T < 3). */
+int dfa_cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap);
+/* dynamic LDS bytes of the ragged CNN1D launch for a batch padded to T_max (<= 160 KiB) */
+size_t dfa_cnn1d_ragged_lds_bytes(int T_max, int F);
+
 /* ---- CNN2D training step (replaces, for src/train.py:71-76, torch autograd over src/model.py:13-39) ------------ */
 size_t dfa_cnn2d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, int precision);
 /* train-mode forward: BatchNorm uses batch statistics (and updates running_mean/var in place through the pointers
@@ -307,7 +332,8 @@ int dfa_mse_fwd_bwd(dfa_ctx* ctx, const float* recon, const void* x, int x_dtype
 
 /* ---- shared ------------------------------------------------------------------------------------ */
 size_t dfa_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T, int F, int precision);
-/* workspace of dfa_cnn2d_forward_ragged for B utterances padded to T_max frames (0 for a model without a ragged forward) */
+/* workspace of dfa_cnn2d_forward_ragged / dfa_cnn1d_forward_ragged for B utterances padded to T_max frames (0 for a model
+ * without a ragged forward) */
 size_t dfa_ragged_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T_max, int F, int precision);
 /* names of the device kernels a forward launches, for profile post-processing ("" when unknown) */
 const char* dfa_dominant_kernel(int model, int precision);

@@ -1,10 +1,13 @@
-"""Ragged CNN2D throughput (bf16): in one process, alternating timed legs of
+"""Ragged throughput of CNN2D (bf16, the default) or CNN1D (--model cnn1d, fp32 features): in one process, alternating timed legs of
   ragged   B=256, F=180, lengths drawn with a fixed seed uniformly from [161, 481] (mean 321),
   uniform  [256, 321, 180],
   ragged32 the first 32 of those lengths (the reference's predict batch size),
-  loop     the same 32 utterances one call at a time (what a user runs without lengths=).
-Prints one JSON line: per leg the median utt/s and frames/s over the pairs, with min and max.
-usage: timeout -k 10 300 python tools/gpu_ragged_bench.py [--pairs 5] [--iters 20]"""
+  loop     the same 32 utterances one call at a time (what a user runs without lengths=; for cnn1d each utterance is its own
+           contiguous [F, T_i] tensor, copied outside the timed region, so the uniform split-bf16 kernel takes those it can).
+Prints one JSON line: per leg the median utt/s and frames/s over the pairs, with min and max, and per pair ragged32 / loop.
+--stamps (cnn1d): one extra ragged call with the kernel's clock stamps on, reporting the share of the stamped workgroups'
+time spent in multi-segment utterances.
+usage: timeout -k 10 300 python tools/gpu_ragged_bench.py [--model cnn2d|cnn1d] [--pairs 5] [--iters 20] [--stamps]"""
 import argparse
 import json
 import os
@@ -22,21 +25,33 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--model", default="cnn2d", choices=["cnn2d", "cnn1d"])
+    ap.add_argument("--stamps", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
-    model = CNN2D(precision="bf16").to("cuda").eval()
     lengths = np.random.default_rng(321).integers(161, 482, size=256)
     T_max = int(lengths.max())
     gen = torch.Generator().manual_seed(1)
-    xr = (torch.randn(256, 180, T_max, generator=gen) * 3.2).to(torch.bfloat16).to("cuda").transpose(1, 2)
-    xu = (torch.randn(256, 180, 321, generator=gen) * 3.2).to(torch.bfloat16).to("cuda").transpose(1, 2)
     l32 = lengths[:32]
+    if args.model == "cnn1d":
+        from dfa_amd.model_cnn1d import CNN1D
+        model = CNN1D().to("cuda").eval()
+        T_pad = -(-T_max // 4) * 4                       # 16-byte rows, as dataloaders.RaggedBatcher pads
+        xr = (torch.randn(256, 180, T_pad, generator=gen) * 3.2).to("cuda").transpose(1, 2)[:, :T_max]
+        xu = (torch.randn(256, 180, 321, generator=gen) * 3.2).to("cuda").transpose(1, 2)
+        own = [xr[i, :int(T)].t().contiguous()[None].transpose(1, 2) for i, T in enumerate(l32)]
+        loop = lambda: [model(u) for u in own]           # noqa: E731
+    else:
+        model = CNN2D(precision="bf16").to("cuda").eval()
+        xr = (torch.randn(256, 180, T_max, generator=gen) * 3.2).to(torch.bfloat16).to("cuda").transpose(1, 2)
+        xu = (torch.randn(256, 180, 321, generator=gen) * 3.2).to(torch.bfloat16).to("cuda").transpose(1, 2)
+        loop = lambda: [model(xr[i:i + 1, :int(T)]) for i, T in enumerate(l32)]      # noqa: E731
     x32 = xr[:32, :int(l32.max())]
     legs = {
         "ragged": (lambda: model(xr, lengths=lengths), 256, int(lengths.sum())),
         "uniform": (lambda: model(xu), 256, 256 * 321),
         "ragged32": (lambda: model(x32, lengths=l32), 32, int(l32.sum())),
-        "loop": (lambda: [model(xr[i:i + 1, :int(T)]) for i, T in enumerate(l32)], 32, int(l32.sum())),
+        "loop": (loop, 32, int(l32.sum())),
     }
     res = {k: [] for k in legs}
     for _ in range(2):                                   # warm-up: preparation, workspace, clocks
@@ -53,7 +68,7 @@ def main():
             t1.synchronize()
             s = t0.elapsed_time(t1) / 1e3 / args.iters
             res[name].append((n_utt / s, n_frames / s))
-    out = {"precision": "bf16", "pairs": args.pairs, "iters": args.iters, "mean_length": float(lengths.mean())}
+    out = {"model": args.model, "precision": "bf16" if args.model == "cnn2d" else "fp32 (split bf16)", "pairs": args.pairs, "iters": args.iters, "mean_length": float(lengths.mean())}
     for name, v in res.items():
         u = np.array([a for a, _ in v]); f = np.array([b for _, b in v])
         out[name] = {"utt_per_s": float(np.median(u)), "utt_min": float(u.min()), "utt_max": float(u.max()),
@@ -61,6 +76,29 @@ def main():
     out["ragged_over_uniform_utt"] = out["ragged"]["utt_per_s"] / out["uniform"]["utt_per_s"]
     out["ragged_over_uniform_frames"] = out["ragged"]["frames_per_s"] / out["uniform"]["frames_per_s"]
     out["ragged32_over_loop"] = out["ragged32"]["utt_per_s"] / out["loop"]["utt_per_s"]
+    out["ragged32_over_loop_pairs"] = [a[0] / b[0] for a, b in zip(res["ragged32"], res["loop"])]
+    if args.stamps and args.model == "cnn1d":
+        # stamps of the (up to 128) first utterances: [8b] start, [8b + 3] end (s_memtime), [8b + 5] / [8b + 6] the same in
+        # s_memrealtime, [8b + 4] length, [8b + 7] segments
+        import ctypes as C
+        from dfa_amd import _lib
+        ctx = _lib.Context.get(torch.device("cuda"))
+        ctx.set_option("clock_probe", 1)
+        model(xr, lengths=lengths)
+        torch.cuda.synchronize()
+        buf = (C.c_longlong * 1024)()
+        _lib.check(ctx.handle, ctx.lib.dfa_ctx_debug_read(ctx.handle, buf, 1024))
+        ctx.set_option("clock_probe", 0)
+        st = np.array(buf[:], dtype=np.int64).reshape(128, 8)
+        dur, nseg = (st[:, 3] - st[:, 0]).astype(np.float64), st[:, 7]
+        ok = (st[:, 4] == lengths[:128]) & (dur > 0)
+        real = (st[:, 6] - st[:, 5]).astype(np.float64) / 100.0          # s_memrealtime ticks at 100 MHz -> microseconds
+        out["stamps"] = {"workgroups": int(ok.sum()), "longest_workgroup_us": float(real[ok].max()),
+                         "median_workgroup_us": float(np.median(real[ok])),
+                         "span_first_start_to_last_end_us": float((st[ok, 6].max() - st[ok, 5].min()) / 100.0), "multi_segment_workgroups": int((ok & (nseg > 1)).sum()),
+                         "multi_segment_time_share": float(dur[ok & (nseg > 1)].sum() / max(dur[ok].sum(), 1.0)),
+                         "cycles_per_frame_one_segment": float((dur / np.maximum(st[:, 4], 1))[ok & (nseg == 1)].mean()) if (ok & (nseg == 1)).any() else None,
+                         "cycles_per_frame_multi_segment": float((dur / np.maximum(st[:, 4], 1))[ok & (nseg > 1)].mean()) if (ok & (nseg > 1)).any() else None}
     print(json.dumps(out))
 
 
