@@ -900,4 +900,84 @@ int dfa_cae_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int 
   return DFA_OK;
 }
 
+// Ragged auto-encoder scoring.  Workspace: the uniform plan at T_max with the table (4 * B words) behind it.  Table words
+// [0, B) lengths, [B, 2B) dispatch order, [2B, 3B) 1 / (T_b F) as float bits, [3B, 4B) the utterance's decoder tile count.
+// A planner of its own: dfa_ragged_workspace_bytes(DFA_MODEL_CAE) keeps its historical 0 (include/dfa_hip.h).
+size_t dfa_cae_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F, int precision) {
+  (void)ctx;
+  if (B < 1 || T_max < 1 || F < 1) return 0;
+  return plan_cae(B, T_max, F, precision).total + align_up((size_t)4 * B * 4, 256);
+}
+
+int dfa_cae_score_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b, int64_t stride_t,
+                         int64_t stride_f, const int32_t* lengths, const float* mu, const float* sigma, float* mse, void* workspace,
+                         size_t workspace_bytes) {
+  TraceRange trace_("dfa_cae_score_ragged");
+  if (!ctx) return DFA_E_NULL_PTR;
+  CaeState& m = ctx->cae;
+  if (m.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cae_prepare has not been called since the last set_params");
+  if (!x || !workspace || !lengths || !mse) return fail(ctx, DFA_E_NULL_PTR, "x, lengths, mse and workspace must be non-null");
+  if ((mu == nullptr) != (sigma == nullptr)) return fail(ctx, DFA_E_NULL_PTR, "mu and sigma must both be given or both be NULL");
+  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
+  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
+  if (T_max < 16) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: four 2x2 average pools need T >= 16", T_max);
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] < 16 || lengths[b] > T_max)
+      return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [16, T_max=%d]", b, (int)lengths[b], T_max);
+  const int prec = m.prepared_prec;
+  if (prec != DFA_PREC_BF16)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score has kernels for precision bf16 only (prepared: %d)", prec);
+  const CaePlan pl = plan_cae(B, T_max, F, prec);
+  if (!pl.ok)
+    return fail(ctx, DFA_E_BAD_SHAPE, "F=%d: decoder would rebuild %d columns (needs F = 16*(F/16)+4, e.g. 180; src/model_cae.py:68-69)", F, pl.Wd[3]);
+  if (!ctx->cae_dec_fused || !ctx->cae_enc1_mfma || !ctx->cae_enc_dma || !ctx->lds_pipe)   // the uniform forward would run other kernels
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score needs the default options cae_dec_fused=1, cae_enc1_mfma=1, "
+                "cae_enc_dma=1 and lds_pipe=1");
+  if (F > 1022 || !cae_dec_fused_supports(T_max, F, stride_t, stride_f))
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score needs F <= 1022, non-negative strides and 32-bit element "
+                "offsets inside an utterance (F=%d, stride_t=%lld, stride_f=%lld)", F, (long long)stride_t, (long long)stride_f);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged score cannot be captured into a graph: its lengths are copied per call");
+  const size_t tab_off = pl.total, words = (size_t)4 * B, need = pl.total + align_up(words * 4, 256);
+  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
+  char* ws = (char*)workspace;
+  const int* dtab = (const int*)(ws + tab_off);
+  hipStream_t s = ctx->stream;
+  {
+    const int rc = stage_ragged_table(ctx, lengths, B, words, ws + tab_off, [&](int32_t* tab) {
+      for (int b = 0; b < B; ++b) {
+        const float inv_n = 1.0f / ((float)lengths[b] * (float)F);     // as the uniform call forms it
+        memcpy(&tab[2 * B + b], &inv_n, 4);
+        tab[3 * B + b] = cae_dec_fused_tiles(lengths[b] / 16, pl.W[4]);
+      }
+    });
+    if (rc != DFA_OK) return rc;
+  }
+  const RaggedTab rt{dtab, B};
+  void* e[4] = {ws + pl.e_off[0], ws + pl.e_off[1], ws + pl.e_off[2], ws + pl.e_off[3]};
+  { ScopedSlot ts(ctx, 8);
+    DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma_ragged(x, x_dtype, stride_b, stride_t, stride_f, mu, sigma, m.c1pack, m.c1bias, e[0], B, T_max, F,
+                                                   dtab, s)); }
+  const int ecout[3] = {64, 128, 256};
+  for (int l = 0; l < 3; ++l) {
+    ScopedSlot ts(ctx, 9 + l);
+    ConvArgs a{};
+    a.in = e[l]; a.wpack = m.enc[l].wpack; a.bias = m.enc[l].bias; a.out = e[l + 1];
+    a.B = B; a.H = pl.H[l + 1]; a.W = pl.W[l + 1]; a.COUT = ecout[l]; a.relu = 1; a.zero_page = ctx->zero_page;
+    DFA_HIP_CHECK(ctx, launch_cae_enc_ragged(l, a, rt, s));
+  }
+  {
+    ScopedSlot ts(ctx, 12);
+    float* partial = (float*)(ws + pl.part_off);
+    DFA_HIP_CHECK(ctx, launch_cae_dec_fused_ragged(e[3], m.dec[0].wpack, m.dec[0].bias, m.dec[1].wpack, m.dec[1].bias, m.dec[2].wpack,
+                                                   m.dec[2].bias, m.p[42], m.p[43], m.dec4pack, m.opad_cst, x, x_dtype, stride_b, stride_t,
+                                                   stride_f, mu, sigma, partial, B, pl.H[4], pl.W[4], T_max, F, dtab, s));
+    DFA_HIP_CHECK(ctx, launch_cae_mse_finalize_ragged(partial, cae_dec_fused_tiles(pl.H[4], pl.W[4]), dtab, mse, B, s));
+  }
+  return DFA_OK;
+}
+
 }  // extern "C"

@@ -160,14 +160,22 @@ __global__ __launch_bounds__(256) void cae_dec4_mse_kernel(const T* __restrict__
   if (tid == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// RAGGED = true (dfa_cae_score_ragged): utterance b owns tab[3 B + b] partial sums of its row (row pitch nblk = the longest
+// utterance's count) and the divisor 1 / (T_b F) the host computed as the uniform launch does (tab[2 B + b], float bits)
+#define DFA_KERNEL_BODY_SCOPE   // the kernel bodies below include cae_mse_finalize_body.h
 __global__ void cae_mse_finalize_kernel(const float* __restrict__ partial, int nblk, float inv_n, float* __restrict__ mse,
                                         int B) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  double s = 0.0;
-  for (int k = 0; k < nblk; ++k) s += (double)partial[(size_t)b * nblk + k];
-  mse[b] = (float)(s * (double)inv_n);
+  constexpr bool RAGGED = false;
+  const int* const tab = nullptr;
+#include "cae_mse_finalize_body.h"
 }
+__global__ void cae_mse_finalize_ragged_kernel(const float* __restrict__ partial, int nblk, const int* __restrict__ tab,
+                                               float* __restrict__ mse, int B) {
+  constexpr bool RAGGED = true;
+  const float inv_n = 0.f;
+#include "cae_mse_finalize_body.h"
+}
+#undef DFA_KERNEL_BODY_SCOPE
 
 template <typename T>
 __device__ __forceinline__ float to_float(T v);
@@ -238,6 +246,11 @@ hipError_t launch_cae_dec4_mse(const void* d3, int prec, const float* w4, const 
 
 hipError_t launch_cae_mse_finalize(const float* partial, int nblk, float inv_n, float* mse, int B, hipStream_t s) {
   hipLaunchKernelGGL(cae_mse_finalize_kernel, dim3((B + 255) / 256), dim3(256), 0, s, partial, nblk, inv_n, mse, B);
+  return hipGetLastError();
+}
+
+hipError_t launch_cae_mse_finalize_ragged(const float* partial, int nblk, const int* tab, float* mse, int B, hipStream_t s) {
+  hipLaunchKernelGGL(cae_mse_finalize_ragged_kernel, dim3((B + 255) / 256), dim3(256), 0, s, partial, nblk, tab, mse, B);
   return hipGetLastError();
 }
 

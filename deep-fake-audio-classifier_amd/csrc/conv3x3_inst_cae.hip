@@ -47,6 +47,15 @@ hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStrea
   return launch_conv3x3<float, 64, 4, 1, 1, 1, EPI_POOL_2X2, 1, true>(p2, s);
 }
 
+// Ragged batch (dfa_cae_score_ragged; bf16, the default staging and pipelining only): the ragged twins of the three default
+// instantiations above.  layer 0, 1, 2 = encoder block 2, 3, 4; a.H = the layer's input height of the longest utterance, an
+// utterance's own is T_b >> (layer + 1).
+hipError_t launch_cae_enc_ragged(int layer, const ConvArgs& a, const RaggedTab& rt, hipStream_t s) {
+  if (layer == 0) return launch_conv3x3_ragged<bf16_t, 32, 2, 2, 2, 1, EPI_POOL_2X2, 2, false, true>(a, rt, 1, s);
+  if (layer == 1) return launch_conv3x3_ragged<bf16_t, 64, 4, 1, 1, 1, EPI_POOL_2X2, 2, false, true>(a, rt, 2, s);
+  return launch_conv3x3_ragged<bf16_t, 128, 4, 1, 1, 1, EPI_POOL_2X2, 1, false, true>(a, rt, 3, s);
+}
+
 hipError_t launch_cae_dec(int prec, int cin, const ConvTArgs& a, hipStream_t s) {
   if (a.stats_partial) {   // train mode: pre-BatchNorm output + per-workgroup statistics records (cae_dec_stats_records of them)
     if (prec == DFA_PREC_BF16) {

@@ -238,6 +238,9 @@ hipError_t launch_fold_conv1d(const float* w, const float* b, const float* g, co
 // cae_enc1_mfma.hip: auto-encoder block 1 (conv 1 -> 32 + ReLU + 2 x 2 pool) on the matrix cores, bf16 mode
 hipError_t launch_cae_enc1_mfma(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma,
                                 const uint4* c1pack, const float* c1bias, void* out, int B, int T, int F, hipStream_t s);
+hipError_t launch_cae_enc1_mfma_ragged(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma,
+                                       const uint4* c1pack, const float* c1bias, void* out, int B, int T, int F, const int* tab,
+                                       hipStream_t s);
 hipError_t launch_pack_cae_enc1_mfma(const float* w1, const float* b1, uint4* pack, float* bias, hipStream_t s);
 // cae_dec_fused.hip: the auto-encoder's decoder + per-sample squared error as one kernel (bf16 mode)
 int cae_dec_fused_tiles(int H4, int W4);
@@ -247,9 +250,15 @@ hipError_t launch_cae_dec_fused(const void* lat, const uint4* wp1, const float* 
                                 const float* b3, const float* w4, const float* b4, const uint4* w4pack, const float* cst, const void* x,
                                 int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma, float* recon,
                                 float* partial, int B, int H4, int W4, int T, int F, hipStream_t s, long long* stamps = nullptr);
+hipError_t launch_cae_dec_fused_ragged(const void* lat, const uint4* wp1, const float* b1, const uint4* wp2, const float* b2,
+                                       const uint4* wp3, const float* b3, const float* w4, const float* b4, const uint4* w4pack,
+                                       const float* cst, const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu,
+                                       const float* sigma, float* partial, int B, int H4, int W4, int T, int F, const int* tab,
+                                       hipStream_t s);
 bool cae_dec_fused_supports(int T, int F, int64_t st, int64_t sf);
 hipError_t launch_pack_cae_dec4(const float* w4, uint4* pack, hipStream_t s);
 hipError_t launch_cae_mse_finalize(const float* partial, int nblk, float inv_n, float* mse, int B, hipStream_t s);
+hipError_t launch_cae_mse_finalize_ragged(const float* partial, int nblk, const int* tab, float* mse, int B, hipStream_t s);
 // cnn1d_fused.hip: the whole CNN1D eval forward as one kernel (fp32 matrix cores, activations in LDS)
 int cnn1d_fused_ncp_pad(int cin, int layer);
 size_t cnn1d_fused_pack_floats(int cin, int cout, int layer);
@@ -420,6 +429,7 @@ struct ConvTArgs;
 hipError_t launch_cae_enc2(int prec, const ConvArgs& a, hipStream_t s, int pipe = 1, int dma = 0);
 hipError_t launch_cae_enc3(int prec, const ConvArgs& a, hipStream_t s, int pipe = 1, int dma = 0);
 hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int dma = 0);
+hipError_t launch_cae_enc_ragged(int layer, const ConvArgs& a, const RaggedTab& rt, hipStream_t s);
 hipError_t launch_cae_dec(int prec, int cin, const ConvTArgs& a, hipStream_t s);
 int cae_dec_stats_records(int prec, int cin, long P);
 

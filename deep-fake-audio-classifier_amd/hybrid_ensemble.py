@@ -17,7 +17,7 @@ import torch
 
 from . import distributed as dfa_dist
 from . import fusion
-from .dataloaders import FlatBatcher
+from .dataloaders import FlatBatcher, RaggedBatcher
 from .dataset_cae import FeatureNormalizer
 from .evaluation import calculate_eer
 from .model import CNN2D
@@ -48,6 +48,57 @@ def score_models(stored_features: torch.Tensor, cnn2d=None, cnn1d=None, cae=None
         if cae is not None:
             out["cae"].append(cae.score(x, mean, std))
     return {k: (torch.cat(v).double().cpu().numpy() if v else np.zeros(0)) for k, v in out.items()}
+
+
+@torch.no_grad()
+def score_models_ragged(feature_list, cnn2d=None, cnn1d=None, cae=None, normalizer=None, batch_size=256, device="cuda",
+                        rank=0, world=1):
+    """score_models for a list of per-utterance [F, T_i] tensors of unequal lengths: one RaggedBatcher pass over this rank's
+    shard, every given model scores the same resident padded batch with `lengths=`, and the results come back in input
+    order.  Same return dict as score_models."""
+    for m in (cnn2d, cnn1d, cae):
+        if m is not None:
+            m.eval()
+    mean = std = None
+    if cae is not None and normalizer is not None:
+        mean, std = normalizer.mean.to(device), normalizer.std.to(device)
+    out = {k: [] for k, m in (("cnn2d", cnn2d), ("cnn1d", cnn1d), ("cae", cae)) if m is not None}
+    batcher = RaggedBatcher(feature_list, None, batch_size, device=device, rank=rank, world=world)
+    for x, _, lengths in batcher:
+        if cnn2d is not None:
+            out["cnn2d"].append(torch.sigmoid(cnn2d(x, lengths=lengths).squeeze(-1)))
+        if cnn1d is not None:
+            out["cnn1d"].append(torch.sigmoid(cnn1d(x, lengths=lengths).squeeze(-1)))
+        if cae is not None:
+            out["cae"].append(cae.score(x, mean, std, lengths=lengths))
+    return {k: (batcher.restore(v).double().cpu().numpy() if v else np.zeros(0)) for k, v in out.items()}
+
+
+def is_ragged(df) -> bool:
+    """Does the feature column hold utterances of unequal shapes?"""
+    return len({tuple(f.shape) for f in df["features"]}) > 1
+
+
+def check_ragged_members(members, precision: str) -> None:
+    """Can a features.pkl whose utterances differ in length be scored by these ensemble members ("cnn2d", "cnn1d", "cae")
+    at this precision?  cnn1d takes any length at any precision; cnn2d and the auto-encoder have ragged kernels for
+    --precision bf16 only.  Raises ValueError when not.  Pure: touches neither the GPU nor the file."""
+    members = list(members)
+    unknown = [m for m in members if m not in ("cnn2d", "cnn1d", "cae")]
+    if unknown:
+        raise ValueError(f"unknown ensemble member {unknown[0]!r} (choices: cnn2d, cnn1d, cae)")
+    needs = [m for m in members if m in ("cnn2d", "cae")]
+    if needs and precision != "bf16":
+        raise ValueError(f"the feature file holds utterances of unequal lengths: {' and '.join(sorted(set(needs)))} score such a "
+                         f"file with --precision bf16 only (got --precision {precision}); cnn1d takes any length")
+
+
+def score_table(df, cnn2d=None, cnn1d=None, cae=None, normalizer=None, batch_size=256, device="cuda", rank=0, world=1):
+    """score_models on the stacked features of an equal-length table, score_models_ragged on a table of unequal lengths."""
+    if is_ragged(df):
+        return score_models_ragged([f.float() for f in df["features"]], cnn2d, cnn1d, cae, normalizer, batch_size, device,
+                                   rank, world)
+    return score_models(_stack(df), cnn2d, cnn1d, cae, normalizer, batch_size, device, rank, world)
 
 
 def hybrid_report(sup_scores, cae_scores, labels, alpha_steps=21):
@@ -87,11 +138,13 @@ def main(argv=None):
     rank, world = dfa_dist.init()
     table = pd.merge(pd.read_pickle(args.dev_features), pd.read_pickle(args.dev_labels), on="uttid", how="inner") \
         .reset_index(drop=True)
+    if is_ragged(table):
+        check_ragged_members(["cnn2d", "cae"] + (["cnn1d"] if args.cnn1d_checkpoint else []), args.precision)
     sup = _load(CNN2D, args.sup_checkpoint, args.device, in_features=180, dropout=0.2, precision=args.precision)
     cae = _load(ConvAutoencoder, args.cae_checkpoint, args.device, precision=args.precision)
     c1d = _load(CNN1D, args.cnn1d_checkpoint, args.device) if args.cnn1d_checkpoint else None
     norm = FeatureNormalizer.load(args.cae_normalizer)
-    local = score_models(_stack(table), sup, c1d, cae, norm, args.batch_size, args.device, rank, world)
+    local = score_table(table, sup, c1d, cae, norm, args.batch_size, args.device, rank, world)
     scores = {k: dfa_dist.gather_scores(v) for k, v in local.items()}
     if rank != 0:
         return

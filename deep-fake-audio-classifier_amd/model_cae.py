@@ -6,6 +6,8 @@ in torch's (Cin, Cout, 2, 2) layout) and call contract: `model(x[B,T,F]) -> (rec
 Beyond the reference: `model.score(x, mean=None, std=None)` returns the per-sample reconstruction MSE
 (src/evaluation_cae.py:52-53) computed on the GPU with the FeatureNormalizer z-score fused into the loads, so the
 anomaly scores of a raw feature batch need no normalised copy, no reconstruction tensor and no latent export.
+`model.score(x, mean, std, lengths=...)` scores a variable-length (ragged) batch padded to its longest utterance: every
+utterance gets, bit for bit, the score it gets alone (bf16 precision; score only -- no reconstruction, latent or train mode).
 """
 from __future__ import annotations
 
@@ -118,11 +120,46 @@ class ConvAutoencoder(nn.Module):
         recon, latent, _ = self._run(x, None, None, True, True, False)
         return recon, latent
 
+    def _score_ragged(self, x, mean, std, lengths):
+        if x.device.type != "cuda":
+            raise RuntimeError("dfa_amd.ConvAutoencoder runs on the GPU only: move the input with .to('cuda')")
+        B, T, F = x.shape
+        ctx = _lib.Context.get(x.device)
+        with torch.cuda.device(ctx.index):
+            ctx.use_current_stream()
+            self._ensure_prepared(ctx)
+            prec = _lib.PRECISIONS[self.precision]
+            nbytes = ctx.lib.dfa_cae_ragged_workspace_bytes(ctx.handle, B, T, F, prec)
+            ws = ctx.workspace(max(nbytes, 256))
+            dev = x.device
+            mse = torch.empty((B,), dtype=torch.float32, device=dev)
+            if mean is not None:
+                mean = mean.to(device=dev, dtype=torch.float32).contiguous()
+                std = std.to(device=dev, dtype=torch.float32).contiguous()
+                if mean.numel() != F or std.numel() != F:
+                    raise ValueError(f"normaliser statistics must have {F} entries")
+
+            def ptr(t):
+                return C.c_void_p(t.data_ptr() if t is not None else None)
+            sb, st, sf = x.stride()
+            code = ctx.lib.dfa_cae_score_ragged(ctx.handle, ptr(x), _lib.x_dtype_code(x), B, T, F, sb, st, sf,
+                                                C.c_void_p(lengths.ctypes.data), ptr(mean), ptr(std), ptr(mse), ptr(ws),
+                                                ws.numel())
+            _lib.check(ctx.handle, code)
+        return mse
+
     @torch.no_grad()
-    def score(self, x: torch.Tensor, mean: torch.Tensor | None = None, std: torch.Tensor | None = None):
-        """Per-sample reconstruction MSE [B].  With mean/std the input is the RAW feature view and the z-score is fused."""
+    def score(self, x: torch.Tensor, mean: torch.Tensor | None = None, std: torch.Tensor | None = None, lengths=None):
+        """Per-sample reconstruction MSE [B].  With mean/std the input is the RAW feature view and the z-score is fused.
+        lengths: None, or the per-utterance frame counts (each in [16, T]) of a ragged batch padded to T (a list, numpy array
+        or int tensor): utterance b is scored as x[b:b+1, :lengths[b]] alone would be, bit for bit, and its padding rows are
+        never read.  Ragged batches run in bf16 precision."""
         if (mean is None) != (std is None):
             raise ValueError("mean and std must be given together")
+        if lengths is not None:
+            if x.dim() != 3:
+                raise ValueError(f"ConvAutoencoder expects x of shape (B, T, F), got {tuple(x.shape)}")
+            return self._score_ragged(x, mean, std, _lib.host_lengths(lengths, x.shape[0], x.shape[1], 16))
         return self._run(x, mean, std, False, False, True)[2]
 
 

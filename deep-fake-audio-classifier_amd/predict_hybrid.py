@@ -20,7 +20,7 @@ import torch
 from . import distributed as dfa_dist
 from . import fusion
 from .dataset_cae import FeatureNormalizer
-from .hybrid_ensemble import _load, _stack, score_models
+from .hybrid_ensemble import _load, check_ragged_members, is_ragged, score_table
 from .model import CNN2D
 from .model_cae import ConvAutoencoder
 
@@ -82,10 +82,12 @@ def main(argv=None):
         raise ValueError("features.pkl must contain 'uttid'")
     if rank == 0:
         print(f"Test set: {len(features_df)} samples")
+    if is_ragged(features_df):
+        check_ragged_members(["cnn2d", "cae"], args.precision)
     sup = _load(CNN2D, args.sup_checkpoint, device, in_features=180, dropout=0.2, precision=args.precision)
     cae = _load(ConvAutoencoder, args.cae_checkpoint, device, precision=args.precision)
     norm = FeatureNormalizer.load(args.cae_normalizer)
-    local = score_models(_stack(features_df), sup, None, cae, norm, args.batch_size, device, rank, world)
+    local = score_table(features_df, sup, None, cae, norm, args.batch_size, device, rank, world)
     dev = torch.device(device) if str(device).startswith("cuda") else None
     scores = {k: dfa_dist.gather_scores(v, device=dev) for k, v in local.items()}
     if rank != 0:

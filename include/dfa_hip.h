@@ -323,6 +323,24 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
                      int64_t stride_f, const float* drecon, float* const* grads, int ngrads, void* workspace,
                      size_t workspace_bytes);
 
+/* anomaly scores of a variable-length (ragged) batch in five launches: utterance b is x[b, :lengths[b], :] and mse[b] is, bit for
+ * bit, the mse dfa_cae_forward gives x[b:b+1, :lengths[b], :] alone (layer heights T_b/2, T_b/4, T_b/8, T_b/16, zero
+ * reconstruction rows t >= 16 (T_b/16), divisor T_b * F; src/model_cae.py:107-125, src/evaluation_cae.py:52-53) -- whatever
+ * B, T_max, the utterance's position in the batch or the dispatch order.  Replaces one dfa_cae_forward per uncropped utterance.
+ *   x: the padded [B, T_max, F] strided view, float32 or bf16; rows t >= lengths[b] are never read (may hold NaN);
+ *   lengths: HOST int32[B], 16 <= lengths[b] <= T_max (else DFA_E_BAD_SHAPE naming the index); copied into the workspace on the
+ *      context's stream;
+ *   mu, sigma: the fused z-score as in dfa_cae_forward, or both NULL;  mse: device float[B];
+ *   workspace: device, 256-byte aligned, >= dfa_cae_ragged_workspace_bytes(ctx, B, T_max, F, DFA_PREC_BF16) bytes; rows past an
+ *      utterance's own height are never read in any activation, so it may hold stale data.
+ * Score only: no reconstruction, no latent export, no train mode.  Precision bf16 with the default kernel options only:
+ * a context prepared for fp32, one with cae_dec_fused = 0, cae_enc1_mfma = 0, cae_enc_dma = 0 or lds_pipe = 0 (the uniform
+ * forward would run other kernels), an input the fused decoder does not take (32-bit offsets inside an utterance,
+ * non-negative strides) or F > 1022, or a capturing stream returns DFA_E_UNSUPPORTED. */
+int dfa_cae_score_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b, int64_t stride_t,
+                         int64_t stride_f, const int32_t* lengths, const float* mu, const float* sigma, float* mse,
+                         void* workspace, size_t workspace_bytes);
+
 /* MSELoss(recon, x) forward + backward in one pass (replaces nn.MSELoss + its autograd node, src/train_cae.py:67-68,203):
  * loss[0] = mean((recon - x)^2) over B*T*F elements (fixed-order two-stage reduction), drecon = 2*(recon - x)/(B*T*F).
  * recon: device float[B*T*F] contiguous; x: as in dfa_cae_forward (dtype + element strides); loss / drecon: device, either may be
@@ -335,6 +353,10 @@ size_t dfa_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T, int F, i
 /* workspace of dfa_cnn2d_forward_ragged / dfa_cnn1d_forward_ragged for B utterances padded to T_max frames (0 for a model
  * without a ragged forward) */
 size_t dfa_ragged_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T_max, int F, int precision);
+/* workspace of dfa_cae_score_ragged: the uniform plan at T_max plus the per-call table (4 * B int32 words), a multiple of
+ * 256; 0 for B < 1.  The auto-encoder has a planner of its own because dfa_ragged_workspace_bytes(DFA_MODEL_CAE) returned 0
+ * ("no ragged forward") before this entry point existed and callers test for that value: it keeps returning 0. */
+size_t dfa_cae_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F, int precision);
 /* names of the device kernels a forward launches, for profile post-processing ("" when unknown) */
 const char* dfa_dominant_kernel(int model, int precision);
 /* ---- per-kernel timing (HIP events recorded on the context's stream around every launch) -------------

@@ -1,11 +1,15 @@
 """A/B two builds of the library (separate processes, alternating): DFA_LIB=<file name under lib/>; DFA_AB_MODE=train times the
-bf16 training step instead of the eval forward."""
+bf16 training step instead of the eval forward, DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
+z-score fused) at [256, 321, 180]."""
 import os, sys, time, torch
 sys.path.insert(0, os.getcwd())
 from dfa_amd import _lib
 name = os.environ.get("DFA_LIB")
 if name:
     _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), name)
+    import ctypes
+    probe = ctypes.CDLL(_lib.LIB_PATH)
+    _lib.SYMBOLS[:] = [s for s in _lib.SYMBOLS if hasattr(probe, s[0])]   # an older build lacks the newer entry points
 import bench
 if os.environ.get("DFA_AB_MODE") == "train":
     from dfa_amd.model import CNN2D
@@ -25,6 +29,29 @@ if os.environ.get("DFA_AB_MODE") == "train":
         torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 10 * 1e3)
     print(name, "train step ms median %.3f min %.3f" % (sorted(res)[2], min(res)),
           "losses", ["%.4f" % v for v in losses], "last %.4f" % float(last), flush=True)
+    sys.exit(0)
+if os.environ.get("DFA_AB_MODE") == "cae":
+    from dfa_amd.model_cae import ConvAutoencoder
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(1234)
+    x = (torch.randn(256, 180, 321, generator=g) * 3.2 - 0.07).to(device=dev, dtype=torch.bfloat16).transpose(1, 2)
+    mean, std = torch.randn(180, generator=g).to(dev), (torch.rand(180, generator=g) + 0.5).to(dev)
+    torch.manual_seed(0)
+    model = ConvAutoencoder(precision="bf16").to(dev).eval()
+    ctx = _lib.Context.get(dev)
+    for _ in range(10): last = model.score(x, mean, std)
+    out = []
+    for rnd in range(5):
+        ctx.timing_reset(); ctx.timing(True)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(20): last = model.score(x, mean, std)
+        torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 20
+        ctx.timing(False)
+        sl = [ctx.timing_read(s) for s in range(8, 13)]
+        out.append((round(dt * 1e3, 4), [round(ms / max(n, 1), 4) for ms, n in sl]))
+    ms = sorted(o[0] for o in out)
+    print(name, "cae score ms median %.4f min %.4f max %.4f" % (ms[2], ms[0], ms[-1]), "slots 8-12 of the median round", sorted(out)[2][1],
+          "checksum %.9g" % float(last.double().sum()), flush=True)
     sys.exit(0)
 dev = torch.device("cuda", 0)
 g = torch.Generator().manual_seed(1234)

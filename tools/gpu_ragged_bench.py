@@ -1,4 +1,5 @@
-"""Ragged throughput of CNN2D (bf16, the default) or CNN1D (--model cnn1d, fp32 features): in one process, alternating timed legs of
+"""Ragged throughput of CNN2D (bf16, the default), CNN1D (--model cnn1d, fp32 features) or the auto-encoder's anomaly score
+(--model cae, bf16, raw features with the z-score fused): in one process, alternating timed legs of
   ragged   B=256, F=180, lengths drawn with a fixed seed uniformly from [161, 481] (mean 321),
   uniform  [256, 321, 180],
   ragged32 the first 32 of those lengths (the reference's predict batch size),
@@ -7,7 +8,7 @@
 Prints one JSON line: per leg the median utt/s and frames/s over the pairs, with min and max, and per pair ragged32 / loop.
 --stamps (cnn1d): one extra ragged call with the kernel's clock stamps on, reporting the share of the stamped workgroups'
 time spent in multi-segment utterances.
-usage: timeout -k 10 300 python tools/gpu_ragged_bench.py [--model cnn2d|cnn1d] [--pairs 5] [--iters 20] [--stamps]"""
+usage: timeout -k 10 300 python tools/gpu_ragged_bench.py [--model cnn2d|cnn1d|cae] [--pairs 5] [--iters 20] [--stamps]"""
 import argparse
 import json
 import os
@@ -25,7 +26,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--model", default="cnn2d", choices=["cnn2d", "cnn1d"])
+    ap.add_argument("--model", default="cnn2d", choices=["cnn2d", "cnn1d", "cae"])
     ap.add_argument("--stamps", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
@@ -41,6 +42,14 @@ def main():
         xu = (torch.randn(256, 180, 321, generator=gen) * 3.2).to("cuda").transpose(1, 2)
         own = [xr[i, :int(T)].t().contiguous()[None].transpose(1, 2) for i, T in enumerate(l32)]
         loop = lambda: [model(u) for u in own]           # noqa: E731
+    elif args.model == "cae":
+        from dfa_amd.model_cae import ConvAutoencoder
+        cae = ConvAutoencoder(precision="bf16").to("cuda").eval()
+        mean, std = torch.randn(180, generator=gen).to("cuda"), (torch.rand(180, generator=gen) + 0.5).to("cuda")
+        xr = (torch.randn(256, 180, T_max, generator=gen) * 3.2).to(torch.bfloat16).to("cuda").transpose(1, 2)
+        xu = (torch.randn(256, 180, 321, generator=gen) * 3.2).to(torch.bfloat16).to("cuda").transpose(1, 2)
+        model = lambda x, lengths=None: cae.score(x, mean, std, lengths=lengths)     # noqa: E731
+        loop = lambda: [model(xr[i:i + 1, :int(T)]) for i, T in enumerate(l32)]      # noqa: E731
     else:
         model = CNN2D(precision="bf16").to("cuda").eval()
         xr = (torch.randn(256, 180, T_max, generator=gen) * 3.2).to(torch.bfloat16).to("cuda").transpose(1, 2)
@@ -68,7 +77,7 @@ def main():
             t1.synchronize()
             s = t0.elapsed_time(t1) / 1e3 / args.iters
             res[name].append((n_utt / s, n_frames / s))
-    out = {"model": args.model, "precision": "bf16" if args.model == "cnn2d" else "fp32 (split bf16)", "pairs": args.pairs, "iters": args.iters, "mean_length": float(lengths.mean())}
+    out = {"model": args.model, "precision": "fp32 (split bf16)" if args.model == "cnn1d" else "bf16", "pairs": args.pairs, "iters": args.iters, "mean_length": float(lengths.mean())}
     for name, v in res.items():
         u = np.array([a for a, _ in v]); f = np.array([b for _, b in v])
         out[name] = {"utt_per_s": float(np.median(u)), "utt_min": float(u.min()), "utt_max": float(u.max()),
