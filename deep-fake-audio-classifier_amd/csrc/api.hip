@@ -181,6 +181,12 @@ int dfa_ctx_create(int device_id, void* hip_stream, dfa_ctx** out) {
     delete c;
     return DFA_E_HIP;
   }
+  // the persistent CNN2D kernel sizes its grid by the CU count: asked once here, so a forward (a captured one too) asks nothing
+  if (hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || c->num_cus < 1) {
+    (void)hipFree(c->zero_page);
+    delete c;
+    return DFA_E_HIP;
+  }
   const char* dma = getenv("DFA_CONV_DMA");   // unset = per-kernel choice measured on MI355X (see launch_cnn2d_block*)
   c->conv_dma = (dma && (dma[0] == '0' || dma[0] == '1')) ? dma[0] - '0' : -1;
   *out = c;
@@ -274,6 +280,7 @@ int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "block3_m16") == 0) { ctx->block3_m16 = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "fuse_conv1") == 0) { ctx->fuse_conv1 = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "fuse_blocks123") == 0) { ctx->fuse_blocks123 = value ? 1 : 0; return DFA_OK; }
+  if (strcmp(name, "persist123") == 0) { ctx->persist123 = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "lds_pipe") == 0) { ctx->lds_pipe = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "conv_dma") == 0) { ctx->conv_dma = value < 0 ? -1 : value; return DFA_OK; }
   return fail(ctx, DFA_E_UNSUPPORTED, "unknown option '%s'", name);
@@ -454,7 +461,12 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   const bool fused123 = fused12 && ctx->block3_m16 && ctx->fuse_blocks123 && ctx->time_split <= 0 && B * nstrips30 >= 512 &&
                         seg_iters_for((pl.H1 + 3) / 4, B * nstrips30, 512, 6, ctx->time_split) == 0 &&
                         seg_iters_for(niter3, B * nstrips30, 512, chunk3, ctx->time_split) == 0;
-  if (fused123) {
+  if (fused123 && ctx->persist123) {      // one workgroup per CU walks a contiguous range of the same units (conv123_persist.hip)
+    ScopedSlot ts(ctx, 2);
+    DFA_HIP_CHECK(ctx, launch_conv123_persist(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
+                                              m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
+                                              ctx->num_cus, s, ctx->lds_pipe));
+  } else if (fused123) {
     ScopedSlot ts(ctx, 2);
     DFA_HIP_CHECK(ctx, launch_conv123_fused(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
                                             m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,

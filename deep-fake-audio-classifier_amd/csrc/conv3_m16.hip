@@ -102,12 +102,8 @@ hipError_t launch_fold_pack_conv3x3_m16(const float* w, const float* b, const fl
 template <bool PIPE, bool TRAIN>
 static hipError_t launch_m16_t(const ConvArgs& a, hipStream_t stream) {
   auto kern = conv3_m16_meant_kernel<PIPE, TRAIN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, m16::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, m16::LDS_BYTES);
+  if (e != hipSuccess) return e;       // (the attribute is per device: set on every launch, it is cheap)
   const int nseg = a.seg_iters ? ((a.H + m16::BR - 1) / m16::BR + a.seg_iters - 1) / a.seg_iters : 1;
   hipLaunchKernelGGL(kern, dim3(a.B * a.nstrips, a.COUT / 128, nseg), dim3(256), m16::LDS_BYTES, stream, a);
 #ifdef DFA_STAMPS
@@ -144,12 +140,8 @@ hipError_t launch_cnn2d_block3_m16_ragged(const ConvArgs& a0, const RaggedTab& r
   ConvArgs a = a0;
   a.nstrips = (a.W + m16::SW - 1) / m16::SW;
   auto kern = pipe ? conv3_m16_ragged_kernel<true> : conv3_m16_ragged_kernel<false>;
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[pipe ? 1 : 0]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, m16::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set[pipe ? 1 : 0] = true;
-  }
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, m16::LDS_BYTES);
+  if (e != hipSuccess) return e;       // (per device: set on every launch)
   hipLaunchKernelGGL(kern, dim3(a.B * a.nstrips, a.COUT / 128, a.seg_iters ? nseg : 1), dim3(256), m16::LDS_BYTES, stream, a, rt);
   return hipGetLastError();
 }

@@ -124,6 +124,8 @@ struct dfa_ctx {
   int block3_m16 = 1;          // bf16 block 3 on v_mfma_f32_16x16x32_bf16 (conv3_m16.hip); 0 = the 32x32x16 kernel
   int fuse_conv1 = 1;          // bf16 mode: blocks 1 and 2 in one kernel (conv12_fused.hip; fp32 features are rounded to bf16 on load); 0 = two kernels
   int fuse_blocks123 = 1;      // bf16 mode, fuse_conv1 && block3_m16, no time split: blocks 1-3 + time mean in one kernel (conv123_fused.hip)
+  int persist123 = 1;          // where blocks 1-3 are fused: 1 = one workgroup per CU over a contiguous range of units (conv123_persist.hip), 0 = one workgroup per unit
+  int num_cus = 0;             // hipDeviceAttributeMultiprocessorCount of `device`, asked once in dfa_ctx_create (grid of the persistent kernel)
   int lds_pipe = 1;            // 1 = asm-pipelined LDS fragment reads where instantiated, 0 = compiler-scheduled twins (test hook)
   int time_split = -1;         // eval forward, small batches: -1 = automatic time-axis split, 0 = off, n > 0 = force n segments
   int conv1_bwd_fused = 1;     // CNN2D training: block-1 backward as ONE pass over da1 (train_conv1.hip BWD_FUSED); 0 = reduce pass + weight-gradient pass
@@ -423,6 +425,11 @@ hipError_t launch_conv123_fused(const void* x, int x_dtype, int64_t sb, int64_t 
                                 const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
                                 const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
                                 hipStream_t s, int pipe = 1);
+// the same units, one persistent workgroup per CU (grid = min(units, num_cus)): conv123_persist.hip
+hipError_t launch_conv123_persist(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
+                                  const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
+                                  const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
+                                  int num_cus, hipStream_t s, int pipe = 1);
 hipError_t launch_cnn2d_block2(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);
 hipError_t launch_cnn2d_block3(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);
 struct ConvTArgs;

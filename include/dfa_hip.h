@@ -76,6 +76,9 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *   "fuse_blocks123" 1 (default) = CNN2D bf16 eval forward with fuse_conv1 and block3_m16 set runs blocks 1-3 + the time
  *                   mean as ONE kernel (a2 stays in LDS) wherever neither old kernel would split the time axis (B * strips >= 512,
  *                   no forced time_split); 0 = the two-kernel path.  Bit-identical results either way
+ *   "persist123"    1 (default) = where fuse_blocks123 applies, the fused kernel runs as one persistent workgroup per CU that
+ *                   walks a contiguous range of (utterance, strip) units and stages the next unit under the tail of the current
+ *                   one (static ranges, no communication between workgroups); 0 = one workgroup per unit.  Bit-identical results
  *   "time_split"    -1 (default) = CNN2D eval forward splits the time axis over workgroups when the batch alone cannot fill
  *                   the chip (B * strips below the resident-workgroup count, e.g. the reference's predict batch of 32), 0 =
  *                   never, n > 0 = force n segments (at most 4).  Logits and embeddings are bit-identical for every setting and
