@@ -150,6 +150,10 @@ static int stage_ragged_table(dfa_ctx* ctx, const int32_t* lengths, int B, size_
   return DFA_OK;
 }
 
+int dfa::stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void* dst) {
+  return stage_ragged_table(ctx, lengths, B, (size_t)2 * B, dst, [](int32_t*) {});
+}
+
 extern "C" {
 
 int dfa_version(void) { return DFA_VERSION; }

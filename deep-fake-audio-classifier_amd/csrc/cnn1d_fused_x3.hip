@@ -247,6 +247,7 @@ struct Conv1dX3Args {
   float* z;                    // [B][Cout][T]
   int T, Cin, Cout, NT, nks, slab_floats, offW;
   AugCfg aug;                  // AUG instantiation (training layer 1): x is read through the armed train-time augmentation (rng.h)
+  const int* lens;             // RAGGED instantiation (training layer 1 of a ragged batch): device [B], utterance b owns frames [0, lens[b]) of T
 };
 
 // A-fragment images with TERMS bf16 terms per weight: wx[m][tap][ks][term][lane]
@@ -357,7 +358,7 @@ __device__ __forceinline__ void split8n(const float (&v)[8], uint4 (&f)[TERMS]) 
   for (int t = 0; t < TERMS; ++t) f[t] = make_uint4(q[t][0], q[t][1], q[t][2], q[t][3]);
 }
 
-template <int MT, int TERMS, bool AUG = false>
+template <int MT, int TERMS, bool AUG = false, bool RAGGED = false>
 __global__ __launch_bounds__(512) void conv1d_x3_kernel(Conv1dX3Args a) {
   using namespace c1x;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -391,6 +392,25 @@ __global__ __launch_bounds__(512) void conv1d_x3_kernel(Conv1dX3Args a) {
           e[u] = aug_apply(a.aug, xf[(size_t)f * T + aug_src_t(a.aug, t)], b, t, f);
         }
         xr[k] = make_float4(e[0], e[1], e[2], e[3]);
+      }
+    } else if constexpr (RAGGED) {
+      // the same 16-byte loads; the padding frames t >= lens[b] of every channel row are cleared bit-wise (they may hold NaN / Inf):
+      // the slab is 16 rows of T floats back to back, so element `flat` is frame flat mod T
+      const float4* src = xg + (size_t)4 * sc * T;
+      const int Tb = a.lens[b];
+#pragma unroll
+      for (int k = 0; k < NLD; ++k) {
+        const int i = min(k * NTH + tid, n4 - 1);
+        const float4 v = src[i];
+        const int flat = 4 * i, t0 = flat - (flat / T) * T;
+        unsigned q[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          int t = t0 + u;
+          t = t >= T ? t - T : t;                              // T >= 3: at most one wrap into the next row
+          q[u] = t < Tb ? q[u] : 0u;
+        }
+        xr[k] = make_float4(__uint_as_float(q[0]), __uint_as_float(q[1]), __uint_as_float(q[2]), __uint_as_float(q[3]));
       }
     } else {
       const float4* src = xg + (size_t)4 * sc * T;
@@ -532,9 +552,10 @@ bool conv1d_x3_supports(const float* x, int64_t sb, int64_t sc, int64_t st, cons
 }
 
 hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int Cout, int T,
-                            int terms, hipStream_t s, int mode, const AugCfg* aug) {
+                            int terms, hipStream_t s, int mode, const AugCfg* aug, const int* lens) {
   Conv1dX3Args a{};
   if (aug && aug->on) a.aug = *aug;
+  a.lens = lens;
   a.x = x; a.sb = sb; a.w = (const uint4*)wx; a.bias = bias; a.z = z; a.T = T; a.Cin = Cin; a.Cout = Cout;
   a.NT = (T + 31) / 32; a.nks = cnn1d_x3_nks(Cin);
   const int mt = conv1d_x3_mt(T, Cin, Cout, terms, mode);
@@ -546,6 +567,10 @@ hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const fl
     hipLaunchKernelGGL(kern, dim3(B, Cout / (32 * mt)), dim3(c1x::NTH), total, s, a);
     return hipGetLastError();
   };
+  if (lens) {                     // ragged layer 1 (one channel tile), never with an augmentation
+    if (mt != 1 || a.aug.on) return hipErrorInvalidValue;
+    return terms == 3 ? go(conv1d_x3_kernel<1, 3, false, true>) : go(conv1d_x3_kernel<1, 2, false, true>);
+  }
   if (a.aug.on) {                 // layer 1 only (one channel tile)
     if (mt != 1) return hipErrorInvalidValue;
     return terms == 3 ? go(conv1d_x3_kernel<1, 3, true>) : go(conv1d_x3_kernel<1, 2, true>);

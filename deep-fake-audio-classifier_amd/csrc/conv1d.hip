@@ -15,12 +15,15 @@ constexpr int C1D_OT = 32, C1D_TT = 64, C1D_CC = 16;
 
 // AUG (train-mode layer 1 only): x is read through the armed train-time augmentation (rng.h aug_apply; channel = feature dim,
 // dfa_cnn1d_set_train_augment) -- the element the stand-alone dfa_augment_batch pass would have written, never materialised.
-template <bool MEAN, bool RELU = true, bool AUG = false>
+// RAGGED (train-mode layer 1 of a ragged batch): x is padded to T frames, utterance b owns [0, lens[b]); a padding frame is
+// never loaded (it may hold NaN / Inf) and reads as the utterance's own zero padding.
+template <bool MEAN, bool RELU = true, bool AUG = false, bool RAGGED = false>
 __global__ __launch_bounds__(256) void conv1d_k3_bn_relu_kernel(const float* __restrict__ x, int64_t sb, int64_t sc,
                                                                  int64_t st, const float* __restrict__ w,
                                                                  const float* __restrict__ bias,
                                                                  float* __restrict__ out, int Cin, int Cout, int T,
-                                                                 float inv_t, AugCfg aug = AugCfg{}) {
+                                                                 float inv_t, AugCfg aug = AugCfg{},
+                                                                 const int* __restrict__ lens = nullptr) {
   __shared__ float xs[C1D_CC][C1D_TT + 4];
   __shared__ float ws[C1D_CC][3][C1D_OT];
   __shared__ float red[C1D_OT][17];
@@ -28,6 +31,7 @@ __global__ __launch_bounds__(256) void conv1d_k3_bn_relu_kernel(const float* __r
   const int tq = tid & 15, oq = tid >> 4;       // 16 frame-quads x 16 channel-pairs
   const int b = blockIdx.z, o0 = blockIdx.y * C1D_OT;
   const float* xb = x + (int64_t)b * sb;
+  const int Tx = RAGGED ? lens[b] : T;         // frames of x that exist
   const float b0 = bias[o0 + 2 * oq], b1 = bias[o0 + 2 * oq + 1];
   float msum0 = 0.f, msum1 = 0.f;
 
@@ -46,7 +50,7 @@ __global__ __launch_bounds__(256) void conv1d_k3_bn_relu_kernel(const float* __r
         if constexpr (AUG)
           xs[c][tt] = (ci < Cin && t >= 0 && t < T) ? aug_apply(aug, xb[(int64_t)ci * sc + (int64_t)aug_src_t(aug, t) * st], b, t, ci) : 0.f;
         else
-          xs[c][tt] = (ci < Cin && t >= 0 && t < T) ? xb[(int64_t)ci * sc + (int64_t)t * st] : 0.f;
+          xs[c][tt] = (ci < Cin && t >= 0 && t < Tx) ? xb[(int64_t)ci * sc + (int64_t)t * st] : 0.f;
       }
       for (int e = tid; e < C1D_CC * 3 * C1D_OT; e += 256) {
         const int o = e & (C1D_OT - 1), k = (e / C1D_OT) % 3, c = e / (3 * C1D_OT);
@@ -121,7 +125,13 @@ hipError_t launch_fold_conv1d(const float* w, const float* b, const float* g, co
 }
 
 hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, const float* w, const float* bias,
-                         float* out, int B, int Cin, int Cout, int T, bool mean, hipStream_t s, bool relu, const AugCfg* aug) {
+                         float* out, int B, int Cin, int Cout, int T, bool mean, hipStream_t s, bool relu, const AugCfg* aug, const int* lens) {
+  if (lens) {             // train-mode layer 1 of a ragged batch
+    if (relu || mean || (aug && aug->on)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, false, true>), dim3((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256),
+                       0, s, x, sb, sc, st, w, bias, out, Cin, Cout, T, 0.f, AugCfg{}, lens);
+    return hipGetLastError();
+  }
   if (aug && aug->on) {   // train-mode layer 1 with the augmentation folded into the x loads
     if (relu || mean) return hipErrorInvalidValue;
     hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, true>), dim3((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256),

@@ -87,6 +87,8 @@ struct Cnn1dState {
   void* wx3[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // per-step bf16x3 A-fragment images: forward layers 1-3, data gradients 3->2, 2->1 (conv1d_x3_kernel)
   DropCfg train_drop{};
   int train_B = 0, train_T = 0;
+  int train_ragged = 0;       // the forward_train in flight was dfa_cnn1d_forward_train_ragged (its table sits behind the plan in the workspace)
+  double train_frames = 0.0;  // ... and its frame count, the sum of the lengths
   AugCfg aug_armed{};   // dfa_cnn1d_set_train_augment: consumed by the next forward_train
   AugCfg train_aug{};   // the augmentation of the forward_train in flight (the layer-1 weight gradient re-reads x through it)
 };
@@ -286,27 +288,31 @@ hipError_t launch_cnn1d_fused_x3(const float* x, const void* w1, const float* b1
                                  long long* stamps = nullptr);
 hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, const float* w, const float* bias,
                          float* out, int B, int Cin, int Cout, int T, bool mean, hipStream_t s, bool relu = true,
-                         const AugCfg* aug = nullptr);
+                         const AugCfg* aug = nullptr, const int* lens = nullptr);
+// api.hip: the per-call table of a ragged batch ([0, B) lengths, [B, 2B) dispatch order: 2 B words) through the next pinned staging
+// slot to `dst` (device) on the context's stream
+int stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void* dst);
 // train_cnn1d.hip
 int cm_chunks(int B);
 int conv1d_wgrad_chunks(int B);
-hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s);
+// lens (device, [B]) != null selects the ragged twins: utterance b owns frames [0, lens[b]) of the T the batch is padded to
+hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens = nullptr);
 hipError_t launch_cm_bn_relu_drop(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                  const float* beta, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s);
+                                  const float* beta, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s, const int* lens = nullptr);
 hipError_t launch_cm_bn_relu_meant(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                   const float* beta, float* pooled, int B, int C, int T, hipStream_t s);
+                                   const float* beta, float* pooled, int B, int C, int T, hipStream_t s, const int* lens = nullptr);
 hipError_t launch_cm_bn_bwd(int src, const float* z, const float* mean, const float* invstd, const float* gamma,
                             const float* beta, const float* up, float* partial, float* sums, float* dz, int B, int C,
-                            int T, const DropCfg& dc, hipStream_t s, const BnSync* sync = nullptr);
+                            int T, const DropCfg& dc, hipStream_t s, const BnSync* sync = nullptr, const int* lens = nullptr, double n_valid = 0.0);
 bool conv1d_x3_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms);
 hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int Cout, int T,
-                            int terms, hipStream_t s, int mode = 1, const AugCfg* aug = nullptr);
+                            int terms, hipStream_t s, int mode = 1, const AugCfg* aug = nullptr, const int* lens = nullptr);
 size_t conv1d_terms_pack_bytes(int cin, int cout, int terms);
 hipError_t launch_pack_conv1d_terms(const float* wf, void* wx, int cin, int cout, int terms, hipStream_t s);
 hipError_t launch_pack_conv1d_train_all(const float* w1, const float* w2, const float* w3, void* const* dst, int F, int terms, float* zero_bias,
                                         hipStream_t s);
 hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int64_t hsc, int64_t hst, float* partial,
-                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug = nullptr, int x3 = 0);
+                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug = nullptr, int x3 = 0, const int* lens = nullptr);
 hipError_t launch_conv1d_dgrad_pack(const float* w, float* wt, float* zero_bias, int cin, int cout, hipStream_t s);
 // cae.hip
 hipError_t launch_cae_enc1(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu,

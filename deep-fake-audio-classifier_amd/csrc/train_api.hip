@@ -477,22 +477,20 @@ float* sums1d(char* ws, const Train1dPlan& pl, int l) {
   return (float*)(ws + pl.sums) + 2 * off[l];
 }
 
-}  // namespace
+// A ragged batch (dfa_cnn1d_forward_train_ragged): x is padded to T = T_max frames, utterance b is x[b, :lengths[b], :].  The step
+// is the reference model's on the utterances concatenated along time: each Conv1d zero-pads an utterance at
+// its own two ends, BatchNorm1d's statistics run over the N = sum lengths[b] valid frames, the time mean of utterance b over its own.
+// It is reached with the UNIFORM convolution / weight-gradient / data-gradient kernels on the padded batch, because three things
+// hold at every padding frame t >= lengths[b]: x reads as zero (a bound in the loads of the kernels that read x), every activation
+// h is written as an exact zero, and so is every dz.  The table ([0, B) lengths, [B, 2B) the staging's dispatch order, unused here)
+// sits behind the uniform plan in the workspace; the backward reads it from there.
+size_t ragged1d_tab_bytes(int B) { return al((size_t)2 * B * sizeof(int32_t)); }
 
-extern "C" {
-
-size_t dfa_cnn1d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F) {
-  (void)ctx;
-  if (B < 1 || T < 1 || F < 1) return 0;
-  return plan_train1d(B, T, F).total;
-}
-
-int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
-                            int64_t stride_t, int64_t stride_f, float p_drop, uint64_t seed, uint64_t offset,
-                            float momentum, int update_running_stats, float* logits, void* workspace,
-                            size_t workspace_bytes) {
-  TraceRange trace_("dfa_cnn1d_forward_train");
-  if (!ctx) return DFA_E_NULL_PTR;
+// lengths == nullptr: the uniform step
+int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
+                             int64_t stride_t, int64_t stride_f, const int32_t* lengths, float p_drop, uint64_t seed, uint64_t offset,
+                             float momentum, int update_running_stats, float* logits, void* workspace,
+                             size_t workspace_bytes) {
   Cnn1dState& m = ctx->cnn1d;
   const AugCfg armed = m.aug_armed;     // one-shot: consumed here, also by a call that fails its checks below
   m.aug_armed = AugCfg{};
@@ -503,13 +501,40 @@ int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   if (B < 1 || T < 1) return fail(ctx, DFA_E_BAD_SHAPE, "B and T must be >= 1 (got %d, %d)", B, T);
   if (F != m.in_features) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d", F, m.in_features);
   if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(ctx, DFA_E_BAD_SHAPE, "dropout p must be in [0, 1)");
+  double frames = (double)B * T;             // frames BatchNorm1d counts
+  if (lengths) {
+    if (T < 3) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: a ragged cnn1d batch needs T_max >= 3", T);
+    frames = 0.0;
+    for (int b = 0; b < B; ++b) {
+      if (lengths[b] < 3 || lengths[b] > T)
+        return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [3, T_max=%d]", b, (int)lengths[b], T);
+      frames += (double)lengths[b];
+    }
+  }
   const Train1dPlan pl = plan_train1d(B, T, F);
-  if (workspace_bytes < pl.total) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small: %zu < %zu bytes", workspace_bytes, pl.total);
+  const size_t need = pl.total + (lengths ? ragged1d_tab_bytes(B) : 0);
+  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small: %zu < %zu bytes", workspace_bytes, need);
   if (armed.on && (armed.T != T || armed.F != F))
     return fail(ctx, DFA_E_BAD_SHAPE, "armed augmentation is for [T=%d, F=%d], the batch is [T=%d, F=%d]", armed.T, armed.F, T, F);
+  DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int* lens = nullptr;                 // device table of a ragged batch
+  if (lengths) {
+    if (armed.on)
+      return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step takes no train augmentation (dfa_cnn1d_set_train_augment was armed): "
+                                          "a time roll has no per-utterance meaning yet");
+    if (ctx->bn_sync.fn)
+      return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed): "
+                                          "the ranks' frame counts differ and the hook carries sums only");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
+    if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
+      return fail(ctx, DFA_E_UNSUPPORTED, "the ragged training step cannot be captured into a graph: its lengths are copied per call");
+    const int rc = stage_ragged_lengths(ctx, lengths, B, (char*)workspace + pl.total);
+    if (rc != DFA_OK) return rc;
+    lens = (const int*)((char*)workspace + pl.total);
+  }
   m.train_aug = armed;
   const AugCfg* aug = m.train_aug.on ? &m.train_aug : nullptr;
-  DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (!m.train_packed) {
     const size_t n = al((size_t)64 * 32 * 3 * 4) + al((size_t)128 * 64 * 3 * 4) + al(256 * 4);
     DFA_HIP_CHECK(ctx, hipMalloc(&m.train_packed, n));
@@ -546,6 +571,7 @@ int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   dc.scale = 1.0f / (1.0f - p_drop);
   dc.seed = seed; dc.offset = offset;
   m.train_drop = dc; m.train_B = B; m.train_T = T;
+  m.train_ragged = lengths ? 1 : 0; m.train_frames = frames;
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
   const int C[3] = {32, 64, 128}, Cin[3] = {F, 32, 64};
@@ -555,9 +581,9 @@ int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
     const float* const* q = p + 6 * l;
     if (l == 0) {
       if (x3 && conv1d_x3_supports((const float*)x, stride_b, stride_f, stride_t, z, T, F, 32, terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3((const float*)x, stride_b, m.wx3[0], q[1], z, B, F, 32, T, terms, s, x3, aug));
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3((const float*)x, stride_b, m.wx3[0], q[1], z, B, F, 32, T, terms, s, x3, aug, lens));
       else
-        DFA_HIP_CHECK(ctx, launch_conv1d((const float*)x, stride_b, stride_f, stride_t, q[0], q[1], z, B, F, 32, T, false, s, false, aug));
+        DFA_HIP_CHECK(ctx, launch_conv1d((const float*)x, stride_b, stride_f, stride_t, q[0], q[1], z, B, F, 32, T, false, s, false, aug, lens));
     } else {
       const float* hin = (const float*)(ws + pl.h[l - 1]);
       if (x3 && conv1d_x3_supports(hin, (int64_t)Cin[l] * T, T, 1, z, T, Cin[l], C[l], terms))
@@ -566,37 +592,40 @@ int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
         DFA_HIP_CHECK(ctx, launch_conv1d(hin, (int64_t)Cin[l] * T, T, 1, q[0], q[1], z, B, Cin[l], C[l], T, false, s, false));
     }
     St st = st1d(ws, pl, l);
-    DFA_HIP_CHECK(ctx, launch_cm_stats(z, partial, B, C[l], T, s));
-    { const int rc = finalize_bn_stats(ctx, partial, nch, C[l], (double)B * T, st.mean, st.var, st.invstd,
+    DFA_HIP_CHECK(ctx, launch_cm_stats(z, partial, B, C[l], T, s, lens));
+    { const int rc = finalize_bn_stats(ctx, partial, nch, C[l], frames, st.mean, st.var, st.invstd,
                                        update_running_stats ? (float*)q[4] : nullptr, update_running_stats ? (float*)q[5] : nullptr, momentum, nullptr);
       if (rc != DFA_OK) return rc; }
     if (l < 2) {
       dc.layer = 1 + l;
-      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_drop(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.h[l]), B, C[l], T, dc, s));
+      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_drop(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.h[l]), B, C[l], T, dc, s, lens));
     } else {
-      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_meant(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.pooled), B, 128, T, s));
+      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_meant(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.pooled), B, 128, T, s, lens));
     }
   }
   DFA_HIP_CHECK(ctx, launch_linear((const float*)(ws + pl.pooled), p[18], p[19], logits, B, 128, s));
   return DFA_OK;
 }
 
-int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
-                       int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
-                       size_t workspace_bytes) {
-  TraceRange trace_("dfa_cnn1d_backward");
-  if (!ctx) return DFA_E_NULL_PTR;
+// ragged = which of the two entry points this is: it must be the one whose forward is in flight
+int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
+                        int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
+                        size_t workspace_bytes) {
   Cnn1dState& m = ctx->cnn1d;
-  if (!m.train_packed || m.train_B != B || m.train_T != T)
-    return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_backward must follow dfa_cnn1d_forward_train on the same batch");
+  if (!m.train_packed || m.train_B != B || m.train_T != T || m.train_ragged != ragged)
+    return ragged ? fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_backward_ragged must follow dfa_cnn1d_forward_train_ragged on the same batch")
+                  : fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_backward must follow dfa_cnn1d_forward_train on the same batch");
   if (!x || !dlogits || !grads || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, dlogits, grads and workspace must be non-null");
   if (x_dtype != DFA_DTYPE_F32) return fail(ctx, DFA_E_BAD_DTYPE, "cnn1d takes float32 input");
   if (ngrads != 14) return fail(ctx, DFA_E_BAD_SHAPE, "cnn1d has 14 parameters, got %d gradient pointers", ngrads);
   for (int i = 0; i < 14; ++i)
     if (!grads[i]) return fail(ctx, DFA_E_NULL_PTR, "gradient pointer %d is null", i);
   const Train1dPlan pl = plan_train1d(B, T, F);
-  if (workspace_bytes < pl.total) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small");
+  if (workspace_bytes < pl.total + (ragged ? ragged1d_tab_bytes(B) : 0)) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small");
+  if (ragged && ctx->bn_sync.fn)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed)");
   char* ws = (char*)workspace;
+  const int* lens = ragged ? (const int*)(ws + pl.total) : nullptr;     // the table the forward left behind the plan
   float* partial = (float*)(ws + pl.partial);
   const float* const* p = m.p;
   hipStream_t s = ctx->stream;
@@ -612,11 +641,11 @@ int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
     const float* up = (l == 2) ? dpooled : (const float*)(ws + pl.dh[l]);
     dc.layer = 1 + l;
     DFA_HIP_CHECK(ctx, launch_cm_bn_bwd(l == 2 ? 0 : 1, (const float*)(ws + pl.z[l]), st.mean, st.invstd, q[2], q[3], up, partial, sm, dz,
-                                        B, C[l], T, dc, s, ctx->bn_sync.fn ? &ctx->bn_sync : nullptr));
+                                        B, C[l], T, dc, s, ctx->bn_sync.fn ? &ctx->bn_sync : nullptr, lens, m.train_frames));
     hipLaunchKernelGGL(split_sums_kernel, dim3(1), dim3(128), 0, s, sm, grads[4 * l + 2], grads[4 * l + 3], C[l]);
     if (l == 0) {
       DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)x, stride_b, stride_f, stride_t, partial, grads[0], grads[1], B, F, 32, T, s,
-                                             m.train_aug.on ? &m.train_aug : nullptr, m.train_x3));
+                                             m.train_aug.on ? &m.train_aug : nullptr, m.train_x3, lens));
     } else {
       DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)(ws + pl.h[l - 1]), (int64_t)Cin[l] * T, T, 1, partial, grads[4 * l],
                                              grads[4 * l + 1], B, Cin[l], C[l], T, s, nullptr, m.train_x3));
@@ -631,6 +660,62 @@ int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
   }
   DFA_HIP_CHECK(ctx, hipGetLastError());
   return DFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dfa_cnn1d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F) {
+  (void)ctx;
+  if (B < 1 || T < 1 || F < 1) return 0;
+  return plan_train1d(B, T, F).total;
+}
+
+int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
+                            int64_t stride_t, int64_t stride_f, float p_drop, uint64_t seed, uint64_t offset,
+                            float momentum, int update_running_stats, float* logits, void* workspace,
+                            size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_forward_train");
+  if (!ctx) return DFA_E_NULL_PTR;
+  return cnn1d_forward_train_impl(ctx, x, x_dtype, B, T, F, stride_b, stride_t, stride_f, nullptr, p_drop, seed, offset, momentum,
+                                  update_running_stats, logits, workspace, workspace_bytes);
+}
+
+int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
+                       int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
+                       size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_backward");
+  if (!ctx) return DFA_E_NULL_PTR;
+  return cnn1d_backward_impl(ctx, 0, x, x_dtype, B, T, F, stride_b, stride_t, stride_f, dlogits, grads, ngrads, workspace, workspace_bytes);
+}
+
+size_t dfa_cnn1d_train_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F) {
+  (void)ctx;
+  if (B < 1 || T_max < 3 || F < 1) return 0;
+  return plan_train1d(B, T_max, F).total + ragged1d_tab_bytes(B);
+}
+
+int dfa_cnn1d_forward_train_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,
+                                   int64_t stride_t, int64_t stride_f, const int32_t* lengths, float p_drop, uint64_t seed,
+                                   uint64_t offset, float momentum, int update_running_stats, float* logits, void* workspace,
+                                   size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_forward_train_ragged");
+  if (!ctx) return DFA_E_NULL_PTR;
+  if (!lengths) {
+    ctx->cnn1d.aug_armed = AugCfg{};      // one-shot, as in every forward_train
+    return fail(ctx, DFA_E_NULL_PTR, "lengths must be non-null");
+  }
+  return cnn1d_forward_train_impl(ctx, x, x_dtype, B, T_max, F, stride_b, stride_t, stride_f, lengths, p_drop, seed, offset, momentum,
+                                  update_running_stats, logits, workspace, workspace_bytes);
+}
+
+int dfa_cnn1d_backward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b, int64_t stride_t,
+                              int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
+                              size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_backward_ragged");
+  if (!ctx) return DFA_E_NULL_PTR;
+  return cnn1d_backward_impl(ctx, 1, x, x_dtype, B, T_max, F, stride_b, stride_t, stride_f, dlogits, grads, ngrads, workspace, workspace_bytes);
 }
 
 }  // extern "C"

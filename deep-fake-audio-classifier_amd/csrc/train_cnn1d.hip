@@ -8,16 +8,24 @@
 
 namespace dfa {
 
+// ---- RAGGED twins of the channel-major kernels below (dfa_cnn1d_forward_train_ragged / dfa_cnn1d_backward_ragged): the batch is
+// padded to T frames, utterance b owns frames [0, lens[b]) (lens = the device table the forward staged).  Sums and the time mean
+// run over an utterance's own frames in the uniform loops' order, the element-wise kernels write an exact zero at every padding
+// frame (the next convolution / weight gradient reads it as that utterance's zero padding).  Each of these kernels is one *_body function
+// instantiated twice: RAGGED = false behind the uniform kernel (name and arguments as before the twins existed), RAGGED = true behind
+// *_ragged_kernel, which takes the table.
+
 // ---- per-channel sum / sum of squares of z[B][C][T]: one block per (channel, batch chunk) -> partial[chunk][C][2]
-__global__ __launch_bounds__(256) void cm_stats_kernel(const float* __restrict__ z, float* __restrict__ partial, int B,
-                                                       int C, int T, int bchunk) {
+template <bool RAGGED>
+__device__ __forceinline__ void cm_stats_body(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens) {
   __shared__ float r1[256], r2[256];
   const int c = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
   const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
   float s1 = 0.f, s2 = 0.f;
   for (int b = b0; b < b1; ++b) {
     const float* row = z + ((size_t)b * C + c) * T;
-    for (int t = tid; t < T; t += 256) { const float v = row[t]; s1 += v; s2 = fmaf(v, v, s2); }
+    const int Tb = RAGGED ? lens[b] : T;
+    for (int t = tid; t < Tb; t += 256) { const float v = row[t]; s1 += v; s2 = fmaf(v, v, s2); }
   }
   r1[tid] = s1; r2[tid] = s2;
   __syncthreads();
@@ -26,6 +34,12 @@ __global__ __launch_bounds__(256) void cm_stats_kernel(const float* __restrict__
     __syncthreads();
   }
   if (tid == 0) { partial[((size_t)ch * C + c) * 2] = r1[0]; partial[((size_t)ch * C + c) * 2 + 1] = r2[0]; }
+}
+__global__ __launch_bounds__(256) void cm_stats_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk) {
+  cm_stats_body<false>(z, partial, B, C, T, bchunk, nullptr);
+}
+__global__ __launch_bounds__(256) void cm_stats_ragged_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens) {
+  cm_stats_body<true>(z, partial, B, C, T, bchunk, lens);
 }
 
 __device__ __forceinline__ float drop1(const DropCfg& dc, uint64_t idx) {
@@ -36,43 +50,50 @@ __device__ __forceinline__ float drop1(const DropCfg& dc, uint64_t idx) {
 }
 
 // ---- forward: h = dropout(relu(bn(z)))  (elementwise, [B][C][T])
-__global__ void cm_bn_relu_drop_kernel(const float* __restrict__ z, const float* __restrict__ mean,
-                                       const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                       const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n,
-                                       DropCfg dc) {
+template <bool RAGGED>
+__device__ __forceinline__ void cm_bn_relu_drop_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n, DropCfg dc, const int* __restrict__ lens) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int c = (int)((i / T) % C);
+  if constexpr (RAGGED) {
+    const size_t bc = i / T;
+    if ((int)(i - bc * T) >= lens[bc / C]) { h[i] = 0.f; return; }
+  }
   const float y = fmaf((z[i] - mean[c]) * invstd[c], gamma[c], beta[c]);
   h[i] = fmaxf(y, 0.f) * drop1(dc, i);
 }
+__global__ void cm_bn_relu_drop_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n, DropCfg dc) {
+  cm_bn_relu_drop_body<false>(z, mean, invstd, gamma, beta, h, C, T, n, dc, nullptr);
+}
+__global__ void cm_bn_relu_drop_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n, DropCfg dc, const int* __restrict__ lens) {
+  cm_bn_relu_drop_body<true>(z, mean, invstd, gamma, beta, h, C, T, n, dc, lens);
+}
 
 // ---- forward: pooled[b][c] = mean_t relu(bn(z[b][c][t]))   (one wave per (b, c) row)
-__global__ __launch_bounds__(256) void cm_bn_relu_meant_kernel(const float* __restrict__ z, const float* __restrict__ mean,
-                                                               const float* __restrict__ invstd,
-                                                               const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, float* __restrict__ pooled,
-                                                               int C, int T, int rows) {
+template <bool RAGGED>
+__device__ __forceinline__ void cm_bn_relu_meant_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ pooled, int C, int T, int rows, const int* __restrict__ lens) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int c = row % C;
   const float sc = gamma[c] * invstd[c], sh = beta[c] - mean[c] * sc;
   float s = 0.f;
-  for (int t = lane; t < T; t += 64) s += fmaxf(fmaf(z[(size_t)row * T + t], sc, sh), 0.f);
+  const int Tb = RAGGED ? lens[row / C] : T;
+  for (int t = lane; t < Tb; t += 64) s += fmaxf(fmaf(z[(size_t)row * T + t], sc, sh), 0.f);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) pooled[row] = s / (float)T;
+  if (lane == 0) pooled[row] = s / (float)Tb;
+}
+__global__ __launch_bounds__(256) void cm_bn_relu_meant_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ pooled, int C, int T, int rows) {
+  cm_bn_relu_meant_body<false>(z, mean, invstd, gamma, beta, pooled, C, T, rows, nullptr);
+}
+__global__ __launch_bounds__(256) void cm_bn_relu_meant_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ pooled, int C, int T, int rows, const int* __restrict__ lens) {
+  cm_bn_relu_meant_body<true>(z, mean, invstd, gamma, beta, pooled, C, T, rows, lens);
 }
 
 // ---- BatchNorm1d backward, channel-major.  Upstream gradient of the BN output after the ReLU mask:
 //   SRC 0 (mean over T then Linear): dy = (y > 0) * dpooled[b][c] / T;   SRC 1 (dropout): dy = (y > 0) * dropscale * dh[b][c][t]
-template <int SRC>
-__global__ __launch_bounds__(256) void cm_bn_bwd_reduce_kernel(const float* __restrict__ z, const float* __restrict__ mean,
-                                                               const float* __restrict__ invstd,
-                                                               const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta,
-                                                               const float* __restrict__ up, float* __restrict__ partial,
-                                                               int B, int C, int T, int bchunk, DropCfg dc) {
+template <int SRC, bool RAGGED>
+__device__ __forceinline__ void cm_bn_bwd_reduce_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ up, float* __restrict__ partial, int B, int C, int T, int bchunk, DropCfg dc, const int* __restrict__ lens) {
   __shared__ float r1[256], r2[256];
   const int c = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
   const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
@@ -80,9 +101,10 @@ __global__ __launch_bounds__(256) void cm_bn_bwd_reduce_kernel(const float* __re
   float s1 = 0.f, s2 = 0.f;
   for (int b = b0; b < b1; ++b) {
     const size_t base = ((size_t)b * C + c) * T;
-    for (int t = tid; t < T; t += 256) {
+    const int Tb = RAGGED ? lens[b] : T;
+    for (int t = tid; t < Tb; t += 256) {
       const float xh = (z[base + t] - mu) * is;
-      float g = (SRC == 0) ? up[(size_t)b * C + c] / (float)T : up[base + t] * drop1(dc, base + t);
+      float g = (SRC == 0) ? up[(size_t)b * C + c] / (float)Tb : up[base + t] * drop1(dc, base + t);
       const float dy = (fmaf(gm, xh, bt) > 0.f) ? g : 0.f;
       s1 += dy;
       s2 = fmaf(dy, xh, s2);
@@ -96,31 +118,52 @@ __global__ __launch_bounds__(256) void cm_bn_bwd_reduce_kernel(const float* __re
   }
   if (tid == 0) { partial[((size_t)ch * C + c) * 2] = r1[0]; partial[((size_t)ch * C + c) * 2 + 1] = r2[0]; }
 }
-
 template <int SRC>
-__global__ void cm_bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ mean,
-                                       const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                       const float* __restrict__ beta, const float* __restrict__ sums,
-                                       const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n,
-                                       float inv_n, DropCfg dc) {
+__global__ __launch_bounds__(256) void cm_bn_bwd_reduce_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ up, float* __restrict__ partial, int B, int C, int T, int bchunk, DropCfg dc) {
+  cm_bn_bwd_reduce_body<SRC, false>(z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc, nullptr);
+}
+template <int SRC>
+__global__ __launch_bounds__(256) void cm_bn_bwd_reduce_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ up, float* __restrict__ partial, int B, int C, int T, int bchunk, DropCfg dc, const int* __restrict__ lens) {
+  cm_bn_bwd_reduce_body<SRC, true>(z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc, lens);
+}
+
+template <int SRC, bool RAGGED>
+__device__ __forceinline__ void cm_bn_bwd_apply_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n, float inv_n, DropCfg dc, const int* __restrict__ lens) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int c = (int)((i / T) % C);
   const size_t bc = i / T;
+  int Tb = T;
+  if constexpr (RAGGED) {
+    Tb = lens[bc / C];
+    if ((int)(i - bc * T) >= Tb) { dz[i] = 0.f; return; }      // an exact zero: the padding frame is no frame of the batch
+  }
   const float xh = (z[i] - mean[c]) * invstd[c];
-  const float g = (SRC == 0) ? up[bc] / (float)T : up[i] * drop1(dc, i);
+  const float g = (SRC == 0) ? up[bc] / (float)Tb : up[i] * drop1(dc, i);
   const float dy = (fmaf(gamma[c], xh, beta[c]) > 0.f) ? g : 0.f;
   dz[i] = gamma[c] * invstd[c] * (dy - sums[2 * c] * inv_n - xh * sums[2 * c + 1] * inv_n);
+}
+template <int SRC>
+__global__ void cm_bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n, float inv_n, DropCfg dc) {
+  cm_bn_bwd_apply_body<SRC, false>(z, mean, invstd, gamma, beta, sums, up, dz, C, T, n, inv_n, dc, nullptr);
+}
+template <int SRC>
+__global__ void cm_bn_bwd_apply_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n, float inv_n, DropCfg dc, const int* __restrict__ lens) {
+  cm_bn_bwd_apply_body<SRC, true>(z, mean, invstd, gamma, beta, sums, up, dz, C, T, n, inv_n, dc, lens);
 }
 
 // ---- Conv1d weight gradient: dW[o][c][k] = sum_{b,t} dz[b][o][t] * h[b][c][t+k-1],  db[o] = sum dz.
 // Block = (16 output channels x 16 input channels) tile for one batch chunk; thread (o, c) keeps its 3 taps (+ bias
 // sum) in registers and walks time through LDS slabs of 64 frames.  partial[chunk][Cout][Cin][3] (+ [Cout] for db).
+// RAGGED (all three weight-gradient kernels, layer 1 of a ragged batch): h = x padded to T frames, utterance b owns [0, lens[b]); a
+// padding frame is never loaded (it may hold NaN / Inf, and dz = 0 there would not clear it) -- another bound in the load, in a
+// branch of its own so that the uniform and AUG instantiations keep their code.
 constexpr int W1D_TT = 64;
+template <bool RAGGED = false>
 __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ h,
                                                            int64_t hsb, int64_t hsc, int64_t hst,
                                                            float* __restrict__ partial, int B, int Cin, int Cout, int T,
-                                                           int bchunk) {
+                                                           int bchunk, const int* __restrict__ lens = nullptr) {
   __shared__ float dzs[16][W1D_TT];
   __shared__ float hs[16][W1D_TT + 2];
   const int tid = threadIdx.x, ol = tid >> 4, cl = tid & 15;
@@ -137,6 +180,9 @@ __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(const float* __restri
       for (int e = tid; e < 16 * (W1D_TT + 2); e += 256) {
         const int cc = e / (W1D_TT + 2), tt = e - cc * (W1D_TT + 2);
         const int t = t0 - 1 + tt, ci = c0 + cc;
+        if constexpr (RAGGED)
+          hs[cc][tt] = (ci < Cin && t >= 0 && t < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
+        else
         hs[cc][tt] = (ci < Cin && t >= 0 && t < T) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
       }
       __syncthreads();
@@ -165,11 +211,11 @@ __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(const float* __restri
 // them straight from LDS tiles (lane = channel, k = frame parity).  One wave per (o tile, c tile, utterance chunk):
 // 96 MFMAs per 64-frame slab; the VALU kernel above spent 4 LDS reads on every 3 FMAs and ran at 128-512 blocks.
 // AUG (layer 1 only): h = x read through the armed train-time augmentation, as the forward read it (conv1d.hip)
-template <bool AUG>
+template <bool AUG, bool RAGGED = false>
 __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __restrict__ dz, const float* __restrict__ h,
                                                                int64_t hsb, int64_t hsc, int64_t hst,
                                                                float* __restrict__ partial, int B, int Cin, int Cout, int T,
-                                                               int bchunk, AugCfg aug) {
+                                                               int bchunk, AugCfg aug, const int* __restrict__ lens = nullptr) {
   __shared__ float dzs[32][W1D_TT + 1];
   __shared__ float hs[32][W1D_TT + 3];
   const int lane = threadIdx.x, r = lane & 31, hh = lane >> 5;
@@ -197,6 +243,8 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
       const int ci = c0 + cc;
       if constexpr (AUG)
         rh[cc] = (ci < Cin && t >= 0 && t < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)aug_src_t(aug, t) * hst], b, t, ci) : 0.f;
+      else if constexpr (RAGGED)
+        rh[cc] = (ci < Cin && t >= 0 && t < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
       else
         rh[cc] = (ci < Cin && t >= 0 && t < T) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
     }
@@ -204,6 +252,8 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
     const int ci2 = c0 + (lane & 31), t2 = t0 + 63 + (lane >> 5);
     if constexpr (AUG)
       rh2 = (ci2 < Cin && t2 < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)aug_src_t(aug, t2) * hst], b, t2, ci2) : 0.f;
+    else if constexpr (RAGGED)
+      rh2 = (ci2 < Cin && t2 < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
     else
       rh2 = (ci2 < Cin && t2 < T) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
   };
@@ -264,11 +314,11 @@ __device__ __forceinline__ f32x16_t w1d_mma(const uint4& a, const uint4& b, f32x
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
 
-template <bool AUG>
+template <bool AUG, bool RAGGED = false>
 __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __restrict__ dz, const float* __restrict__ h,
                                                              int64_t hsb, int64_t hsc, int64_t hst,
                                                              float* __restrict__ partial, int B, int Cin, int Cout, int T,
-                                                             int bchunk, AugCfg aug) {
+                                                             int bchunk, AugCfg aug, const int* __restrict__ lens = nullptr) {
   constexpr int PITCH = 68;
   __shared__ __attribute__((aligned(16))) float dzs[32][PITCH];
   __shared__ __attribute__((aligned(16))) float hs[32][PITCH];      // hs[c][i] = frame t0 - 1 + i, i < 66 (67 = zero)
@@ -295,12 +345,16 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __rest
       const int ci = c0 + cc;
       if constexpr (AUG)
         rh[cc] = (ci < Cin && t >= 0 && t < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)aug_src_t(aug, t) * hst], b, t, ci) : 0.f;
+      else if constexpr (RAGGED)
+        rh[cc] = (ci < Cin && t >= 0 && t < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
       else
         rh[cc] = (ci < Cin && t >= 0 && t < T) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
     }
     const int ci2 = c0 + (lane & 31), t2 = t0 + 63 + (lane >> 5);
     if constexpr (AUG)
       rh2 = (ci2 < Cin && t2 < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)aug_src_t(aug, t2) * hst], b, t2, ci2) : 0.f;
+    else if constexpr (RAGGED)
+      rh2 = (ci2 < Cin && t2 < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
     else
       rh2 = (ci2 < Cin && t2 < T) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
   };
@@ -388,33 +442,39 @@ __global__ __launch_bounds__(256) void reduce_record2_kernel(const float* __rest
 constexpr int kCmChunks = 64;   // batch chunks of the channel-major reductions: 16 left the 32->64 weight gradient at 128 blocks on 256 CUs
 int cm_chunks(int B) { return B < kCmChunks ? B : kCmChunks; }
 
-hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s) {
+hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens) {
   const int nch = cm_chunks(B), bchunk = (B + nch - 1) / nch;
-  hipLaunchKernelGGL(cm_stats_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk);
+  if (lens) hipLaunchKernelGGL(cm_stats_ragged_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, lens);
+  else hipLaunchKernelGGL(cm_stats_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk);
   return hipGetLastError();
 }
 hipError_t launch_cm_bn_relu_drop(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                  const float* beta, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s) {
+                                  const float* beta, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s, const int* lens) {
   const size_t n = (size_t)B * C * T;
-  hipLaunchKernelGGL(cm_bn_relu_drop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, mean, invstd, gamma, beta, h, C, T, n, dc);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (lens) hipLaunchKernelGGL(cm_bn_relu_drop_ragged_kernel, grid, dim3(256), 0, s, z, mean, invstd, gamma, beta, h, C, T, n, dc, lens);
+  else hipLaunchKernelGGL(cm_bn_relu_drop_kernel, grid, dim3(256), 0, s, z, mean, invstd, gamma, beta, h, C, T, n, dc);
   return hipGetLastError();
 }
 hipError_t launch_cm_bn_relu_meant(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                   const float* beta, float* pooled, int B, int C, int T, hipStream_t s) {
+                                   const float* beta, float* pooled, int B, int C, int T, hipStream_t s, const int* lens) {
   const int rows = B * C;
-  hipLaunchKernelGGL(cm_bn_relu_meant_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, z, mean, invstd, gamma, beta, pooled, C, T, rows);
+  if (lens) hipLaunchKernelGGL(cm_bn_relu_meant_ragged_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, z, mean, invstd, gamma, beta, pooled, C, T, rows, lens);
+  else hipLaunchKernelGGL(cm_bn_relu_meant_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, z, mean, invstd, gamma, beta, pooled, C, T, rows);
   return hipGetLastError();
 }
+// lens != null: the ragged twins, n_valid = the batch's frame count (sum of the lengths)
 hipError_t launch_cm_bn_bwd(int src, const float* z, const float* mean, const float* invstd, const float* gamma,
                             const float* beta, const float* up, float* partial, float* sums, float* dz, int B, int C,
-                            int T, const DropCfg& dc, hipStream_t s, const BnSync* sync) {
+                            int T, const DropCfg& dc, hipStream_t s, const BnSync* sync, const int* lens, double n_valid) {
   const int nch = cm_chunks(B), bchunk = (B + nch - 1) / nch;
   const size_t n = (size_t)B * C * T;
-  float inv_n = (float)(1.0 / ((double)B * T));
-  if (src == 0)
-    hipLaunchKernelGGL(cm_bn_bwd_reduce_kernel<0>, dim3(C, nch), dim3(256), 0, s, z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc);
-  else
-    hipLaunchKernelGGL(cm_bn_bwd_reduce_kernel<1>, dim3(C, nch), dim3(256), 0, s, z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc);
+  float inv_n = (float)(1.0 / (lens ? n_valid : (double)B * T));
+  const dim3 rgrid(C, nch), agrid((unsigned)((n + 255) / 256));
+  auto reduce = [&](auto kern) { hipLaunchKernelGGL(kern, rgrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc); };
+  auto reduce_r = [&](auto kern) { hipLaunchKernelGGL(kern, rgrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc, lens); };
+  if (src == 0) { if (lens) reduce_r(cm_bn_bwd_reduce_ragged_kernel<0>); else reduce(cm_bn_bwd_reduce_kernel<0>); }
+  else { if (lens) reduce_r(cm_bn_bwd_reduce_ragged_kernel<1>); else reduce(cm_bn_bwd_reduce_kernel<1>); }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = launch_reduce_partials(partial, nch, C * 2, 1.0f, sums, s, nullptr);
@@ -424,30 +484,39 @@ hipError_t launch_cm_bn_bwd(int src, const float* z, const float* mean, const fl
   e = bn_sync_sums(sync, sums, C * 2, s, &sums_a, &isc);          // synchronised BatchNorm: global sums, global count
   if (e != hipSuccess) return e;
   inv_n *= isc;
-  if (src == 0)
-    hipLaunchKernelGGL(cm_bn_bwd_apply_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, mean, invstd, gamma, beta, sums_a, up, dz, C, T, n, inv_n, dc);
-  else
-    hipLaunchKernelGGL(cm_bn_bwd_apply_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, mean, invstd, gamma, beta, sums_a, up, dz, C, T, n, inv_n, dc);
+  auto apply = [&](auto kern) { hipLaunchKernelGGL(kern, agrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, sums_a, up, dz, C, T, n, inv_n, dc); };
+  auto apply_r = [&](auto kern) { hipLaunchKernelGGL(kern, agrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, sums_a, up, dz, C, T, n, inv_n, dc, lens); };
+  if (src == 0) { if (lens) apply_r(cm_bn_bwd_apply_ragged_kernel<0>); else apply(cm_bn_bwd_apply_kernel<0>); }
+  else { if (lens) apply_r(cm_bn_bwd_apply_ragged_kernel<1>); else apply(cm_bn_bwd_apply_kernel<1>); }
   return hipGetLastError();
 }
 // partial: conv1d_wgrad_chunks(B) * (Cout*Cin*3 + Cout) floats
 int conv1d_wgrad_chunks(int B) { return B < 256 ? B : 256; }
 hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int64_t hsc, int64_t hst, float* partial,
-                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug, int x3) {
+                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug, int x3, const int* lens) {
   const int nch = conv1d_wgrad_chunks(B), bchunk = (B + nch - 1) / nch;
+  if (lens && aug && aug->on) return hipErrorInvalidValue;     // a time roll has no per-utterance meaning
+  if (lens) {                      // ragged layer 1: h = the padded x, bounded per utterance in the loads
+    if (x3 && Cout % 32 == 0)
+      hipLaunchKernelGGL((conv1d_wgrad_x3_kernel<false, true>), dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, lens);
+    else if (Cout % 32 == 0)
+      hipLaunchKernelGGL((conv1d_wgrad_mfma_kernel<false, true>), dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, lens);
+    else
+      hipLaunchKernelGGL(conv1d_wgrad_kernel<true>, dim3(Cout / 16, (Cin + 15) / 16, nch), dim3(256), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, lens);
+  } else
   if (x3 && Cout % 32 == 0) {      // three-term bf16 matrix-core form (fp32-grade sums)
     const dim3 grid(Cout / 32, (Cin + 31) / 32, nch);
     if (aug && aug->on)
-      hipLaunchKernelGGL(conv1d_wgrad_x3_kernel<true>, grid, dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, *aug);
+      hipLaunchKernelGGL(conv1d_wgrad_x3_kernel<true>, grid, dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, *aug, nullptr);
     else
-      hipLaunchKernelGGL(conv1d_wgrad_x3_kernel<false>, grid, dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{});
+      hipLaunchKernelGGL(conv1d_wgrad_x3_kernel<false>, grid, dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, nullptr);
   } else if (aug && aug->on) {
     if (Cout % 32 != 0) return hipErrorInvalidValue;   // the folded form exists for the MFMA kernel only (layer 1: Cout = 32)
-    hipLaunchKernelGGL(conv1d_wgrad_mfma_kernel<true>, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, *aug);
+    hipLaunchKernelGGL(conv1d_wgrad_mfma_kernel<true>, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, *aug, nullptr);
   } else if (Cout % 32 == 0)
-    hipLaunchKernelGGL(conv1d_wgrad_mfma_kernel<false>, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{});
+    hipLaunchKernelGGL(conv1d_wgrad_mfma_kernel<false>, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, nullptr);
   else
-    hipLaunchKernelGGL(conv1d_wgrad_kernel, dim3(Cout / 16, (Cin + 15) / 16, nch), dim3(256), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk);
+    hipLaunchKernelGGL(conv1d_wgrad_kernel<false>, dim3(Cout / 16, (Cin + 15) / 16, nch), dim3(256), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, nullptr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int n = Cout * Cin * 3;

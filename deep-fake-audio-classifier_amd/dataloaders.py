@@ -315,10 +315,16 @@ class RaggedBatcher:
     labels: [b] on `device` or None; lengths: int32 [b] on the CPU.  rank/world shard the utterances contiguously like
     FlatBatcher.  Each utterance's output is independent of its batch companions, so a shard is walked in order of length
     (longest first) to cut padding; `restore` puts per-batch outputs back in input order.
+
+    shuffle_seed (training): every pass over the batcher is a new epoch with its own batches.  The shard is permuted by a
+    generator seeded with (shuffle_seed, epoch), cut into buckets of `bucket` utterances (rounded to whole batches; default 16
+    batches), each bucket is sorted by length (longest first) and cut into batches -- companions are similar in length, yet
+    change from epoch to epoch -- and the batch order is shuffled.  Every utterance appears exactly once per epoch; `batches`
+    (and `restore`) describe the latest pass.  shuffle_seed=None: the fixed longest-first order above.
     """
 
     def __init__(self, features, labels=None, batch_size: int = 32, device="cuda", rank: int = 0, world: int = 1,
-                 dtype: torch.dtype | None = None):
+                 dtype: torch.dtype | None = None, *, shuffle_seed: int | None = None, bucket: int | None = None):
         n = len(features)
         per = -(-n // world)
         self.lo, self.hi = min(rank * per, n), min((rank + 1) * per, n)
@@ -330,12 +336,29 @@ class RaggedBatcher:
         lens = np.array([int(f.shape[-1]) for f in features[self.lo:self.hi]], dtype=np.int64)
         self.order = self.lo + np.argsort(-lens, kind="stable")          # longest first, ties in input order
         self.batches = [self.order[i:i + batch_size] for i in range(0, len(self.order), batch_size)]
+        self.shuffle_seed, self.epoch = shuffle_seed, 0
+        nb = 16 if bucket is None else max(1, -(-int(bucket) // batch_size))       # batches per bucket
+        self.bucket = nb * batch_size
+        self._lens = lens
 
     def __len__(self):
         return len(self.batches)
 
+    def _shuffled_batches(self, epoch: int):
+        rng = np.random.default_rng([int(self.shuffle_seed), int(epoch)])
+        perm = rng.permutation(self.hi - self.lo)
+        batches = []
+        for b0 in range(0, len(perm), self.bucket):
+            part = perm[b0:b0 + self.bucket]
+            part = part[np.argsort(-self._lens[part], kind="stable")]
+            batches += [self.lo + part[i:i + self.batch_size] for i in range(0, len(part), self.batch_size)]
+        return [batches[i] for i in rng.permutation(len(batches))]
+
     def __iter__(self):
         pin = self.device.type == "cuda"
+        if self.shuffle_seed is not None:
+            self.batches = self._shuffled_batches(self.epoch)
+            self.epoch += 1
         for idx in self.batches:
             utts = [torch.as_tensor(self.features[i]) for i in idx]
             dtype = self.dtype or utts[0].dtype

@@ -125,6 +125,31 @@ def evaluate_sharded(model, features: torch.Tensor, labels: torch.Tensor, criter
     return {"avg_loss": avg_loss, "eer": eer, "threshold": threshold}, scores.tolist(), y.tolist()
 
 
+def evaluate_ragged(model, features, labels, criterion=None, device="cuda", apply_sigmoid: bool = False, batch_size: int = 32):
+    """`evaluate` for a list of per-utterance [F, T_i] tensors (of unequal lengths, or not) with their 0/1 labels: batches
+    padded to their longest utterance (dataloaders.RaggedBatcher, longest first) through `model(x, lengths=...)`, logits put
+    back in input order (`restore`).  Same returns as `evaluate`: (metrics{avg_loss, eer, threshold}, scores, labels); the
+    loss is the criterion's mean over all utterances, which is what evaluate's sample-weighted mean of batch means is."""
+    from .dataloaders import RaggedBatcher
+    model.eval()
+    batcher = RaggedBatcher(features, None, batch_size, device=device)
+    outs = []
+    with torch.no_grad():
+        for x, _, lengths in batcher:
+            outs.append(model(x, lengths=lengths).squeeze(-1).detach())
+    if not outs:
+        return {"avg_loss": None, "eer": None, "threshold": None}, [], []
+    logits = batcher.restore(outs)
+    y = torch.as_tensor(np.asarray(labels), dtype=torch.float32).to(logits.device)
+    if y.numel() != logits.numel():
+        raise ValueError(f"{logits.numel()} scores for {y.numel()} labels")
+    avg_loss = float(criterion(logits, y).item()) if criterion is not None else None
+    out = torch.sigmoid(logits) if apply_sigmoid else logits
+    scores, labs = out.cpu().tolist(), y.cpu().tolist()
+    eer, threshold = calculate_eer(scores, labs)
+    return {"avg_loss": avg_loss, "eer": eer, "threshold": threshold}, scores, labs
+
+
 def verify_uttid_alignment(features_path: str, labels_path: str) -> None:
     """ValueError unless both pickles carry 'uttid' and describe the same utterances (src/evaluation.py:107-124)."""
     feats = pd.read_pickle(features_path)

@@ -23,7 +23,7 @@ from . import distributed as dfa_dist
 from .augmentation import FusedAugment, channel_drop, compose, gaussian_jitter, spec_augment, time_shift
 from .dataloaders import FlatBatcher, IndexedFlatBatcher, ResidentBatcher, make_loader, open_flat, train_shard_indices
 from .dataset import AudioDeepfakeDataset
-from .evaluation import evaluate, evaluate_sharded
+from .evaluation import evaluate, evaluate_ragged, evaluate_sharded
 from .model import CNN2D
 from .training import save_checkpoint
 
@@ -168,6 +168,54 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+def check_ragged_train_args(args, world: int = 1) -> None:
+    """Can a --train-features file whose utterances differ in length be trained on with these arguments?  Raises ValueError
+    naming the limitation when not: variable-length training is the CNN1D's all-native step on one rank, on the stored [F, T_i]
+    layout, without augmentation.  Pure: touches neither the GPU nor a file."""
+    head = "--train-features holds utterances of unequal lengths: "
+    if args.model != "cnn1d":
+        raise ValueError(head + f"variable-length training is --model cnn1d only in this version (got --model {args.model})")
+    if not args.swap_tf:
+        raise ValueError(head + "--no-swap-tf is not supported for such a file (the stored [F, T] layout is the only ragged layout)")
+    aug = [f for f in ("spec_augment", "feature_mask", "time_shift", "channel_drop", "gaussian_jitter") if getattr(args, f, False)]
+    if aug:
+        raise ValueError(head + "train-time augmentation is not supported for such a file yet (a time roll has no per-utterance "
+                         "meaning): drop --" + " --".join(a.replace("_", "-") for a in aug))
+    if getattr(args, "sync_bn", False):
+        raise ValueError(head + "--sync-bn is not supported for such a file (the ranks' frame counts differ)")
+    if world > 1:
+        raise ValueError(head + f"variable-length training runs on one rank in this version (world size {world})")
+    if not args.native:
+        raise ValueError(head + "variable-length training needs --native (the all-native step; the autograd bridge has no "
+                         "variable-length form)")
+
+
+def _load_utterances(features_path, labels_path):
+    """(list of per-utterance [F, T_i] float tensors, labels float32 [N]) of a features.pkl / labels.pkl pair, merged on uttid."""
+    data = AudioDeepfakeDataset(features_path, labels_path).data
+    return [f.float() for f in data["features"]], np.asarray(data["label"].values, dtype=np.float32)
+
+
+def _ragged_train_set(args):
+    """The training utterances when --train-features is a features.pkl whose utterances differ in length, else None (a flat
+    prefix made by dfa_amd.ingest is uniform by construction)."""
+    if os.path.exists(args.train_features + ".npy") and os.path.exists(args.train_features + ".json"):
+        return None
+    utts, labels = _load_utterances(args.train_features, args.train_labels)
+    return (utts, labels) if len({tuple(u.shape) for u in utts}) > 1 else None
+
+
+def train_one_epoch_ragged(trainer, batcher):
+    """One pass with the all-native variable-length step; `batcher` is a dataloaders.RaggedBatcher with labels."""
+    total, count = None, 0
+    for x, labels, lengths in batcher:
+        loss = trainer.step(x, labels, lengths=lengths)
+        term = loss.detach().double().squeeze() * labels.size(0)
+        total = term if total is None else total + term
+        count += labels.size(0)
+    return (float(total.item()) / count) if count else None
+
+
 def set_seed(seed: int) -> None:
     random.seed(seed)
     np.random.seed(seed)
@@ -186,6 +234,10 @@ def main(argv=None):
     if device.type == "cuda":
         torch.cuda.set_device(device)
     rank, world = dfa_dist.init(device=device)
+    # utterances of unequal lengths: the CNN1D's variable-length native step (checked before a model or a file cache exists)
+    ragged_set = _ragged_train_set(args)
+    if ragged_set is not None:
+        check_ragged_train_args(args, world)
     out_dir = os.path.join(args.checkpoint_dir, args.run_name) if args.run_name else args.checkpoint_dir
     best_path, last_path = os.path.join(out_dir, f"{args.model}_best.pt"), os.path.join(out_dir, f"{args.model}_last.pt")
 
@@ -206,7 +258,15 @@ def main(argv=None):
 
     flat_mode = args.native or world > 1          # one flat parameter / gradient buffer, one all-reduce per step
     trainer = None
-    if flat_mode:
+    ragged_batcher = None
+    if ragged_set is not None:
+        from .dataloaders import RaggedBatcher
+        from .training.train_step import NativeTrainer
+        optimizer = trainer = NativeTrainer(model, lr=args.lr, weight_decay=weight_decay, label_smoothing=args.label_smoothing)
+        # a new set of length-bucketed batches every epoch, drawn from the run seed
+        ragged_batcher = RaggedBatcher(ragged_set[0], ragged_set[1], args.batch_size, device=device, shuffle_seed=args.seed)
+        dev_utts, dev_utt_labels = _load_utterances(args.dev_features, args.dev_labels)
+    elif flat_mode:
         from .training.train_step import NativeTrainer
         # all-C-ABI step for both classifiers: 464,644-byte (CNN2D) / 195,204-byte (CNN1D) flat gradient, one all-reduce
         trainer = NativeTrainer(model, lr=args.lr, weight_decay=weight_decay, label_smoothing=args.label_smoothing,
@@ -236,7 +296,12 @@ def main(argv=None):
     no_improve, last_epoch = 0, 0
     resident = None
     for epoch in range(1, args.epochs + 1):
-        if flat_mode:
+        if ragged_batcher is not None:
+            train_loss = train_one_epoch_ragged(trainer, ragged_batcher)
+            model._prepared = None
+            metrics, _, _ = evaluate_ragged(model, dev_utts, dev_utt_labels, criterion=criterion, device=device,
+                                            batch_size=args.batch_size)
+        elif flat_mode:
             # every rank draws the SAME permutation and takes its rows of every global batch: equal step counts and equal
             # local batch sizes on all ranks (dataloaders.train_shard_indices)
             perm = torch.randperm(feats.shape[0], generator=torch.Generator().manual_seed(args.seed + epoch))

@@ -21,7 +21,7 @@ from .. import _lib
 KINDS = {"CNN2D": "cnn2d", "CNN1D": "cnn1d", "ConvAutoencoder": "cae"}      # model class -> C-ABI prefix / context slot
 
 # what a raw backward needs from its forward: the context, the workspace that holds the saved activations, the forward's
-# generation on the context's slot and its batch key (B, T, F, precision, x dtype)
+# generation on the context's slot and its batch key (B, T, F, precision, x dtype, lengths of a ragged batch or None)
 TrainState = namedtuple("TrainState", "ctx ws gen key")
 
 
@@ -53,9 +53,17 @@ def _bind(model, ctx, kind):
     model._prepared = None   # eval-mode folded images are stale after any training step
 
 
-def _batch_key(model, kind, x):
+def _batch_key(model, kind, x, lengths=None):
     B, T, F = x.shape
-    return B, T, F, (None if kind == "cnn1d" else _lib.PRECISIONS[model.precision]), x.dtype
+    return (B, T, F, (None if kind == "cnn1d" else _lib.PRECISIONS[model.precision]), x.dtype,
+            None if lengths is None else tuple(int(v) for v in lengths))
+
+
+def _ragged_lengths(model, x, lengths):
+    """Host int32 lengths of a ragged training batch, checked before anything is launched (CNN1D only in this version)."""
+    if type(model).__name__ != "CNN1D":
+        raise ValueError(f"variable-length (ragged) training is CNN1D only in this version, got {type(model).__name__}")
+    return _lib.host_lengths(lengths, x.shape[0], x.shape[1], 3)
 
 
 def _next_dropout_offset(model, n_elems):
@@ -64,23 +72,28 @@ def _next_dropout_offset(model, n_elems):
     return off
 
 
-def forward_train_raw(model, x, want=("recon", "latent")):
+def forward_train_raw(model, x, want=("recon", "latent"), lengths=None):
     """One train-mode forward (dfa_<kind>_forward_train: batch statistics, running statistics updated, dropout in the
     classifiers); returns (outputs, TrainState).  outputs: (logits[B,1],) for the classifiers; for the auto-encoder the
-    tensors named in `want` out of recon[B,T,F], latent[B,8C,T/16,F/16] and the per-sample mse[B], in that order."""
+    tensors named in `want` out of recon[B,T,F], latent[B,8C,T/16,F/16] and the per-sample mse[B], in that order.
+    lengths (CNN1D): x is a ragged batch padded to T frames, utterance b is x[b, :lengths[b]] -- the step of
+    dfa_cnn1d_forward_train_ragged (BatchNorm statistics over the valid frames only); `backward_raw` then runs its backward."""
     kind = KINDS[type(model).__name__]
+    if lengths is not None:
+        lengths = _ragged_lengths(model, x, lengths)
     if x.device.type != "cuda":
         raise RuntimeError(f"dfa_amd.{type(model).__name__} runs on the GPU only: move the input with .to('cuda')")
     if kind == "cnn1d" and x.dtype != torch.float32:
         raise ValueError(f"CNN1D takes float32 input, got {x.dtype}")
-    key = _batch_key(model, kind, x)
-    B, T, F, prec, _ = key
+    key = _batch_key(model, kind, x, lengths)
+    B, T, F, prec = key[:4]
     ctx = _lib.Context.get(x.device)
     lib, h = ctx.lib, ctx.handle
     with torch.cuda.device(ctx.index):
         ctx.use_current_stream()
         _bind(model, ctx, kind)
-        nbytes = getattr(lib, f"dfa_{kind}_train_workspace_bytes")(h, B, T, F, *(() if prec is None else (prec,)))
+        ragged = "_ragged" if lengths is not None else ""
+        nbytes = getattr(lib, f"dfa_{kind}_train{ragged}_workspace_bytes")(h, B, T, F, *(() if prec is None else (prec,)))
         if nbytes == 0:
             raise ValueError(f"bad {type(model).__name__} training shape (B={B}, T={T}, F={F})"
                              + (": need T >= 16 and F = 16k+4" if kind == "cae" else ""))
@@ -100,8 +113,10 @@ def forward_train_raw(model, x, want=("recon", "latent")):
             args = (float(model.dropout), seed, offset, 0.1, 1, _ptr(outs[0]))
             args = (prec, *args, None) if kind == "cnn2d" else args
             bns = [model.conv[i] for i in model._BN_IDX]
-        _lib.check(h, getattr(lib, f"dfa_{kind}_forward_train")(h, _ptr(x), _lib.x_dtype_code(x), B, T, F, *x.stride(), *args,
-                                                                 _ptr(ws), ws.numel()))
+        if lengths is not None:
+            args = (lengths.ctypes.data_as(C.c_void_p), *args)
+        _lib.check(h, getattr(lib, f"dfa_{kind}_forward_train{ragged}")(h, _ptr(x), _lib.x_dtype_code(x), B, T, F, *x.stride(), *args,
+                                                                         _ptr(ws), ws.numel()))
         torch._foreach_add_([bn.num_batches_tracked for bn in bns], 1)      # one multi-tensor launch
     st = TrainState(ctx, ws, ctx.next_train_gen(kind), key)
     model.__dict__["_train_last"] = (st.gen, key)        # for the per-model entry points below (no Module.__setattr__)
@@ -116,12 +131,13 @@ def backward_raw(model, x, dout, grads, st):
     kind = KINDS[type(model).__name__]
     ctx = st.ctx
     ctx.check_train_gen(kind, st.gen, model)
-    if _batch_key(model, kind, x) != st.key:
+    if _batch_key(model, kind, x) != (*st.key[:5], None):
         raise RuntimeError("backward called with a batch shape / precision / dtype other than its forward's")
     B, T, F = x.shape
+    ragged = "_ragged" if len(st.key) > 5 and st.key[5] is not None else ""       # the forward's table is in its workspace
     with torch.cuda.device(ctx.index):
         ctx.use_current_stream()
-        _lib.check(ctx.handle, getattr(ctx.lib, f"dfa_{kind}_backward")(
+        _lib.check(ctx.handle, getattr(ctx.lib, f"dfa_{kind}_backward{ragged}")(
             ctx.handle, _ptr(x), _lib.x_dtype_code(x), B, T, F, *x.stride(), _ptr(dout), _lib.ptr_array(grads), len(grads),
             _ptr(st.ws), st.ws.numel()))
 
@@ -330,14 +346,22 @@ class NativeTrainer(_FlatAdamW):
         self.dlogits = None
         self.kind = KINDS[type(model).__name__]
 
-    def step(self, x, y):
-        """One optimisation step on batch (x[B,T,F], y[B]); returns the (device) loss scalar of this rank's batch."""
+    def step(self, x, y, lengths=None):
+        """One optimisation step on batch (x[B,T,F], y[B]); returns the (device) loss scalar of this rank's batch.
+        lengths (CNN1D, one rank): x is a ragged batch padded to T frames, utterance b is x[b, :lengths[b]]; the step is the
+        reference model's on the utterances concatenated along time (BatchNorm statistics over the valid frames, the time mean
+        over each utterance's own frames); frames past an utterance's length are never used."""
         model = self.model
+        if lengths is not None:                 # refused before anything is launched: the model class, SyncBN, the lengths
+            lengths = _ragged_lengths(model, x, lengths)
+            if self.bn_sync is not None:
+                raise ValueError("variable-length (ragged) training does not support sync_bn on more than one rank: the ranks' "
+                                 "frame counts differ and the synchronisation hook carries sums only")
         model.train()
         if self.bn_sync is not None:
             self.bn_sync.arm()
         try:
-            (logits,), st = forward_train_raw(model, x)
+            (logits,), st = forward_train_raw(model, x, lengths=lengths)
             B = x.shape[0]
             if self.dlogits is None or self.dlogits.numel() != B:
                 self.dlogits = torch.empty(B, dtype=torch.float32, device=x.device)

@@ -287,6 +287,29 @@ int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
                        int64_t stride_t, int64_t stride_f, const float* dlogits, float* const* grads, int ngrads,
                        void* workspace, size_t workspace_bytes);
 
+/* CNN1D training step on a variable-length (ragged) batch: x is the batch padded to T_max frames, utterance b is
+ * x[b, :lengths[b], :] with 3 <= lengths[b] <= T_max (lengths: HOST int32[B], validated here: DFA_E_BAD_SHAPE names the index).
+ * The step is the reference model's on the utterances concatenated along time: every Conv1d zero-pads an utterance at its own two
+ * ends, each BatchNorm1d takes its batch statistics over the N = sum lengths[b] valid frames (biased variance to normalise, the
+ * N / (N - 1) correction in the running variance, momentum as above), the time mean of utterance b runs over its own frames.
+ * Frames t >= lengths[b] of x are never used: they may hold anything, NaN and Inf included.  With every length equal to T_max the
+ * pair computes the uniform pair's results bit for bit.
+ *   workspace: dfa_cnn1d_train_ragged_workspace_bytes (the uniform plan at T_max plus the per-call table).  The backward reads the
+ *   table the forward left there, so it takes no lengths; the pairs do not mix: dfa_cnn1d_backward after a ragged forward, and
+ *   dfa_cnn1d_backward_ragged after a uniform one, return DFA_E_NOT_PREPARED.
+ *   DFA_E_UNSUPPORTED: a capturing stream (the lengths are copied per call), an armed dfa_cnn1d_set_train_augment (a time roll has no
+ *   per-utterance meaning), an armed dfa_ctx_set_bn_sync (the ranks' frame counts differ, the hook carries sums only).
+ * Everything else -- dtype (float32), strides, option cnn1d_train_x3, dropout, running statistics, gradients -- as in the
+ * uniform pair. */
+size_t dfa_cnn1d_train_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F);
+int dfa_cnn1d_forward_train_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,
+                                   int64_t stride_t, int64_t stride_f, const int32_t* lengths, float p_drop, uint64_t seed,
+                                   uint64_t offset, float momentum, int update_running_stats, float* logits, void* workspace,
+                                   size_t workspace_bytes);
+int dfa_cnn1d_backward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,
+                              int64_t stride_t, int64_t stride_f, const float* dlogits, float* const* grads, int ngrads,
+                              void* workspace, size_t workspace_bytes);
+
 /* ---- ConvAutoencoder (replaces ConvAutoencoder.forward, src/model_cae.py:83-125, and the per-sample MSE of
  *      src/evaluation_cae.py:52-53 / src/hybrid_ensemble.py:55) ------------------------------------------------ */
 /* params: 44 device pointers (fp32) in state_dict order without num_batches_tracked:

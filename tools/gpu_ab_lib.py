@@ -1,5 +1,5 @@
 """A/B two builds of the library (separate processes, alternating): DFA_LIB=<file name under lib/>; DFA_AB_MODE=train times the
-bf16 training step instead of the eval forward, DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
+bf16 training step instead of the eval forward, DFA_AB_MODE=train1d the CNN1D's (fp32) uniform training step, DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
 z-score fused) at [256, 321, 180]."""
 import os, sys, time, torch
 sys.path.insert(0, os.getcwd())
@@ -29,6 +29,24 @@ if os.environ.get("DFA_AB_MODE") == "train":
         torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 10 * 1e3)
     print(name, "train step ms median %.3f min %.3f" % (sorted(res)[2], min(res)),
           "losses", ["%.4f" % v for v in losses], "last %.4f" % float(last), flush=True)
+    sys.exit(0)
+if os.environ.get("DFA_AB_MODE") == "train1d":
+    from dfa_amd.model_cnn1d import CNN1D
+    from dfa_amd.training.train_step import NativeTrainer
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(1)
+    x = (torch.randn(256, 180, 321, generator=g) * 3.2 - 0.07).to(dev).transpose(1, 2)
+    y = (torch.rand(256, generator=g) > 0.5).float().to(dev)
+    torch.manual_seed(0)
+    tr = NativeTrainer(CNN1D(dropout=0.2).to(dev), label_smoothing=0.05, lr=1e-6)
+    losses = [float(tr.step(x, y)) for _ in range(5)]
+    res = []
+    for rnd in range(7):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(40): last = tr.step(x, y)
+        torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 40 * 1e3)
+    print(name, "cnn1d train step ms median %.4f min %.4f max %.4f" % (sorted(res)[3], min(res), max(res)),
+          "losses", ["%.6f" % v for v in losses], "last %.6f" % float(last), flush=True)
     sys.exit(0)
 if os.environ.get("DFA_AB_MODE") == "cae":
     from dfa_amd.model_cae import ConvAutoencoder

@@ -8,7 +8,10 @@
 Prints one JSON line: per leg the median utt/s and frames/s over the pairs, with min and max, and per pair ragged32 / loop.
 --stamps (cnn1d): one extra ragged call with the kernel's clock stamps on, reporting the share of the stamped workgroups'
 time spent in multi-segment utterances.
-usage: timeout -k 10 300 python tools/gpu_ragged_bench.py [--model cnn2d|cnn1d|cae] [--pairs 5] [--iters 20] [--stamps]"""
+--model cnn1d --train: the TRAINING step (NativeTrainer.step: forward, loss, backward, fused AdamW; dropout 0.2, tiny lr) in
+three alternating legs: ragged B=256 with lengths drawn with a fixed seed from [161, 384] (the matrix-core convolutions reach
+T <= 384), uniform_tmax [256, 384, 180] (the same convolution work) and uniform_mean [256, mean length, 180] (the same frames).
+usage: timeout -k 10 300 python tools/gpu_ragged_bench.py [--model cnn2d|cnn1d|cae] [--train] [--pairs 5] [--iters 20] [--stamps]"""
 import argparse
 import json
 import os
@@ -22,13 +25,58 @@ import dfa_amd  # noqa: E402,F401
 from dfa_amd.model import CNN2D  # noqa: E402
 
 
+def train_legs(args):
+    from dfa_amd.model_cnn1d import CNN1D
+    from dfa_amd.training.train_step import NativeTrainer
+    lengths = np.random.default_rng(321).integers(161, 385, size=256)
+    T_max, T_mean = 384, int(round(float(lengths.mean())))
+    gen = torch.Generator().manual_seed(1)
+    y = (torch.rand(256, generator=gen) > 0.5).float().to("cuda")
+    xs = {T: (torch.randn(256, 180, T, generator=gen) * 3.2 - 0.07).to("cuda").transpose(1, 2) for T in (T_max, T_mean)}
+    torch.manual_seed(0)
+    tr = NativeTrainer(CNN1D(dropout=0.2).to("cuda"), label_smoothing=0.05, lr=1e-6)     # tiny lr: every leg times the same regime
+    legs = {
+        "ragged": (lambda: tr.step(xs[T_max], y, lengths), int(lengths.sum())),
+        "uniform_tmax": (lambda: tr.step(xs[T_max], y), 256 * T_max),
+        "uniform_mean": (lambda: tr.step(xs[T_mean], y), 256 * T_mean),
+    }
+    res = {k: [] for k in legs}
+    for _ in range(3):
+        for fn, _ in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(args.pairs):
+        for name, (fn, _) in legs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(args.iters):
+                fn()
+            t1.record()
+            t1.synchronize()
+            res[name].append(t0.elapsed_time(t1) / args.iters)
+    out = {"model": "cnn1d", "mode": "train", "pairs": args.pairs, "iters": args.iters, "T_max": T_max, "T_mean": T_mean,
+           "mean_length": float(lengths.mean())}
+    for name, v in res.items():
+        ms = np.array(v)
+        out[name] = {"step_ms": float(np.median(ms)), "ms_min": float(ms.min()), "ms_max": float(ms.max()),
+                     "utt_per_s": 256e3 / float(np.median(ms)), "frames_per_s": legs[name][1] * 1e3 / float(np.median(ms))}
+    out["ragged_over_uniform_tmax_ms"] = out["ragged"]["step_ms"] / out["uniform_tmax"]["step_ms"]
+    out["ragged_over_uniform_mean_ms"] = out["ragged"]["step_ms"] / out["uniform_mean"]["step_ms"]
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--model", default="cnn2d", choices=["cnn2d", "cnn1d", "cae"])
     ap.add_argument("--stamps", action="store_true")
+    ap.add_argument("--train", action="store_true", help="cnn1d: time the training step instead of the forward")
     args = ap.parse_args()
+    if args.train:
+        if args.model != "cnn1d":
+            ap.error("--train: the variable-length training step exists for --model cnn1d only")
+        return train_legs(args)
     torch.manual_seed(0)
     lengths = np.random.default_rng(321).integers(161, 482, size=256)
     T_max = int(lengths.max())
