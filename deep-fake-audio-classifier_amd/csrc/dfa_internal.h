@@ -296,7 +296,7 @@ int stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void* dst)
 int cm_chunks(int B);
 int conv1d_wgrad_chunks(int B);
 // lens (device, [B]) != null selects the ragged twins: utterance b owns frames [0, lens[b]) of the T the batch is padded to
-hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens = nullptr);
+hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens = nullptr, bool shifted = false);
 hipError_t launch_cm_bn_relu_drop(const float* z, const float* mean, const float* invstd, const float* gamma,
                                   const float* beta, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s, const int* lens = nullptr);
 hipError_t launch_cm_bn_relu_meant(const float* z, const float* mean, const float* invstd, const float* gamma,
@@ -327,7 +327,8 @@ hipError_t launch_cae_dec4_mse(const void* d3, int prec, const float* w4, const 
 hipError_t launch_cae_latent_export(const void* lat, int prec, float* out, int B, int HW, int C, hipStream_t s);
 // train_elem.hip / train_conv1.hip / wgrad_mfma.hip
 hipError_t launch_bn_finalize(const float* partial, int nparts, int C, double n, float* mean, float* var, float* invstd,
-                              float* running_mean, float* running_var, float momentum, hipStream_t s);
+                              float* running_mean, float* running_var, float momentum, hipStream_t s,
+                              const float* shift = nullptr, int shift_stride = 0);   // sums of z - shift[c * shift_stride]
 hipError_t launch_reduce_partials(const float* partial, int nparts, int n, float scale, float* out, hipStream_t s,
                                   float* scratch = nullptr);
 hipError_t launch_reduce_partials_strided(const float* partial, int nparts, int stride, int off, int n, float* out,

@@ -81,11 +81,11 @@ struct StatPtrs { float *mean, *var, *invstd; };
 // the records are first reduced to one [C][2] record in the caller's buffer, summed over the ranks by the caller's hook, and the
 // statistics come from those sums and the global count -- every rank ends with the same mean / variance / running statistics.
 static int finalize_bn_stats(dfa_ctx* ctx, const float* partial, int nparts, int C, double n, float* mean, float* var, float* invstd,
-                             float* rm, float* rv, float momentum, float* scratch) {
+                             float* rm, float* rv, float momentum, float* scratch, const float* shift = nullptr, int shift_stride = 0) {
   const dfa::BnSync& sy = ctx->bn_sync;
   hipStream_t s = ctx->stream;
-  if (!sy.fn) {
-    DFA_HIP_CHECK(ctx, launch_bn_finalize(partial, nparts, C, n, mean, var, invstd, rm, rv, momentum, s));
+  if (!sy.fn) {       // (shift: the records are sums of z - shift[c * shift_stride]; never given under synchronised BatchNorm)
+    DFA_HIP_CHECK(ctx, launch_bn_finalize(partial, nparts, C, n, mean, var, invstd, rm, rv, momentum, s, shift, shift_stride));
     return DFA_OK;
   }
   DFA_HIP_CHECK(ctx, launch_reduce_partials(partial, nparts, C * 2, 1.0f, sy.buf, s, scratch));
@@ -592,9 +592,11 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
         DFA_HIP_CHECK(ctx, launch_conv1d(hin, (int64_t)Cin[l] * T, T, 1, q[0], q[1], z, B, Cin[l], C[l], T, false, s, false));
     }
     St st = st1d(ws, pl, l);
-    DFA_HIP_CHECK(ctx, launch_cm_stats(z, partial, B, C[l], T, s, lens));
+    const bool shifted = !ctx->bn_sync.fn;       // sums of z - z[0][c][0]: see cm_stats_body
+    DFA_HIP_CHECK(ctx, launch_cm_stats(z, partial, B, C[l], T, s, lens, shifted));
     { const int rc = finalize_bn_stats(ctx, partial, nch, C[l], frames, st.mean, st.var, st.invstd,
-                                       update_running_stats ? (float*)q[4] : nullptr, update_running_stats ? (float*)q[5] : nullptr, momentum, nullptr);
+                                       update_running_stats ? (float*)q[4] : nullptr, update_running_stats ? (float*)q[5] : nullptr, momentum, nullptr,
+                                       shifted ? z : nullptr, T);
       if (rc != DFA_OK) return rc; }
     if (l < 2) {
       dc.layer = 1 + l;

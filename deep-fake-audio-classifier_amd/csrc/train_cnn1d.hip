@@ -16,16 +16,21 @@ namespace dfa {
 // *_ragged_kernel, which takes the table.
 
 // ---- per-channel sum / sum of squares of z[B][C][T]: one block per (channel, batch chunk) -> partial[chunk][C][2]
+// shifted: the sums are those of z - k, k = the channel's first sample z[0][c][0] (the same for every chunk; bn_finalize_kernel adds
+// it back to the mean).  E[z^2] - mean^2 from fp32 sums loses mean^2 / var of its 24 bits -- a channel fed by activations of large
+// mean and small spread had mean^2 / var = 3000 and an invstd off by 1e-4; with the shift the ratio is that of one sample's
+// distance from the mean.  Off under synchronised BatchNorm: the ranks' first samples differ and the hook carries plain sums.
 template <bool RAGGED>
-__device__ __forceinline__ void cm_stats_body(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens) {
+__device__ __forceinline__ void cm_stats_body(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens, int shifted) {
   __shared__ float r1[256], r2[256];
   const int c = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
   const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
+  const float k = shifted ? z[(size_t)c * T] : 0.f;
   float s1 = 0.f, s2 = 0.f;
   for (int b = b0; b < b1; ++b) {
     const float* row = z + ((size_t)b * C + c) * T;
     const int Tb = RAGGED ? lens[b] : T;
-    for (int t = tid; t < Tb; t += 256) { const float v = row[t]; s1 += v; s2 = fmaf(v, v, s2); }
+    for (int t = tid; t < Tb; t += 256) { const float v = row[t] - k; s1 += v; s2 = fmaf(v, v, s2); }
   }
   r1[tid] = s1; r2[tid] = s2;
   __syncthreads();
@@ -35,11 +40,11 @@ __device__ __forceinline__ void cm_stats_body(const float* __restrict__ z, float
   }
   if (tid == 0) { partial[((size_t)ch * C + c) * 2] = r1[0]; partial[((size_t)ch * C + c) * 2 + 1] = r2[0]; }
 }
-__global__ __launch_bounds__(256) void cm_stats_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk) {
-  cm_stats_body<false>(z, partial, B, C, T, bchunk, nullptr);
+__global__ __launch_bounds__(256) void cm_stats_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, int shifted) {
+  cm_stats_body<false>(z, partial, B, C, T, bchunk, nullptr, shifted);
 }
-__global__ __launch_bounds__(256) void cm_stats_ragged_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens) {
-  cm_stats_body<true>(z, partial, B, C, T, bchunk, lens);
+__global__ __launch_bounds__(256) void cm_stats_ragged_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens, int shifted) {
+  cm_stats_body<true>(z, partial, B, C, T, bchunk, lens, shifted);
 }
 
 __device__ __forceinline__ float drop1(const DropCfg& dc, uint64_t idx) {
@@ -442,10 +447,10 @@ __global__ __launch_bounds__(256) void reduce_record2_kernel(const float* __rest
 constexpr int kCmChunks = 64;   // batch chunks of the channel-major reductions: 16 left the 32->64 weight gradient at 128 blocks on 256 CUs
 int cm_chunks(int B) { return B < kCmChunks ? B : kCmChunks; }
 
-hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens) {
+hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens, bool shifted) {
   const int nch = cm_chunks(B), bchunk = (B + nch - 1) / nch;
-  if (lens) hipLaunchKernelGGL(cm_stats_ragged_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, lens);
-  else hipLaunchKernelGGL(cm_stats_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk);
+  if (lens) hipLaunchKernelGGL(cm_stats_ragged_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, lens, (int)shifted);
+  else hipLaunchKernelGGL(cm_stats_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, (int)shifted);
   return hipGetLastError();
 }
 hipError_t launch_cm_bn_relu_drop(const float* z, const float* mean, const float* invstd, const float* gamma,

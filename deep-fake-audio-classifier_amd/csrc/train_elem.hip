@@ -42,7 +42,8 @@ __device__ __forceinline__ void st8<bf16_t>(bf16_t* p, const float* v) {
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partial, int nparts, int C, double n,
                                                           float* __restrict__ mean, float* __restrict__ var,
                                                           float* __restrict__ invstd, float* __restrict__ running_mean,
-                                                          float* __restrict__ running_var, float momentum) {
+                                                          float* __restrict__ running_var, float momentum,
+                                                          const float* __restrict__ shift, int shift_stride) {
   __shared__ double r1[256], r2[256];
   const int c = blockIdx.x, tid = threadIdx.x;
   double s1 = 0.0, s2 = 0.0;
@@ -57,9 +58,10 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     __syncthreads();
   }
   if (tid == 0) {
-    const double m = r1[0] / n;
-    double v = r2[0] / n - m * m;
+    const double ms = r1[0] / n;                 // mean of z - k (k = 0 without a shift); the variance does not see k
+    double v = r2[0] / n - ms * ms;
     if (v < 0.0) v = 0.0;
+    const double m = ms + (shift ? (double)shift[(size_t)c * shift_stride] : 0.0);
     mean[c] = (float)m;
     var[c] = (float)v;
     invstd[c] = (float)(1.0 / sqrt(v + (double)kBnEps));
@@ -784,9 +786,10 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 
 // ================================================================================================ launchers
 hipError_t launch_bn_finalize(const float* partial, int nparts, int C, double n, float* mean, float* var, float* invstd,
-                              float* running_mean, float* running_var, float momentum, hipStream_t s) {
+                              float* running_mean, float* running_var, float momentum, hipStream_t s, const float* shift,
+                              int shift_stride) {
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, partial, nparts, C, n, mean, var, invstd, running_mean,
-                     running_var, momentum);
+                     running_var, momentum, shift, shift_stride);
   return hipGetLastError();
 }
 

@@ -141,7 +141,8 @@ class _RoundGrad(torch.autograd.Function):
         return g.float().to(torch.bfloat16).to(g.dtype)
 
 
-def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", round_x=True, return_stats=False):
+def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", round_x=True, return_stats=False,
+                              return_margins=False, dtype=torch.float64):
     """One CNN2D training forward/backward (dropout 0) restated with the ROUNDING POINTS of the product's bf16 training
     mode (src/train.py:71-76 over src/model.py:13-39 in train mode): a1, z2, a2, z3 and their gradients da1, dz2, da2, dz3
     are stored in bf16, the MFMA convolutions of blocks 2 and 3 (forward, data gradient, weight gradient) take bf16
@@ -151,10 +152,12 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
     round_x=False feeds x unrounded in bf16 mode too (a batch with folded jitter noise reaches block 1 in fp32).
     Returns (logits [B], loss, {parameter name: gradient}) with the names of the model's named_parameters(); with
     return_stats=True a fourth item {BatchNorm prefix: (batch mean, biased batch variance, element count)} from which the
-    running-statistics update of nn.BatchNorm2d follows (momentum m: (1-m)*old + m*mean, (1-m)*old + m*var*n/(n-1))."""
-    f64 = torch.float64
+    running-statistics update of nn.BatchNorm2d follows (momentum m: (1-m)*old + m*mean, (1-m)*old + m*var*n/(n-1)).
+    return_margins=True appends {BatchNorm prefix: smallest |BatchNorm output| of that layer} (how far the nearest ReLU input
+    is from zero); dtype is the arithmetic everything "float64" above runs in (torch.float32: the same restatement in fp32)."""
+    f64 = dtype
     on = emulate == "bf16"
-    stats = {}
+    stats, margins = {}, {}
     if emulate not in (None, "bf16"):
         raise ValueError(emulate)
     P = {k: _t(sd, k).to(f64).clone().requires_grad_(True) for k in sd
@@ -169,7 +172,9 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
         var = za.var(dim=(0, 2, 3), unbiased=False, keepdim=True)
         stats[pfx] = (mean.detach().flatten().float(), var.detach().flatten().float(), za.numel() // za.shape[1])
         zs = rnd(za)
-        return (zs - mean) / torch.sqrt(var + 1e-5) * P[pfx + ".weight"][None, :, None, None] + P[pfx + ".bias"][None, :, None, None]
+        out = (zs - mean) / torch.sqrt(var + 1e-5) * P[pfx + ".weight"][None, :, None, None] + P[pfx + ".bias"][None, :, None, None]
+        margins[pfx] = float(out.detach().abs().min())
+        return out
 
     xb = (x.to(torch.bfloat16) if (on and round_x) else x).to(f64).unsqueeze(1)
     # block 1: fp32 VALU convolution from x, z1 is never stored (no rounding of z1 or dz1)
@@ -178,6 +183,7 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
     v1 = z1.var(dim=(0, 2, 3), unbiased=False, keepdim=True)
     stats["conv.1"] = (m1.detach().flatten().float(), v1.detach().flatten().float(), z1.numel() // z1.shape[1])
     y1 = (z1 - m1) / torch.sqrt(v1 + 1e-5) * P["conv.1.weight"][None, :, None, None] + P["conv.1.bias"][None, :, None, None]
+    margins["conv.1"] = float(y1.detach().abs().min())
     a1 = store(F.avg_pool2d(F.relu(y1), (2, 1)))
     w2 = P["conv.5.weight"]
     w2b = w2 + (rnd(w2) - w2).detach() if on else w2
@@ -191,24 +197,27 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
     loss = F.binary_cross_entropy_with_logits(logits, ys)
     loss.backward()
     out = (logits.detach().float(), float(loss), {k: v.grad.float() for k, v in P.items()})
-    return out + (stats,) if return_stats else out
+    return out + ((stats,) if return_stats else ()) + ((margins,) if return_margins else ())
 
 
-def cnn1d_train_step(sd, x, y, label_smoothing=0.0, return_stats=False):
+def cnn1d_train_step(sd, x, y, label_smoothing=0.0, return_stats=False, return_margins=False, dtype=torch.float64):
     """One CNN1D training forward/backward (dropout 0; src/train.py:71-76 over src/model_cnn1d.py:13-46 in train mode) in float64
     with torch autograd -- the product's CNN1D path is fp32 end to end, so there are no rounding points to restate.  x is the
-    [B,T,F] view the harness feeds.  Returns (logits [B], loss, {parameter: gradient}[, {BatchNorm prefix: (mean, biased var, n)}])."""
-    f64 = torch.float64
+    [B,T,F] view the harness feeds.  Returns (logits [B], loss, {parameter: gradient}[, {BatchNorm prefix: (mean, biased var, n)}]
+    [, {BatchNorm prefix: smallest |BatchNorm output|}]); dtype=torch.float32 runs the same restatement in fp32."""
+    f64 = dtype
     P = {k: _t(sd, k).to(f64).clone().requires_grad_(True) for k in sd
          if k.endswith(("weight", "bias")) and not k.endswith(("running_mean", "running_var"))}
-    stats = {}
+    stats, margins = {}, {}
 
     def block(h, conv, bn):
         z = F.conv1d(h, P[conv + ".weight"], P[conv + ".bias"], padding=1)
         mean = z.mean(dim=(0, 2), keepdim=True)
         var = z.var(dim=(0, 2), unbiased=False, keepdim=True)
         stats[bn] = (mean.detach().flatten().float(), var.detach().flatten().float(), z.numel() // z.shape[1])
-        return F.relu((z - mean) / torch.sqrt(var + 1e-5) * P[bn + ".weight"][None, :, None] + P[bn + ".bias"][None, :, None])
+        out = (z - mean) / torch.sqrt(var + 1e-5) * P[bn + ".weight"][None, :, None] + P[bn + ".bias"][None, :, None]
+        margins[bn] = float(out.detach().abs().min())
+        return F.relu(out)
     h = block(x.to(f64).transpose(1, 2), "conv.0", "conv.1")
     h = block(h, "conv.4", "conv.5")
     h = block(h, "conv.8", "conv.9")
@@ -217,7 +226,7 @@ def cnn1d_train_step(sd, x, y, label_smoothing=0.0, return_stats=False):
     loss = F.binary_cross_entropy_with_logits(logits, ys)
     loss.backward()
     out = (logits.detach().float(), float(loss), {k: v.grad.float() for k, v in P.items()})
-    return out + (stats,) if return_stats else out
+    return out + ((stats,) if return_stats else ()) + ((margins,) if return_margins else ())
 
 
 def state_after_adamw_step(sd, grads, stats, lr=1e-3, weight_decay=0.01, momentum=0.1):

@@ -17,30 +17,36 @@ from oracle import torch_ref as R
 BLOCKS = (("conv.0", "conv.1"), ("conv.4", "conv.5"), ("conv.8", "conv.9"))
 
 
-def cnn1d_ragged_train_step(sd, x, lengths, y, label_smoothing=0.0):
+def cnn1d_ragged_train_step(sd, x, lengths, y, label_smoothing=0.0, return_margins=False, dtype=torch.float64):
     """sd: CNN1D state_dict (tensors or numpy); x: [B, T_max, F] (the view the trainer is fed); lengths: B ints; y: [B] 0/1.
     Returns a dict, everything float64: logits [B], loss (float), grads {parameter name: gradient},
-    stats {BatchNorm prefix: (batch mean [C], biased batch variance [C], N)}."""
-    f64 = torch.float64
+    stats {BatchNorm prefix: (batch mean [C], biased batch variance [C], N)}; with return_margins=True also
+    margins {BatchNorm prefix: smallest |BatchNorm output| of that layer}.  dtype=torch.float32 runs the same statement in fp32."""
+    f64 = dtype
     lengths = [int(v) for v in lengths]
     B = x.shape[0]
     assert len(lengths) == B and all(3 <= t <= x.shape[1] for t in lengths), lengths
     P = {k: R._t(sd, k).to(f64).clone().requires_grad_(True) for k in sd
          if k.endswith(("weight", "bias")) and not k.endswith(("running_mean", "running_var"))}
-    stats = {}
+    stats, margins = {}, {}
     hs = [x[b, :lengths[b], :].to(f64).transpose(0, 1).unsqueeze(0) for b in range(B)]          # [1, F, T_b] each
     for conv, bn in BLOCKS:
         zs = [F.conv1d(h, P[conv + ".weight"], P[conv + ".bias"], padding=1) for h in hs]
         zc = torch.cat(zs, dim=2)                                                               # [1, C, N]
         stats[bn] = (zc.detach().mean(dim=(0, 2)), zc.detach().var(dim=(0, 2), unbiased=False), zc.shape[2])
-        a = F.relu(F.batch_norm(zc, None, None, P[bn + ".weight"], P[bn + ".bias"], training=True, momentum=0.1, eps=1e-5))
+        yc = F.batch_norm(zc, None, None, P[bn + ".weight"], P[bn + ".bias"], training=True, momentum=0.1, eps=1e-5)
+        margins[bn] = float(yc.detach().abs().min())
+        a = F.relu(yc)
         hs = list(torch.split(a, lengths, dim=2))
     pooled = torch.cat([h.mean(dim=2) for h in hs], dim=0)                                      # [B, 128]
     logits = F.linear(pooled, P["classifier.weight"], P["classifier.bias"]).squeeze(-1)
     ys = y.to(f64) * (1.0 - label_smoothing) + 0.5 * label_smoothing if label_smoothing > 0 else y.to(f64)
     loss = F.binary_cross_entropy_with_logits(logits, ys)
     loss.backward()
-    return {"logits": logits.detach(), "loss": float(loss.detach()), "grads": {k: v.grad.clone() for k, v in P.items()}, "stats": stats}
+    out = {"logits": logits.detach(), "loss": float(loss.detach()), "grads": {k: v.grad.clone() for k, v in P.items()}, "stats": stats}
+    if return_margins:
+        out["margins"] = margins
+    return out
 
 
 def state_after_step(sd, out, lr=1e-3, weight_decay=0.01, momentum=0.1):
