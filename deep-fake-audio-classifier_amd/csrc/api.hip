@@ -154,6 +154,12 @@ int dfa::stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void*
   return stage_ragged_table(ctx, lengths, B, (size_t)2 * B, dst, [](int32_t*) {});
 }
 
+int dfa::stage_ragged_lengths_extra(dfa_ctx* ctx, const int32_t* lengths, int B, const int32_t* extra, size_t n_extra, void* dst) {
+  return stage_ragged_table(ctx, lengths, B, (size_t)2 * B + n_extra, dst, [&](int32_t* tab) {
+    for (size_t i = 0; i < n_extra; ++i) tab[2 * B + i] = extra[i];
+  });
+}
+
 extern "C" {
 
 int dfa_version(void) { return DFA_VERSION; }
@@ -206,6 +212,7 @@ int dfa_ctx_destroy(dfa_ctx* ctx) {
   if (ctx->cnn1d.train_packed) (void)hipFree(ctx->cnn1d.train_packed);
   if (ctx->cae.packed) (void)hipFree(ctx->cae.packed);
   if (ctx->cae.train_packed) (void)hipFree(ctx->cae.train_packed);
+  if (ctx->dlq.packed) (void)hipFree(ctx->dlq.packed);
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   if (ctx->clock_buf) (void)hipFree(ctx->clock_buf);
   if (ctx->mse_partial) (void)hipFree(ctx->mse_partial);

@@ -115,6 +115,17 @@ struct CaeState {
   int train_prec = -1, train_B = 0, train_T = 0;
 };
 
+// DeepfakeDetector eval forward (dlq.hip, dlq_api.hip)
+struct DlqState {
+  const float* p[DFA_DLQ_NPARAMS] = {nullptr};
+  bool have_params = false;
+  bool prepared = false;
+  int in_ch = 0;
+  void* packed = nullptr;                       // one device allocation: the three A-fragment images, then the folded biases
+  void* w[3] = {nullptr, nullptr, nullptr};     // three-term bf16 A-fragment images, BatchNorm folded
+  float* b[3] = {nullptr, nullptr, nullptr};    // folded biases [256]
+};
+
 }  // namespace dfa
 
 struct dfa_ctx {
@@ -162,6 +173,7 @@ struct dfa_ctx {
   dfa::Cnn2dState cnn2d;
   dfa::Cnn1dState cnn1d;
   dfa::CaeState cae;
+  dfa::DlqState dlq;
   unsigned timing = 0;         // bit s set: record HIP events around the launches of timing slot s
   dfa::SlotTimer slots[dfa::kMaxSlots];
 };
@@ -292,6 +304,26 @@ hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, con
 // api.hip: the per-call table of a ragged batch ([0, B) lengths, [B, 2B) dispatch order: 2 B words) through the next pinned staging
 // slot to `dst` (device) on the context's stream
 int stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void* dst);
+// the same with `extra` words the caller supplies behind them: [2B, 2B + extra) (words = 2 B + extra)
+int stage_ragged_lengths_extra(dfa_ctx* ctx, const int32_t* lengths, int B, const int32_t* extra, size_t n_extra, void* dst);
+// dlq.hip: the DeepfakeDetector layers (one launch each over the tile list) and the pool + head kernel
+struct DlqLayerArgs {
+  const float* x;        // layer 1: element (b, c, t) at b sb + c sc + t
+  int64_t sb, sc;
+  const uint4* hin;      // layers 2, 3: [B][T_max] split pixels (three bf16 terms of 256 channels, 1536 bytes)
+  uint4* hout;           // layers 1, 2
+  const uint4* w;
+  const float* bias;
+  const int* tab;        // [0, B) lengths; [2B, 3B) dispatch order; [3B, 4B] first tile of each dispatch position
+  float* part;           // layer 3: [tile][mean 256 | M2 256]
+  int B, T_max, C, nks;
+};
+int dlq_nks(int cin);
+size_t dlq_pack_bytes(int cin, int taps);
+hipError_t launch_dlq_pack(const float* const* p6, int cin, int taps, void* wp, float* bias, hipStream_t s);
+hipError_t launch_dlq_layer(int layer, const DlqLayerArgs& a, int ntiles, hipStream_t s);
+hipError_t launch_dlq_finish(const float* part, const int* tab, const float* w0, const float* b0, const float* w3, const float* b3, float* logits,
+                             float* pooled, int B, hipStream_t s);
 // train_cnn1d.hip
 int cm_chunks(int B);
 int conv1d_wgrad_chunks(int B);

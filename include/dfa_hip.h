@@ -374,6 +374,35 @@ int dfa_cae_score_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_
 int dfa_mse_fwd_bwd(dfa_ctx* ctx, const float* recon, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
                     int64_t stride_t, int64_t stride_f, float* loss, float* drecon);
 
+/* ---- DeepfakeDetector (replaces DeepfakeDetector.forward in eval mode, src/dlqueen_model.py:115-173) ------------------------
+ * Conv1d(C -> 256, k5) + BN + GELU, 2 x (Conv1d(256 -> 256, k3) + BN + GELU), masked mean / std pool over each utterance's own
+ * frames, Linear(512 -> 256) + GELU + Linear(256 -> 1).  Variable-length batches only (the model takes `lengths` by definition).
+ * params: 22 device pointers (fp32) in state_dict order without num_batches_tracked:
+ *   enc.net.0.{weight,bias}, enc.net.1.{weight,bias,running_mean,running_var}, enc.net.4.*, enc.net.5.*, enc.net.8.*, enc.net.9.*,
+ *   head.0.{weight,bias}, head.3.{weight,bias}.
+ * hidden must be 256, in_ch a multiple of 4 in [4, 256]: anything else returns DFA_E_UNSUPPORTED. */
+#define DFA_DLQ_NPARAMS 22
+#define DFA_DLQ_TILE_FRAMES 64 /* frames of one utterance a workgroup owns */
+int dfa_dlq_set_params(dfa_ctx* ctx, const float* const* device_params, int n, int in_ch, int hidden);
+/* folds every BatchNorm into its convolution and packs hi + lo bf16 matrix-core images (once per weight set) */
+int dfa_dlq_prepare(dfa_ctx* ctx);
+/* bytes of workspace for B utterances padded to T_max frames (a multiple of 256; 0 for B < 1 or T_max < 1) */
+size_t dfa_dlq_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int in_ch);
+/* x: device float32, element (b, c, t) at x + b stride_b + c stride_c + t (time fastest: the stored [C, T] layout of a features.pkl
+ *    row, padded to the batch's longest utterance); x 16-byte aligned, stride_c % 4 == 0, stride_c >= T_max, stride_b % 4 == 0,
+ *    every row readable up to T_max rounded up to 4 frames (else DFA_E_UNSUPPORTED).
+ * lengths: HOST int32[B], 1 <= lengths[b] <= T_max (else DFA_E_BAD_SHAPE naming the index).
+ * The padded-batch rule: the reference's encoder is not masked, only its pool is.  Frames t >= lengths[b] of x are taken as zero
+ * and never used (they may hold NaN); layer 1's output exists on frames < min(T_max, len + 2), layer 2's on frames
+ * < min(T_max, len + 1), layer 3's on frames < len; everything past those is the convolution's zero padding.  logits[b] is, bit for
+ * bit, a function of (x[b, :, :len], len, min(T_max - len, 2)): not of B, the position in the batch, the other utterances, the
+ * memory behind the padding or the workspace's previous contents.
+ * logits: device float[B]; pooled: device float[B * 512] ([mean 256 | std 256]) or NULL.
+ * workspace: device, 256-byte aligned, >= dfa_dlq_workspace_bytes bytes.  A capturing stream returns DFA_E_UNSUPPORTED (the
+ * lengths are copied per call).  Timing slots: 4, 5, 6 = layers 1-3, 7 = pool + head. */
+int dfa_dlq_forward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, int64_t stride_b, int64_t stride_c,
+                    const int32_t* lengths, float* logits, float* pooled, void* workspace, size_t workspace_bytes);
+
 /* ---- shared ------------------------------------------------------------------------------------ */
 size_t dfa_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T, int F, int precision);
 /* workspace of dfa_cnn2d_forward_ragged / dfa_cnn1d_forward_ragged for B utterances padded to T_max frames (0 for a model
