@@ -9,6 +9,8 @@ import threading
 
 import torch
 
+from ._params import tensors_signature
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdfa_hip.so")
 
@@ -271,6 +273,73 @@ def ptr_array(tensors):
     for i, t in enumerate(tensors):
         arr[i] = t.data_ptr()
     return arr
+
+
+def ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+# ---- the eval bridge: what every model's eval-mode forward does around its one ABI call --------------------------------------------
+def ensure_prepared(model, ctx: Context, slot: str, set_params: str, dims, prepare: str, precision=None):
+    """Bind model._abi_tensors() to the context's `slot` (`set_params`(ctx, pointers, n, *dims)) and fold them for the eval
+    forward (`prepare`(ctx[, precision code])), unless that is what the slot already holds: model._prepared remembers the
+    signature (device, precision where the model has one, tensor addresses and versions) of the last preparation."""
+    ts = model._abi_tensors()
+    for t in ts:
+        if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"{type(model).__name__} parameters must be contiguous float32 tensors on the GPU "
+                               "(call model.to('cuda')); dfa_amd has no CPU path")
+    sig = (ctx.index, tensors_signature(ts)) if precision is None else (ctx.index, precision, tensors_signature(ts))
+    stale = ctx.owner_changed(slot, model)      # another model of this class used the ctx's weight slot
+    if sig == model._prepared and not stale:
+        return
+    arr = ptr_array([t.detach() for t in ts])
+    check(ctx.handle, getattr(ctx.lib, set_params)(ctx.handle, arr, len(ts), *dims))
+    check(ctx.handle, getattr(ctx.lib, prepare)(ctx.handle, *(() if precision is None else (PRECISIONS[precision],))))
+    model._prepared = sig
+
+
+def require_gpu(model, x):
+    if x.device.type != "cuda":
+        raise RuntimeError(f"dfa_amd.{type(model).__name__} runs on the GPU only: move the input with .to('cuda')")
+
+
+class launch:
+    """`with launch(model, x) as ctx`: the context of x's device, ready for one eval-mode ABI call on `model` -- x's device
+    current, the context on torch's current stream, the model's weights prepared.  (A class, not a contextlib generator: this
+    runs once per forward, and the generator's frame costs about a microsecond of it.)"""
+    __slots__ = ("model", "ctx", "guard")
+
+    def __init__(self, model, x):
+        require_gpu(model, x)
+        self.model, self.ctx = model, Context.get(x.device)
+        self.guard = torch.cuda.device(self.ctx.index)
+
+    def __enter__(self):
+        self.guard.__enter__()
+        try:
+            self.ctx.use_current_stream()
+            self.model._ensure_prepared(self.ctx)
+        except BaseException:
+            self.guard.__exit__(None, None, None)
+            raise
+        return self.ctx
+
+    def __exit__(self, *exc):
+        return self.guard.__exit__(*exc)
+
+
+def stored_layout(x, in_place: bool, time_last: bool):
+    """A float32 batch in the stored channel-major layout [B][C][T_pad] (time fastest, rows of T_pad = T rounded up to 4 frames:
+    16-byte rows): x itself when the caller's test `in_place` found it to be one already, else a zero-padded copy on x's device.
+    time_last: x is [B, C, T] (else [B, T, C]); the result has x's shape."""
+    if in_place:
+        return x
+    cm = x if time_last else x.transpose(1, 2)
+    B, Cc, T = cm.shape
+    stored = torch.zeros((B, Cc, -(-T // 4) * 4), dtype=torch.float32, device=x.device)
+    stored[:, :, :T] = cm
+    return stored[:, :, :T] if time_last else stored.transpose(1, 2)[:, :T]
 
 
 def host_lengths(lengths, B: int, T_max: int, min_len: int):

@@ -5,15 +5,13 @@
 
 #include <algorithm>
 
-#include "dfa_internal.h"
+#include "dfa_checks.h"
 #include "trace.h"
 #include "convt2x2_mfma.h"
 
 using namespace dfa;
 
 namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 constexpr int kMaxSeg = 4;
 
@@ -258,6 +256,23 @@ hipError_t launch_poison_lds(dfa_ctx* ctx, unsigned half) {
 }
 }  // namespace
 
+namespace {
+// the options that are one int of the context: a 0/1 switch (any non-zero value = 1) or the value as given
+enum OptionKind { OPT_FLAG, OPT_INT };
+struct Option { const char* name; int dfa_ctx::*field; OptionKind kind; };
+const Option kOptions[] = {
+    {"time_split", &dfa_ctx::time_split, OPT_INT},
+    {"conv1_bwd_fused", &dfa_ctx::conv1_bwd_fused, OPT_FLAG}, {"dgrad_m16", &dfa_ctx::dgrad_m16, OPT_FLAG},
+    {"conv1_mfma", &dfa_ctx::conv1_mfma, OPT_FLAG}, {"cae_enc1_mfma", &dfa_ctx::cae_enc1_mfma, OPT_FLAG},
+    {"cae_enc_dma", &dfa_ctx::cae_enc_dma, OPT_FLAG}, {"cae_dgrad_mfma", &dfa_ctx::cae_dgrad_mfma, OPT_FLAG},
+    {"cae_conv_stats", &dfa_ctx::cae_conv_stats, OPT_FLAG}, {"cae_bwd_fold", &dfa_ctx::cae_bwd_fold, OPT_FLAG},
+    {"cae_enc4_wide", &dfa_ctx::cae_enc4_wide, OPT_FLAG}, {"cae_dec_fused", &dfa_ctx::cae_dec_fused, OPT_FLAG},
+    {"block3_m16", &dfa_ctx::block3_m16, OPT_FLAG}, {"fuse_conv1", &dfa_ctx::fuse_conv1, OPT_FLAG},
+    {"fuse_blocks123", &dfa_ctx::fuse_blocks123, OPT_FLAG}, {"persist123", &dfa_ctx::persist123, OPT_FLAG},
+    {"lds_pipe", &dfa_ctx::lds_pipe, OPT_FLAG},
+};
+}  // namespace
+
 int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value) {
   if (!ctx || !name) return DFA_E_NULL_PTR;
   if (strcmp(name, "poison_lds") == 0) {
@@ -266,7 +281,6 @@ int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value) {
   }
   if (strcmp(name, "train_conv_variant") == 0) { set_train_conv_variant(value); return DFA_OK; }
   if (strcmp(name, "wgrad_variant") == 0) { set_wgrad_variant(value); return DFA_OK; }
-  if (strcmp(name, "time_split") == 0) { ctx->time_split = value; return DFA_OK; }
   if (strcmp(name, "clock_probe") == 0) {
     if (value && !ctx->clock_buf) {
       DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -276,24 +290,11 @@ int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value) {
     ctx->clock_probe = value ? 1 : 0;
     return DFA_OK;
   }
-  if (strcmp(name, "conv1_bwd_fused") == 0) { ctx->conv1_bwd_fused = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "dgrad_m16") == 0) { ctx->dgrad_m16 = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "conv1_mfma") == 0) { ctx->conv1_mfma = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "cae_enc1_mfma") == 0) { ctx->cae_enc1_mfma = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "cae_enc_dma") == 0) { ctx->cae_enc_dma = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "cae_dgrad_mfma") == 0) { ctx->cae_dgrad_mfma = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "cae_conv_stats") == 0) { ctx->cae_conv_stats = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "cae_bwd_fold") == 0) { ctx->cae_bwd_fold = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "cae_enc4_wide") == 0) { ctx->cae_enc4_wide = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "cae_dec_fused") == 0) { ctx->cae_dec_fused = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "cnn1d_train_x3") == 0) { ctx->cnn1d_train_x3 = (value < 0 || value > 3) ? 1 : value; return DFA_OK; }
   if (strcmp(name, "cnn1d_fused") == 0) { ctx->cnn1d_fused = value < 0 ? 0 : (value > 2 ? 1 : value); return DFA_OK; }
-  if (strcmp(name, "block3_m16") == 0) { ctx->block3_m16 = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "fuse_conv1") == 0) { ctx->fuse_conv1 = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "fuse_blocks123") == 0) { ctx->fuse_blocks123 = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "persist123") == 0) { ctx->persist123 = value ? 1 : 0; return DFA_OK; }
-  if (strcmp(name, "lds_pipe") == 0) { ctx->lds_pipe = value ? 1 : 0; return DFA_OK; }
   if (strcmp(name, "conv_dma") == 0) { ctx->conv_dma = value < 0 ? -1 : value; return DFA_OK; }
+  for (const Option& o : kOptions)
+    if (strcmp(name, o.name) == 0) { ctx->*o.field = (o.kind == OPT_FLAG) ? (value ? 1 : 0) : value; return DFA_OK; }
   return fail(ctx, DFA_E_UNSUPPORTED, "unknown option '%s'", name);
 }
 
@@ -366,15 +367,12 @@ const char* dfa_dominant_kernel(int model, int precision) {
 
 /* ------------------------------------------------------------------------------------------------ CNN2D */
 int dfa_cnn2d_set_params(dfa_ctx* ctx, const float* const* device_params, int n, int in_features, int base_channels) {
-  if (!ctx || !device_params) return DFA_E_NULL_PTR;
-  if (n != DFA_CNN2D_NPARAMS) return fail(ctx, DFA_E_BAD_SHAPE, "cnn2d expects %d parameter pointers, got %d", DFA_CNN2D_NPARAMS, n);
-  if (base_channels != 32) return fail(ctx, DFA_E_UNSUPPORTED, "cnn2d HIP path is built for base_channels=32 (got %d)", base_channels);
-  if (in_features < 1) return fail(ctx, DFA_E_BAD_SHAPE, "in_features must be positive (got %d)", in_features);
-  for (int i = 0; i < n; ++i)
-    if (!device_params[i]) return fail(ctx, DFA_E_NULL_PTR, "cnn2d parameter %d is null", i);
-  for (int i = 0; i < n; ++i) ctx->cnn2d.p[i] = device_params[i];
+  DFA_TRY(set_params_core(ctx, &dfa_ctx::cnn2d, "cnn2d", device_params, n, [&]() -> int {
+    if (base_channels != 32) return fail(ctx, DFA_E_UNSUPPORTED, "cnn2d HIP path is built for base_channels=32 (got %d)", base_channels);
+    if (in_features < 1) return fail(ctx, DFA_E_BAD_SHAPE, "in_features must be positive (got %d)", in_features);
+    return DFA_OK;
+  }));
   ctx->cnn2d.in_features = in_features;
-  ctx->cnn2d.have_params = true;
   ctx->cnn2d.prepared_prec = -1;
   return DFA_OK;
 }
@@ -432,25 +430,35 @@ size_t dfa_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T, int F, i
   return 0;
 }
 
+// the checks dfa_cnn2d_forward and dfa_cnn2d_forward_ragged make first, in this order (have_ptrs: no required pointer is null)
+static int cnn2d_forward_front(dfa_ctx* ctx, bool ragged, bool have_ptrs, int x_dtype, int B, int T, int F) {
+  const Cnn2dState& m = ctx->cnn2d;
+  if (m.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn2d_prepare has not been called since the last set_params");
+  if (!have_ptrs) return fail(ctx, DFA_E_NULL_PTR, "x, %slogits and workspace must be non-null", ragged ? "lengths, " : "");
+  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
+  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
+  if (F != m.in_features)
+    return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d of the classifier (src/model.py:31)", F, m.in_features);
+  if (T < 4) return fail(ctx, DFA_E_BAD_SHAPE, "%s=%d is too short: two (2,1) average pools need T >= 4", ragged ? "T_max" : "T", T);
+  return DFA_OK;
+}
+// ... and last: the workspace, and the embedding (emb_reduce_kernel / the block-3 epilogues store 16 bytes at a time)
+static int cnn2d_forward_buffers(dfa_ctx* ctx, const void* workspace, size_t workspace_bytes, size_t need, const float* embedding) {
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, need));
+  if (embedding && ((uintptr_t)embedding & 15) != 0)
+    return fail(ctx, DFA_E_BAD_SHAPE, "embedding must be 16-byte aligned (got %p)", (void*)embedding);
+  return DFA_OK;
+}
+
 int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
                       int64_t stride_f, float* logits, float* embedding, void* workspace, size_t workspace_bytes) {
   TraceRange trace_("dfa_cnn2d_forward");
   if (!ctx) return DFA_E_NULL_PTR;
   Cnn2dState& m = ctx->cnn2d;
-  if (m.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn2d_prepare has not been called since the last set_params");
-  if (!x || !logits || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, logits and workspace must be non-null");
-  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
-  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
-  if (F != m.in_features)
-    return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d of the classifier (src/model.py:31)", F, m.in_features);
-  if (T < 4) return fail(ctx, DFA_E_BAD_SHAPE, "T=%d is too short: two (2,1) average pools need T >= 4", T);
+  DFA_TRY(cnn2d_forward_front(ctx, false, x && logits && workspace, x_dtype, B, T, F));
   const int prec = m.prepared_prec;
   const Cnn2dPlan pl = plan_cnn2d(B, T, F, prec, ctx->time_split);
-  if (workspace_bytes < pl.total)
-    return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, pl.total);
-  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
-  if (embedding && ((uintptr_t)embedding & 15) != 0)   // emb_reduce_kernel / the block-3 epilogues store 16 bytes at a time
-    return fail(ctx, DFA_E_BAD_SHAPE, "embedding must be 16-byte aligned (got %p)", (void*)embedding);
+  DFA_TRY(cnn2d_forward_buffers(ctx, workspace, workspace_bytes, pl.total, embedding));
   char* ws = (char*)workspace;
   void* a1 = ws + pl.a1_off;
   void* a2 = ws + pl.a2_off;
@@ -553,49 +561,32 @@ int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   TraceRange trace_("dfa_cnn2d_forward_ragged");
   if (!ctx) return DFA_E_NULL_PTR;
   Cnn2dState& m = ctx->cnn2d;
-  if (m.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn2d_prepare has not been called since the last set_params");
-  if (!x || !logits || !workspace || !lengths) return fail(ctx, DFA_E_NULL_PTR, "x, lengths, logits and workspace must be non-null");
-  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
-  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
-  if (F != m.in_features)
-    return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d of the classifier (src/model.py:31)", F, m.in_features);
-  if (T_max < 4) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: two (2,1) average pools need T >= 4", T_max);
-  for (int b = 0; b < B; ++b)
-    if (lengths[b] < 4 || lengths[b] > T_max)
-      return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [4, T_max=%d]", b, (int)lengths[b], T_max);
+  DFA_TRY(cnn2d_forward_front(ctx, true, x && logits && workspace && lengths, x_dtype, B, T_max, F));
+  DFA_TRY(check_lengths(ctx, lengths, B, 4, T_max));
   const int prec = m.prepared_prec;
   if (prec != DFA_PREC_BF16)
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward has kernels for precision bf16 only (prepared: %d)", prec);
   if (!ctx->fuse_conv1 || !ctx->block3_m16)   // the uniform forward would run other kernels: no bit-identity promise there
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward needs the default options fuse_conv1=1 and block3_m16=1");
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
-  if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
-    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward cannot be captured into a graph: its lengths are copied per call");
+  DFA_TRY(refuse_capture(ctx, "forward"));
   const Cnn2dPlan pl = plan_cnn2d(B, T_max, F, prec, ctx->time_split);
   const size_t tab_off = pl.total, need = pl.total + align_up((size_t)4 * B * 4, 256);
-  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
-  if (embedding && ((uintptr_t)embedding & 15) != 0)
-    return fail(ctx, DFA_E_BAD_SHAPE, "embedding must be 16-byte aligned (got %p)", (void*)embedding);
+  DFA_TRY(cnn2d_forward_buffers(ctx, workspace, workspace_bytes, need, embedding));
   // the ragged table (conv3x3_mfma.h: RaggedTab) through the next pinned staging slot
   const size_t words = (size_t)4 * B;
   int nseg3 = 1;
   char* ws = (char*)workspace;
   const int* dtab = (const int*)(ws + tab_off);
   hipStream_t s = ctx->stream;
-  {
-    const int rc = stage_ragged_table(ctx, lengths, B, words, ws + tab_off, [&](int32_t* tab) {
-      for (int b = 0; b < B; ++b) {
-        const int h2 = lengths[b] / 4, niter3 = (h2 + 1) / 2, chunk = chunk3_for(niter3);
-        const float inv_h = 1.0f / (float)h2;
-        memcpy(&tab[2 * B + b], &inv_h, 4);
-        tab[3 * B + b] = chunk;
-        nseg3 = std::max(nseg3, (niter3 + chunk - 1) / chunk);
-      }
-    });
-    if (rc != DFA_OK) return rc;
-  }
+  DFA_TRY(stage_ragged_table(ctx, lengths, B, words, ws + tab_off, [&](int32_t* tab) {
+    for (int b = 0; b < B; ++b) {
+      const int h2 = lengths[b] / 4, niter3 = (h2 + 1) / 2, chunk = chunk3_for(niter3);
+      const float inv_h = 1.0f / (float)h2;
+      memcpy(&tab[2 * B + b], &inv_h, 4);
+      tab[3 * B + b] = chunk;
+      nseg3 = std::max(nseg3, (niter3 + chunk - 1) / chunk);
+    }
+  }));
   const RaggedTab rt{dtab, B};
   void* a2 = ws + pl.a2_off;
   float* emb = embedding ? embedding : (float*)(ws + pl.emb_off);
@@ -634,15 +625,12 @@ int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
 
 /* ------------------------------------------------------------------------------------------------ CNN1D */
 int dfa_cnn1d_set_params(dfa_ctx* ctx, const float* const* device_params, int n, int in_features, int base_channels) {
-  if (!ctx || !device_params) return DFA_E_NULL_PTR;
-  if (n != DFA_CNN1D_NPARAMS) return fail(ctx, DFA_E_BAD_SHAPE, "cnn1d expects %d parameter pointers, got %d", DFA_CNN1D_NPARAMS, n);
-  if (base_channels != 32) return fail(ctx, DFA_E_UNSUPPORTED, "cnn1d HIP path is built for base_channels=32 (got %d)", base_channels);
-  if (in_features < 1) return fail(ctx, DFA_E_BAD_SHAPE, "in_features must be positive (got %d)", in_features);
-  for (int i = 0; i < n; ++i)
-    if (!device_params[i]) return fail(ctx, DFA_E_NULL_PTR, "cnn1d parameter %d is null", i);
-  for (int i = 0; i < n; ++i) ctx->cnn1d.p[i] = device_params[i];
+  DFA_TRY(set_params_core(ctx, &dfa_ctx::cnn1d, "cnn1d", device_params, n, [&]() -> int {
+    if (base_channels != 32) return fail(ctx, DFA_E_UNSUPPORTED, "cnn1d HIP path is built for base_channels=32 (got %d)", base_channels);
+    if (in_features < 1) return fail(ctx, DFA_E_BAD_SHAPE, "in_features must be positive (got %d)", in_features);
+    return DFA_OK;
+  }));
   ctx->cnn1d.in_features = in_features;
-  ctx->cnn1d.have_params = true;
   ctx->cnn1d.prepared = false;
   return DFA_OK;
 }
@@ -687,7 +675,7 @@ int dfa_cnn1d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   if (F != m.in_features)
     return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d of the first Conv1d (src/model_cnn1d.py:17)", F, m.in_features);
   const Cnn1dPlan pl = plan_cnn1d(B, T);
-  if (workspace_bytes < pl.total) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, pl.total);
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total, false));   // (this entry point never asked for the alignment)
   char* ws = (char*)workspace;
   float *h1 = (float*)(ws + pl.h1_off), *h2 = (float*)(ws + pl.h2_off), *pooled = (float*)(ws + pl.pooled_off);
   hipStream_t s = ctx->stream;
@@ -731,36 +719,22 @@ int dfa_cnn1d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   if (F != m.in_features)
     return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d of the first Conv1d (src/model_cnn1d.py:17)", F, m.in_features);
   if (T_max < 3) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: the ragged cnn1d kernel needs T >= 3", T_max);
-  for (int b = 0; b < B; ++b)
-    if (lengths[b] < 3 || lengths[b] > T_max)
-      return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [3, T_max=%d]", b, (int)lengths[b], T_max);
+  DFA_TRY(check_lengths(ctx, lengths, B, 3, T_max));
   // layout: the stored channel-major batch [B][F][T_pad] seen as [B, T_max, F] -- frames contiguous, 16-byte aligned rows
   if (stride_t != 1)
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward takes the channel-major storage only: stride_t=%lld, needs 1", (long long)stride_t);
   if ((F & 3) != 0) return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs F %% 4 == 0 (got F=%d)", F);
-  if ((stride_f & 3) != 0 || stride_f < T_max)
-    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs stride_f %% 4 == 0 and stride_f >= T_max=%d (got stride_f=%lld)", T_max,
-                (long long)stride_f);
-  if ((stride_b & 3) != 0 || stride_b < 0)
-    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs a non-negative stride_b %% 4 == 0 (got stride_b=%lld)", (long long)stride_b);
-  if (((uintptr_t)x & 15) != 0) return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs x 16-byte aligned (got %p)", x);
+  DFA_TRY(check_channel_major(ctx, "ragged cnn1d forward", "stride_f", x, stride_b, stride_f, T_max));
   if ((int64_t)F * stride_f >= ((int64_t)1 << 31))   // (the kernel addresses an utterance's elements with 32-bit offsets)
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs F * stride_f < 2^31 (got %d * %lld)", F, (long long)stride_f);
   if (ctx->cnn1d_fused != 1)   // the uniform forward would run other kernels: no bit-identity promise there
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d forward needs the default option cnn1d_fused=1 (got %d)", ctx->cnn1d_fused);
   if (cnn1d_ragged_segments(3, F, nullptr, nullptr, nullptr, nullptr, 0) < 1)
     return fail(ctx, DFA_E_UNSUPPORTED, "F=%d: the layer-1 weights leave no LDS for a time window", F);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
-  if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
-    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward cannot be captured into a graph: its lengths are copied per call");
-  const size_t words = (size_t)2 * B, need = align_up(words * 4, 256);
-  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
-  {
-    const int rc = stage_ragged_table(ctx, lengths, B, words, workspace, [](int32_t*) {});
-    if (rc != DFA_OK) return rc;
-  }
+  DFA_TRY(refuse_capture(ctx, "forward"));
+  const size_t words = (size_t)2 * B;
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, align_up(words * 4, 256)));
+  DFA_TRY(stage_ragged_table(ctx, lengths, B, words, workspace, [](int32_t*) {}));
   ScopedSlot ts(ctx, 4);
   DFA_HIP_CHECK(ctx, launch_cnn1d_ragged_x3((const float*)x, stride_b, stride_f, (const int*)workspace, m.wx[0], m.b[0], m.wx[1], m.b[1], m.wx[2],
                                             m.b[2], m.p[18], m.p[19], logits, B, T_max, F, ctx->stream,
@@ -782,13 +756,10 @@ size_t dfa_cnn1d_ragged_lds_bytes(int T_max, int F) {
 
 /* ------------------------------------------------------------------------------------------------ CAE */
 int dfa_cae_set_params(dfa_ctx* ctx, const float* const* device_params, int n, int base_channels) {
-  if (!ctx || !device_params) return DFA_E_NULL_PTR;
-  if (n != DFA_CAE_NPARAMS) return fail(ctx, DFA_E_BAD_SHAPE, "cae expects %d parameter pointers, got %d", DFA_CAE_NPARAMS, n);
-  if (base_channels != 32) return fail(ctx, DFA_E_UNSUPPORTED, "cae HIP path is built for base_channels=32 (got %d)", base_channels);
-  for (int i = 0; i < n; ++i)
-    if (!device_params[i]) return fail(ctx, DFA_E_NULL_PTR, "cae parameter %d is null", i);
-  for (int i = 0; i < n; ++i) ctx->cae.p[i] = device_params[i];
-  ctx->cae.have_params = true;
+  DFA_TRY(set_params_core(ctx, &dfa_ctx::cae, "cae", device_params, n, [&]() -> int {
+    if (base_channels != 32) return fail(ctx, DFA_E_UNSUPPORTED, "cae HIP path is built for base_channels=32 (got %d)", base_channels);
+    return DFA_OK;
+  }));
   ctx->cae.prepared_prec = -1;
   return DFA_OK;
 }
@@ -854,24 +825,31 @@ int dfa_cae_prepare(dfa_ctx* ctx, int precision) {
   return DFA_OK;
 }
 
+// the checks dfa_cae_forward and dfa_cae_score_ragged make first, in this order (have_ptrs: no required pointer is null)
+static int cae_forward_front(dfa_ctx* ctx, bool ragged, bool have_ptrs, const float* mu, const float* sigma, int x_dtype, int B, int T) {
+  if (ctx->cae.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cae_prepare has not been called since the last set_params");
+  if (!have_ptrs) return fail(ctx, DFA_E_NULL_PTR, ragged ? "x, lengths, mse and workspace must be non-null" : "x and workspace must be non-null");
+  if ((mu == nullptr) != (sigma == nullptr)) return fail(ctx, DFA_E_NULL_PTR, "mu and sigma must both be given or both be NULL");
+  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
+  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
+  if (T < 16) return fail(ctx, DFA_E_BAD_SHAPE, "%s=%d is too short: four 2x2 average pools need T >= 16", ragged ? "T_max" : "T", T);
+  return DFA_OK;
+}
+static int cae_refuse_F(dfa_ctx* ctx, int F, const CaePlan& pl) {
+  return fail(ctx, DFA_E_BAD_SHAPE, "F=%d: decoder would rebuild %d columns (needs F = 16*(F/16)+4, e.g. 180; src/model_cae.py:68-69)", F, pl.Wd[3]);
+}
+
 int dfa_cae_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
                     int64_t stride_f, const float* mu, const float* sigma, float* recon, float* latent, float* mse,
                     void* workspace, size_t workspace_bytes) {
   TraceRange trace_("dfa_cae_forward");
   if (!ctx) return DFA_E_NULL_PTR;
   CaeState& m = ctx->cae;
-  if (m.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cae_prepare has not been called since the last set_params");
-  if (!x || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x and workspace must be non-null");
-  if ((mu == nullptr) != (sigma == nullptr)) return fail(ctx, DFA_E_NULL_PTR, "mu and sigma must both be given or both be NULL");
-  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
-  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
-  if (T < 16) return fail(ctx, DFA_E_BAD_SHAPE, "T=%d is too short: four 2x2 average pools need T >= 16", T);
+  DFA_TRY(cae_forward_front(ctx, false, x && workspace, mu, sigma, x_dtype, B, T));
   const int prec = m.prepared_prec;
   const CaePlan pl = plan_cae(B, T, F, prec);
-  if (!pl.ok)
-    return fail(ctx, DFA_E_BAD_SHAPE, "F=%d: decoder would rebuild %d columns (needs F = 16*(F/16)+4, e.g. 180; src/model_cae.py:68-69)", F, pl.Wd[3]);
-  if (workspace_bytes < pl.total) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, pl.total);
-  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
+  if (!pl.ok) return cae_refuse_F(ctx, F, pl);
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total));
   char* ws = (char*)workspace;
   void* e[4] = {ws + pl.e_off[0], ws + pl.e_off[1], ws + pl.e_off[2], ws + pl.e_off[3]};
   void* d[3] = {ws + pl.d_off[0], ws + pl.d_off[1], ws + pl.d_off[2]};
@@ -938,47 +916,32 @@ int dfa_cae_score_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_
   TraceRange trace_("dfa_cae_score_ragged");
   if (!ctx) return DFA_E_NULL_PTR;
   CaeState& m = ctx->cae;
-  if (m.prepared_prec < 0) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cae_prepare has not been called since the last set_params");
-  if (!x || !workspace || !lengths || !mse) return fail(ctx, DFA_E_NULL_PTR, "x, lengths, mse and workspace must be non-null");
-  if ((mu == nullptr) != (sigma == nullptr)) return fail(ctx, DFA_E_NULL_PTR, "mu and sigma must both be given or both be NULL");
-  if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
-  if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got %d)", B);
-  if (T_max < 16) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: four 2x2 average pools need T >= 16", T_max);
-  for (int b = 0; b < B; ++b)
-    if (lengths[b] < 16 || lengths[b] > T_max)
-      return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [16, T_max=%d]", b, (int)lengths[b], T_max);
+  DFA_TRY(cae_forward_front(ctx, true, x && workspace && lengths && mse, mu, sigma, x_dtype, B, T_max));
+  DFA_TRY(check_lengths(ctx, lengths, B, 16, T_max));
   const int prec = m.prepared_prec;
   if (prec != DFA_PREC_BF16)
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score has kernels for precision bf16 only (prepared: %d)", prec);
   const CaePlan pl = plan_cae(B, T_max, F, prec);
-  if (!pl.ok)
-    return fail(ctx, DFA_E_BAD_SHAPE, "F=%d: decoder would rebuild %d columns (needs F = 16*(F/16)+4, e.g. 180; src/model_cae.py:68-69)", F, pl.Wd[3]);
+  if (!pl.ok) return cae_refuse_F(ctx, F, pl);
   if (!ctx->cae_dec_fused || !ctx->cae_enc1_mfma || !ctx->cae_enc_dma || !ctx->lds_pipe)   // the uniform forward would run other kernels
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score needs the default options cae_dec_fused=1, cae_enc1_mfma=1, "
                 "cae_enc_dma=1 and lds_pipe=1");
   if (F > 1022 || !cae_dec_fused_supports(T_max, F, stride_t, stride_f))
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score needs F <= 1022, non-negative strides and 32-bit element "
                 "offsets inside an utterance (F=%d, stride_t=%lld, stride_f=%lld)", F, (long long)stride_t, (long long)stride_f);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
-  if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
-    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged score cannot be captured into a graph: its lengths are copied per call");
-  const size_t tab_off = pl.total, words = (size_t)4 * B, need = pl.total + align_up(words * 4, 256);
-  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
+  DFA_TRY(refuse_capture(ctx, "score"));
+  const size_t tab_off = pl.total, words = (size_t)4 * B;
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total + align_up(words * 4, 256)));
   char* ws = (char*)workspace;
   const int* dtab = (const int*)(ws + tab_off);
   hipStream_t s = ctx->stream;
-  {
-    const int rc = stage_ragged_table(ctx, lengths, B, words, ws + tab_off, [&](int32_t* tab) {
-      for (int b = 0; b < B; ++b) {
-        const float inv_n = 1.0f / ((float)lengths[b] * (float)F);     // as the uniform call forms it
-        memcpy(&tab[2 * B + b], &inv_n, 4);
-        tab[3 * B + b] = cae_dec_fused_tiles(lengths[b] / 16, pl.W[4]);
-      }
-    });
-    if (rc != DFA_OK) return rc;
-  }
+  DFA_TRY(stage_ragged_table(ctx, lengths, B, words, ws + tab_off, [&](int32_t* tab) {
+    for (int b = 0; b < B; ++b) {
+      const float inv_n = 1.0f / ((float)lengths[b] * (float)F);     // as the uniform call forms it
+      memcpy(&tab[2 * B + b], &inv_n, 4);
+      tab[3 * B + b] = cae_dec_fused_tiles(lengths[b] / 16, pl.W[4]);
+    }
+  }));
   const RaggedTab rt{dtab, B};
   void* e[4] = {ws + pl.e_off[0], ws + pl.e_off[1], ws + pl.e_off[2], ws + pl.e_off[3]};
   { ScopedSlot ts(ctx, 8);

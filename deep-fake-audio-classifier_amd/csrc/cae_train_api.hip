@@ -1,7 +1,7 @@
 // cae_train_api.hip -- C ABI of the ConvAutoencoder training step (replaces, for src/train_cae.py:58-82, torch autograd
 // over src/model_cae.py:32-125):  dfa_cae_forward_train (BatchNorm with batch statistics, running-stat update, keeps
 // what backward needs in the workspace) and dfa_cae_backward (gradients of the 30 parameters from d(loss)/d(recon)).
-#include "dfa_internal.h"
+#include "dfa_checks.h"
 #include "trace.h"
 #include "convt2x2_mfma.h"
 
@@ -151,7 +151,7 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
   if (B < 1 || T < 16) return fail(ctx, DFA_E_BAD_SHAPE, "need B >= 1 and T >= 16 (got %d, %d)", B, T);
   const CaeTrainPlan pl = plan_cae_train(B, T, F, precision);
   if (!pl.ok) return fail(ctx, DFA_E_BAD_SHAPE, "F=%d: decoder would rebuild %d columns (needs F = 16*(F/16)+4)", F, pl.Wd[3]);
-  if (workspace_bytes < pl.total) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small: %zu < %zu bytes", workspace_bytes, pl.total);
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total, false, "train "));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int prec = precision;
   if (!m.train_packed) {  // raw conv images enc2-4 (+ their dgrad images), raw convT images, conv1 fold target, biases

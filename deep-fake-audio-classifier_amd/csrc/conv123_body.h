@@ -63,6 +63,20 @@ static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert(P_OFF + RING_BYTES < 65536 + P_OFF, "");
 }  // namespace c123
 
+// host: the arguments both launchers pass (launch_conv123_fused / launch_conv123_persist, same parameters)
+static inline Conv123Args c123_args(const void* x, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack, const float* c1bias,
+                                    const uint4* wpack2, const float* bias2, const uint4* wpack3, const float* bias3, float* emb, int B,
+                                    int T, int F, int chunk_iters, long long* clock_stamps) {
+  Conv123Args a{};
+  a.x = x; a.sxb = sb; a.sxt = st; a.sxf = sf;
+  a.c1pack = c1pack; a.c1bias = c1bias; a.wpack2 = wpack2; a.bias2 = bias2; a.wpack3 = wpack3; a.bias3 = bias3; a.emb = emb;
+  a.B = B; a.T = T; a.F = F; a.H1 = T / 2; a.H2 = a.H1 / 2; a.nstrips = (F + c123::SW - 1) / c123::SW;
+  a.inv_h = 1.0f / (float)a.H2;
+  a.chunk_iters = chunk_iters;
+  a.clock_stamps = clock_stamps;
+  return a;
+}
+
 __device__ __forceinline__ float ld_as_float123(const float* p) { return *p; }
 __device__ __forceinline__ float ld_as_float123(const bf16_t* p) { return bf16_to_float(*p); }
 __device__ __forceinline__ f32x4_t mma16_123(const uint4& w, const uint4& x, f32x4_t c) {

@@ -85,13 +85,7 @@ hipError_t launch_conv123_persist(const void* x, int x_dtype, int64_t sb, int64_
                                   const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
                                   int num_cus, hipStream_t s, int pipe) {
   if (num_cus < 1) return hipErrorInvalidValue;
-  Conv123Args a{};
-  a.x = x; a.sxb = sb; a.sxt = st; a.sxf = sf;
-  a.c1pack = c1pack; a.c1bias = c1bias; a.wpack2 = wpack2; a.bias2 = bias2; a.wpack3 = wpack3; a.bias3 = bias3; a.emb = emb;
-  a.B = B; a.T = T; a.F = F; a.H1 = T / 2; a.H2 = a.H1 / 2; a.nstrips = (F + c123::SW - 1) / c123::SW;
-  a.inv_h = 1.0f / (float)a.H2;
-  a.chunk_iters = chunk_iters;
-  a.clock_stamps = clock_stamps;
+  const Conv123Args a = c123_args(x, sb, st, sf, c1pack, c1bias, wpack2, bias2, wpack3, bias3, emb, B, T, F, chunk_iters, clock_stamps);
   if (x_dtype == DFA_DTYPE_BF16) return pipe ? launch_conv123_persist_t<bf16_t, true>(a, num_cus, s) : launch_conv123_persist_t<bf16_t, false>(a, num_cus, s);
   return pipe ? launch_conv123_persist_t<float, true>(a, num_cus, s) : launch_conv123_persist_t<float, false>(a, num_cus, s);
 }

@@ -3,14 +3,13 @@
 #include <algorithm>
 #include <vector>
 
-#include "dfa_internal.h"
+#include "dfa_checks.h"
 #include "trace.h"
 
 using namespace dfa;
 
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr int NF = DFA_DLQ_TILE_FRAMES;
 
 // workspace: [table: 4 B + 1 words] [h1: B T_max pixels of 1.5 KB] [h2: the same] [per-tile pool records: B ceil(T_max / NF) x 512 floats]
@@ -36,16 +35,13 @@ DlqPlan plan_dlq(int B, int T_max) {
 extern "C" {
 
 int dfa_dlq_set_params(dfa_ctx* ctx, const float* const* device_params, int n, int in_ch, int hidden) {
-  if (!ctx || !device_params) return DFA_E_NULL_PTR;
-  if (n != DFA_DLQ_NPARAMS) return fail(ctx, DFA_E_BAD_SHAPE, "DeepfakeDetector expects %d parameter pointers, got %d", DFA_DLQ_NPARAMS, n);
-  if (hidden != 256) return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector HIP path is built for hidden=256 (got %d)", hidden);
-  if (in_ch < 4 || in_ch > 256 || (in_ch & 3) != 0)
-    return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector HIP path needs in_ch %% 4 == 0 and 4 <= in_ch <= 256 (got in_ch=%d)", in_ch);
-  for (int i = 0; i < n; ++i)
-    if (!device_params[i]) return fail(ctx, DFA_E_NULL_PTR, "DeepfakeDetector parameter %d is null", i);
-  for (int i = 0; i < n; ++i) ctx->dlq.p[i] = device_params[i];
+  DFA_TRY(set_params_core(ctx, &dfa_ctx::dlq, "DeepfakeDetector", device_params, n, [&]() -> int {
+    if (hidden != 256) return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector HIP path is built for hidden=256 (got %d)", hidden);
+    if (in_ch < 4 || in_ch > 256 || (in_ch & 3) != 0)
+      return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector HIP path needs in_ch %% 4 == 0 and 4 <= in_ch <= 256 (got in_ch=%d)", in_ch);
+    return DFA_OK;
+  }));
   ctx->dlq.in_ch = in_ch;
-  ctx->dlq.have_params = true;
   ctx->dlq.prepared = false;
   return DFA_OK;
 }
@@ -87,22 +83,11 @@ int dfa_dlq_forward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, in
   if (T_max < 1) return fail(ctx, DFA_E_BAD_SHAPE, "T_max must be >= 1 (got %d)", T_max);
   if (in_ch != m.in_ch)
     return fail(ctx, DFA_E_BAD_SHAPE, "channel dim %d does not match in_ch=%d of the first Conv1d (src/dlqueen_model.py:136)", in_ch, m.in_ch);
-  for (int b = 0; b < B; ++b)
-    if (lengths[b] < 1 || lengths[b] > T_max)
-      return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [1, T_max=%d]", b, (int)lengths[b], T_max);
-  if ((stride_c & 3) != 0 || stride_c < T_max)
-    return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector forward needs stride_c %% 4 == 0 and stride_c >= T_max=%d (got stride_c=%lld)", T_max,
-                (long long)stride_c);
-  if ((stride_b & 3) != 0 || stride_b < 0)
-    return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector forward needs a non-negative stride_b %% 4 == 0 (got stride_b=%lld)", (long long)stride_b);
-  if (((uintptr_t)x & 15) != 0) return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector forward needs x 16-byte aligned (got %p)", x);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
-  if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
-    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged forward cannot be captured into a graph: its lengths are copied per call");
+  DFA_TRY(check_lengths(ctx, lengths, B, 1, T_max));
+  DFA_TRY(check_channel_major(ctx, "DeepfakeDetector forward", "stride_c", x, stride_b, stride_c, T_max));
+  DFA_TRY(refuse_capture(ctx, "forward"));
   const DlqPlan pl = plan_dlq(B, T_max);
-  if (workspace_bytes < pl.total) return fail(ctx, DFA_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, pl.total);
-  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total));
 
   // the tile list: utterances longest first (ties in batch order); position i owns tiles [first[i], first[i + 1]) of NF frames
   // over the frames layer 1 produces, min(T_max, len + 2)
@@ -118,10 +103,7 @@ int dfa_dlq_forward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, in
   }
   first[B] = (int32_t)ntiles;
   if (ntiles >= ((long long)1 << 31)) return fail(ctx, DFA_E_UNSUPPORTED, "the batch needs %lld tiles (limit 2^31 - 1)", ntiles);
-  {
-    const int rc = stage_ragged_lengths_extra(ctx, lengths, B, extra.data(), extra.size(), workspace);
-    if (rc != DFA_OK) return rc;
-  }
+  DFA_TRY(stage_ragged_lengths_extra(ctx, lengths, B, extra.data(), extra.size(), workspace));
   char* ws = (char*)workspace;
   DlqLayerArgs a{};
   a.x = (const float*)x;

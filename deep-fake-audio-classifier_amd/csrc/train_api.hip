@@ -5,7 +5,7 @@
 //   dfa_cnn2d_backward      : gradients of all 14 parameters from dlogits (in parameters() order)
 //   dfa_bce_smooth_fwd_bwd  : BCEWithLogitsLoss(mean) on smoothed labels + dlogits      (src/train.py:311-320)
 //   dfa_adamw_step          : torch.optim.AdamW update of one flat fp32 buffer           (src/train.py:326-328)
-#include "dfa_internal.h"
+#include "dfa_checks.h"
 #include "trace.h"
 
 using namespace dfa;
@@ -136,8 +136,7 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   if (F != m.in_features) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d", F, m.in_features);
   if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(ctx, DFA_E_BAD_SHAPE, "dropout p must be in [0, 1)");
   const TrainPlan pl = plan_train(B, T, F, precision);
-  if (workspace_bytes < pl.total) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small: %zu < %zu bytes", workspace_bytes, pl.total);
-  if (((uintptr_t)workspace & 255) != 0) return fail(ctx, DFA_E_WORKSPACE, "workspace must be 256-byte aligned");
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total, true, "train "));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // train-mode weight images: raw convs (BN is its own pass) + data-gradient images; rebuilt every step (weights move)
   if (!m.train_packed) {
@@ -504,16 +503,12 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   double frames = (double)B * T;             // frames BatchNorm1d counts
   if (lengths) {
     if (T < 3) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: a ragged cnn1d batch needs T_max >= 3", T);
+    DFA_TRY(check_lengths(ctx, lengths, B, 3, T));
     frames = 0.0;
-    for (int b = 0; b < B; ++b) {
-      if (lengths[b] < 3 || lengths[b] > T)
-        return fail(ctx, DFA_E_BAD_SHAPE, "lengths[%d]=%d is outside [3, T_max=%d]", b, (int)lengths[b], T);
-      frames += (double)lengths[b];
-    }
+    for (int b = 0; b < B; ++b) frames += (double)lengths[b];
   }
   const Train1dPlan pl = plan_train1d(B, T, F);
-  const size_t need = pl.total + (lengths ? ragged1d_tab_bytes(B) : 0);
-  if (workspace_bytes < need) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total + (lengths ? ragged1d_tab_bytes(B) : 0), false, "train "));
   if (armed.on && (armed.T != T || armed.F != F))
     return fail(ctx, DFA_E_BAD_SHAPE, "armed augmentation is for [T=%d, F=%d], the batch is [T=%d, F=%d]", armed.T, armed.F, T, F);
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -525,12 +520,8 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
     if (ctx->bn_sync.fn)
       return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed): "
                                           "the ranks' frame counts differ and the hook carries sums only");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    DFA_HIP_CHECK(ctx, hipStreamIsCapturing(ctx->stream, &cap));
-    if (cap != hipStreamCaptureStatusNone)       // a captured copy would replay this call's lengths forever
-      return fail(ctx, DFA_E_UNSUPPORTED, "the ragged training step cannot be captured into a graph: its lengths are copied per call");
-    const int rc = stage_ragged_lengths(ctx, lengths, B, (char*)workspace + pl.total);
-    if (rc != DFA_OK) return rc;
+    DFA_TRY(refuse_capture(ctx, "training step"));
+    DFA_TRY(stage_ragged_lengths(ctx, lengths, B, (char*)workspace + pl.total));
     lens = (const int*)((char*)workspace + pl.total);
   }
   m.train_aug = armed;

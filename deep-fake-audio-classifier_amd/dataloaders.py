@@ -135,6 +135,10 @@ class FlatBatcher:
         finally:
             self._unregister()
 
+    def restore(self, outputs):
+        """Per-batch outputs -> one tensor in input order (the batches already are)."""
+        return torch.cat(list(outputs))
+
 
 class IndexedFlatBatcher:
     """Batches of ARBITRARY rows of a flat [N,180,321] source -- the data-parallel TRAINING loader (the
@@ -377,3 +381,24 @@ class RaggedBatcher:
         cat = torch.cat(list(outputs))
         inv = torch.from_numpy(np.argsort(np.concatenate(self.batches) - self.lo, kind="stable")).to(cat.device)
         return cat[inv]
+
+
+class EvalBatches:
+    """One face for both inference sources: a stacked [N, F, T] tensor (FlatBatcher) or a list of per-utterance [F, T_i] tensors
+    of unequal lengths (RaggedBatcher).  Iterates (x [b, T, F] on `device`, lengths): lengths is None for a stacked source --
+    the model is then called without `lengths=` -- and x its transposed view (the stored batch itself with swap_tf=False);
+    `restore` puts per-batch outputs back in input order."""
+
+    def __init__(self, source, batch_size: int, device="cuda", rank: int = 0, world: int = 1, dtype=None, swap_tf: bool = True):
+        self.ragged, self.swap_tf = isinstance(source, (list, tuple)), swap_tf
+        self.batcher = (RaggedBatcher if self.ragged else FlatBatcher)(source, None, batch_size, device=device, rank=rank,
+                                                                      world=world, dtype=dtype)
+        self.restore = self.batcher.restore
+
+    def __iter__(self):
+        if self.ragged:
+            for x, _, lengths in self.batcher:
+                yield x, lengths
+        else:
+            for feats, _ in self.batcher:
+                yield (feats.transpose(1, 2) if self.swap_tf else feats), None        # src/predict.py:104-105

@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._params import BatchNormParams, ConvParams, LinearParams, Slots, tensors_signature
+from ._params import BatchNormParams, ConvParams, LinearParams, Slots
 
 TILE_FRAMES = 64     # DFA_DLQ_TILE_FRAMES: frames of one utterance a workgroup owns (tests probe the sizes around it)
 _EVAL_ONLY = ("dfa_amd.dlqueen_model is eval-only in this version: the DeepfakeDetector training step (AdamW, EMA, class "
@@ -60,19 +60,7 @@ class DeepfakeDetector(nn.Module):
         return out + [self.head[0].weight, self.head[0].bias, self.head[3].weight, self.head[3].bias]
 
     def _ensure_prepared(self, ctx):
-        ts = self._abi_tensors()
-        for t in ts:
-            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError("DeepfakeDetector parameters must be contiguous float32 tensors on the GPU "
-                                   "(call model.to('cuda')); dfa_amd has no CPU path")
-        sig = (ctx.index, tensors_signature(ts))
-        stale = ctx.owner_changed("dlq", self)
-        if sig == self._prepared and not stale:
-            return
-        arr = _lib.ptr_array([t.detach() for t in ts])
-        _lib.check(ctx.handle, ctx.lib.dfa_dlq_set_params(ctx.handle, arr, len(ts), self.in_ch, self.hidden))
-        _lib.check(ctx.handle, ctx.lib.dfa_dlq_prepare(ctx.handle))
-        self._prepared = sig
+        _lib.ensure_prepared(self, ctx, "dlq", "dfa_dlq_set_params", (self.in_ch, self.hidden), "dfa_dlq_prepare")
 
     @staticmethod
     def _conforms(x) -> bool:
@@ -93,8 +81,7 @@ class DeepfakeDetector(nn.Module):
             raise NotImplementedError(_EVAL_ONLY + "; call model.eval()")
         if x.dim() != 3:
             raise ValueError(f"DeepfakeDetector expects x of shape (B, C, T), got {tuple(x.shape)}")
-        if x.device.type != "cuda":
-            raise RuntimeError("dfa_amd.DeepfakeDetector runs on the GPU only: move the input with .to('cuda')")
+        _lib.require_gpu(self, x)       # (launch() asks again: here it keeps its place in front of the checks below)
         if not x.is_floating_point():
             raise ValueError(f"DeepfakeDetector takes a floating-point input, got {x.dtype}")
         B, Cc, T = x.shape
@@ -102,22 +89,14 @@ class DeepfakeDetector(nn.Module):
         if B == 0:
             empty = torch.empty(0, dtype=torch.float32, device=x.device)
             return (empty, empty.reshape(0, 2 * self.hidden)) if return_pooled else empty
-        if not self._conforms(x):
-            stored = torch.zeros((B, Cc, -(-T // 4) * 4), dtype=torch.float32, device=x.device)
-            stored[:, :, :T] = x
-            x = stored[:, :, :T]
+        x = _lib.stored_layout(x, self._conforms(x), time_last=True)
         sb, sc, _ = x.stride()
-        ctx = _lib.Context.get(x.device)
-        with torch.cuda.device(ctx.index):
-            ctx.use_current_stream()
-            self._ensure_prepared(ctx)
+        with _lib.launch(self, x) as ctx:
             ws = ctx.workspace(ctx.lib.dfa_dlq_workspace_bytes(ctx.handle, B, T, Cc))
             logits = torch.empty(B, dtype=torch.float32, device=x.device)
             pooled = torch.empty((B, 2 * self.hidden), dtype=torch.float32, device=x.device) if return_pooled else None
-            code = ctx.lib.dfa_dlq_forward(
-                ctx.handle, C.c_void_p(x.data_ptr()), B, T, Cc, sb, sc, C.c_void_p(lengths.ctypes.data),
-                C.c_void_p(logits.data_ptr()), C.c_void_p(pooled.data_ptr()) if return_pooled else None,
-                C.c_void_p(ws.data_ptr()), ws.numel())
+            code = ctx.lib.dfa_dlq_forward(ctx.handle, _lib.ptr(x), B, T, Cc, sb, sc, C.c_void_p(lengths.ctypes.data),
+                                           _lib.ptr(logits), _lib.ptr(pooled), _lib.ptr(ws), ws.numel())
             _lib.check(ctx.handle, code)
         return (logits, pooled) if return_pooled else logits
 

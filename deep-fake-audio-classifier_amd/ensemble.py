@@ -16,7 +16,7 @@ import torch
 from . import distributed as dfa_dist
 from . import fusion
 from .evaluation import calculate_eer
-from .hybrid_ensemble import _stack, check_ragged_members, is_ragged, score_models, score_models_ragged
+from .hybrid_ensemble import _stack, check_ragged_members, is_ragged, score_models
 from .model import CNN2D
 from .model_cnn1d import CNN1D
 from .predict import load_weights
@@ -69,7 +69,7 @@ def main(argv=None):
     for spec in args.checkpoints:
         arch, path = spec.split(":", 1)
         model = load_model(arch, path, device, args.in_features, args.dropout, args.precision)
-        local = (score_models_ragged if ragged else score_models)(stored, cnn2d=model if arch == "cnn2d" else None, cnn1d=model if arch == "cnn1d" else None,
+        local = score_models(stored, cnn2d=model if arch == "cnn2d" else None, cnn1d=model if arch == "cnn1d" else None,
                              batch_size=args.batch_size, device=device, rank=rank, world=world)[arch]
         scores = dfa_dist.gather_scores(local, device=dev)
         all_scores.append(scores)

@@ -17,7 +17,7 @@ import torch
 
 from . import distributed as dfa_dist
 from . import fusion
-from .dataloaders import FlatBatcher, RaggedBatcher
+from .dataloaders import EvalBatches
 from .dataset_cae import FeatureNormalizer
 from .evaluation import calculate_eer
 from .model import CNN2D
@@ -27,11 +27,11 @@ from .predict import load_weights
 
 
 @torch.no_grad()
-def score_models(stored_features: torch.Tensor, cnn2d=None, cnn1d=None, cae=None, normalizer=None, batch_size=256,
-                 device="cuda", rank=0, world=1):
-    """One pass over this rank's shard; returns dict of numpy score vectors for the models that were given:
-    'cnn2d' / 'cnn1d' sigmoid scores (src/hybrid_ensemble.py:31-43, src/ensemble.py:52-62), 'cae' per-sample MSE
-    (src/hybrid_ensemble.py:46-61)."""
+def score_models(source, cnn2d=None, cnn1d=None, cae=None, normalizer=None, batch_size=256, device="cuda", rank=0, world=1):
+    """One pass over this rank's shard of `source` -- the stacked stored features [N,180,321], or a list of per-utterance
+    [F, T_i] tensors of unequal lengths (then every given model scores the same resident padded batch with `lengths=`, and the
+    results come back in input order); returns dict of numpy score vectors for the models that were given: 'cnn2d' / 'cnn1d'
+    sigmoid scores (src/hybrid_ensemble.py:31-43, src/ensemble.py:52-62), 'cae' per-sample MSE (src/hybrid_ensemble.py:46-61)."""
     for m in (cnn2d, cnn1d, cae):
         if m is not None:
             m.eval()
@@ -39,39 +39,19 @@ def score_models(stored_features: torch.Tensor, cnn2d=None, cnn1d=None, cae=None
     if cae is not None and normalizer is not None:
         mean, std = normalizer.mean.to(device), normalizer.std.to(device)
     out = {k: [] for k, m in (("cnn2d", cnn2d), ("cnn1d", cnn1d), ("cae", cae)) if m is not None}
-    for feats, _ in FlatBatcher(stored_features, None, batch_size, device=device, rank=rank, world=world):
-        x = feats.transpose(1, 2)                                    # the strided [b,T,F] view, no copy
+    batches = EvalBatches(source, batch_size, device=device, rank=rank, world=world)
+    for x, lengths in batches:                                       # uniform: the strided [b,T,F] view, no copy
+        kw = {} if lengths is None else {"lengths": lengths}
         if cnn2d is not None:
-            out["cnn2d"].append(torch.sigmoid(cnn2d(x).squeeze(-1)))
+            out["cnn2d"].append(torch.sigmoid(cnn2d(x, **kw).squeeze(-1)))
         if cnn1d is not None:
-            out["cnn1d"].append(torch.sigmoid(cnn1d(x).squeeze(-1)))
+            out["cnn1d"].append(torch.sigmoid(cnn1d(x, **kw).squeeze(-1)))
         if cae is not None:
-            out["cae"].append(cae.score(x, mean, std))
-    return {k: (torch.cat(v).double().cpu().numpy() if v else np.zeros(0)) for k, v in out.items()}
+            out["cae"].append(cae.score(x, mean, std, **kw))
+    return {k: (batches.restore(v).double().cpu().numpy() if v else np.zeros(0)) for k, v in out.items()}
 
 
-@torch.no_grad()
-def score_models_ragged(feature_list, cnn2d=None, cnn1d=None, cae=None, normalizer=None, batch_size=256, device="cuda",
-                        rank=0, world=1):
-    """score_models for a list of per-utterance [F, T_i] tensors of unequal lengths: one RaggedBatcher pass over this rank's
-    shard, every given model scores the same resident padded batch with `lengths=`, and the results come back in input
-    order.  Same return dict as score_models."""
-    for m in (cnn2d, cnn1d, cae):
-        if m is not None:
-            m.eval()
-    mean = std = None
-    if cae is not None and normalizer is not None:
-        mean, std = normalizer.mean.to(device), normalizer.std.to(device)
-    out = {k: [] for k, m in (("cnn2d", cnn2d), ("cnn1d", cnn1d), ("cae", cae)) if m is not None}
-    batcher = RaggedBatcher(feature_list, None, batch_size, device=device, rank=rank, world=world)
-    for x, _, lengths in batcher:
-        if cnn2d is not None:
-            out["cnn2d"].append(torch.sigmoid(cnn2d(x, lengths=lengths).squeeze(-1)))
-        if cnn1d is not None:
-            out["cnn1d"].append(torch.sigmoid(cnn1d(x, lengths=lengths).squeeze(-1)))
-        if cae is not None:
-            out["cae"].append(cae.score(x, mean, std, lengths=lengths))
-    return {k: (batcher.restore(v).double().cpu().numpy() if v else np.zeros(0)) for k, v in out.items()}
+score_models_ragged = score_models      # (the name the ragged-only callers know)
 
 
 def is_ragged(df) -> bool:
@@ -94,11 +74,9 @@ def check_ragged_members(members, precision: str) -> None:
 
 
 def score_table(df, cnn2d=None, cnn1d=None, cae=None, normalizer=None, batch_size=256, device="cuda", rank=0, world=1):
-    """score_models on the stacked features of an equal-length table, score_models_ragged on a table of unequal lengths."""
-    if is_ragged(df):
-        return score_models_ragged([f.float() for f in df["features"]], cnn2d, cnn1d, cae, normalizer, batch_size, device,
-                                   rank, world)
-    return score_models(_stack(df), cnn2d, cnn1d, cae, normalizer, batch_size, device, rank, world)
+    """score_models on the stacked features of an equal-length table, on the list of utterances of a table of unequal lengths."""
+    source = [f.float() for f in df["features"]] if is_ragged(df) else _stack(df)
+    return score_models(source, cnn2d, cnn1d, cae, normalizer, batch_size, device, rank, world)
 
 
 def hybrid_report(sup_scores, cae_scores, labels, alpha_steps=21):

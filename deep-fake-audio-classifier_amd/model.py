@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._params import BatchNormParams, ConvParams, LinearParams, Slots, tensors_signature
+from ._params import BatchNormParams, ConvParams, LinearParams, Slots
 
 
 class CNN2D(nn.Module):
@@ -69,20 +69,8 @@ class CNN2D(nn.Module):
         return self
 
     def _ensure_prepared(self, ctx: "_lib.Context"):
-        ts = self._abi_tensors()
-        for t in ts:
-            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError("CNN2D parameters must be contiguous float32 tensors on the GPU "
-                                   "(call model.to('cuda')); dfa_amd has no CPU path")
-        sig = (ctx.index, self.precision, tensors_signature(ts))
-        stale = ctx.owner_changed("cnn2d", self)      # another model of this class used the ctx's weight slot
-        if sig == self._prepared and not stale:
-            return
-        arr = _lib.ptr_array([t.detach() for t in ts])
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn2d_set_params(ctx.handle, arr, len(ts), self.in_features,
-                                                            self.base_channels))
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn2d_prepare(ctx.handle, _lib.PRECISIONS[self.precision]))
-        self._prepared = sig
+        _lib.ensure_prepared(self, ctx, "cnn2d", "dfa_cnn2d_set_params", (self.in_features, self.base_channels),
+                             "dfa_cnn2d_prepare", self.precision)
 
     # ---- forward -----------------------------------------------------------------------------------------------
     def forward(self, x, return_embedding=False, lengths=None):
@@ -98,52 +86,25 @@ class CNN2D(nn.Module):
             from .training import cnn2d_train_forward  # train-mode path (batch-stat BN, dropout, autograd)
             return cnn2d_train_forward(self, x, return_embedding)
         if lengths is not None:
-            return self._ragged_forward(x, return_embedding, _lib.host_lengths(lengths, x.shape[0], x.shape[1], 4))
-        return self._eval_forward(x, return_embedding)
+            lengths = _lib.host_lengths(lengths, x.shape[0], x.shape[1], 4)
+        return self._forward(x, return_embedding, lengths)
 
-    def _ragged_forward(self, x, return_embedding, lengths):
-        if x.device.type != "cuda":
-            raise RuntimeError("dfa_amd.CNN2D runs on the GPU only: move the input with .to('cuda')")
+    def _forward(self, x, return_embedding, lengths):
+        """lengths: None, or the checked host int32 array of a ragged batch"""
         B, T, F = x.shape
-        ctx = _lib.Context.get(x.device)
-        with torch.cuda.device(ctx.index):
-            ctx.use_current_stream()
-            self._ensure_prepared(ctx)
-            prec = _lib.PRECISIONS[self.precision]
-            nbytes = ctx.lib.dfa_ragged_workspace_bytes(ctx.handle, _lib.MODEL_CNN2D, B, T, F, prec)
-            ws = ctx.workspace(nbytes)
+        with _lib.launch(self, x) as ctx:
+            lib, prec = ctx.lib, _lib.PRECISIONS[self.precision]
+            planner = lib.dfa_workspace_bytes if lengths is None else lib.dfa_ragged_workspace_bytes
+            ws = ctx.workspace(planner(ctx.handle, _lib.MODEL_CNN2D, B, T, F, prec))
             logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
             emb = torch.empty((B, 4 * self.base_channels * F), dtype=torch.float32, device=x.device) \
                 if return_embedding else None
-            sb, st, sf = x.stride()
-            code = ctx.lib.dfa_cnn2d_forward_ragged(
-                ctx.handle, C.c_void_p(x.data_ptr()), _lib.x_dtype_code(x), B, T, F, sb, st, sf,
-                C.c_void_p(lengths.ctypes.data), C.c_void_p(logits.data_ptr()),
-                C.c_void_p(emb.data_ptr() if emb is not None else None), C.c_void_p(ws.data_ptr()), ws.numel())
-            _lib.check(ctx.handle, code)
-        if return_embedding:
-            return logits, emb
-        return logits
-
-    def _eval_forward(self, x, return_embedding):
-        if x.device.type != "cuda":
-            raise RuntimeError("dfa_amd.CNN2D runs on the GPU only: move the input with .to('cuda')")
-        B, T, F = x.shape
-        ctx = _lib.Context.get(x.device)
-        with torch.cuda.device(ctx.index):
-            ctx.use_current_stream()
-            self._ensure_prepared(ctx)
-            prec = _lib.PRECISIONS[self.precision]
-            nbytes = ctx.lib.dfa_workspace_bytes(ctx.handle, _lib.MODEL_CNN2D, B, T, F, prec)
-            ws = ctx.workspace(nbytes)
-            logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
-            emb = torch.empty((B, 4 * self.base_channels * F), dtype=torch.float32, device=x.device) \
-                if return_embedding else None
-            sb, st, sf = x.stride()
-            code = ctx.lib.dfa_cnn2d_forward(
-                ctx.handle, C.c_void_p(x.data_ptr()), _lib.x_dtype_code(x), B, T, F, sb, st, sf,
-                C.c_void_p(logits.data_ptr()), C.c_void_p(emb.data_ptr() if emb is not None else None),
-                C.c_void_p(ws.data_ptr()), ws.numel())
+            head = (ctx.handle, _lib.ptr(x), _lib.x_dtype_code(x), B, T, F, *x.stride())
+            tail = (_lib.ptr(logits), _lib.ptr(emb), _lib.ptr(ws), ws.numel())
+            if lengths is None:
+                code = lib.dfa_cnn2d_forward(*head, *tail)
+            else:
+                code = lib.dfa_cnn2d_forward_ragged(*head, C.c_void_p(lengths.ctypes.data), *tail)
             _lib.check(ctx.handle, code)
         if return_embedding:
             return logits, emb

@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._params import BatchNormParams, ConvParams, Slots, tensors_signature
+from ._params import BatchNormParams, ConvParams, Slots
 
 
 class ConvAutoencoder(nn.Module):
@@ -66,34 +66,18 @@ class ConvAutoencoder(nn.Module):
         return out
 
     def _ensure_prepared(self, ctx):
-        ts = self._abi_tensors()
-        for t in ts:
-            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError("ConvAutoencoder parameters must be contiguous float32 tensors on the GPU "
-                                   "(call model.to('cuda')); dfa_amd has no CPU path")
-        sig = (ctx.index, self.precision, tensors_signature(ts))
-        stale = ctx.owner_changed("cae", self)      # another model of this class used the ctx's weight slot
-        if sig == self._prepared and not stale:
-            return
-        arr = _lib.ptr_array([t.detach() for t in ts])
-        _lib.check(ctx.handle, ctx.lib.dfa_cae_set_params(ctx.handle, arr, len(ts), self.base_channels))
-        _lib.check(ctx.handle, ctx.lib.dfa_cae_prepare(ctx.handle, _lib.PRECISIONS[self.precision]))
-        self._prepared = sig
+        _lib.ensure_prepared(self, ctx, "cae", "dfa_cae_set_params", (self.base_channels,), "dfa_cae_prepare", self.precision)
 
-    def _run(self, x, mean, std, want_recon, want_latent, want_mse):
+    def _run(self, x, mean, std, want_recon, want_latent, want_mse, lengths=None):
+        """lengths: None, or the checked host int32 array of a ragged batch (score only: want_mse alone)"""
         if x.dim() != 3:
             raise ValueError(f"ConvAutoencoder expects x of shape (B, T, F), got {tuple(x.shape)}")
-        if x.device.type != "cuda":
-            raise RuntimeError("dfa_amd.ConvAutoencoder runs on the GPU only: move the input with .to('cuda')")
         B, T, F = x.shape
-        ctx = _lib.Context.get(x.device)
-        with torch.cuda.device(ctx.index):
-            ctx.use_current_stream()
-            self._ensure_prepared(ctx)
-            prec = _lib.PRECISIONS[self.precision]
-            nbytes = ctx.lib.dfa_workspace_bytes(ctx.handle, _lib.MODEL_CAE, B, T, F, prec)
+        with _lib.launch(self, x) as ctx:
+            lib, prec, dev, ptr = ctx.lib, _lib.PRECISIONS[self.precision], x.device, _lib.ptr
+            nbytes = lib.dfa_workspace_bytes(ctx.handle, _lib.MODEL_CAE, B, T, F, prec) if lengths is None else \
+                lib.dfa_cae_ragged_workspace_bytes(ctx.handle, B, T, F, prec)
             ws = ctx.workspace(max(nbytes, 256))
-            dev = x.device
             recon = torch.empty((B, T, F), dtype=torch.float32, device=dev) if want_recon else None
             latent = torch.empty((B, 8 * self.base_channels, T // 16, F // 16), dtype=torch.float32, device=dev) \
                 if want_latent else None
@@ -103,12 +87,12 @@ class ConvAutoencoder(nn.Module):
                 std = std.to(device=dev, dtype=torch.float32).contiguous()
                 if mean.numel() != F or std.numel() != F:
                     raise ValueError(f"normaliser statistics must have {F} entries")
-
-            def ptr(t):
-                return C.c_void_p(t.data_ptr() if t is not None else None)
-            sb, st, sf = x.stride()
-            code = ctx.lib.dfa_cae_forward(ctx.handle, ptr(x), _lib.x_dtype_code(x), B, T, F, sb, st, sf, ptr(mean),
-                                           ptr(std), ptr(recon), ptr(latent), ptr(mse), ptr(ws), ws.numel())
+            head = (ctx.handle, ptr(x), _lib.x_dtype_code(x), B, T, F, *x.stride())
+            if lengths is None:
+                code = lib.dfa_cae_forward(*head, ptr(mean), ptr(std), ptr(recon), ptr(latent), ptr(mse), ptr(ws), ws.numel())
+            else:
+                code = lib.dfa_cae_score_ragged(*head, C.c_void_p(lengths.ctypes.data), ptr(mean), ptr(std), ptr(mse), ptr(ws),
+                                                ws.numel())
             _lib.check(ctx.handle, code)
         return recon, latent, mse
 
@@ -119,34 +103,6 @@ class ConvAutoencoder(nn.Module):
             return cae_train_forward(self, x)
         recon, latent, _ = self._run(x, None, None, True, True, False)
         return recon, latent
-
-    def _score_ragged(self, x, mean, std, lengths):
-        if x.device.type != "cuda":
-            raise RuntimeError("dfa_amd.ConvAutoencoder runs on the GPU only: move the input with .to('cuda')")
-        B, T, F = x.shape
-        ctx = _lib.Context.get(x.device)
-        with torch.cuda.device(ctx.index):
-            ctx.use_current_stream()
-            self._ensure_prepared(ctx)
-            prec = _lib.PRECISIONS[self.precision]
-            nbytes = ctx.lib.dfa_cae_ragged_workspace_bytes(ctx.handle, B, T, F, prec)
-            ws = ctx.workspace(max(nbytes, 256))
-            dev = x.device
-            mse = torch.empty((B,), dtype=torch.float32, device=dev)
-            if mean is not None:
-                mean = mean.to(device=dev, dtype=torch.float32).contiguous()
-                std = std.to(device=dev, dtype=torch.float32).contiguous()
-                if mean.numel() != F or std.numel() != F:
-                    raise ValueError(f"normaliser statistics must have {F} entries")
-
-            def ptr(t):
-                return C.c_void_p(t.data_ptr() if t is not None else None)
-            sb, st, sf = x.stride()
-            code = ctx.lib.dfa_cae_score_ragged(ctx.handle, ptr(x), _lib.x_dtype_code(x), B, T, F, sb, st, sf,
-                                                C.c_void_p(lengths.ctypes.data), ptr(mean), ptr(std), ptr(mse), ptr(ws),
-                                                ws.numel())
-            _lib.check(ctx.handle, code)
-        return mse
 
     @torch.no_grad()
     def score(self, x: torch.Tensor, mean: torch.Tensor | None = None, std: torch.Tensor | None = None, lengths=None):
@@ -159,8 +115,8 @@ class ConvAutoencoder(nn.Module):
         if lengths is not None:
             if x.dim() != 3:
                 raise ValueError(f"ConvAutoencoder expects x of shape (B, T, F), got {tuple(x.shape)}")
-            return self._score_ragged(x, mean, std, _lib.host_lengths(lengths, x.shape[0], x.shape[1], 16))
-        return self._run(x, mean, std, False, False, True)[2]
+            lengths = _lib.host_lengths(lengths, x.shape[0], x.shape[1], 16)
+        return self._run(x, mean, std, False, False, True, lengths)[2]
 
 
 if __name__ == "__main__":

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._params import BatchNormParams, ConvParams, LinearParams, Slots, tensors_signature
+from ._params import BatchNormParams, ConvParams, LinearParams, Slots
 
 
 class CNN1D(nn.Module):
@@ -42,20 +42,8 @@ class CNN1D(nn.Module):
         return out + [self.classifier.weight, self.classifier.bias]
 
     def _ensure_prepared(self, ctx):
-        ts = self._abi_tensors()
-        for t in ts:
-            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError("CNN1D parameters must be contiguous float32 tensors on the GPU "
-                                   "(call model.to('cuda')); dfa_amd has no CPU path")
-        sig = (ctx.index, tensors_signature(ts))
-        stale = ctx.owner_changed("cnn1d", self)      # another model of this class used the ctx's weight slot
-        if sig == self._prepared and not stale:
-            return
-        arr = _lib.ptr_array([t.detach() for t in ts])
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn1d_set_params(ctx.handle, arr, len(ts), self.in_features,
-                                                            self.base_channels))
-        _lib.check(ctx.handle, ctx.lib.dfa_cnn1d_prepare(ctx.handle))
-        self._prepared = sig
+        _lib.ensure_prepared(self, ctx, "cnn1d", "dfa_cnn1d_set_params", (self.in_features, self.base_channels),
+                             "dfa_cnn1d_prepare")
 
     def forward(self, x, lengths=None):
         """lengths: None (every utterance spans all T frames: the reference's call), or the per-utterance frame counts of a
@@ -71,51 +59,34 @@ class CNN1D(nn.Module):
             from .training import cnn1d_train_forward
             return cnn1d_train_forward(self, x)
         if lengths is not None:
-            return self._ragged_forward(x, _lib.host_lengths(lengths, x.shape[0], x.shape[1], 3))
-        if x.device.type != "cuda":
-            raise RuntimeError("dfa_amd.CNN1D runs on the GPU only: move the input with .to('cuda')")
-        if x.dtype != torch.float32:
-            raise ValueError(f"CNN1D takes float32 input, got {x.dtype}")
-        B, T, F = x.shape
-        ctx = _lib.Context.get(x.device)
-        with torch.cuda.device(ctx.index):
-            ctx.use_current_stream()
-            self._ensure_prepared(ctx)
-            nbytes = ctx.lib.dfa_workspace_bytes(ctx.handle, _lib.MODEL_CNN1D, B, T, F, _lib.PREC_F32)
-            ws = ctx.workspace(nbytes)
-            logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
-            sb, st, sf = x.stride()
-            code = ctx.lib.dfa_cnn1d_forward(ctx.handle, C.c_void_p(x.data_ptr()), _lib.DTYPE_F32, B, T, F, sb, st, sf,
-                                             C.c_void_p(logits.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel())
-            _lib.check(ctx.handle, code)
-        return logits
+            lengths = _lib.host_lengths(lengths, x.shape[0], x.shape[1], 3)
+        return self._forward(x, lengths)
 
-    def _ragged_forward(self, x, lengths):
-        """x: float32 [B, T, F] on the GPU.  The kernel reads the stored channel-major layout -- the transposed view of a
-        [B, F, T_pad] batch with T_pad % 4 == 0, what dataloaders.RaggedBatcher yields -- in place.  A tensor in any other
-        layout (a contiguous [B, T, F], a pitch that is not a multiple of 4, a misaligned base) is first copied into such a
-        zero-padded channel-major batch on the GPU; the result is the same."""
-        if x.device.type != "cuda":
-            raise RuntimeError("dfa_amd.CNN1D runs on the GPU only: move the input with .to('cuda')")
+    def _forward(self, x, lengths):
+        """x: float32 [B, T, F] on the GPU; lengths: None, or the checked host int32 array of a ragged batch.  The ragged kernel
+        reads the stored channel-major layout -- the transposed view of a [B, F, T_pad] batch with T_pad % 4 == 0, what
+        dataloaders.RaggedBatcher yields -- in place.  A tensor in any other layout (a contiguous [B, T, F], a pitch that is not a
+        multiple of 4, a misaligned base) is first copied into such a zero-padded channel-major batch on the GPU; the result is
+        the same."""
+        _lib.require_gpu(self, x)       # (launch() asks again: here it keeps its place in front of the dtype check)
         if x.dtype != torch.float32:
             raise ValueError(f"CNN1D takes float32 input, got {x.dtype}")
         B, T, F = x.shape
-        sb, st, sf = x.stride()
-        if B and not (st == 1 and sf % 4 == 0 and sf >= T and sb % 4 == 0 and sb >= 0 and x.data_ptr() % 16 == 0):
-            stored = torch.zeros((B, F, -(-T // 4) * 4), dtype=torch.float32, device=x.device)
-            stored[:, :, :T] = x.transpose(1, 2)
-            x = stored.transpose(1, 2)[:, :T]
+        if lengths is not None:
             sb, st, sf = x.stride()
-        ctx = _lib.Context.get(x.device)
-        with torch.cuda.device(ctx.index):
-            ctx.use_current_stream()
-            self._ensure_prepared(ctx)
-            nbytes = ctx.lib.dfa_ragged_workspace_bytes(ctx.handle, _lib.MODEL_CNN1D, B, T, F, _lib.PREC_F32)
-            ws = ctx.workspace(nbytes)
+            x = _lib.stored_layout(x, not B or (st == 1 and sf % 4 == 0 and sf >= T and sb % 4 == 0 and sb >= 0
+                                                and x.data_ptr() % 16 == 0), time_last=False)
+        with _lib.launch(self, x) as ctx:
+            lib = ctx.lib
+            planner = lib.dfa_workspace_bytes if lengths is None else lib.dfa_ragged_workspace_bytes
+            ws = ctx.workspace(planner(ctx.handle, _lib.MODEL_CNN1D, B, T, F, _lib.PREC_F32))
             logits = torch.empty((B, 1), dtype=torch.float32, device=x.device)
-            code = ctx.lib.dfa_cnn1d_forward_ragged(
-                ctx.handle, C.c_void_p(x.data_ptr()), _lib.DTYPE_F32, B, T, F, sb, st, sf,
-                C.c_void_p(lengths.ctypes.data), C.c_void_p(logits.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel())
+            head = (ctx.handle, _lib.ptr(x), _lib.DTYPE_F32, B, T, F, *x.stride())
+            tail = (_lib.ptr(logits), _lib.ptr(ws), ws.numel())
+            if lengths is None:
+                code = lib.dfa_cnn1d_forward(*head, *tail)
+            else:
+                code = lib.dfa_cnn1d_forward_ragged(*head, C.c_void_p(lengths.ctypes.data), *tail)
             _lib.check(ctx.handle, code)
         return logits
 

@@ -33,18 +33,35 @@ def load_weights(model, checkpoint_path: str, device="cuda"):
     return model
 
 
+def _forward_batches(model, source, batch_size, device, rank, world, input_dtype, swap_tf=True, return_embedding=False):
+    """The one scoring loop: `source` (a stacked tensor or a list of [F, T_i] tensors: dataloaders.EvalBatches) through
+    `model(x)` / `model(x, lengths=...)` -> (logits [n] on the device, embeddings [n, 128*F] on the host or None), in input
+    order; (None, None) when this rank's shard is empty."""
+    from .dataloaders import EvalBatches
+    model.eval()
+    batches = EvalBatches(source, batch_size, device=device, rank=rank, world=world, dtype=input_dtype, swap_tf=swap_tf)
+    outs, embs = [], []
+    for x, lengths in batches:
+        kw = {} if lengths is None else {"lengths": lengths}
+        if return_embedding:
+            logits, e = model(x, return_embedding=True, **kw)
+            embs.append(e.cpu())
+        else:
+            logits = model(x, **kw)
+        outs.append(logits.squeeze(-1))
+    if not outs:
+        return None, None
+    return batches.restore(outs), (batches.restore(embs) if embs else None)
+
+
 @torch.no_grad()
 def predict_scores(model, features: torch.Tensor, batch_size: int = 32, device="cuda", apply_sigmoid: bool = True,
                    swap_tf: bool = True, rank: int = 0, world: int = 1, input_dtype=None) -> torch.Tensor:
     """Scores for a stacked [N,180,321] feature tensor (this rank's shard when world > 1), as one GPU tensor."""
-    from .dataloaders import FlatBatcher
-    model.eval()
-    outs = []
-    for feats, _ in FlatBatcher(features, None, batch_size, device=device, rank=rank, world=world, dtype=input_dtype):
-        x = feats.transpose(1, 2) if swap_tf else feats          # src/predict.py:104-105
-        logits = model(x).squeeze(-1)
-        outs.append(torch.sigmoid(logits) if apply_sigmoid else logits)
-    return torch.cat(outs) if outs else torch.empty(0, device=device)
+    logits, _ = _forward_batches(model, features, batch_size, device, rank, world, input_dtype, swap_tf)
+    if logits is None:
+        return torch.empty(0, device=device)
+    return torch.sigmoid(logits) if apply_sigmoid else logits
 
 
 def check_ragged_args(model: str, precision: str, swap_tf: bool = True) -> None:
@@ -67,21 +84,14 @@ def predict_scores_ragged(model, feature_list, batch_size: int = 32, device="cud
     """Scores for a list of per-utterance [F, T_i] tensors of unequal lengths, in input order, as one GPU tensor: batches
     padded to their longest utterance (dataloaders.RaggedBatcher, longest first) through `model(x, lengths=...)`.
     return_embedding (cnn2d): also the [N, 128*F] embeddings, as a host tensor."""
-    from .dataloaders import RaggedBatcher
-    model.eval()
-    batcher = RaggedBatcher(feature_list, None, batch_size, device=device, rank=rank, world=world, dtype=input_dtype)
-    outs, embs = [], []
-    for x, _, lengths in batcher:
-        if return_embedding:
-            logits, e = model(x, return_embedding=True, lengths=lengths)
-            embs.append(e.cpu())
-        else:
-            logits = model(x, lengths=lengths)
-        logits = logits.squeeze(-1)
-        outs.append(torch.sigmoid(logits) if apply_sigmoid else logits)
-    scores = batcher.restore(outs) if outs else torch.empty(0, device=device)
+    logits, emb = _forward_batches(model, feature_list, batch_size, device, rank, world, input_dtype,
+                                   return_embedding=return_embedding)
+    if logits is None:
+        scores = torch.empty(0, device=device)
+    else:
+        scores = torch.sigmoid(logits) if apply_sigmoid else logits
     if return_embedding:
-        return scores, (batcher.restore(embs) if embs else torch.empty(0, 0))
+        return scores, (emb if emb is not None else torch.empty(0, 0))
     return scores
 
 
@@ -92,19 +102,12 @@ def extract_embeddings(model, features: torch.Tensor, batch_size: int = 256, dev
     forward hooks for its OC-SVM / GMM stage) together with the logits [N]: the HIP forward writes the embedding rows
     straight from the block-3 epilogue (`return_embedding=True`), so the export costs one extra 92 KB store per utterance.
     Returns (embeddings, logits) as host tensors (this rank's shard when world > 1)."""
-    from .dataloaders import FlatBatcher
-    if not hasattr(model, "_eval_forward"):
+    if not isinstance(model, CNN2D):
         raise ValueError("extract_embeddings needs the CNN2D model (the 1D CNN has no [128*F] embedding)")
-    model.eval()
-    embs, logits = [], []
-    for feats, _ in FlatBatcher(features, None, batch_size, device=device, rank=rank, world=world, dtype=input_dtype):
-        x = feats.transpose(1, 2) if swap_tf else feats
-        lg, e = model(x, return_embedding=True)
-        embs.append(e.cpu())
-        logits.append(lg.squeeze(-1).cpu())
-    if not embs:
+    logits, emb = _forward_batches(model, features, batch_size, device, rank, world, input_dtype, swap_tf, return_embedding=True)
+    if logits is None:
         return torch.empty(0, 0), torch.empty(0)
-    return torch.cat(embs), torch.cat(logits)
+    return emb, logits.cpu()
 
 
 def write_predictions(uttids, scores, out_path: str) -> pd.DataFrame:

@@ -82,6 +82,33 @@ int main() {
   for (int i = 0; i < 20; ++i) ptrs[i] = out;
   EXPECT(dfa_cnn2d_set_params(ctx, ptrs, 19, 180, 32) != DFA_OK);
   EXPECT(dfa_cnn2d_set_params(ctx, ptrs, 20, 180, 31) != DFA_OK);
+  // the option table: every plain 0/1 or raw-int option is accepted (unknown and null names: above)
+  const char* table_options[] = {"time_split", "conv1_bwd_fused", "dgrad_m16", "conv1_mfma", "cae_enc1_mfma", "cae_enc_dma", "cae_dgrad_mfma",
+                                 "cae_conv_stats", "cae_bwd_fold", "cae_enc4_wide", "cae_dec_fused", "block3_m16", "fuse_conv1",
+                                 "fuse_blocks123", "persist123", "lds_pipe"};
+  for (const char* name : table_options) EXPECT(dfa_ctx_set_option(ctx, name, 1) == DFA_OK);   // (1 is the default of every flag)
+  EXPECT(dfa_ctx_set_option(ctx, "time_split", -1) == DFA_OK);                                  // ... and -1 that of time_split
+  // the shared set_params core, all four models: pointer count, a null entry
+  const float* many[44];
+  for (int i = 0; i < 44; ++i) many[i] = out;
+  EXPECT(dfa_cnn1d_set_params(ctx, many, 21, 180, 32) == DFA_E_BAD_SHAPE);
+  EXPECT(dfa_cae_set_params(ctx, many, 43, 32) == DFA_E_BAD_SHAPE);
+  EXPECT(dfa_dlq_set_params(ctx, many, 20, 180, 256) == DFA_E_BAD_SHAPE);
+  EXPECT(dfa_dlq_set_params(ctx, many, 22, 180, 128) == DFA_E_UNSUPPORTED);
+  many[7] = nullptr;
+  EXPECT(dfa_cnn2d_set_params(ctx, many, 20, 180, 32) == DFA_E_NULL_PTR);
+  EXPECT(dfa_cae_set_params(ctx, many, 44, 32) == DFA_E_NULL_PTR);
+  many[7] = out;
+  // bound, nothing prepared: the shared lengths and workspace checks, reached through the training entry points (in front of any launch)
+  EXPECT(dfa_cnn1d_set_params(ctx, many, 20, 180, 32) == DFA_OK);
+  int32_t lens[2] = {16, 17};
+  EXPECT(dfa_cnn1d_forward_train_ragged(ctx, out, DFA_DTYPE_F32, 2, 16, 180, 2880, 180, 1, lens, 0.f, 0, 0, 0.1f, 1, out, out, 1024) == DFA_E_BAD_SHAPE);
+  lens[1] = 2;
+  EXPECT(dfa_cnn1d_forward_train_ragged(ctx, out, DFA_DTYPE_F32, 2, 16, 180, 2880, 180, 1, lens, 0.f, 0, 0, 0.1f, 1, out, out, 1024) == DFA_E_BAD_SHAPE);
+  lens[1] = 16;
+  EXPECT(dfa_cnn1d_forward_train_ragged(ctx, out, DFA_DTYPE_F32, 2, 16, 180, 2880, 180, 1, lens, 0.f, 0, 0, 0.1f, 1, out, out, 1024) == DFA_E_WORKSPACE);
+  EXPECT(dfa_cnn2d_set_params(ctx, many, 20, 180, 32) == DFA_OK);
+  EXPECT(dfa_cnn2d_forward_train(ctx, out, DFA_DTYPE_F32, 1, 16, 180, 2880, 180, 1, DFA_PREC_F32, 0.f, 0, 0, 0.1f, 1, out, nullptr, out, 1024) == DFA_E_WORKSPACE);
   EXPECT(dfa_cnn2d_set_train_augment(ctx, 1, 321, 180, 5, nullptr, 300, 40, 0, 0, 0.f, 1, 0) == DFA_E_BAD_SHAPE);
   EXPECT(dfa_bce_smooth_fwd_bwd(ctx, out, out, 0.7f, 4, out, out) == DFA_E_BAD_SHAPE);
   float ms = 0.f; int cnt = 0;
