@@ -1,0 +1,265 @@
+// cnn1d_train_api.hip -- C ABI of the CNN1D training step, uniform and ragged (src/model_cnn1d.py in train mode, src/train.py:71-76):
+// dfa_cnn1d_forward_train[_ragged] (Conv1d -> BatchNorm1d on batch statistics -> ReLU -> Dropout twice, Conv1d -> BN -> ReLU -> mean_T
+// -> Linear) and dfa_cnn1d_backward[_ragged] (14 gradients from dlogits).  Arming, SyncBN hook, loss, optimiser: train_api.hip.
+#include "train_host.h"
+#include "trace.h"
+
+using namespace dfa;
+
+namespace {
+
+struct Train1dPlan {
+  size_t z[3], h[2], pooled, dpooled, dz[3], dh[2], stats, sums, partial, total;
+};
+
+Train1dPlan plan_train1d(int B, int T, int F) {
+  Train1dPlan p;
+  Bump take;
+  const int C[3] = {32, 64, 128};
+  for (int l = 0; l < 3; ++l) p.z[l] = take((size_t)B * C[l] * T * 4);
+  for (int l = 0; l < 2; ++l) p.h[l] = take((size_t)B * C[l] * T * 4);
+  p.pooled = take((size_t)B * 128 * 4);
+  p.dpooled = take((size_t)B * 128 * 4);
+  for (int l = 0; l < 3; ++l) p.dz[l] = take((size_t)B * C[l] * T * 4);
+  for (int l = 0; l < 2; ++l) p.dh[l] = take((size_t)B * C[l] * T * 4);
+  p.stats = take((32 + 64 + 128) * 3 * 4);
+  p.sums = take((32 + 64 + 128) * 2 * 4);
+  const size_t nch = (size_t)cm_chunks(B);
+  size_t pb = nch * 128 * 2 * 4;
+  const size_t wch = (size_t)conv1d_wgrad_chunks(B);
+  pb = std::max(pb, wch * ((size_t)32 * F * 3 + 32) * 4);
+  pb = std::max(pb, wch * ((size_t)128 * 64 * 3 + 128) * 4);
+  p.partial = take(pb);
+  p.total = take.off;
+  return p;
+}
+
+const int kBnOff[3] = {0, 32, 96}, kBnC[3] = {32, 64, 128};     // BN layer order in the stats / sums blocks: layers 1-3
+BnStats st1d(char* ws, const Train1dPlan& pl, int l) { return bn_stats(ws + pl.stats, kBnOff[l], kBnC[l]); }
+float* sums1d(char* ws, const Train1dPlan& pl, int l) { return bn_sums(ws + pl.sums, kBnOff[l]); }
+
+// A ragged batch (dfa_cnn1d_forward_train_ragged): x is padded to T = T_max frames, utterance b is x[b, :lengths[b], :].  The step
+// is the reference model's on the utterances concatenated along time: each Conv1d zero-pads an utterance at
+// its own two ends, BatchNorm1d's statistics run over the N = sum lengths[b] valid frames, the time mean of utterance b over its own.
+// It is reached with the UNIFORM convolution / weight-gradient / data-gradient kernels on the padded batch, because three things
+// hold at every padding frame t >= lengths[b]: x reads as zero (a bound in the loads of the kernels that read x), every activation
+// h is written as an exact zero, and so is every dz.  The table ([0, B) lengths, [B, 2B) the staging's dispatch order, unused here)
+// sits behind the uniform plan in the workspace; the backward reads it from there.
+size_t ragged1d_tab_bytes(int B) { return align_up((size_t)2 * B * sizeof(int32_t), 256); }
+
+// lengths == nullptr: the uniform step
+int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
+                             int64_t stride_t, int64_t stride_f, const int32_t* lengths, float p_drop, uint64_t seed, uint64_t offset,
+                             float momentum, int update_running_stats, float* logits, void* workspace,
+                             size_t workspace_bytes) {
+  Cnn1dState& m = ctx->cnn1d;
+  const AugCfg armed = m.aug_armed;     // one-shot: consumed here, also by a call that fails its checks below
+  m.aug_armed = AugCfg{};
+  m.train_aug = AugCfg{};
+  if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_set_params has not been called");
+  if (!x || !logits || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, logits and workspace must be non-null");
+  if (x_dtype != DFA_DTYPE_F32) return fail(ctx, DFA_E_BAD_DTYPE, "cnn1d takes float32 input (got dtype %d)", x_dtype);
+  if (B < 1 || T < 1) return fail(ctx, DFA_E_BAD_SHAPE, "B and T must be >= 1 (got %d, %d)", B, T);
+  if (F != m.in_features) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d", F, m.in_features);
+  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(ctx, DFA_E_BAD_SHAPE, "dropout p must be in [0, 1)");
+  double frames = (double)B * T;             // frames BatchNorm1d counts
+  if (lengths) {
+    if (T < 3) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: a ragged cnn1d batch needs T_max >= 3", T);
+    DFA_TRY(check_lengths(ctx, lengths, B, 3, T));
+    frames = 0.0;
+    for (int b = 0; b < B; ++b) frames += (double)lengths[b];
+  }
+  const Train1dPlan pl = plan_train1d(B, T, F);
+  DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total + (lengths ? ragged1d_tab_bytes(B) : 0), false, "train "));
+  if (armed.on && (armed.T != T || armed.F != F))
+    return fail(ctx, DFA_E_BAD_SHAPE, "armed augmentation is for [T=%d, F=%d], the batch is [T=%d, F=%d]", armed.T, armed.F, T, F);
+  DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int* lens = nullptr;                 // device table of a ragged batch
+  if (lengths) {
+    if (armed.on)
+      return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step takes no train augmentation (dfa_cnn1d_set_train_augment was armed): "
+                                          "a time roll has no per-utterance meaning yet");
+    if (ctx->bn_sync.fn)
+      return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed): "
+                                          "the ranks' frame counts differ and the hook carries sums only");
+    DFA_TRY(refuse_capture(ctx, "training step"));
+    DFA_TRY(stage_ragged_lengths(ctx, lengths, B, (char*)workspace + pl.total));
+    lens = (const int*)((char*)workspace + pl.total);
+  }
+  m.train_aug = armed;
+  const AugCfg* aug = m.train_aug.on ? &m.train_aug : nullptr;
+  if (!m.train_packed) {
+    Bump take;
+    const size_t wt0 = take((size_t)64 * 32 * 3 * 4), wt1 = take((size_t)128 * 64 * 3 * 4), zb = take(256 * 4);
+    DFA_HIP_CHECK(ctx, hipMalloc(&m.train_packed, take.off));
+    char* base = (char*)m.train_packed;
+    m.wt[0] = (float*)(base + wt0); m.wt[1] = (float*)(base + wt1); m.zero_bias = (float*)(base + zb);
+  }
+  // bf16x3 A-fragment images of this step's weights (they change every step): forward layers 1-3, data gradients 3->2, 2->1
+  const int xcin[5] = {F, 32, 64, 128, 64}, xcout[5] = {32, 64, 128, 64, 32};
+  if (!m.wx3[0] || m.wx3_F != F) {
+    if (m.wx3[0]) { DFA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); DFA_HIP_CHECK(ctx, hipFree(m.wx3[0])); m.wx3[0] = nullptr; }
+    Bump take;
+    size_t off[5];
+    for (int i = 0; i < 5; ++i) off[i] = take(conv1d_terms_pack_bytes(xcin[i], xcout[i], 3));
+    char* base = nullptr;
+    DFA_HIP_CHECK(ctx, hipMalloc((void**)&base, take.off));
+    for (int i = 0; i < 5; ++i) m.wx3[i] = base + off[i];
+    m.wx3_F = F;
+  }
+  const float* const* p = m.p;
+  hipStream_t s = ctx->stream;
+  const int x3 = ctx->cnn1d_train_x3, terms = (x3 == 3) ? 2 : 3;
+  // the fp32 data-gradient images are only read by the vector-ALU fallback (T > 384, option 0)
+  const bool dgrad_x3 = x3 && conv1d_x3_supports((const float*)workspace, (int64_t)128 * T, T, 1, (const float*)workspace, T, 128, 64, terms) &&
+                        conv1d_x3_supports((const float*)workspace, (int64_t)64 * T, T, 1, (const float*)workspace, T, 64, 32, terms);
+  if (!dgrad_x3) {
+    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(p[6], m.wt[0], m.zero_bias, 32, 64, s));
+    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(p[12], m.wt[1], m.zero_bias, 64, 128, s));
+  }
+  if (x3) DFA_HIP_CHECK(ctx, launch_pack_conv1d_train_all(p[0], p[6], p[12], m.wx3, F, terms, m.zero_bias, s));   // all five images, one launch
+  m.train_x3 = x3;
+  DropCfg dc = drop_cfg(p_drop, seed, offset);
+  m.train_drop = dc; m.train_B = B; m.train_T = T;
+  m.train_ragged = lengths ? 1 : 0; m.train_frames = frames;
+  char* ws = (char*)workspace;
+  float* partial = (float*)(ws + pl.partial);
+  const int C[3] = {32, 64, 128}, Cin[3] = {F, 32, 64};
+  const int nch = cm_chunks(B);
+  for (int l = 0; l < 3; ++l) {
+    float* z = (float*)(ws + pl.z[l]);
+    const float* const* q = p + 6 * l;
+    if (l == 0) {
+      if (x3 && conv1d_x3_supports((const float*)x, stride_b, stride_f, stride_t, z, T, F, 32, terms))
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3((const float*)x, stride_b, m.wx3[0], q[1], z, B, F, 32, T, terms, s, x3, aug, lens));
+      else
+        DFA_HIP_CHECK(ctx, launch_conv1d((const float*)x, stride_b, stride_f, stride_t, q[0], q[1], z, B, F, 32, T, false, s, false, aug, lens));
+    } else {
+      const float* hin = (const float*)(ws + pl.h[l - 1]);
+      if (x3 && conv1d_x3_supports(hin, (int64_t)Cin[l] * T, T, 1, z, T, Cin[l], C[l], terms))
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(hin, (int64_t)Cin[l] * T, m.wx3[l], q[1], z, B, Cin[l], C[l], T, terms, s, x3));
+      else
+        DFA_HIP_CHECK(ctx, launch_conv1d(hin, (int64_t)Cin[l] * T, T, 1, q[0], q[1], z, B, Cin[l], C[l], T, false, s, false));
+    }
+    BnStats st = st1d(ws, pl, l);
+    const bool shifted = !ctx->bn_sync.fn;       // sums of z - z[0][c][0]: see cm_stats_body
+    DFA_HIP_CHECK(ctx, launch_cm_stats(z, partial, B, C[l], T, s, lens, shifted));
+    DFA_TRY(finalize_bn_stats(ctx, partial, nch, C[l], frames, st, update_running_stats ? (float*)q[4] : nullptr,
+                              update_running_stats ? (float*)q[5] : nullptr, momentum, nullptr, shifted ? z : nullptr, T));
+    if (l < 2) {
+      dc.layer = 1 + l;
+      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_drop(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.h[l]), B, C[l], T, dc, s, lens));
+    } else {
+      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_meant(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.pooled), B, 128, T, s, lens));
+    }
+  }
+  DFA_HIP_CHECK(ctx, launch_linear((const float*)(ws + pl.pooled), p[18], p[19], logits, B, 128, s));
+  return DFA_OK;
+}
+
+// ragged = which of the two entry points this is: it must be the one whose forward is in flight
+int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
+                        int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
+                        size_t workspace_bytes) {
+  Cnn1dState& m = ctx->cnn1d;
+  Train1dPlan pl;
+  DFA_TRY(check_backward(ctx, {ragged ? "dfa_cnn1d_backward_ragged" : "dfa_cnn1d_backward",
+                               ragged ? "dfa_cnn1d_forward_train_ragged" : "dfa_cnn1d_forward_train", "cnn1d", 14, "dlogits", true},
+                         m.train_packed && m.train_B == B && m.train_T == T && m.train_ragged == ragged, x, x_dtype, dlogits, grads, ngrads,
+                         workspace, workspace_bytes, [&] { return (pl = plan_train1d(B, T, F)).total + (ragged ? ragged1d_tab_bytes(B) : 0); }));
+  if (ragged && ctx->bn_sync.fn)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed)");
+  char* ws = (char*)workspace;
+  const int* lens = ragged ? (const int*)(ws + pl.total) : nullptr;     // the table the forward left behind the plan
+  float* partial = (float*)(ws + pl.partial);
+  const float* const* p = m.p;
+  hipStream_t s = ctx->stream;
+  DropCfg dc = m.train_drop;
+  const int C[3] = {32, 64, 128}, Cin[3] = {F, 32, 64};
+  float* dpooled = (float*)(ws + pl.dpooled);
+  DFA_HIP_CHECK(ctx, launch_linear_bwd(dlogits, p[18], (const float*)(ws + pl.pooled), dpooled, grads[12], grads[13], B, 128, s));
+  for (int l = 2; l >= 0; --l) {
+    const float* const* q = p + 6 * l;
+    BnStats st = st1d(ws, pl, l);
+    float* sm = sums1d(ws, pl, l);
+    float* dz = (float*)(ws + pl.dz[l]);
+    const float* up = (l == 2) ? dpooled : (const float*)(ws + pl.dh[l]);
+    dc.layer = 1 + l;
+    DFA_HIP_CHECK(ctx, launch_cm_bn_bwd(l == 2 ? 0 : 1, (const float*)(ws + pl.z[l]), st.mean, st.invstd, q[2], q[3], up, partial, sm, dz,
+                                        B, C[l], T, dc, s, ctx->bn_sync.fn ? &ctx->bn_sync : nullptr, lens, m.train_frames));
+    DFA_HIP_CHECK(ctx, launch_split_sums(sm, grads[4 * l + 2], grads[4 * l + 3], C[l], s));
+    if (l == 0) {
+      DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)x, stride_b, stride_f, stride_t, partial, grads[0], grads[1], B, F, 32, T, s,
+                                             m.train_aug.on ? &m.train_aug : nullptr, m.train_x3, lens));
+    } else {
+      DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)(ws + pl.h[l - 1]), (int64_t)Cin[l] * T, T, 1, partial, grads[4 * l],
+                                             grads[4 * l + 1], B, Cin[l], C[l], T, s, nullptr, m.train_x3));
+      // data gradient: dh[l-1] = conv1d(dz; W'[Cin][Cout][3]) -- a Conv1d with Cout input channels, Cin output channels
+      float* dh = (float*)(ws + pl.dh[l - 1]);
+      const int terms = (m.train_x3 == 3) ? 2 : 3;
+      if (m.train_x3 && conv1d_x3_supports(dz, (int64_t)C[l] * T, T, 1, dh, T, C[l], Cin[l], terms))
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(dz, (int64_t)C[l] * T, m.wx3[l == 2 ? 3 : 4], m.zero_bias, dh, B, C[l], Cin[l], T, terms, s, m.train_x3));
+      else
+        DFA_HIP_CHECK(ctx, launch_conv1d(dz, (int64_t)C[l] * T, T, 1, m.wt[l - 1], m.zero_bias, dh, B, C[l], Cin[l], T, false, s, false));
+    }
+  }
+  return DFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dfa_cnn1d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F) {
+  (void)ctx;
+  if (B < 1 || T < 1 || F < 1) return 0;
+  return plan_train1d(B, T, F).total;
+}
+
+int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
+                            int64_t stride_t, int64_t stride_f, float p_drop, uint64_t seed, uint64_t offset,
+                            float momentum, int update_running_stats, float* logits, void* workspace,
+                            size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_forward_train");
+  if (!ctx) return DFA_E_NULL_PTR;
+  return cnn1d_forward_train_impl(ctx, x, x_dtype, B, T, F, stride_b, stride_t, stride_f, nullptr, p_drop, seed, offset, momentum,
+                                  update_running_stats, logits, workspace, workspace_bytes);
+}
+
+int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
+                       int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
+                       size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_backward");
+  if (!ctx) return DFA_E_NULL_PTR;
+  return cnn1d_backward_impl(ctx, 0, x, x_dtype, B, T, F, stride_b, stride_t, stride_f, dlogits, grads, ngrads, workspace, workspace_bytes);
+}
+
+size_t dfa_cnn1d_train_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F) {
+  (void)ctx;
+  if (B < 1 || T_max < 3 || F < 1) return 0;
+  return plan_train1d(B, T_max, F).total + ragged1d_tab_bytes(B);
+}
+
+int dfa_cnn1d_forward_train_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,
+                                   int64_t stride_t, int64_t stride_f, const int32_t* lengths, float p_drop, uint64_t seed,
+                                   uint64_t offset, float momentum, int update_running_stats, float* logits, void* workspace,
+                                   size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_forward_train_ragged");
+  if (!ctx) return DFA_E_NULL_PTR;
+  if (!lengths) {
+    ctx->cnn1d.aug_armed = AugCfg{};      // one-shot, as in every forward_train
+    return fail(ctx, DFA_E_NULL_PTR, "lengths must be non-null");
+  }
+  return cnn1d_forward_train_impl(ctx, x, x_dtype, B, T_max, F, stride_b, stride_t, stride_f, lengths, p_drop, seed, offset, momentum,
+                                  update_running_stats, logits, workspace, workspace_bytes);
+}
+
+int dfa_cnn1d_backward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b, int64_t stride_t,
+                              int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
+                              size_t workspace_bytes) {
+  TraceRange trace_("dfa_cnn1d_backward_ragged");
+  if (!ctx) return DFA_E_NULL_PTR;
+  return cnn1d_backward_impl(ctx, 1, x, x_dtype, B, T_max, F, stride_b, stride_t, stride_f, dlogits, grads, ngrads, workspace, workspace_bytes);
+}
+
+}  // extern "C"

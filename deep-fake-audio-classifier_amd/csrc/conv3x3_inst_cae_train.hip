@@ -9,8 +9,6 @@ namespace dfa {
 // the CNN2D's blocks 2 / 3 (records [B * strips][COUT][2], conv3x3_mfma.h; block 2 IS the CNN2D's block-2 kernel) -- no separate
 // pass over z.  Block 4 (one 22-column strip per sample at F = 180: little work per workgroup) keeps the separate pass: the
 // epilogue's fixed cost (+49 us) was twice the pass over its 118 MB output.
-hipError_t launch_train_fwd2(int prec, const ConvArgs& a, hipStream_t s);
-hipError_t launch_train_fwd3(int prec, const ConvArgs& a, hipStream_t s);
 hipError_t launch_cae_train_fwd(int prec, int cin, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide) {
   const size_t es = (prec == DFA_PREC_BF16) ? 2 : 4;
   if (cin == 32) {

@@ -1,4 +1,5 @@
-// dfa_checks.h -- the argument checks the C ABI's entry points share (api.hip, dlq_api.hip, train_api.hip, cae_train_api.hip).
+// dfa_checks.h -- the argument checks the C ABI's entry points share (api.hip, dlq_api.hip, train_api.hip, cnn1d_train_api.hip,
+// cae_train_api.hip).
 // Host code only.  Every helper returns DFA_OK or the code it left, with its text, in the context (dfa::fail); an entry point
 // wraps it in DFA_TRY.  The wording belongs to the entry points: where it differs between them it comes in as an argument.
 #pragma once
@@ -48,6 +49,33 @@ inline int check_channel_major(dfa_ctx* ctx, const char* who, const char* cname,
   if ((stride_b & 3) != 0 || stride_b < 0)
     return fail(ctx, DFA_E_UNSUPPORTED, "the %s needs a non-negative stride_b %% 4 == 0 (got stride_b=%lld)", who, (long long)stride_b);
   if (((uintptr_t)x & 15) != 0) return fail(ctx, DFA_E_UNSUPPORTED, "the %s needs x 16-byte aligned (got %p)", who, x);
+  return DFA_OK;
+}
+
+// dfa_<model>_backward: the forward_train of the same batch in flight, no null pointer, [float32 x], the gradient count, no null
+// gradient, the workspace's size (`need`, a callable that forms the plan: only once B and T are known to be the forward's)
+struct BackwardNames {
+  const char* bwd;        // "dfa_cnn2d_backward"
+  const char* fwd;        // "dfa_cnn2d_forward_train"
+  const char* model;      // "cnn2d", "the auto-encoder": the subject of the count's and the dtype's sentence
+  int nparams;
+  const char* upstream;   // "dlogits"; nullptr where the upstream gradient may be null
+  bool f32_only;          // x must be float32 (x_dtype is not looked at otherwise)
+};
+template <typename Need>
+int check_backward(dfa_ctx* ctx, const BackwardNames& w, bool in_flight, const void* x, int x_dtype, const void* upstream,
+                   float* const* grads, int ngrads, const void* workspace, size_t have, Need need) {
+  if (!in_flight) return fail(ctx, DFA_E_NOT_PREPARED, "%s must follow %s on the same batch", w.bwd, w.fwd);
+  if (w.upstream) {
+    if (!x || !upstream || !grads || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, %s, grads and workspace must be non-null", w.upstream);
+  } else if (!x || !grads || !workspace) {
+    return fail(ctx, DFA_E_NULL_PTR, "x, grads and workspace must be non-null");
+  }
+  if (w.f32_only && x_dtype != DFA_DTYPE_F32) return fail(ctx, DFA_E_BAD_DTYPE, "%s takes float32 input", w.model);
+  if (ngrads != w.nparams) return fail(ctx, DFA_E_BAD_SHAPE, "%s has %d parameters, got %d gradient pointers", w.model, w.nparams, ngrads);
+  for (int i = 0; i < w.nparams; ++i)
+    if (!grads[i]) return fail(ctx, DFA_E_NULL_PTR, "gradient pointer %d is null", i);
+  if (have < need()) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small");
   return DFA_OK;
 }
 

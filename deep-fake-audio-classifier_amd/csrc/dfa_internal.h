@@ -358,6 +358,9 @@ hipError_t launch_cae_dec4_mse(const void* d3, int prec, const float* w4, const 
                                float* partial, float* mse, int B, int H3, int W3, int T, int F, hipStream_t s);
 hipError_t launch_cae_latent_export(const void* lat, int prec, float* out, int B, int HW, int C, hipStream_t s);
 // train_elem.hip / train_conv1.hip / wgrad_mfma.hip
+// the `mode` of launch_conv1_train and the `src` of launch_bn_bwd (described at their kernels)
+enum { C1M_STATS = 0, C1M_BWD_REDUCE = 1, C1M_WGRAD = 2, C1M_BWD_FUSED = 3, C1M_STATS_XX = 4 };
+enum { SRC_MEANT = 0, SRC_POOL = 1, SRC_DIRECT = 2, SRC_POOL22 = 3 };
 hipError_t launch_bn_finalize(const float* partial, int nparts, int C, double n, float* mean, float* var, float* invstd,
                               float* running_mean, float* running_var, float momentum, hipStream_t s,
                               const float* shift = nullptr, int shift_stride = 0);   // sums of z - shift[c * shift_stride]
@@ -388,6 +391,9 @@ hipError_t launch_bn_bwd(int prec, int src, const void* z, const float* mean, co
                          const float* beta, const float* demb, const void* da, float* partial, float* sums, void* dz,
                          int B, int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch = nullptr, const BnSync* sync = nullptr,
                          BnBwdFold* fold = nullptr);
+// sums[C][2] -> dbeta = S1, dgamma = S2 (C <= 256); the conv1 weight-gradient record [32][10] -> dW1[32][9], db1[32]
+hipError_t launch_split_sums(const float* sums, float* dgamma, float* dbeta, int C, hipStream_t s);
+hipError_t launch_split_c1(const float* rec, float* dw, float* db, hipStream_t s);
 hipError_t launch_bce_smooth(const float* logits, const float* labels, float eps, int B, float* loss, float* dlogits,
                              hipStream_t s);
 hipError_t launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
@@ -436,6 +442,12 @@ hipError_t launch_wgrad3x3(int prec, int cin, int cout, const void* dz, const vo
 // conv3x3_inst_*.hip
 hipError_t launch_fold_pack_conv3x3_m16(const float* w, const float* b, const float* g, const float* beta, const float* mean,
                                         const float* var, int cin, int cout, uint4* wpack, hipStream_t s, int fold = 1);
+hipError_t launch_train_fwd2(int prec, const ConvArgs& a, hipStream_t s);
+hipError_t launch_train_fwd3(int prec, const ConvArgs& a, hipStream_t s);
+hipError_t launch_train_dgrad3(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s);
+hipError_t launch_train_dgrad2(int prec, const ConvArgs& a, hipStream_t s);
+hipError_t launch_cae_train_fwd(int prec, int cin, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide);
+hipError_t launch_cae_dgrad4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide);
 hipError_t launch_train_fwd3_m16(const ConvArgs& a, hipStream_t s, int pipe = 1);
 // conv_split.hip (DFA_PREC_BF16X3)
 hipError_t launch_fold_pack_conv3x3_split(const float* w, const float* b, const float* g, const float* beta, const float* mean,

@@ -16,7 +16,6 @@
 
 namespace dfa {
 
-enum { C1M_STATS = 0, C1M_BWD_REDUCE = 1, C1M_WGRAD = 2, C1M_BWD_FUSED = 3, C1M_STATS_XX = 4 };
 constexpr int C1T_R = 8, C1T_C = 64;
 
 template <typename TX>

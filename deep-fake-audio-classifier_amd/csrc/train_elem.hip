@@ -398,7 +398,6 @@ __global__ __launch_bounds__(256) void linear_bwd_kernel(const float* __restrict
 // reduce: S1[c] = sum dy, S2[c] = sum dy*xhat  (= dbeta, dgamma);  apply: dz = gamma*invstd*(dy - S1/N - xhat*S2/N).
 //   SRC_DIRECT: dy = (y > 0) * da[b][t][f][c]                                   (CAE decoder: ReLU feeds the next layer)
 //   SRC_POOL22: dy = (y > 0) * 0.25 * da[b][t/2][f/2][c], rows/cols beyond 2*(H/2), 2*(W/2) get 0   (CAE encoder)
-enum { SRC_MEANT = 0, SRC_POOL = 1, SRC_DIRECT = 2, SRC_POOL22 = 3 };
 
 template <typename T, int SRC>
 __device__ __forceinline__ void upstream8(const float* demb, const T* da, const DropCfg& dc, int b, int t, int f, int cg,
@@ -1013,6 +1012,29 @@ hipError_t launch_bn_bwd(int prec, int src, const void* z, const float* mean, co
   }
 #undef DFA_BN_BWD
 #undef DFA_BN_BWD_POOL
+  return hipGetLastError();
+}
+
+// dgamma = S2, dbeta = S1 from sums[C][2]
+__global__ void split_sums_kernel(const float* __restrict__ sums, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                  int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) { dbeta[c] = sums[2 * c]; dgamma[c] = sums[2 * c + 1]; }
+}
+// conv1 weight-gradient record [32][10] -> dW1[32][9], db1[32]
+__global__ void split_c1_kernel(const float* __restrict__ rec, float* __restrict__ dw, float* __restrict__ db) {
+  const int i = threadIdx.x;  // 320 threads
+  const int c = i / 10, j = i - c * 10;
+  if (j < 9) dw[c * 9 + j] = rec[i]; else db[c] = rec[i];
+}
+
+hipError_t launch_split_sums(const float* sums, float* dgamma, float* dbeta, int C, hipStream_t s) {   // one block: C <= 256
+  hipLaunchKernelGGL(split_sums_kernel, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, C);
+  return hipGetLastError();
+}
+
+hipError_t launch_split_c1(const float* rec, float* dw, float* db, hipStream_t s) {
+  hipLaunchKernelGGL(split_c1_kernel, dim3(1), dim3(320), 0, s, rec, dw, db);
   return hipGetLastError();
 }
 
