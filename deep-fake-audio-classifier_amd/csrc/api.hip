@@ -211,6 +211,8 @@ int dfa_ctx_destroy(dfa_ctx* ctx) {
   if (ctx->cae.packed) (void)hipFree(ctx->cae.packed);
   if (ctx->cae.train_packed) (void)hipFree(ctx->cae.train_packed);
   if (ctx->dlq.packed) (void)hipFree(ctx->dlq.packed);
+  if (ctx->dlq.train_packed) (void)hipFree(ctx->dlq.train_packed);
+  if (ctx->clip_partial) (void)hipFree(ctx->clip_partial);
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   if (ctx->clock_buf) (void)hipFree(ctx->clock_buf);
   if (ctx->mse_partial) (void)hipFree(ctx->mse_partial);

@@ -124,6 +124,12 @@ struct DlqState {
   void* packed = nullptr;                       // one device allocation: the three A-fragment images, then the folded biases
   void* w[3] = {nullptr, nullptr, nullptr};     // three-term bf16 A-fragment images, BatchNorm folded
   float* b[3] = {nullptr, nullptr, nullptr};    // folded biases [256]
+  // train mode (dlq_train_api.hip): this step's raw weight images -- forward layers 1-3, data gradients 3 -> 2 and 2 -> 1
+  void* train_packed = nullptr;
+  void* tw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int tw_in_ch = 0;
+  int train_B = 0, train_T = 0;                 // the forward_train in flight (0: none); its dropout key
+  DropCfg train_drop{};
 };
 
 }  // namespace dfa
@@ -162,6 +168,7 @@ struct dfa_ctx {
   float* aug_keep = nullptr;        // device copy of the armed augmentation's keep mask (dfa_cnn2d_set_train_augment copies keep_f)
   int aug_keep_cap = 0, aug_keep_slot = 0;
   float* mse_partial = nullptr;     // device, kMseBlocks floats: block sums of dfa_mse_fwd_bwd (allocated on first use)
+  double* clip_partial = nullptr;   // device, 256 doubles: block sums of dfa_clip_grad_norm (allocated on first use)
   // ragged forwards: pinned host staging of the per-call table (RaggedTab), kRaggedSlots slots used in turn; a slot is rewritten
   // only after the event recorded behind its last copy has completed
   static constexpr int kRaggedSlots = 4;
@@ -317,13 +324,61 @@ struct DlqLayerArgs {
   const int* tab;        // [0, B) lengths; [2B, 3B) dispatch order; [3B, 4B] first tile of each dispatch position
   float* part;           // layer 3: [tile][mean 256 | M2 256]
   int B, T_max, C, nks;
+  // the training step's dense launches (launch_dlq_layer_train; tab = the lengths alone)
+  int tpu;               // tiles per utterance, ceil(T_max / NF)
+  float* zout;           // mode 1: z of this layer, mode 2: dy of the layer below; fp32 [B][T_max][256]
+  float* rec;            // per tile: mode 1 [mean 256 | M2 256], mode 2 [256][sum dy, sum dy zhat]
+  const float *zprev, *st_mean, *st_invstd, *gamma, *beta;   // mode 2: z, batch statistics and affine of the layer below
+  DropCfg drop;          // mode 2: the layer below's dropout (drop.layer set)
 };
 int dlq_nks(int cin);
 size_t dlq_pack_bytes(int cin, int taps);
 hipError_t launch_dlq_pack(const float* const* p6, int cin, int taps, void* wp, float* bias, hipStream_t s);
 hipError_t launch_dlq_layer(int layer, const DlqLayerArgs& a, int ntiles, hipStream_t s);
+hipError_t launch_dlq_layer_train(int layer, int mode, const DlqLayerArgs& a, int ntiles, hipStream_t s);
 hipError_t launch_dlq_finish(const float* part, const int* tab, const float* w0, const float* b0, const float* w3, const float* b3, float* logits,
                              float* pooled, int B, hipStream_t s);
+// dlq_train.hip: the DeepfakeDetector training step besides the layer kernel
+struct DlqPackJobs {
+  const float* w[5]; uint4* dst[5];
+  int cin[5], taps[5], dgrad[5], first[6];   // first[q]: the job's first workgroup
+};
+hipError_t launch_dlq_train_pack(const float* w1, const float* w2, const float* w3, void* const* dst, int in_ch, hipStream_t s);
+hipError_t launch_dlq_bn_finalize(const float* rec, int ntiles, int tpu, int T_max, float* mean, float* var, float* invstd, float* rm, float* rv,
+                                  float momentum, hipStream_t s);
+hipError_t launch_dlq_bn_act(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta, void* h,
+                             unsigned char* keep_out, long long N, const DropCfg& dc, hipStream_t s);
+struct DlqHeadArgs {       // layer 3's BN + GELU + dropout, the pool, the head; forward and backward
+  const float *z3, *mean, *invstd, *gamma, *beta;   // layer 3
+  const int* lens;
+  const float *w0, *b0, *w3, *b3;                   // head.0, head.3
+  float *pooled, *pvar, *u, *logits;                // [B][512] mean | std, [B][256] variance, [B][256] head.0's output
+  unsigned char *keep3, *keep4;                     // test hook or null
+  const float* dlogits;
+  float *du, *dpooled;                              // [B][256], [B][512]
+  int T_max;
+  DropCfg drop;                                     // layer = 3; the head's dropout is layer 4
+};
+hipError_t launch_dlq_pool_head(const DlqHeadArgs& a, int B, hipStream_t s);
+hipError_t launch_dlq_head_bwd(const DlqHeadArgs& a, int B, float* dw0, float* db0, float* dw3, float* db3, hipStream_t s);
+hipError_t launch_dlq_dy3(const DlqHeadArgs& a, int B, int tpu, float* dy, float* rec, hipStream_t s);
+int dlq_dz_blocks(long long N);
+hipError_t launch_dlq_dz(const float* dy, const float* z, const float* mean, const float* invstd, const float* gamma, const float* sums, void* dz,
+                         float* dbrec, long long N, hipStream_t s);
+struct DlqWgradArgs {
+  const uint4* dz;       // [N] split pixels
+  const uint4* h;        // the source as split pixels, or
+  const float* x;        // x itself (layer 1): element (b, c, t) at b sb + c sc + t, zero at t >= lens[b]
+  int64_t sb, sc;
+  const int* lens;
+  float* partial;        // [chunks][taps][256][C]
+  long long N;           // B T_max
+  int T_max, C, taps, CH;
+};
+void dlq_wgrad_chunks(long long N, int* CH, int* nch);
+hipError_t launch_dlq_wgrad(const DlqWgradArgs& a, float* dw, hipStream_t s);
+hipError_t launch_bce_pos_weight(const float* logits, const float* labels, float pw, int B, float* loss, float* dlogits, hipStream_t s);
+hipError_t launch_clip_grad_norm(float* g, size_t n, float max_norm, float* norm_out, double* partial, hipStream_t s);
 // train_cnn1d.hip
 int cm_chunks(int B);
 int conv1d_wgrad_chunks(int B);

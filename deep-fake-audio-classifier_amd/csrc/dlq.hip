@@ -22,18 +22,9 @@
 // Tiles are dispatched from a table the host builds from the lengths (longest utterance first): a short utterance costs few tiles.
 #include "dfa_internal.h"
 #include "conv3x3_mfma.h"
+#include "dlq_common.h"
 
 namespace dfa {
-namespace dlq {
-constexpr int NF = DFA_DLQ_TILE_FRAMES;   // frames per tile
-constexpr int HID = 256;
-constexpr int PIXB = 6 * HID;             // bytes per split pixel: three bf16 terms of 256 channels
-constexpr int PIXC = PIXB / 16;           // 16-byte chunks per pixel (term t: chunks [32 t, 32 t + 32))
-constexpr int SLOTS = NF + 4;             // widest halo: 2 frames each side (layer 1, k = 5)
-constexpr int LDS_BYTES = SLOTS * PIXB;   // 104448: one workgroup per CU; the layer-3 epilogue reuses it as float [256][NF + 1] (66560)
-constexpr int NTH = 256;
-static_assert(HID * (NF + 1) * 4 <= LDS_BYTES, "layer-3 epilogue tile does not fit");
-}  // namespace dlq
 
 // ---- weight preparation: BatchNorm folded into the convolution (float64), three-term bf16 A-fragment images ------------------------
 // wp[k][wave][m][term][lane] (uint4), k = tap * nks + ks, term 0 .. 2; lane: co = 64 wave + 32 m + (lane & 31), element j <->
@@ -79,17 +70,6 @@ hipError_t launch_dlq_pack(const float* const* p6, int cin, int taps, void* wp, 
 
 // ---- one layer ---------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ float dlq_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-__device__ __forceinline__ f32x16_t dlq_mma(const uint4& a, const uint4& b, f32x16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-// two floats -> the packed bf16 pairs of their three terms
-__device__ __forceinline__ void dlq_split3(float u0, float u1, unsigned& w0, unsigned& w1, unsigned& w2) {
-  w0 = pack_bf16x2(u0, u1);
-  const float r0 = u0 - __uint_as_float(w0 << 16), r1 = u1 - __uint_as_float(w0 & 0xffff0000u);
-  w1 = pack_bf16x2(r0, r1);
-  w2 = pack_bf16x2(r0 - __uint_as_float(w1 << 16), r1 - __uint_as_float(w1 & 0xffff0000u));
-}
 // dispatch position of workgroup `blk`: the last i with first[i] <= blk
 __device__ __forceinline__ int dlq_find(const int* first, int B, int blk) {
   int lo = 0, hi = B;
@@ -100,17 +80,30 @@ __device__ __forceinline__ int dlq_find(const int* first, int B, int blk) {
   return lo;
 }
 
-template <int LAYER>
+// MODE 0: the eval forward described above.  The training step (dlq_train.hip) runs the same loop DENSE -- every
+// utterance owns ceil(T_max / NF) tiles at every layer, workgroup = b * tpu + tile -- with its own epilogues:
+//   MODE 1 (train forward): z = conv + bias in fp32 frame-major [B][T_max][256] and the tile's per-channel (mean, M2) over its frames;
+//   MODE 2 (data gradient, LAYER 2's shape on the data-gradient image with dz as input): dh of the layer below, turned into
+//          dy = dh * keep / (1 - p) * GELU'(gamma zhat + beta) there (fp32 frame-major) with the tile's per-channel (sum dy, sum dy zhat).
+template <int LAYER, int MODE>
 __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs a) {
   using namespace dlq;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   constexpr int TAPS = LAYER == 1 ? 5 : 3, HALO = TAPS / 2, EXT = LAYER == 1 ? 2 : (LAYER == 2 ? 1 : 0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
   const int blk = blockIdx.x, B = a.B;
-  const int pos = dlq_find(a.tab + 3 * B, B, blk);
-  const int b = a.tab[2 * B + pos], tile = blk - a.tab[3 * B + pos], len = a.tab[b];
+  int b, tile;
+  if (MODE == 0) {
+    const int pos = dlq_find(a.tab + 3 * B, B, blk);
+    b = a.tab[2 * B + pos];
+    tile = blk - a.tab[3 * B + pos];
+  } else {
+    b = blk / a.tpu;
+    tile = blk - b * a.tpu;
+  }
+  const int len = a.tab[b];
   const int t0 = tile * NF;
-  const int e_out = min(a.T_max, len + EXT);       // frames of this layer's output that exist
+  const int e_out = MODE == 0 ? min(a.T_max, len + EXT) : a.T_max;   // frames of this layer's output that exist
   if (t0 >= e_out) return;                         // (the tile list is layer 1's; the later layers have fewer frames)
   const int nact = e_out - t0 > 32 ? 2 : 1;        // 32-frame B tiles that hold an existing frame
 
@@ -146,7 +139,7 @@ __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs 
       }
     }
   } else {
-    const int e_in = min(a.T_max, len + EXT + 1);  // frames of the previous layer's output that exist
+    const int e_in = MODE == 0 ? min(a.T_max, len + EXT + 1) : a.T_max;  // frames of the previous layer's output that exist
     const uint4* src = a.hin + (size_t)b * a.T_max * PIXC;
     for (int i = tid; i < (NF + 2 * HALO) * PIXC; i += NTH) {
       const int s = i / PIXC, ch = i - s * PIXC, f = t0 - HALO + s;
@@ -209,7 +202,62 @@ __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs 
   }
 
   // ---- epilogue: lane = frame, registers 4 g .. 4 g + 3 = channels co0 + 8 g + 4 h + (0 .. 3)
-  if (LAYER != 3) {
+  if (MODE != 0) {
+    // the tile through LDS as float [channel][NF + 1]; then thread = channel walks the tile's frames in order (coalesced over channels)
+    __syncthreads();                               // every wave is done with the input tile
+    float* tile_f = reinterpret_cast<float*>(lds);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      if (n >= nact) continue;
+      const int fc = n * 32 + col;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int co = 64 * wave + 32 * m + 8 * g + 4 * h;
+          float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (MODE == 1) bv = *reinterpret_cast<const float4*>(a.bias + co);
+          tile_f[(co + 0) * (NF + 1) + fc] = acc[m][n][4 * g] + bv.x;
+          tile_f[(co + 1) * (NF + 1) + fc] = acc[m][n][4 * g + 1] + bv.y;
+          tile_f[(co + 2) * (NF + 1) + fc] = acc[m][n][4 * g + 2] + bv.z;
+          tile_f[(co + 3) * (NF + 1) + fc] = acc[m][n][4 * g + 3] + bv.w;
+        }
+    }
+    __syncthreads();
+    const int cnt = min(NF, a.T_max - t0);         // >= 1, and <= 32 when nact == 1
+    const float* row = tile_f + tid * (NF + 1);
+    const size_t fr0 = (size_t)b * a.T_max + t0;   // the tile's first frame in the batch
+    float* out = a.zout + fr0 * HID + tid;
+    float* rec = a.rec + (size_t)blk * 2 * HID;
+    if (MODE == 1) {
+      float sum = 0.f;
+      for (int f = 0; f < cnt; ++f) {
+        sum += row[f];
+        out[(size_t)f * HID] = row[f];
+      }
+      const float mean = sum / (float)cnt;
+      float m2 = 0.f;
+      for (int f = 0; f < cnt; ++f) {
+        const float d = row[f] - mean;
+        m2 += d * d;
+      }
+      rec[tid] = mean;
+      rec[HID + tid] = m2;
+    } else {
+      const float mu = a.st_mean[tid], is = a.st_invstd[tid], ga = a.gamma[tid], be = a.beta[tid];
+      const float* zp = a.zprev + fr0 * HID + tid;
+      float s1 = 0.f, s2 = 0.f;
+      for (int f = 0; f < cnt; ++f) {
+        const float zh = (zp[(size_t)f * HID] - mu) * is;
+        const float dy = row[f] * drop_scale1(a.drop, (fr0 + f) * HID + tid) * dlq_dgelu(ga * zh + be);
+        out[(size_t)f * HID] = dy;
+        s1 += dy;
+        s2 += dy * zh;
+      }
+      rec[2 * tid] = s1;                           // [channel][2]: the record form of launch_reduce_partials / launch_split_sums
+      rec[2 * tid + 1] = s2;
+    }
+  } else if (LAYER != 3) {
     char* dst = reinterpret_cast<char*>(a.hout + (size_t)b * a.T_max * PIXC);
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
@@ -270,12 +318,25 @@ __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs 
 }
 
 hipError_t launch_dlq_layer(int layer, const DlqLayerArgs& a, int ntiles, hipStream_t s) {
-  const void* fn = layer == 1 ? (const void*)dlq_layer_kernel<1> : layer == 2 ? (const void*)dlq_layer_kernel<2> : (const void*)dlq_layer_kernel<3>;
+  const void* fn = layer == 1 ? (const void*)dlq_layer_kernel<1, 0> : layer == 2 ? (const void*)dlq_layer_kernel<2, 0> : (const void*)dlq_layer_kernel<3, 0>;
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, dlq::LDS_BYTES);   // per device: set on every launch
   if (e != hipSuccess) return e;
-  if (layer == 1) hipLaunchKernelGGL(dlq_layer_kernel<1>, dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  else if (layer == 2) hipLaunchKernelGGL(dlq_layer_kernel<2>, dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  else hipLaunchKernelGGL(dlq_layer_kernel<3>, dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
+  if (layer == 1) hipLaunchKernelGGL((dlq_layer_kernel<1, 0>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
+  else if (layer == 2) hipLaunchKernelGGL((dlq_layer_kernel<2, 0>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
+  else hipLaunchKernelGGL((dlq_layer_kernel<3, 0>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
+  return hipGetLastError();
+}
+
+// mode 1: the train forward of `layer`; mode 2: the data gradient (layer 2's shape).  ntiles = B * a.tpu
+hipError_t launch_dlq_layer_train(int layer, int mode, const DlqLayerArgs& a, int ntiles, hipStream_t s) {
+  const void* fn = mode == 2 ? (const void*)dlq_layer_kernel<2, 2>
+                             : layer == 1 ? (const void*)dlq_layer_kernel<1, 1> : layer == 2 ? (const void*)dlq_layer_kernel<2, 1> : (const void*)dlq_layer_kernel<3, 1>;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, dlq::LDS_BYTES);
+  if (e != hipSuccess) return e;
+  if (mode == 2) hipLaunchKernelGGL((dlq_layer_kernel<2, 2>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
+  else if (layer == 1) hipLaunchKernelGGL((dlq_layer_kernel<1, 1>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
+  else if (layer == 2) hipLaunchKernelGGL((dlq_layer_kernel<2, 1>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
+  else hipLaunchKernelGGL((dlq_layer_kernel<3, 1>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 """DeepfakeDetector -- MI355X counterpart of the reference's src/dlqueen_model.py:115-173 (1D conv + StatsPool + wide channels,
-the model its findings name as the winning recipe), eval forward and prediction CLI.
+the model its findings name as the winning recipe), eval forward and prediction CLI.  Training lives beside it:
+training.DlqTrainer (the all-C-ABI step) and the CLI `python -m dfa_amd.train_dlqueen`.
 
 Same constructor / state_dict / call contract: `model(x[B, C, T], lengths) -> logits[B]`.  x is the stored [C, T] layout of a
 features.pkl row padded to the batch's longest utterance; the pool runs over each utterance's own frames.
@@ -10,7 +11,9 @@ depends on the utterance and on min(T - len, 2) -- how many padding frames follo
 forward reproduces exactly that, bit for bit independent of the batch: x past `len` is taken as zero and never used (it may hold
 NaN), layer 1 exists on frames < min(T, len + 2), layer 2 on < min(T, len + 1), layer 3 on < len.
 
-This version is eval-only: training (AdamW, EMA, class weights, AMP, SpecAugment) is not built and is refused with a message."""
+This module is eval-only: `model.train()(x, lengths)` and `--epochs > 0` are refused with a message that points at the trainer.
+The training step is NOT a function of the utterance alone: the reference's BatchNorm1d counts every frame of the padded batch, so
+a step depends on the batch's composition and on T_max; the promise above is an eval promise."""
 from __future__ import annotations
 
 import argparse
@@ -25,8 +28,8 @@ from . import _lib
 from ._params import BatchNormParams, ConvParams, LinearParams, Slots
 
 TILE_FRAMES = 64     # DFA_DLQ_TILE_FRAMES: frames of one utterance a workgroup owns (tests probe the sizes around it)
-_EVAL_ONLY = ("dfa_amd.dlqueen_model is eval-only in this version: the DeepfakeDetector training step (AdamW, EMA, class "
-              "weights, AMP, SpecAugment) is not built")
+_EVAL_ONLY = ("dfa_amd.dlqueen_model is eval-only: the DeepfakeDetector training step runs through dfa_amd.training.DlqTrainer "
+              "(forward_train, BCE(pos_weight), backward, clip, AdamW, EMA on the C ABI) and the CLI `python -m dfa_amd.train_dlqueen`")
 
 
 class _Encoder(nn.Module):
@@ -150,7 +153,7 @@ def parse_args(argv=None):
     ap.add_argument("--ckpt_path", default="best_model.pth")
     ap.add_argument("--prediction_pkl", default="prediction.pkl")
     ap.add_argument("--device", default="cuda")
-    ap.add_argument("--epochs", type=int, default=0, help="must stay 0: this version does not train")
+    ap.add_argument("--epochs", type=int, default=0, help="must stay 0: training is dfa_amd.train_dlqueen")
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--dropout", type=float, default=0.3)
@@ -159,7 +162,7 @@ def parse_args(argv=None):
                     help="batch consecutive files as the reference does (same padding classes) instead of sorting by length")
     args = ap.parse_args(argv)
     if args.epochs > 0:
-        ap.exit(2, f"--epochs {args.epochs}: {_EVAL_ONLY}; train with the reference and pass its --ckpt_path\n")
+        ap.exit(2, f"--epochs {args.epochs}: {_EVAL_ONLY}; train with `python -m dfa_amd.train_dlqueen` (or the reference) and pass its --ckpt_path\n")
     return args
 
 

@@ -16,3 +16,10 @@ def cnn1d_train_forward(model, x):
 def cae_train_forward(model, x):
     from .train_step import cae_train_forward as _impl
     return _impl(model, x)
+
+
+def __getattr__(name):
+    if name == "DlqTrainer":        # the DeepfakeDetector's all-C-ABI trainer (train_step.py), imported on first use
+        from .train_step import DlqTrainer
+        return DlqTrainer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

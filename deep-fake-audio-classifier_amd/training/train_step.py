@@ -5,7 +5,7 @@ Two ways to use it:
     optimizer.zero_grad(); loss.backward(); optimizer.step()` -- `model(x)` in train mode goes through `TrainFunction`, a
     torch.autograd.Function whose forward/backward are the C-ABI calls dfa_<kind>_forward_train / dfa_<kind>_backward; any
     torch criterion and optimizer work unchanged.
-  * native (`NativeTrainer`, `CaeNativeTrainer`): forward, loss, backward, ONE all-reduce of the flat gradient buffer
+  * native (`NativeTrainer`, `CaeNativeTrainer`, `DlqTrainer` for the DeepfakeDetector): forward, loss, backward, ONE all-reduce of the flat gradient buffer
     (RCCL over xGMI when torch.distributed is initialised with backend "nccl") and the fused AdamW kernel,
     with no autograd graph and no per-parameter optimizer loop.
 """
@@ -403,6 +403,97 @@ class CaeNativeTrainer(_FlatAdamW):
                 self.bn_sync.disarm()
         self._exchange_and_update()
         return mse.mean()          # every sample has T*F elements: the mean of the per-sample MSEs is nn.MSELoss's mean
+
+
+class DlqTrainer(_FlatAdamW):
+    """Whole DeepfakeDetector training step on the C ABI (src/dlqueen_model.py:255-330 without AMP: everything is fp32-grade,
+    GradScaler / autocast have no counterpart): dfa_dlq_forward_train -> BCEWithLogitsLoss(pos_weight) -> dfa_dlq_backward into the
+    flat gradient views -> clip_grad_norm_(grad_clip) on the device -> fused AdamW -> EMA of the parameters.  The step is dense
+    over the padded batch as the reference's is: BatchNorm1d counts every frame of x[B, C, T_max], padding included, so a step
+    depends on the batch's composition and on T_max.  One rank only in this version."""
+
+    def __init__(self, model, lr=1e-3, weight_decay=1e-4, pos_weight=1.0, grad_clip=5.0, ema_decay=None):
+        if type(model).__name__ != "DeepfakeDetector":
+            raise ValueError(f"DlqTrainer trains a dfa_amd DeepfakeDetector, got {type(model).__name__}")
+        super().__init__(model, lr=lr, weight_decay=weight_decay)
+        if self.world > 1:
+            raise ValueError("DlqTrainer runs on one rank in this version: the DeepfakeDetector step has no gradient exchange and no "
+                             "synchronised BatchNorm yet")
+        self.pos_weight, self.grad_clip, self.ema_decay = float(pos_weight), float(grad_clip), ema_decay
+        dev = self.flat_p.device
+        self.loss_buf = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.norm_buf = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.dlogits = None
+        self.shadow = self.flat_p.clone() if ema_decay is not None else None
+        self.keep_out = None        # test hook: a uint8 tensor of 3 * B * 256 * T + B * 256 elements receives the keep bits
+
+    def step(self, x, lengths, y):
+        """One optimisation step on (x[B, C, T_max] float32 in the stored layout, lengths[B], y[B] in {0, 1}); returns the device
+        loss scalar.  Frames of x behind an utterance's end are taken as zero and never used."""
+        model = self.model
+        if x.dim() != 3:
+            raise ValueError(f"DeepfakeDetector expects x of shape (B, C, T), got {tuple(x.shape)}")
+        _lib.require_gpu(model, x)
+        B, Cc, T = x.shape
+        lengths = _lib.host_lengths(lengths, B, T, 1)
+        x = _lib.stored_layout(x, model._conforms(x), time_last=True)
+        sb, sc, _ = x.stride()
+        model.train()
+        ctx = _lib.Context.get(x.device)
+        lib, h = ctx.lib, ctx.handle
+        with torch.cuda.device(ctx.index):
+            ctx.use_current_stream()
+            ts = model._abi_tensors()
+            sig = (ctx.index, tuple(t.data_ptr() for t in ts))
+            if ctx.owner_changed("dlq", model) or getattr(model, "_bound", None) != sig:
+                _lib.check(h, lib.dfa_dlq_set_params(h, _lib.ptr_array([t.detach() for t in ts]), len(ts), model.in_ch, model.hidden))
+                model._bound = sig
+            model._prepared = None          # the eval images are stale after this step
+            nbytes = lib.dfa_dlq_train_workspace_bytes(h, B, T, Cc)
+            if nbytes == 0:
+                raise ValueError(f"bad DeepfakeDetector training shape (B={B}, C={Cc}, T_max={T}): BatchNorm1d needs B * T_max >= 2")
+            ws = _train_ws(model, ctx, nbytes)
+            if self.dlogits is None or self.dlogits.numel() != B:
+                self.dlogits = torch.empty(B, dtype=torch.float32, device=x.device)
+                self.logits = torch.empty(B, dtype=torch.float32, device=x.device)
+            seed = getattr(model, "_drop_seed", None)
+            if seed is None:
+                seed = model._drop_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+            offset = _next_dropout_offset(model, B * 256 * T)
+            y = y.to(device=x.device, dtype=torch.float32).contiguous()
+            lp = C.c_void_p(lengths.ctypes.data)
+            _lib.check(h, lib.dfa_dlq_forward_train(h, _ptr(x), B, T, Cc, sb, sc, lp, float(model.dropout), seed, offset, 0.1, 1,
+                                                    _ptr(self.logits), _ptr(self.keep_out), _ptr(ws), ws.numel()))
+            torch._foreach_add_([model.enc.net[i].num_batches_tracked for i in model._BN_IDX], 1)
+            _lib.check(h, lib.dfa_bce_pos_weight_fwd_bwd(h, _ptr(self.logits), _ptr(y), self.pos_weight, B, _ptr(self.loss_buf),
+                                                         _ptr(self.dlogits)))
+            _lib.check(h, lib.dfa_dlq_backward(h, _ptr(x), B, T, Cc, sb, sc, _ptr(self.dlogits), _lib.ptr_array(self.grad_views),
+                                               len(self.grad_views), _ptr(ws), ws.numel()))
+            if self.grad_clip > 0:
+                _lib.check(h, lib.dfa_clip_grad_norm(h, _ptr(self.flat_g), self.flat_g.numel(), self.grad_clip, _ptr(self.norm_buf)))
+        self._exchange_and_update()
+        if self.shadow is not None:
+            self.shadow.lerp_(self.flat_p, 1.0 - self.ema_decay)
+        return self.loss_buf
+
+    def ema_applied(self):
+        """Context manager: the EMA shadow in place of the weights (for evaluation), the weights restored on exit."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def swap():
+            if self.shadow is None:
+                yield
+                return
+            saved = self.flat_p.clone()
+            self.flat_p.copy_(self.shadow)
+            self.model._prepared = None
+            try:
+                yield
+            finally:
+                self.flat_p.copy_(saved)
+                self.model._prepared = None
+        return swap()
 
 
 def make_cae_trainer(model, **kw):

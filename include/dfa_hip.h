@@ -403,6 +403,38 @@ size_t dfa_dlq_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int in_ch);
 int dfa_dlq_forward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, int64_t stride_b, int64_t stride_c,
                     const int32_t* lengths, float* logits, float* pooled, void* workspace, size_t workspace_bytes);
 
+/* ---- DeepfakeDetector training step (src/dlqueen_model.py:255-330 without AMP: everything is fp32-grade, GradScaler / autocast have
+ * no counterpart).  The step is DENSE over the padded batch, as the reference's is: the encoder runs on all T_max frames of every
+ * utterance (x at t >= lengths[b] taken as zero by a select, never used), BatchNorm1d's batch statistics count all N = B * T_max
+ * frames, padding included, and only the pool is masked.  The step therefore DEPENDS on the batch's composition and on T_max; the
+ * "function of the utterance alone" promise of dfa_dlq_forward is an eval promise only.  Dropout (p_drop) follows each encoder GELU
+ * and the head's; the keep factor of an element is a function of (seed, offset, layer, index) and is regenerated by the backward.
+ * Raw parameters from dfa_dlq_set_params are used (no prepare); running statistics are updated in place (momentum, unbiased
+ * variance N / (N - 1)) when update_running_stats != 0; num_batches_tracked is the caller's.
+ * x, strides, lengths, workspace alignment: as dfa_dlq_forward.  B * T_max < 2 returns DFA_E_BAD_SHAPE (one value per channel).
+ * keep_out: test hook, NULL in production: device uint8[3 * B * 256 * T_max + B * 256], the keep bits the kernels applied, layers
+ *   1-3 as [B][T_max][256], then the head's [B][256] (layer 3's are drawn for every frame; the pool uses those of frames < len).
+ * An armed dfa_ctx_set_bn_sync hook returns DFA_E_UNSUPPORTED (single rank in this version), a capturing stream too.
+ * dfa_dlq_backward must follow its own forward on the same workspace and shape (else DFA_E_NOT_PREPARED); it WRITES the 16
+ *   gradients in parameters() order: enc.net.{0,1,4,5,8,9}.{weight,bias}, head.{0,3}.{weight,bias}.  The conv-bias gradients in
+ *   front of a BatchNorm are mathematically zero: the rounding noise of the sums is returned.
+ * No atomics: every reduction is per-workgroup records and a fixed-order second stage, so a step is bit-reproducible.
+ * Timing slots: 8 = weight images, 9 = forward convolutions, 10 = BatchNorm statistics / activation passes / pool + head,
+ *   11 = backward head, pool and BatchNorm passes, 12 = data gradients, 13 = weight gradients. */
+size_t dfa_dlq_train_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int in_ch);
+int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, int64_t stride_b, int64_t stride_c,
+                          const int32_t* lengths, float p_drop, uint64_t seed, uint64_t offset, float momentum,
+                          int update_running_stats, float* logits, uint8_t* keep_out, void* workspace, size_t workspace_bytes);
+int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, int64_t stride_b, int64_t stride_c,
+                     const float* dlogits, float* const* grads, int ngrads /* 16 */, void* workspace, size_t workspace_bytes);
+/* loss = mean_b -[pos_weight y log sigmoid(l) + (1 - y) log sigmoid(-l)] (BCEWithLogitsLoss(pos_weight), mean reduction);
+ * dlogits = (sigmoid(l) (1 + (pos_weight - 1) y) - pos_weight y) / B.  loss: device float[1] or NULL; dlogits: device float[B] or NULL */
+int dfa_bce_pos_weight_fwd_bwd(dfa_ctx* ctx, const float* logits, const float* labels, float pos_weight, int B, float* loss,
+                               float* dlogits);
+/* torch.nn.utils.clip_grad_norm_ on one flat buffer, on the device with no host synchronisation: a two-stage fixed-order L2 norm,
+ * then grad *= min(1, max_norm / (norm + 1e-6)).  norm_out: device float[1] (the norm before clipping) or NULL. */
+int dfa_clip_grad_norm(dfa_ctx* ctx, float* grad, size_t n, float max_norm, float* norm_out);
+
 /* ---- shared ------------------------------------------------------------------------------------ */
 size_t dfa_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T, int F, int precision);
 /* workspace of dfa_cnn2d_forward_ragged / dfa_cnn1d_forward_ragged for B utterances padded to T_max frames (0 for a model
