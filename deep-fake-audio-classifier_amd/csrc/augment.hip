@@ -19,8 +19,6 @@ struct AugArgs {
   AugCfg cfg;                               // rng.h: the same definition the training kernels fold into their loads
 };
 
-__device__ __forceinline__ float aug_ld(const float* p) { return *p; }
-__device__ __forceinline__ float aug_ld(const bf16_t* p) { return bf16_to_float(*p); }
 __device__ __forceinline__ void aug_st(float* p, float v) { *p = v; }
 __device__ __forceinline__ void aug_st(bf16_t* p, float v) { *p = float_to_bf16(v); }
 
@@ -44,7 +42,7 @@ __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) {
     if (i >= inner) break;
     const int t = TFAST ? i : o, f = TFAST ? o : i;
     const int ts = aug_src_t(a.cfg, t);
-    const float xraw = aug_ld(xb + (long long)ts * a.sxt + (long long)f * a.sxf);
+    const float xraw = ld1(xb + (long long)ts * a.sxt + (long long)f * a.sxf);
     aug_st(ob + (long long)t * a.sot + (long long)f * a.sof, aug_apply(a.cfg, xraw, b, t, f));
   }
 }

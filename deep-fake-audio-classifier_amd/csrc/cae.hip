@@ -10,13 +10,6 @@
 
 namespace dfa {
 
-template <typename TX>
-__device__ __forceinline__ float ld_x(const TX* p);
-template <>
-__device__ __forceinline__ float ld_x<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ld_x<bf16_t>(const bf16_t* p) { return bf16_to_float(*p); }
-
 constexpr int E1_TI = 16, E1_TJ = 16, E1_XR = 2 * E1_TI + 2, E1_XC = 2 * E1_TJ + 2;
 
 template <typename TX, typename TO>
@@ -36,7 +29,7 @@ __global__ __launch_bounds__(256) void cae_enc1_kernel(const TX* __restrict__ x,
     const int t = t_base + rr, f = f_base + cc;
     float v = 0.f;  // conv zero padding applies to the NORMALISED input
     if (t >= 0 && t < T && f >= 0 && f < F) {
-      v = ld_x<TX>(xb + (int64_t)t * st + (int64_t)f * sf);
+      v = ld1(xb + (int64_t)t * st + (int64_t)f * sf);
       if (mu) v = (v - mu[f]) / sigma[f];
     }
     xs[rr][cc] = v;
@@ -85,30 +78,6 @@ __global__ void cae_opad_col_kernel(T* __restrict__ out, const float* __restrict
   out[((size_t)row * Wo + (Wo - 1)) * C + c] = cvt_out<T>(no_relu ? bias[c] : fmaxf(bias[c], 0.f));
 }
 
-template <typename T>
-__device__ __forceinline__ void load32(const T* p, float* v);
-template <>
-__device__ __forceinline__ void load32<float>(const float* p, float* v) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const float4 q = reinterpret_cast<const float4*>(p)[k];
-    v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
-  }
-}
-template <>
-__device__ __forceinline__ void load32<bf16_t>(const bf16_t* p, float* v) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint4 q = reinterpret_cast<const uint4*>(p)[k];
-    const unsigned u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[8 * k + 2 * e] = __uint_as_float(u[e] << 16);
-      v[8 * k + 2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u);
-    }
-  }
-}
-
 // decoder block 4 + zero time padding + squared error.  One thread per input pixel (i, j) of d3, plus "virtual"
 // rows i >= H3 that only cover the zero-padded tail of the reconstruction.
 template <typename T, typename TX>
@@ -128,7 +97,7 @@ __global__ __launch_bounds__(256) void cae_dec4_mse_kernel(const T* __restrict__
     float r[4] = {0.f, 0.f, 0.f, 0.f};
     if (i < H3) {
       float v[32];
-      load32<T>(d3 + (((size_t)b * H3 + i) * W3 + j) * 32, v);
+      ld32<T>(d3 + (((size_t)b * H3 + i) * W3 + j) * 32, v);
       const float bb = b4[0];
 #pragma unroll
       for (int q = 0; q < 4; ++q) r[q] = bb;
@@ -144,7 +113,7 @@ __global__ __launch_bounds__(256) void cae_dec4_mse_kernel(const T* __restrict__
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int f = 2 * j + c;
-          float xn = ld_x<TX>(x + (int64_t)b * sb + (int64_t)t * st + (int64_t)f * sf);
+          float xn = ld1(x + (int64_t)b * sb + (int64_t)t * st + (int64_t)f * sf);
           if (mu) xn = (xn - mu[f]) / sigma[f];
           const float d = r[2 * a + c] - xn;
           err = fmaf(d, d, err);
@@ -178,20 +147,13 @@ __global__ void cae_mse_finalize_ragged_kernel(const float* __restrict__ partial
 #undef DFA_KERNEL_BODY_SCOPE
 
 template <typename T>
-__device__ __forceinline__ float to_float(T v);
-template <>
-__device__ __forceinline__ float to_float<float>(float v) { return v; }
-template <>
-__device__ __forceinline__ float to_float<bf16_t>(bf16_t v) { return bf16_to_float(v); }
-
-template <typename T>
 __global__ void cae_latent_export_kernel(const T* __restrict__ lat, float* __restrict__ out, int B, int HW, int C) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // over out elements [B][C][HW]
   if (i >= (size_t)B * C * HW) return;
   const int p = (int)(i % HW);
   const int c = (int)((i / HW) % C);
   const int b = (int)(i / ((size_t)HW * C));
-  out[i] = to_float<T>(lat[((size_t)b * HW + p) * C + c]);
+  out[i] = ld1(lat + ((size_t)b * HW + p) * C + c);
 }
 
 hipError_t launch_cae_enc1(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu,

@@ -5,18 +5,6 @@
 
 namespace dfa {
 
-template <typename T>
-__device__ __forceinline__ void cp8(const T* src, T* dst);
-template <>
-__device__ __forceinline__ void cp8<float>(const float* src, float* dst) {
-  reinterpret_cast<float4*>(dst)[0] = reinterpret_cast<const float4*>(src)[0];
-  reinterpret_cast<float4*>(dst)[1] = reinterpret_cast<const float4*>(src)[1];
-}
-template <>
-__device__ __forceinline__ void cp8<bf16_t>(const bf16_t* src, bf16_t* dst) {
-  *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-}
-
 // dz[B][2H][Wo][C] (Wo >= 2W; a trailing output_padding column is skipped) -> zp[(b,i,j)][q = 2a+c][C]
 template <typename T>
 __global__ void pixel_unshuffle_kernel(const T* __restrict__ dz, T* __restrict__ zp, int B, int H, int W, int Wo, int C) {
@@ -46,27 +34,6 @@ __global__ void convt_q_to_w_kernel(const float* __restrict__ dwq, float* __rest
   if (i >= cin * cout * 4) return;
   const int q = i & 3, co = (i >> 2) % cout, ci = i / (4 * cout);
   dw[i] = dwq[(size_t)ci * 4 * cout + q * cout + co];
-}
-
-template <typename T>
-__device__ __forceinline__ void ld32(const T* p, float* v);
-template <>
-__device__ __forceinline__ void ld32<float>(const float* p, float* v) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const float4 q = reinterpret_cast<const float4*>(p)[k];
-    v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
-  }
-}
-template <>
-__device__ __forceinline__ void ld32<bf16_t>(const bf16_t* p, float* v) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint4 q = reinterpret_cast<const uint4*>(p)[k];
-    const unsigned u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[8 * k + 2 * e] = __uint_as_float(u[e] << 16); v[8 * k + 2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u); }
-  }
 }
 
 // decoder block 4 backward (ConvTranspose2d 32 -> 1): for every d3 pixel (i,j) with its 2x2 patch of drecon

@@ -74,20 +74,6 @@ struct Cnn1dX3Args {
   long long* stamps;
 };
 
-__device__ __forceinline__ f32x16_t mma_bf16(const uint4& a, const uint4& b, f32x16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-// 8 floats -> hi / lo bf16 fragments (element j in bf16 position j)
-__device__ __forceinline__ void split8(const float (&v)[8], uint4& hi, uint4& lo) {
-  unsigned h[4], l[4];
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    h[p] = pack_bf16x2(v[2 * p], v[2 * p + 1]);
-    l[p] = pack_bf16x2(v[2 * p] - __uint_as_float(h[p] << 16), v[2 * p + 1] - __uint_as_float(h[p] & 0xffff0000u));
-  }
-  hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
 __device__ __forceinline__ uint4 and4(unsigned m, const uint4& v) { return make_uint4(v.x & m, v.y & m, v.z & m, v.w & m); }   // (a select here became an exec branch)
 
 // one 32-frame tile of a layer whose input lives in LDS as split pixels: acc = sum over (tap, ks) of the three split products.
@@ -123,9 +109,9 @@ __device__ __forceinline__ void split_gemm(const uint4 (&wh)[3 * (CIN / 16)], co
   for (int i = 0; i < NS; ++i) {
     const uint4 xh = qh[i % PD], xl = ql[i % PD];
     if (i + PD < NS) rd(i + PD, qh[i % PD], ql[i % PD]);
-    acc = mma_bf16(wh[i], xh, acc);
-    acc = mma_bf16(wl[i], xh, acc);
-    acc = mma_bf16(wh[i], xl, acc);
+    acc = mma32(wh[i], xh, acc);
+    acc = mma32(wl[i], xh, acc);
+    acc = mma32(wh[i], xl, acc);
     side(i);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -233,7 +219,7 @@ __global__ __launch_bounds__(512) void cnn1d_ragged_x3_kernel(Cnn1dX3Args a, Cnn
 // generalised: a workgroup = (utterance, MT tiles of 32 output channels); 16-channel slabs of the input go through LDS as they are
 // (contiguous 16 T floats, 16-byte loads, two slabs ahead), the lane that owns frame t splits x[c][t-1..t+1] of its 8 channels
 // into bf16 B fragments ONCE per slab and tap and feeds them to every channel tile; this layer's A fragments sit in LDS.
-// TERMS = 3 (default): every fp32 operand = hi + lo + lo2, three bf16 terms = its 24-bit mantissa exactly, six MFMAs per product
+// TERMS = 3 (default): every fp32 operand = hi + lo + lo2, three bf16 terms (split8n<3>, dfa_device.h: the operand exactly), six MFMAs per product
 // (all term pairs of order <= 2; the dropped ones are below 2^-24 of a product): fp32-grade sums.  TERMS = 2: the bf16x3
 // construction of the eval kernel (16-bit operands, three MFMAs, ~1e-5) -- fine for inference's 1e-4 bar, but in a training step
 // a 1e-5 perturbation of a pre-activation flips ~1e-5 of the ReLU masks and every flip moves a gradient by a whole element:
@@ -339,23 +325,6 @@ hipError_t launch_pack_conv1d_train_all(const float* w1, const float* w2, const 
   const int total = a.begin[5] > 256 ? a.begin[5] : 256;
   hipLaunchKernelGGL(pack_conv1d_train_all_kernel, dim3((total + 255) / 256), dim3(256), 0, s, a);
   return hipGetLastError();
-}
-
-// 8 floats -> TERMS bf16 fragments (element j in bf16 position j): v = f[0] + f[1] (+ f[2]), exactly for TERMS = 3
-template <int TERMS>
-__device__ __forceinline__ void split8n(const float (&v)[8], uint4 (&f)[TERMS]) {
-  unsigned q[TERMS][4];
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    float r0 = v[2 * p], r1 = v[2 * p + 1];
-#pragma unroll
-    for (int t = 0; t < TERMS; ++t) {
-      q[t][p] = pack_bf16x2(r0, r1);
-      if (t + 1 < TERMS) { r0 -= __uint_as_float(q[t][p] << 16); r1 -= __uint_as_float(q[t][p] & 0xffff0000u); }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < TERMS; ++t) f[t] = make_uint4(q[t][0], q[t][1], q[t][2], q[t][3]);
 }
 
 template <int MT, int TERMS, bool AUG = false, bool RAGGED = false>
@@ -487,13 +456,13 @@ __global__ __launch_bounds__(512) void conv1d_x3_kernel(Conv1dX3Args a) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
           if constexpr (TERMS == 3) {                      // smallest terms first
-            acc[m][j] = mma_bf16(w[m][2], xs[0], acc[m][j]);
-            acc[m][j] = mma_bf16(w[m][0], xs[2], acc[m][j]);
-            acc[m][j] = mma_bf16(w[m][1], xs[1], acc[m][j]);
+            acc[m][j] = mma32(w[m][2], xs[0], acc[m][j]);
+            acc[m][j] = mma32(w[m][0], xs[2], acc[m][j]);
+            acc[m][j] = mma32(w[m][1], xs[1], acc[m][j]);
           }
-          acc[m][j] = mma_bf16(w[m][1], xs[0], acc[m][j]);
-          acc[m][j] = mma_bf16(w[m][0], xs[1], acc[m][j]);
-          acc[m][j] = mma_bf16(w[m][0], xs[0], acc[m][j]);
+          acc[m][j] = mma32(w[m][1], xs[0], acc[m][j]);
+          acc[m][j] = mma32(w[m][0], xs[1], acc[m][j]);
+          acc[m][j] = mma32(w[m][0], xs[0], acc[m][j]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);

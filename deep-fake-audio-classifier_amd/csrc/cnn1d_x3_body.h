@@ -217,9 +217,9 @@
         if (j < nmine) {
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
-            acc1[j] = mma_bf16(wh[k], xh[j][k], acc1[j]);
-            acc1[j] = mma_bf16(wl[k], xh[j][k], acc1[j]);
-            acc1[j] = mma_bf16(wh[k], xl[j][k], acc1[j]);
+            acc1[j] = mma32(wh[k], xh[j][k], acc1[j]);
+            acc1[j] = mma32(wl[k], xh[j][k], acc1[j]);
+            acc1[j] = mma32(wh[k], xl[j][k], acc1[j]);
           }
         }
       __builtin_amdgcn_sched_barrier(0);

@@ -17,13 +17,6 @@ constexpr int C1_XC = C1_TF + 2;
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
-template <typename TX>
-__device__ __forceinline__ float load_x(const TX* p);
-template <>
-__device__ __forceinline__ float load_x<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float load_x<bf16_t>(const bf16_t* p) { return bf16_to_float(*p); }
-
 // Thread = (pooled pixel, channel octet): lanes 4p..4p+3 own the four 8-channel groups of pixel p, so one wave store
 // instruction writes 16 pixels x 64 bytes = 1 KiB of contiguous channels-last output.  The thread keeps its 8 x 9
 // folded weights in registers (as 4 channel pairs x 9 taps) and walks 4 pixels of the 16 x 16 tile; every tap of every
@@ -65,7 +58,7 @@ __global__ __launch_bounds__(256) void conv1_bn_relu_poolh2_kernel(const TX* __r
       if (t_fast) { cc = e / C1_XR; rr = e - cc * C1_XR; } else { rr = e / C1_XC; cc = e - rr * C1_XC; }
       const int t = 2 * i0 - 1 + rr, f = f_base + cc;
       const bool ok = t >= 0 && t < T && f >= 0 && f < F;     // conv zero padding
-      if (e < C1_XR * C1_XC) xs[buf][rr][cc] = ok ? aug_apply(aug, load_x<TX>(&xr[k]), b, t, f) : 0.f;   // train: augmentation folded in
+      if (e < C1_XR * C1_XC) xs[buf][rr][cc] = ok ? aug_apply(aug, ld1(&xr[k]), b, t, f) : 0.f;   // train: augmentation folded in
     }
   };
   const int q = tid & 3, pl = tid >> 2;   // channel octet, pixel lane (0..63)

@@ -23,8 +23,6 @@
 
 namespace dfa {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 struct Conv123Args {
   const void* x;            // features (bf16 or fp32: template argument TX), element strides below (any layout)
   long long sxb, sxt, sxf;
@@ -75,12 +73,6 @@ static inline Conv123Args c123_args(const void* x, int64_t sb, int64_t st, int64
   a.chunk_iters = chunk_iters;
   a.clock_stamps = clock_stamps;
   return a;
-}
-
-__device__ __forceinline__ float ld_as_float123(const float* p) { return *p; }
-__device__ __forceinline__ float ld_as_float123(const bf16_t* p) { return bf16_to_float(*p); }
-__device__ __forceinline__ f32x4_t mma16_123(const uint4& w, const uint4& x, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
 }
 
 // The persistent kernel's main loops are as tight on registers as the per-unit kernel's (254 of 256), and whatever the code
@@ -255,7 +247,7 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
       xok[k] = xfok[k] && (unsigned)t < (unsigned)T;
       const TX* src = xb + (xok[k] ? xoff[k] + jo : 0);
       if constexpr (sizeof(TX) == 2) xreg[k] = *(const unsigned short*)src;
-      else xreg[k] = cvt_out<bf16_t>(ld_as_float123(src)).v;
+      else xreg[k] = cvt_out<bf16_t>(ld1(src)).v;
     }
   };
   auto x_store = [&](int buf) {   // element (row, c) is tap e of the windows of slots c - e, e = 0..2
@@ -656,8 +648,8 @@ __device__ __forceinline__ void c123_consumer(const Conv123Args& a, char* smem, 
         const uint4 xv = __builtin_bit_cast(uint4, xbuf[c % PF3]);
 #pragma unroll
         for (int ca = 0; ca < 2; ++ca) {
-          if constexpr (i <= 2) acc0[ca][pb] = mma16_123(w[i * 3 + dx][kk][ca], xv, acc0[ca][pb]);
-          if constexpr (i >= 1) acc1[ca][pb] = mma16_123(w[(i - 1) * 3 + dx][kk][ca], xv, acc1[ca][pb]);
+          if constexpr (i <= 2) acc0[ca][pb] = mma16(w[i * 3 + dx][kk][ca], xv, acc0[ca][pb]);
+          if constexpr (i >= 1) acc1[ca][pb] = mma16(w[(i - 1) * 3 + dx][kk][ca], xv, acc1[ca][pb]);
         }
         if constexpr (c == C_RELU0) {
 #pragma unroll

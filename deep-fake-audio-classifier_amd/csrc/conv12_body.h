@@ -88,7 +88,7 @@
       xok[k] = xfok[k] && (unsigned)t < (unsigned)T;
       const TX* src = xb + (xok[k] ? xoff[k] + jo : 0);     // clamped address, branch-free
       if constexpr (sizeof(TX) == 2) xreg[k] = *(const unsigned short*)src;            // bf16 features: the bits as they are
-      else xreg[k] = cvt_out<bf16_t>(ld_as_float(src)).v;                               // fp32 features: RNE on load
+      else xreg[k] = cvt_out<bf16_t>(ld1(src)).v;                               // fp32 features: RNE on load
     }
   };
   auto x_store = [&](int buf) {   // element (row, c) is tap e of the windows of slots c - e, e = 0..2
@@ -118,7 +118,6 @@
   const bool c1_fok = c1_f >= 0 && c1_f < W;
   const int c1_dst = (c1_m * SP + r) * PB;                                         // + ringblk*BR*ROWB
   const int c1_sw = lds_swz<PB>(r);
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
   struct C1State { u32x2_t w0, w1; f32x16_t e, o; float v[16]; };
   auto c1_issue = [&](C1State& st, int j) {       // two window reads (asm: they join the counted LDS pipeline)
     const unsigned addr = c1_win + (j & 1) * XW_BYTES;

@@ -39,9 +39,6 @@ struct Conv12Args {
   int seg_iters;            // time-axis split for small batches: blockIdx.y walks seg_iters iterations (multiple of 6), 0 = all
 };
 
-__device__ __forceinline__ float ld_as_float(const float* p) { return *p; }
-__device__ __forceinline__ float ld_as_float(const bf16_t* p) { return bf16_to_float(*p); }
-
 namespace c12 {
 constexpr int PB = 64, SP = 36, ROWB = SP * PB, BR = 4, NKG = 2, PF = 4, SW = 30;   // SW: output columns per strip
 constexpr int RING_BYTES = 3 * BR * ROWB;

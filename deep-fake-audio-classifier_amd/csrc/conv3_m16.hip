@@ -21,7 +21,6 @@
 
 namespace dfa {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 namespace m16 {
 // A workgroup OWNS SW = 30 output columns (180 = 6 x 30) and loads the SP = 32 columns f0-1 .. f0+30 around them: a ring block is
@@ -34,10 +33,6 @@ constexpr int RING_BYTES = 3 * BR * ROWB, BIAS_BYTES = NSL * 32 * 4, TOT_BYTES =
 constexpr int LDS_BYTES = RING_BYTES + BIAS_BYTES + TOT_BYTES;
 __device__ __forceinline__ int swz(int slot) { return slot & 6; }
 }  // namespace m16
-
-__device__ __forceinline__ f32x4_t mma16(const uint4& w, const uint4& x, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
-}
 
 // PIPE = false: the compiler-scheduled twin (same arithmetic; the GPU tests require bit-identical output)
 // TRAIN = true: the train-mode forward of the same layer (src/train.py:71): the pre-BatchNorm output z is stored (bf16)

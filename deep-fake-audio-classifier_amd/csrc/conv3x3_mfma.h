@@ -49,45 +49,10 @@
 #include <type_traits>
 #include <utility>
 
+#include "dfa_device.h"
 #include "rng.h"
 
 namespace dfa {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
-struct bf16_t {
-  unsigned short v;
-};
-
-__device__ __forceinline__ float bf16_to_float(bf16_t x) { return __uint_as_float(((unsigned)x.v) << 16); }
-__device__ __forceinline__ bf16_t float_to_bf16(float f) {
-  __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32: round-to-nearest-even, NaN preserved
-  bf16_t r;
-  r.v = __builtin_bit_cast(unsigned short, b);
-  return r;
-}
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-  bf16x2_t v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-template <typename T>
-__device__ __forceinline__ T cvt_out(float f);
-template <>
-__device__ __forceinline__ float cvt_out<float>(float f) { return f; }
-template <>
-__device__ __forceinline__ bf16_t cvt_out<bf16_t>(float f) { return float_to_bf16(f); }
-
-// ReLU as ONE instruction: v_med3_f32(x, 0, lim) with lim = +inf held in an SGPR the compiler cannot see through
-// (relu_limit()).  fmaxf(x, 0) costs two -- the compiler canonicalises the operand first -- and so does a med3 against a
-// literal +inf, which it folds back into that max.  Not inline asm either: the MFMA -> VALU hazard nops do not cover asm.
-__device__ __forceinline__ float relu_limit() {
-  float lim = __builtin_inff();
-  asm volatile("" : "+s"(lim));
-  return lim;
-}
-__device__ __forceinline__ float relu1(float x, float lim) { return __builtin_amdgcn_fmed3f(x, 0.f, lim); }
 
 enum { EPI_POOL_H2 = 0, EPI_POOL_2X2 = 1, EPI_MEAN_T = 2, EPI_PLAIN = 3, EPI_RAW = 4 };
 
@@ -170,7 +135,6 @@ struct Mma<float> {
 // buffer (every MFMA pair eats the full LDS latency), so the fragment reads are issued through inline asm PFD reads
 // ahead of their use and retired with counted waits.  LDS operations complete in order, so "lgkmcnt(N)" guarantees
 // everything older than the N youngest reads has landed; reads the compiler adds on its own only make a wait stricter.
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 template <int OFF, bool PIPE>
 __device__ __forceinline__ u32x4_t lds_frag(unsigned addr) {
   u32x4_t v;

@@ -21,7 +21,6 @@
 
 namespace dfa {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 // SPLIT = false: the same kernel on plain bf16 pixels (one MFMA per product) -- the training step's data-gradient
 // convolutions (dz3 -> da2 with 128 input channels in ONE launch, dz2 -> da1), EPI_PLAIN_BF16 epilogue.
@@ -41,10 +40,6 @@ struct SplitCfg {
 };
 
 enum { SPLIT_EPI_POOL_H2 = 0, SPLIT_EPI_MEAN_T = 1, SPLIT_EPI_PLAIN_BF16 = 2 };
-
-static __device__ __forceinline__ f32x4_t mma16s(const uint4& w, const uint4& x, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
-}
 
 #ifdef DFA_STAMPS   // diagnostic build (make stamps): per-wave cycle split of an iteration, printed by the launcher
 static __device__ long long g_diag_split[4096 * 8];
@@ -222,12 +217,12 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_split_kernel(ConvArgs a) {
         if constexpr (PIPE) lds_wait<young>(xbuf[c % PF]);
         const uint4 xv = __builtin_bit_cast(uint4, xbuf[c % PF]);
         if constexpr (i <= 2) {
-          acc0[pb] = mma16s(w[i * 3 + dx][kk][0], xv, acc0[pb]);                        // w_hi * (x_hi | x_lo)
-          if constexpr (SPLIT && hl == 0) acc0[pb] = mma16s(w[i * 3 + dx][kk][HL - 1], xv, acc0[pb]); // w_lo * x_hi
+          acc0[pb] = mma16(w[i * 3 + dx][kk][0], xv, acc0[pb]);                        // w_hi * (x_hi | x_lo)
+          if constexpr (SPLIT && hl == 0) acc0[pb] = mma16(w[i * 3 + dx][kk][HL - 1], xv, acc0[pb]); // w_lo * x_hi
         }
         if constexpr (i >= 1) {
-          acc1[pb] = mma16s(w[(i - 1) * 3 + dx][kk][0], xv, acc1[pb]);
-          if constexpr (SPLIT && hl == 0) acc1[pb] = mma16s(w[(i - 1) * 3 + dx][kk][HL - 1], xv, acc1[pb]);
+          acc1[pb] = mma16(w[(i - 1) * 3 + dx][kk][0], xv, acc1[pb]);
+          if constexpr (SPLIT && hl == 0) acc1[pb] = mma16(w[(i - 1) * 3 + dx][kk][HL - 1], xv, acc1[pb]);
         }
         if constexpr (c == C_RELU0 && EPI != SPLIT_EPI_PLAIN_BF16) {   // rows 0..2 done for acc0: its ReLU hides under acc1's last MFMAs
 #pragma unroll

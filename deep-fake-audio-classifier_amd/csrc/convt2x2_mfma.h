@@ -25,11 +25,6 @@ struct ConvTArgs {
   float* stats_partial;
 };
 
-__device__ __forceinline__ void convt_st4(bf16_t* p, const float* v) {
-  *(uint2*)p = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-}
-__device__ __forceinline__ void convt_st4(float* p, const float* v) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-
 template <typename T, int CIN, int MSUB, bool STATS = false>
 __global__ __launch_bounds__(256) void convt2x2_mfma_kernel(ConvTArgs a) {
   constexpr int ES = sizeof(T), KG = 32 / ES, NKG = CIN / KG, PB = CIN * ES, CPP = PB / 16;
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(256) void convt2x2_mfma_kernel(ConvTArgs a) {
             if (STATS) { st1[4 * g + e] += v[e]; st2[4 * g + e] = fmaf(v[e], v[e], st2[4 * g + e]); }
             if (!STATS && !a.no_relu) v[e] = fmaxf(v[e], 0.f);
           }
-          convt_st4(o + 8 * g, v);
+          st4(o + 8 * g, v);
         }
       }
     }

@@ -1,7 +1,7 @@
 // dlq.hip -- eval forward of the reference's DeepfakeDetector (src/dlqueen_model.py:115-173: three Conv1d + BatchNorm1d + GELU
 // layers of 256 channels, masked mean / std pooling, a 512 -> 256 -> 1 head) on a variable-length batch.
 //   * every convolution is an implicit GEMM on v_mfma_f32_32x32x16_bf16 at fp32 grade: each fp32 operand is carried as THREE bf16 terms
-//     (t0 + t1 + t2 = its 24-bit mantissa) and every product is the six MFMAs of order <= 2 (w0 x0, w1 x0, w0 x1, w2 x0, w0 x2, w1 x1; fp32
+//     (t0 + t1 + t2 = its 24-bit mantissa: dfa_device.h, the term split) and every product is the six MFMAs of order <= 2 (w0 x0, w1 x0, w0 x1, w2 x0, w0 x2, w1 x1; fp32
 //     accumulate) -- the construction of the CNN1D training kernels (train_cnn1d.hip).  Two terms (hi + lo, three MFMAs: bf16x3) carry 16
 //     bits: 2^-17 per operand, which a float64 emulation of this network put at 4.6e-6 of the largest logit before any cancellation in
 //     the head -- no margin under the 2^-17 parity bound;
@@ -21,7 +21,6 @@
 //     square root and runs the head in fp32.  No atomics anywhere: a logit is a fixed-order function of its utterance.
 // Tiles are dispatched from a table the host builds from the lengths (longest utterance first): a short utterance costs few tiles.
 #include "dfa_internal.h"
-#include "conv3x3_mfma.h"
 #include "dlq_common.h"
 
 namespace dfa {
@@ -130,7 +129,7 @@ __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs 
         const bool in = f < len;                   // a select, never a product: the padding may hold NaN
         const float u0 = in ? r0[j] : 0.f, u1 = in ? r1[j] : 0.f;
         unsigned w0, w1, w2;
-        dlq_split3(u0, u1, w0, w1, w2);
+        split3_pair(u0, u1, w0, w1, w2);
         const int ch = p >> 2, sw = s & 15;        // chunk of 8 channels = 4 pairs
         unsigned* px = reinterpret_cast<unsigned*>(lds + s * PIXB);
         px[((ch ^ sw) << 2) + (p & 3)] = w0;
@@ -188,12 +187,12 @@ __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs 
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         const uint4 *w3 = af + 3 * m;
-        acc[m][n] = dlq_mma(w3[1], xf[n][1], acc[m][n]);
-        acc[m][n] = dlq_mma(w3[2], xf[n][0], acc[m][n]);
-        acc[m][n] = dlq_mma(w3[0], xf[n][2], acc[m][n]);
-        acc[m][n] = dlq_mma(w3[1], xf[n][0], acc[m][n]);
-        acc[m][n] = dlq_mma(w3[0], xf[n][1], acc[m][n]);
-        acc[m][n] = dlq_mma(w3[0], xf[n][0], acc[m][n]);
+        acc[m][n] = mma32(w3[1], xf[n][1], acc[m][n]);
+        acc[m][n] = mma32(w3[2], xf[n][0], acc[m][n]);
+        acc[m][n] = mma32(w3[0], xf[n][2], acc[m][n]);
+        acc[m][n] = mma32(w3[1], xf[n][0], acc[m][n]);
+        acc[m][n] = mma32(w3[0], xf[n][1], acc[m][n]);
+        acc[m][n] = mma32(w3[0], xf[n][0], acc[m][n]);
       }
     }
 #pragma unroll
@@ -273,8 +272,8 @@ __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs 
           const float v0 = dlq_gelu(acc[m][n][4 * g] + bv.x), v1 = dlq_gelu(acc[m][n][4 * g + 1] + bv.y);
           const float v2 = dlq_gelu(acc[m][n][4 * g + 2] + bv.z), v3 = dlq_gelu(acc[m][n][4 * g + 3] + bv.w);
           unsigned p0, p1, p2, q0, q1, q2;
-          dlq_split3(v0, v1, p0, p1, p2);
-          dlq_split3(v2, v3, q0, q1, q2);
+          split3_pair(v0, v1, p0, p1, p2);
+          split3_pair(v2, v3, q0, q1, q2);
           *reinterpret_cast<uint2*>(px + 2 * co) = make_uint2(p0, q0);
           *reinterpret_cast<uint2*>(px + 2 * HID + 2 * co) = make_uint2(p1, q1);
           *reinterpret_cast<uint2*>(px + 4 * HID + 2 * co) = make_uint2(p2, q2);

@@ -1,8 +1,9 @@
 // dlq_common.h -- what the DeepfakeDetector kernels share (dlq.hip: the layer kernel and the eval finish; dlq_train.hip: the training
-// step's other kernels): the tile constants, GELU, the three-term split and the MFMA wrapper.
+// step's other kernels): the tile constants, GELU and its derivative, the per-element dropout scale.  The three-term split (split3_pair) and the MFMA wrapper
+// (mma32) come from dfa_device.h; nothing of the 3x3 convolution header is used here.
 #pragma once
 #include "dfa_internal.h"
-#include "conv3x3_mfma.h"
+#include "dfa_device.h"
 
 namespace dfa {
 namespace dlq {
@@ -17,22 +18,13 @@ static_assert(HID * (NF + 1) * 4 <= LDS_BYTES, "layer-3 epilogue tile does not f
 }  // namespace dlq
 
 __device__ __forceinline__ float dlq_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-__device__ __forceinline__ f32x16_t dlq_mma(const uint4& a, const uint4& b, f32x16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-// two floats -> the packed bf16 pairs of their three terms
-__device__ __forceinline__ void dlq_split3(float u0, float u1, unsigned& w0, unsigned& w1, unsigned& w2) {
-  w0 = pack_bf16x2(u0, u1);
-  const float r0 = u0 - __uint_as_float(w0 << 16), r1 = u1 - __uint_as_float(w0 & 0xffff0000u);
-  w1 = pack_bf16x2(r0, r1);
-  w2 = pack_bf16x2(r0 - __uint_as_float(w1 << 16), r1 - __uint_as_float(w1 & 0xffff0000u));
-}
 
 // d/dv GELU(v), erf form
 __device__ __forceinline__ float dlq_dgelu(float v) {
   return 0.5f * (1.f + erff(v * 0.70710678118654752440f)) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
 }
 // the keep-scale factor drop_scale8 gives element idx (the same draw, one element of its group of 8)
+// (drop1 of train_cnn1d.hip is the same value picked by an indexed array read; this one is a select chain, the two compile differently)
 __device__ __forceinline__ float drop_scale1(const DropCfg& d, uint64_t idx) {
   if (d.thresh == 0) return 1.f;
   float f[8];

@@ -107,7 +107,7 @@ hipError_t launch_dlq_bn_finalize(const float* rec, int ntiles, int tpu, int T_m
 __device__ __forceinline__ void dlq_store_pixel8(uint4* px, int g, const float* v) {
   unsigned a[4], b[4], c[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) dlq_split3(v[2 * j], v[2 * j + 1], a[j], b[j], c[j]);
+  for (int j = 0; j < 4; ++j) split3_pair(v[2 * j], v[2 * j + 1], a[j], b[j], c[j]);
   px[g] = make_uint4(a[0], a[1], a[2], a[3]);
   px[32 + g] = make_uint4(b[0], b[1], b[2], b[3]);
   px[64 + g] = make_uint4(c[0], c[1], c[2], c[3]);
@@ -438,12 +438,12 @@ __global__ __launch_bounds__(256) void dlq_wgrad_kernel(const DlqWgradArgs a) {
         for (int t = 0; t < 3; ++t) bf[n][t] = *reinterpret_cast<const uint4*>(Bs + (t * HID + 64 * wave + 32 * n + col) * WG_ROW + 16 * ks + 8 * h);
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-          acc[m][n] = dlq_mma(af[m][1], bf[n][1], acc[m][n]);
-          acc[m][n] = dlq_mma(af[m][2], bf[n][0], acc[m][n]);
-          acc[m][n] = dlq_mma(af[m][0], bf[n][2], acc[m][n]);
-          acc[m][n] = dlq_mma(af[m][1], bf[n][0], acc[m][n]);
-          acc[m][n] = dlq_mma(af[m][0], bf[n][1], acc[m][n]);
-          acc[m][n] = dlq_mma(af[m][0], bf[n][0], acc[m][n]);
+          acc[m][n] = mma32(af[m][1], bf[n][1], acc[m][n]);
+          acc[m][n] = mma32(af[m][2], bf[n][0], acc[m][n]);
+          acc[m][n] = mma32(af[m][0], bf[n][2], acc[m][n]);
+          acc[m][n] = mma32(af[m][1], bf[n][0], acc[m][n]);
+          acc[m][n] = mma32(af[m][0], bf[n][1], acc[m][n]);
+          acc[m][n] = mma32(af[m][0], bf[n][0], acc[m][n]);
         }
       }
     }

@@ -16,13 +16,6 @@
 
 namespace dfa {
 
-template <typename T>
-__device__ __forceinline__ float ldg1(const T* p);
-template <>
-__device__ __forceinline__ float ldg1<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ldg1<bf16_t>(const bf16_t* p) { return bf16_to_float(*p); }
-
 constexpr int GM = 64, GN = 64, GK = 32;
 
 template <typename TA, typename TB>
@@ -47,13 +40,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const TA* __restrict__ A,
       int mm, k;
       if (a_kfast) { mm = e / GK; k = e - mm * GK; } else { k = e / GM; mm = e - k * GM; }
       const int m = m0 + mm, kg = kk + k;
-      As[mm][k] = (m < M && kg < k1) ? ldg1<TA>(A + (int64_t)m * sam + (int64_t)kg * sak) : 0.f;
+      As[mm][k] = (m < M && kg < k1) ? ld1(A + (int64_t)m * sam + (int64_t)kg * sak) : 0.f;
     }
     for (int e = tid; e < GK * GN; e += 256) {
       int k, nn;
       if (b_nfast) { k = e / GN; nn = e - k * GN; } else { nn = e / GK; k = e - nn * GK; }
       const int n = n0 + nn, kg = kk + k;
-      Bs[k][nn] = (n < N && kg < k1) ? ldg1<TB>(Bm + (int64_t)kg * sbk + (int64_t)n * sbn) : 0.f;
+      Bs[k][nn] = (n < N && kg < k1) ? ld1(Bm + (int64_t)kg * sbk + (int64_t)n * sbn) : 0.f;
     }
     __syncthreads();
 #pragma unroll

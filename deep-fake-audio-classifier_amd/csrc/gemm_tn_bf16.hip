@@ -11,8 +11,6 @@
 
 namespace dfa {
 
-typedef __attribute__((ext_vector_type(4))) short tn_s16x4_t;
-
 namespace tn {
 constexpr int TM = 64, TN = 128, TK = 64;                 // workgroup tile and k-rows per staged item
 constexpr int XS = TM * 2 + 64, ZS = TN * 2 + 64;         // LDS bytes per k-row: == 64 (mod 128), conflict-free tr reads
@@ -76,8 +74,8 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const bf16_t* __restr
     }
   };
   auto tr8 = [&](const char* p0, int stride4) {   // 8 consecutive k of the lane's column: two transposed reads
-    const tn_s16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4_t*)(p0));
-    const tn_s16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4_t*)(p0 + stride4));
+    const s16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0));
+    const s16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0 + stride4));
     const uint2 u0 = __builtin_bit_cast(uint2, a0), u1 = __builtin_bit_cast(uint2, a1);
     return make_uint4(u0.x, u0.y, u1.x, u1.y);
   };

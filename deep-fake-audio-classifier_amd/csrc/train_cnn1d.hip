@@ -47,6 +47,7 @@ __global__ __launch_bounds__(256) void cm_stats_ragged_kernel(const float* __res
   cm_stats_body<true>(z, partial, B, C, T, bchunk, lens, shifted);
 }
 
+// (drop_scale1 of dlq_common.h is the same value picked by a select chain; this one reads an indexed array, the two compile differently)
 __device__ __forceinline__ float drop1(const DropCfg& dc, uint64_t idx) {
   if (dc.thresh == 0) return 1.f;
   float f[8];
@@ -294,30 +295,13 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
 }
 
 // ---- the same weight gradient on the bf16 matrix cores at fp32 grade: every fp32 operand is carried as three bf16 terms
-// (hi + lo + lo2 = its 24-bit mantissa exactly) and every product is six v_mfma_f32_32x32x16_bf16 (all term pairs of order <= 2),
+// (split8n<3>; dfa_device.h has why three terms are the operand exactly) and every product is six v_mfma_f32_32x32x16_bf16 (all term pairs of order <= 2),
 // as the training convolutions of cnn1d_fused_x3.hip do.  The fp32 matrix pipe issues one 32x32x2 MFMA per ~80 cycles: 24 of them
 // per 16 frames and tap triple = 1920 cycles; the same products cost 18 x 32 = 576 matrix-pipe cycles here plus the splits.
 // Same decomposition and slab pipeline as the kernel above; the LDS tiles are laid out for aligned 16-byte fragment reads (row
 // pitch 68 floats: the 16 lanes of a ds_read_b128 group fall on distinct banks): a lane reads its row's 8 dz frames (two reads)
 // and 12 h frames (three reads: frames t-1 .. t+10) per 16-frame k-step, the three taps are register windows [k, k + 8) of
 // those 12 values.
-__device__ __forceinline__ void w1d_split3(const float (&v)[8], uint4 (&f)[3]) {
-  unsigned q[3][4];
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    float r0 = v[2 * p], r1 = v[2 * p + 1];
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      q[t][p] = pack_bf16x2(r0, r1);
-      if (t < 2) { r0 -= __uint_as_float(q[t][p] << 16); r1 -= __uint_as_float(q[t][p] & 0xffff0000u); }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 3; ++t) f[t] = make_uint4(q[t][0], q[t][1], q[t][2], q[t][3]);
-}
-__device__ __forceinline__ f32x16_t w1d_mma(const uint4& a, const uint4& b, f32x16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 
 template <bool AUG, bool RAGGED = false>
 __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __restrict__ dz, const float* __restrict__ h,
@@ -385,18 +369,18 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __rest
 #pragma unroll
       for (int j = 0; j < 8; ++j) ab += dv[j];
       uint4 a[3];
-      w1d_split3(dv, a);
+      split8n<3>(dv, a);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const float win[8] = {hv[k], hv[k + 1], hv[k + 2], hv[k + 3], hv[k + 4], hv[k + 5], hv[k + 6], hv[k + 7]};
         uint4 bq[3];
-        w1d_split3(win, bq);
-        acc[k] = w1d_mma(a[2], bq[0], acc[k]);          // smallest terms first
-        acc[k] = w1d_mma(a[0], bq[2], acc[k]);
-        acc[k] = w1d_mma(a[1], bq[1], acc[k]);
-        acc[k] = w1d_mma(a[1], bq[0], acc[k]);
-        acc[k] = w1d_mma(a[0], bq[1], acc[k]);
-        acc[k] = w1d_mma(a[0], bq[0], acc[k]);
+        split8n<3>(win, bq);
+        acc[k] = mma32(a[2], bq[0], acc[k]);          // smallest terms first
+        acc[k] = mma32(a[0], bq[2], acc[k]);
+        acc[k] = mma32(a[1], bq[1], acc[k]);
+        acc[k] = mma32(a[1], bq[0], acc[k]);
+        acc[k] = mma32(a[0], bq[1], acc[k]);
+        acc[k] = mma32(a[0], bq[0], acc[k]);
       }
     }
   }

@@ -18,34 +18,6 @@ namespace dfa {
 
 constexpr int C1T_R = 8, C1T_C = 64;
 
-template <typename TX>
-__device__ __forceinline__ float ldx(const TX* p);
-template <>
-__device__ __forceinline__ float ldx<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ldx<bf16_t>(const bf16_t* p) { return bf16_to_float(*p); }
-template <typename T>
-__device__ __forceinline__ float ldf(const T* p);
-template <>
-__device__ __forceinline__ float ldf<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ldf<bf16_t>(const bf16_t* p) { return bf16_to_float(*p); }
-
-template <typename T>
-__device__ __forceinline__ void ld8f(const T* p, float* v);
-template <>
-__device__ __forceinline__ void ld8f<float>(const float* p, float* v) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <>
-__device__ __forceinline__ void ld8f<bf16_t>(const bf16_t* p, float* v) {
-  const uint4 q = *reinterpret_cast<const uint4*>(p);
-  const unsigned u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(u[e] << 16); v[2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u); }
-}
-
 // Thread = (pixel lane, channel octet): lanes 4p..4p+3 own the four 8-channel groups of a pixel, so the upstream
 // gradient da1 is one 16/32-byte load per thread, the dropout mask costs two Philox calls per 8 elements, and the x taps
 // are LDS broadcasts.  Every thread keeps its 8 channels' weights, BN constants and accumulators in registers and walks
@@ -108,7 +80,7 @@ __global__ __launch_bounds__(256) void conv1_train_kernel(const TX* __restrict__
       if (t_fast) { cc = e / (C1T_R + 2); rr = e - cc * (C1T_R + 2); } else { rr = e / (C1T_C + 2); cc = e - rr * (C1T_C + 2); }
       const int t = t0 - 1 + rr, f = f0 - 1 + cc;
       xs[rr][cc] = (t >= 0 && t < Tt && f >= 0 && f < F)
-                       ? aug_apply(aug, ldx<TX>(xb + (int64_t)aug_src_t(aug, t) * st + (int64_t)f * sf), b, t, f) : 0.f;
+                       ? aug_apply(aug, ld1(xb + (int64_t)aug_src_t(aug, t) * st + (int64_t)f * sf), b, t, f) : 0.f;
     }
     __syncthreads();
 #pragma unroll 1
@@ -139,7 +111,7 @@ __global__ __launch_bounds__(256) void conv1_train_kernel(const TX* __restrict__
       if (!STATS && POOLW == 1 && to < Ho) {          // AvgPool2d((2,1)) + Dropout upstream (CNN2D)
         const size_t idx = (((size_t)b * Ho + to) * F + f) * 32 + q * 8;
         float d[8], ds[8];
-        ld8f<T>(da1 + idx, d);
+        ld8<T>(da1 + idx, d);
         drop_scale8(dc, idx, ds);
 #pragma unroll
         for (int c = 0; c < 8; ++c) g[c] = 0.5f * d[c] * ds[c];
@@ -147,7 +119,7 @@ __global__ __launch_bounds__(256) void conv1_train_kernel(const TX* __restrict__
       if (!STATS && POOLW == 2 && to < Ho && (f >> 1) < (F >> 1)) {   // AvgPool2d(2) upstream (CAE)
         const size_t idx = (((size_t)b * Ho + to) * (F >> 1) + (f >> 1)) * 32 + q * 8;
         float d[8];
-        ld8f<T>(da1 + idx, d);
+        ld8<T>(da1 + idx, d);
 #pragma unroll
         for (int c = 0; c < 8; ++c) g[c] = 0.25f * d[c];
       }

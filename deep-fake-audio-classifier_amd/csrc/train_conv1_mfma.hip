@@ -37,19 +37,6 @@ namespace dfa {
 
 namespace {
 constexpr int NT = 2, NR = 2 * NT + 2, NCR = 2 * NT;   // pooled rows per step; feature rows / convolution rows in LDS
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ u32x2_t lds_tr16(unsigned addr) {
-  return __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(size_t)addr));
-}
-__device__ __forceinline__ f32x16_t mma32(const uint4& w, const uint4& x, f32x16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4_t mma16(const uint4& a, const uint4& b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 }  // namespace
 
 // bytes per feature row in LDS: (FP + 2) bf16, padded to 3 (mod 32) dwords -- the 32 lanes of a ds_write_b16 group hold (row
@@ -115,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void conv1_mfma_kernel(C1xArgs a) {
       const float m0 = bf16_to_float(float_to_bf16(v[0] - h0)), m1 = bf16_to_float(float_to_bf16(v[1] - h1));
       hi[j] = pack_bf16x2(v[0], v[1]);
       lo[j] = pack_bf16x2(v[0] - h0, v[1] - h1);
-      l2[j] = pack_bf16x2((v[0] - h0) - m0, (v[1] - h1) - m1);      // three bf16 terms = the 24-bit mantissa: the fp32 weight, exactly
+      l2[j] = pack_bf16x2((v[0] - h0) - m0, (v[1] - h1) - m1);      // three bf16 terms: the fp32 weight, exactly (dfa_device.h, the term split)
     }
     whi = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     wlo = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -260,7 +247,7 @@ __global__ __launch_bounds__(256, 2) void conv1_mfma_kernel(C1xArgs a) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
           const unsigned ad = col0 + (p ? cbo : cbe) + tr_off;
-          const u32x2_t t0 = lds_tr16(ad), t1 = lds_tr16(ad + 160);          // + 4 pixels = 2 pair slots
+          const u32x2_t t0 = lds_read_tr16(ad), t1 = lds_read_tr16(ad + 160);          // + 4 pixels = 2 pair slots
           const uint4 op = make_uint4(t0[0], t0[1], t1[0], t1[1]);
           gxx = mma16(op, op, gxx);
         }
@@ -308,7 +295,7 @@ __global__ __launch_bounds__(256, 2) void conv1_mfma_kernel(C1xArgs a) {
               dv[u] = (y0 > 0.f ? (dpk[4 * j + u] & 0x0000ffffu) : 0u) | (y1 > 0.f ? (dpk[4 * j + u] & 0xffff0000u) : 0u);
             }
             // col^T for pixels 16j + 4h + {0..3} and 16j + 8 + 4h + {0..3}: the K order of the registers above
-            const u32x2_t t0 = lds_tr16(cb + (unsigned)(16 * j * 40)), t1 = lds_tr16(cb + (unsigned)((16 * j + 8) * 40));
+            const u32x2_t t0 = lds_read_tr16(cb + (unsigned)(16 * j * 40)), t1 = lds_read_tr16(cb + (unsigned)((16 * j + 8) * 40));
             gw = mma32(make_uint4(t0[0], t0[1], t1[0], t1[1]), make_uint4(dv[0], dv[1], dv[2], dv[3]), gw);
           }
         }

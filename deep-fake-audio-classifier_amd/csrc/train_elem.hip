@@ -8,35 +8,6 @@
 
 namespace dfa {
 
-template <typename T>
-__device__ __forceinline__ void ld8(const T* p, float* v);
-template <>
-__device__ __forceinline__ void ld8<float>(const float* p, float* v) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <>
-__device__ __forceinline__ void ld8<bf16_t>(const bf16_t* p, float* v) {
-  const uint4 q = *reinterpret_cast<const uint4*>(p);
-  const unsigned u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(u[e] << 16); v[2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u); }
-}
-template <typename T>
-__device__ __forceinline__ void st8(T* p, const float* v);
-template <>
-__device__ __forceinline__ void st8<float>(float* p, const float* v) {
-  reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-  reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
-template <>
-__device__ __forceinline__ void st8<bf16_t>(bf16_t* p, const float* v) {
-  bf16_t o[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = float_to_bf16(v[j]);
-  *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(o);
-}
-
 // ---- BatchNorm statistics: partial[k][C][2] (sum, sum of squares) -> mean, biased var, invstd; running stats update
 // (torch.nn.BatchNorm2d train mode: running = (1-m)*running + m*batch, with the UNBIASED batch variance).
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partial, int nparts, int C, double n,

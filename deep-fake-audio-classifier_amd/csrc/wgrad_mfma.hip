@@ -12,21 +12,6 @@
 
 namespace dfa {
 
-template <typename T>
-__device__ __forceinline__ void widen8(const T* p, float* v);
-template <>
-__device__ __forceinline__ void widen8<float>(const float* p, float* v) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <>
-__device__ __forceinline__ void widen8<bf16_t>(const bf16_t* p, float* v) {
-  const uint4 q = *reinterpret_cast<const uint4*>(p);
-  const unsigned u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(u[e] << 16); v[2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u); }
-}
-
 constexpr int WG_SEG = 64;  // pixels (columns of one row) per work item
 
 // tiles: (co slice cs, ci slice is, tap).  CS = COUT/32 must be 4 or 2.
@@ -69,7 +54,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_mfma_kernel(const T* __restri
     for (int e = tid; e < WG_SEG * (COUT / 8); e += 256) {
       const int p = e / (COUT / 8), cg = e % (COUT / 8);
       float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (f0 + p < W) widen8<T>(dz + ((((size_t)b * H + t) * W + f0 + p) * dzs_c + cg * 8), v);
+      if (f0 + p < W) ld8<T>(dz + ((((size_t)b * H + t) * W + f0 + p) * dzs_c + cg * 8), v);
       float4* d = reinterpret_cast<float4*>(dzs + p * COUT + cg * 8);
       d[0] = make_float4(v[0], v[1], v[2], v[3]);
       d[1] = make_float4(v[4], v[5], v[6], v[7]);
@@ -79,7 +64,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_mfma_kernel(const T* __restri
       const int sl = (e / (CIN / 8)) % (WG_SEG + 2), row = e / ((CIN / 8) * (WG_SEG + 2));
       const int tt = t + row - 1, ff = f0 - 1 + sl;
       float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (tt >= 0 && tt < H && ff >= 0 && ff < W) widen8<T>(a + ((((size_t)b * H + tt) * W + ff) * as_c + cg * 8), v);
+      if (tt >= 0 && tt < H && ff >= 0 && ff < W) ld8<T>(a + ((((size_t)b * H + tt) * W + ff) * as_c + cg * 8), v);
       float4* d = reinterpret_cast<float4*>(as + (row * (WG_SEG + 2) + sl) * CIN + cg * 8);
       d[0] = make_float4(v[0], v[1], v[2], v[3]);
       d[1] = make_float4(v[4], v[5], v[6], v[7]);
@@ -129,8 +114,6 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_mfma_kernel(const T* __restri
 // 4-pixel x 16-channel block transposed per 16-lane group), and because a pixel is a ROW of the tile the 3x3 tap shift
 // is a plain row offset -- no unaligned accesses.  Pixel rows are padded to a stride == 64 (mod 128) bytes so the 4
 // rows x 64 bytes a half-wave touches fall on disjoint bank windows (conflict-free).
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-
 constexpr int wg_stride(int c) { return (c * 2 % 128 == 64) ? c * 2 : c * 2 + 64; }
 
 // ---- bf16 kernel, second version (kept as the reference the tests compare v3 against).  The first one (removed) gave
@@ -294,15 +277,13 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_bf16_v2_kernel(const bf16_t* 
 // tools/check_lds_pipeline.py + the bit-identity test against the PIPE = false twin).
 //   KS = 1 (64 -> 128): waves = 2 ci slices x 4 dz slices on the same pixels.
 //   KS = 4 (32 -> 64):  waves = 2 dz slices x 4 k-step groups; each k-step group writes its own partial record.
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 template <int OFF, bool PIPE>
 __device__ __forceinline__ u32x2_t lds_tr(unsigned addr) {
   u32x2_t v;
   if constexpr (PIPE) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
   } else {
-    v = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                        (__attribute__((address_space(3))) s16x4_t*)(size_t)(addr + OFF)));
+    v = lds_read_tr16(addr + OFF);
   }
   return v;
 }
@@ -351,7 +332,6 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_v3_kernel(const bf16_t* 
   // queue and BLOCKED their waves for 1556 of an item's 4861 cycles (stamps build), with the memory system then idle
   // through compute, LDS store and barrier.  The compiler sees the asm outputs as ready at once; the s_waitcnt vmcnt(0)
   // in front of store_item carries them as "+v" operands (same contract as the LDS fragment reads).
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
   typedef int i32x4_t __attribute__((ext_vector_type(4)));
   constexpr int NP = NDZ + NA;
   u32x4_t sdz[NDZ], sa[NA];
