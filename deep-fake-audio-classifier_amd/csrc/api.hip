@@ -271,7 +271,7 @@ const Option kOptions[] = {
     {"cae_enc4_wide", &dfa_ctx::cae_enc4_wide, OPT_FLAG}, {"cae_dec_fused", &dfa_ctx::cae_dec_fused, OPT_FLAG},
     {"block3_m16", &dfa_ctx::block3_m16, OPT_FLAG}, {"fuse_conv1", &dfa_ctx::fuse_conv1, OPT_FLAG},
     {"fuse_blocks123", &dfa_ctx::fuse_blocks123, OPT_FLAG}, {"persist123", &dfa_ctx::persist123, OPT_FLAG},
-    {"lds_pipe", &dfa_ctx::lds_pipe, OPT_FLAG},
+    {"lds_pipe", &dfa_ctx::lds_pipe, OPT_FLAG}, {"carry_a1", &dfa_ctx::carry_a1, OPT_FLAG},
 };
 }  // namespace
 
@@ -350,6 +350,8 @@ int dfa_ctx_clock_read(dfa_ctx* ctx, double* ghz_median, double* ghz_min, double
   *workgroups = n;
   return DFA_OK;
 }
+
+int dfa_ctx_last_conv123_form(const dfa_ctx* ctx) { return ctx ? ctx->last_conv123_form : DFA_E_NULL_PTR; }
 
 int dfa_ctx_debug_read(dfa_ctx* ctx, long long* host_words, int n) {
   if (!ctx || !host_words) return DFA_E_NULL_PTR;
@@ -482,7 +484,19 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   const bool fused123 = fused12 && ctx->block3_m16 && ctx->fuse_blocks123 && ctx->time_split <= 0 && B * nstrips30 >= 512 &&
                         seg_iters_for((pl.H1 + 3) / 4, B * nstrips30, 512, 6, ctx->time_split) == 0 &&
                         seg_iters_for(niter3, B * nstrips30, 512, chunk3, ctx->time_split) == 0;
-  if (fused123 && ctx->persist123) {      // one workgroup per CU walks a contiguous range of the same units (conv123_persist.hip)
+  // ... and where every workgroup's range is a whole number of utterances (it starts at strip 0: the range formula of
+  // conv123_persist.hip with no remainder) and the side buffer fits the CU's LDS, the form that carries two a1 columns from
+  // strip to strip instead of computing them twice (conv123_carry.hip)
+  const int nunits123 = B * nstrips30, grid123 = std::min(nunits123, ctx->num_cus);
+  const bool carry123 = fused123 && ctx->persist123 && ctx->carry_a1 && grid123 > 0 && nunits123 % grid123 == 0 &&
+                        (nunits123 / grid123) % nstrips30 == 0 && conv123_carry_lds_bytes(T) <= (size_t)160 * 1024;
+  ctx->last_conv123_form = carry123 ? DFA_CONV123_CARRY : fused123 ? (ctx->persist123 ? DFA_CONV123_PERSIST : DFA_CONV123_PER_UNIT) : DFA_CONV123_NONE;
+  if (carry123) {
+    ScopedSlot ts(ctx, 2);
+    DFA_HIP_CHECK(ctx, launch_conv123_carry(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
+                                            m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
+                                            ctx->num_cus, s, ctx->lds_pipe));
+  } else if (fused123 && ctx->persist123) {      // one workgroup per CU walks a contiguous range of the same units (conv123_persist.hip)
     ScopedSlot ts(ctx, 2);
     DFA_HIP_CHECK(ctx, launch_conv123_persist(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
                                               m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,

@@ -1,11 +1,13 @@
-// conv123_body.h -- the producer and consumer units of the CNN2D blocks 1-3 kernels, one text for two kernels:
+// conv123_body.h -- the producer and consumer units of the CNN2D blocks 1-3 kernels, one text for three kernels:
 //   conv123_fused.hip    one workgroup per (utterance, 30-column strip) unit            (PERSIST = false)
 //   conv123_persist.hip  one workgroup per CU walking a contiguous range of units        (PERSIST = true)
+//   conv123_carry.hip    the persistent form, two a1 columns carried from strip to strip (PERSIST = true, CARRY = true)
 // The roles, the column bookkeeping and the per-step schedule are described at the top of conv123_fused.hip; the unit
-// boundary of the persistent form at the top of conv123_persist.hip.  With PERSIST = false every `if constexpr (PERSIST)`
-// below drops out and the functions are the per-unit kernel's bodies.
+// boundary of the persistent form at the top of conv123_persist.hip, the carried columns at the top of conv123_carry.hip.
+// With PERSIST = false every `if constexpr (PERSIST)` below drops out and the functions are the per-unit kernel's bodies;
+// with CARRY = false every `CARRY` term is a constant and the producers are those of the two older kernels.
 #ifndef DFA_CONV123_BODY_SCOPE
-#error "conv123_body.h holds kernel bodies: include it only from conv123_fused.hip and conv123_persist.hip"
+#error "conv123_body.h holds kernel bodies: include it only from conv123_fused.hip, conv123_persist.hip and conv123_carry.hip"
 #endif
 #ifndef DFA_CONV123_BODY_H
 #define DFA_CONV123_BODY_H
@@ -19,6 +21,11 @@
 
 #ifndef DFA_C123_PRIO
 #define DFA_C123_PRIO 0   // s_setprio 1 on one role: 0 = neither, 1 = consumers, 2 = producers
+#endif
+// CARRY, set by conv123_carry.hip alone.  A macro behind the constant: what only the carry form needs (lane constants, lambdas)
+// is not declared at all in the two older kernels, whose instruction streams an unused lambda already disturbs.
+#ifndef DFA_C123_CARRY
+#define DFA_C123_CARRY 0
 #endif
 
 namespace dfa {
@@ -57,6 +64,13 @@ constexpr int XCOLS = 36;                 // feature columns per ring block: f0-
 constexpr int NSLOT = 34;                 // live a1 slots: f0-2 .. f0+31
 constexpr int NX = XROWS * XCOLS;
 constexpr int NXLD = (NX + 255) / 256;
+// CARRY: the side buffer behind the producer region, one entry (ring slots 0 and 1 of an a1 row, as the ring holds them) per
+// a1 row of a unit = BR entries per ring block, ring blocks 0 .. niter3 + 1
+constexpr bool CARRY = DFA_C123_CARRY != 0;
+constexpr int CS = CARRY ? 2 : 0;          // slot of tile-0 lane 0
+constexpr int CY = 2, SIDE_OFF = P_OFF + P_BYTES, SIDE_ROWB = CY * PB, SIDE_BLKB = BR * SIDE_ROWB;
+constexpr int side_bytes(int niter3) { return (niter3 + 2) * SIDE_BLKB; }
+static_assert(SIDE_OFF % 16 == 0, "");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert(P_OFF + RING_BYTES < 65536 + P_OFF, "");
 }  // namespace c123
@@ -173,10 +187,13 @@ static void c123_print_stamps(const char* tag, int nwg) {
 // the second block-1 tile and the a2 hand-off.  Barrier count: niter3 (one per unit) + 4 (prologue) + 2 (idle steps).
 // PERSIST: (b, f0) is unit u, the first of the workgroup's range [u, u_end); every later unit of the range executes
 // niter3 + 3 barriers (one boundary barrier instead of the four of the prologue: conv123_persist.hip), in both roles.
+// CARRY (PERSIST only; every range starts at the first strip of an utterance): no second tile.  Tile 0 is slots 2 .. 33, and
+// slots 0, 1 of a row are the previous strip's slots 30, 31 of that row, kept in the side buffer (conv123_carry.hip).
 template <typename TX, bool PIPE, bool PERSIST>
 __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, unsigned lds0, int tid, int wave, int b, int f0,
                                               int niter3, int u, int u_end) {
   using namespace c123;
+  static_assert(PERSIST || !CARRY, "the carried columns come from the previous unit of the workgroup");
   const int lane = tid & 63;
   const int nsl = wave & 1, mg = wave >> 1;
   const int r = lane & 31, h = lane >> 5;
@@ -271,13 +288,22 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
 
   // ---- block 1: a1 row m = wave of ring block j; tile 0 = slots 0..31, tile 1 = slots 32, 33 (lanes r = 0, 1)
   const int c1_m = wave;
-  const unsigned c1_win0 = plds + XW_OFF + ((2 * c1_m + 2 * h) * SP + r) * 8;
+  const unsigned c1_win0 = plds + XW_OFF + ((2 * c1_m + 2 * h) * SP + CS + r) * 8;
   const unsigned c1_win1 = plds + XW_OFF + ((2 * c1_m + 2 * h) * SP + 32 + (r & 1)) * 8;
-  const int c1_f0 = f0 - 2 + r, c1_f1 = f0 + 30 + (r & 1);
+  const int c1_f0 = f0 - 2 + CS + r, c1_f1 = f0 + 30 + (r & 1);
   bool c1_fok0 = c1_f0 >= 0 && c1_f0 < W, c1_fok1 = c1_f1 < W;       // (per unit)
-  const int c1_dst0 = (c1_m * SP + r) * PB, c1_dst1 = (c1_m * SP + 32 + (r & 1)) * PB;
-  const int c1_sw0 = lds_swz<PB>(r), c1_sw1 = lds_swz<PB>(32 + (r & 1));
+  const int c1_dst0 = (c1_m * SP + CS + r) * PB, c1_dst1 = (c1_m * SP + 32 + (r & 1)) * PB;
+  const int c1_sw0 = lds_swz<PB>(CS + r), c1_sw1 = lds_swz<PB>(32 + (r & 1));
   const bool c1_live1 = r < 2;
+#if DFA_C123_CARRY
+  // CARRY: lanes r = SW - 2, SW - 1 hold slots 30, 31 = the next strip's slots 0, 1; each of the four keeps its two 16-byte
+  // chunks of the row's side entry and, one unit later, moves them into the ring (chunk swizzle of slots 0, 1: none)
+  static_assert(PB == 64 && CY <= 4 && (SW - CY) % 2 == 0, "lds_swz<64> of slots 0 .. 3 is 0");
+  const bool cy_lane = (r >> 1) == (SW - CY) / 2;
+  const unsigned cy_side = lds0 + SIDE_OFF + c1_m * SIDE_ROWB + (r & 1) * PB + (h << 4);
+  const int cy_dst = (c1_m * SP + (r & 1)) * PB + (h << 4);
+  bool cy_on = f0 != 0;                                               // (per unit) false: the carried columns are off the image
+#endif
   typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
   struct C1State { u32x2_t w0, w1, w2, w3; f32x16_t e, o; float v[16]; };
   auto c1_issue = [&](C1State& st, int j) {       // four window reads (asm: they join the counted LDS pipeline)
@@ -285,18 +311,23 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
     if constexpr (PIPE) {
       asm volatile("ds_read_b64 %0, %1" : "=v"(st.w0) : "v"(a0));
       asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(st.w1) : "v"(a0), "n"(XW_ROWB));
-      asm volatile("ds_read_b64 %0, %1" : "=v"(st.w2) : "v"(a1));
-      asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(st.w3) : "v"(a1), "n"(XW_ROWB));
+      if constexpr (!CARRY) {
+        asm volatile("ds_read_b64 %0, %1" : "=v"(st.w2) : "v"(a1));
+        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(st.w3) : "v"(a1), "n"(XW_ROWB));
+      }
     } else {
       st.w0 = *(const u32x2_t*)((const __attribute__((address_space(3))) char*)(size_t)a0);
       st.w1 = *(const u32x2_t*)((const __attribute__((address_space(3))) char*)(size_t)(a0 + XW_ROWB));
-      st.w2 = *(const u32x2_t*)((const __attribute__((address_space(3))) char*)(size_t)a1);
-      st.w3 = *(const u32x2_t*)((const __attribute__((address_space(3))) char*)(size_t)(a1 + XW_ROWB));
+      if constexpr (!CARRY) {
+        st.w2 = *(const u32x2_t*)((const __attribute__((address_space(3))) char*)(size_t)a1);
+        st.w3 = *(const u32x2_t*)((const __attribute__((address_space(3))) char*)(size_t)(a1 + XW_ROWB));
+      }
     }
   };
   auto c1_mfma = [&](C1State& st, auto t_c) {
     constexpr int TL = decltype(t_c)::value;
-    if constexpr (PIPE) asm volatile("" : "+v"(st.w0), "+v"(st.w1), "+v"(st.w2), "+v"(st.w3));
+    if constexpr (PIPE && CARRY) asm volatile("" : "+v"(st.w0), "+v"(st.w1));
+    else if constexpr (PIPE) asm volatile("" : "+v"(st.w0), "+v"(st.w1), "+v"(st.w2), "+v"(st.w3));
     const uint4 xv = TL == 0 ? make_uint4(st.w0[0], st.w0[1], st.w1[0], st.w1[1]) : make_uint4(st.w2[0], st.w2[1], st.w3[0], st.w3[1]);
     st.e = Mma<bf16_t>::run(c1w[0], xv, bias1);
     st.o = Mma<bf16_t>::run(c1w[2], xv, bias1);
@@ -329,6 +360,79 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
       }
     }
   };
+#if DFA_C123_CARRY
+  // ---- CARRY.  Per a1 row (ring block j, row c1_m), in this program order and all by wave c1_m:
+  //   cy_issue   read the row's side entry (the previous unit's slots 30, 31)
+  //   c1_store_cy  tile 0 into ring slots 2 .. 33, then slots 30, 31 (lanes cy_lane) over the side entry
+  //   cy_store   (the reads landed) ring slots 0, 1 = the entry, or zeros where the unit is the first strip of its utterance
+  // `side` / `dst` / `live` are cy_side / cy_dst / cy_lane, or the same values from a fresh lane number between two units.
+  auto cy_issue = [&](u32x4_t& c0, u32x4_t& c2, int j, unsigned side) {
+    const unsigned sa = side + j * SIDE_BLKB;
+    if constexpr (PIPE) {
+      asm volatile("ds_read_b128 %0, %1" : "=v"(c0) : "v"(sa));
+      asm volatile("ds_read_b128 %0, %1 offset:32" : "=v"(c2) : "v"(sa));
+    } else {
+      c0 = *(const u32x4_t*)((const __attribute__((address_space(3))) char*)(size_t)sa);
+      c2 = *(const u32x4_t*)((const __attribute__((address_space(3))) char*)(size_t)(sa + 32));
+    }
+  };
+  auto c1_store_cy = [&](C1State& st, int ringblk, int j, int dst0, int sw, int hh, unsigned side, bool live) {
+    u32x4_t pk[2];
+#pragma unroll
+    for (int g = 0; g < 4; g += 2) {
+      const unsigned a0 = pack_bf16x2(st.v[4 * g], st.v[4 * g + 1]), a1 = pack_bf16x2(st.v[4 * g + 2], st.v[4 * g + 3]);
+      const unsigned b0 = pack_bf16x2(st.v[4 * g + 4], st.v[4 * g + 5]), b1 = pack_bf16x2(st.v[4 * g + 6], st.v[4 * g + 7]);
+      const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+      const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+      const unsigned addr = plds + ringblk * (BR * ROWB) + dst0 + (((g + hh) ^ sw) << 4);
+      pk[g / 2] = u32x4_t{s0[0], s1[0], s0[1], s1[1]};
+      if constexpr (PIPE) asm volatile("ds_write_b128 %0, %1" : : "v"(addr), "v"(pk[g / 2]) : "memory");
+      else *(u32x4_t*)((__attribute__((address_space(3))) char*)(size_t)addr) = pk[g / 2];
+    }
+    const unsigned sa = side + j * SIDE_BLKB;
+    if (live) {                    // lanes 28, 29, 60, 61: chunks hh and 2 + hh of slot r - 28
+      if constexpr (PIPE) {
+        asm volatile("ds_write_b128 %0, %1" : : "v"(sa), "v"(pk[0]) : "memory");
+        asm volatile("ds_write_b128 %0, %1 offset:32" : : "v"(sa), "v"(pk[1]) : "memory");
+      } else {
+        *(u32x4_t*)((__attribute__((address_space(3))) char*)(size_t)sa) = pk[0];
+        *(u32x4_t*)((__attribute__((address_space(3))) char*)(size_t)(sa + 32)) = pk[1];
+      }
+    }
+  };
+  auto cy_store = [&](u32x4_t& c0, u32x4_t& c2, int ringblk, int dst, bool live) {
+    if constexpr (PIPE) asm volatile("" : "+v"(c0), "+v"(c2));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { c0[e] = cy_on ? c0[e] : 0u; c2[e] = cy_on ? c2[e] : 0u; }   // a select: stale LDS never multiplies
+    const unsigned addr = plds + ringblk * (BR * ROWB) + dst;
+    if (live) {
+      if constexpr (PIPE) {
+        asm volatile("ds_write_b128 %0, %1" : : "v"(addr), "v"(c0) : "memory");
+        asm volatile("ds_write_b128 %0, %1 offset:32" : : "v"(addr), "v"(c2) : "memory");
+      } else {
+        *(u32x4_t*)((__attribute__((address_space(3))) char*)(size_t)addr) = c0;
+        *(u32x4_t*)((__attribute__((address_space(3))) char*)(size_t)(addr + 32)) = c2;
+      }
+    }
+  };
+  // one a1 row outside the main loop (prologue: FRESH = false; between two units: lane constants from a fresh lane number)
+  auto produce_cy = [&](int j, int ringblk, auto fresh_c) {
+    constexpr bool FRESH = decltype(fresh_c)::value;
+    C1State st;
+    u32x4_t c0, c2;
+    c1_issue(st, j);
+    if constexpr (PIPE) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(st.w0), "+v"(st.w1));
+    c1_mfma(st, std::integral_constant<int, 0>{});
+    c1_relu(st, j, std::integral_constant<int, 0>{});
+    const int fl = FRESH ? c123_fresh_lane() : lane, fr = fl & 31, fh = fl >> 5;
+    const unsigned side = lds0 + SIDE_OFF + c1_m * SIDE_ROWB + (fr & 1) * PB + (fh << 4);
+    const bool live = (fr >> 1) == (SW - CY) / 2;
+    cy_issue(c0, c2, j, side);
+    c1_store_cy(st, ringblk, j, (c1_m * SP + CS + fr) * PB, lds_swz<PB>(CS + fr), fh, side, live);
+    if constexpr (PIPE) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c0), "+v"(c2) : : "memory");
+    cy_store(c0, c2, ringblk, (c1_m * SP + (fr & 1)) * PB + (fh << 4), live);
+  };
+#endif
   // c1_store between two units of the persistent kernel: the same stores, their lane constants from a fresh lane number
   // (c123_fresh_lane; as a mode of c1_store itself the per-unit kernel compiled to other registers)
   auto c1_store_fresh = [&](C1State& st, int ringblk, auto t_c) {
@@ -351,6 +455,10 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
     }
   };
   auto produce_now = [&](int j, int ringblk) {
+#if DFA_C123_CARRY
+    produce_cy(j, ringblk, std::false_type{});
+    return;
+#endif
     C1State st;
     c1_issue(st, j);
     if constexpr (PIPE) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(st.w0), "+v"(st.w1), "+v"(st.w2), "+v"(st.w3));
@@ -362,6 +470,10 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
     c1_store(st, ringblk, std::integral_constant<int, 1>{});
   };
   auto produce_fresh = [&](int j, int ringblk) {     // produce_now between two units of the persistent kernel
+#if DFA_C123_CARRY
+    produce_cy(j, ringblk, std::true_type{});
+    return;
+#endif
     C1State st;
     c1_issue(st, j);
     if constexpr (PIPE) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(st.w0), "+v"(st.w1), "+v"(st.w2), "+v"(st.w3));
@@ -399,9 +511,16 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
     constexpr int S_BAR = 4;
     // consume steps of the block-1 pieces (tile 0, then tile 1 in the same registers) and of the window stores
     constexpr int C_MFMA = 5, C_XLOAD = 7, C_RELU = 10, C_MFMA1 = 11, C_STORE = 13, C_RELU1 = 17, C_XSTORE = 19, C_STORE1 = 21;
-    constexpr int NWR = 4;   // window reads issued behind fragment read S_BAR
+    constexpr int NWR = CARRY ? 2 : 4;   // window reads issued behind fragment read S_BAR
+    // CARRY: behind C_STORE two side reads, two ring stores, two side stores; the reads have landed four consume steps on
+    // (fragment read C_STORE + PF, issued behind them, is retired there), where C_CARRY puts them into ring slots 0, 1
+    constexpr int N_STORE = CARRY ? 6 : 2, C_CARRY = C_STORE + PF;
+    static_assert(C_CARRY == C_RELU1 && C_CARRY + PF - 1 < C_STORE1 + PF - 1 && C_CARRY < NR, "");
     u32x4_t xbuf[PF];
     C1State c1;
+#if DFA_C123_CARRY
+    u32x4_t cy0, cy2;
+#endif
     auto step = [&](auto s_c) {
       constexpr int s = decltype(s_c)::value;
       if constexpr (s < NR) {
@@ -420,8 +539,9 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
         // outstanding LDS operations younger than read c (in order): younger reads, ring stores behind C_STORE / C_STORE1,
         // window stores behind C_XSTORE, window reads behind S_BAR
         constexpr int young_r = (NR - 1 - c) < (PF - 1) ? (NR - 1 - c) : (PF - 1);
-        constexpr int young = young_r + ((c > C_STORE && c <= C_STORE + PF - 1 && c < NR) ? 2 : 0) +
-                              ((c > C_STORE1 && c <= C_STORE1 + PF - 1 && c < NR) ? 2 : 0) +
+        constexpr int C_ST2 = CARRY ? C_CARRY : C_STORE1;   // the second pair of ring stores
+        constexpr int young = young_r + ((c > C_STORE && c <= C_STORE + PF - 1 && c < NR) ? N_STORE : 0) +
+                              ((c > C_ST2 && c <= C_ST2 + PF - 1 && c < NR) ? 2 : 0) +
                               ((c > C_XSTORE && c <= C_XSTORE + PF - 1 && c < NR) ? 3 * NXLD : 0) +
                               ((c > S_BAR - PF && c <= S_BAR) ? NWR : 0);
         if constexpr (PIPE) lds_wait<young>(xbuf[c % PF]);
@@ -431,11 +551,18 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
         if constexpr (c == C_MFMA) c1_mfma(c1, std::integral_constant<int, 0>{});
         if constexpr (c == C_XLOAD) x_load(it + 3);
         if constexpr (c == C_RELU) c1_relu(c1, it + 2, std::integral_constant<int, 0>{});
-        if constexpr (c == C_MFMA1) c1_mfma(c1, std::integral_constant<int, 1>{});
-        if constexpr (c == C_STORE) c1_store(c1, (PH + 2) % 3, std::integral_constant<int, 0>{});
-        if constexpr (c == C_RELU1) c1_relu(c1, it + 2, std::integral_constant<int, 1>{});
+        if constexpr (c == C_MFMA1 && !CARRY) c1_mfma(c1, std::integral_constant<int, 1>{});
+        if constexpr (c == C_STORE && !CARRY) c1_store(c1, (PH + 2) % 3, std::integral_constant<int, 0>{});
+#if DFA_C123_CARRY
+        if constexpr (c == C_STORE) {
+          cy_issue(cy0, cy2, it + 2, cy_side);
+          c1_store_cy(c1, (PH + 2) % 3, it + 2, c1_dst0, c1_sw0, h, cy_side, cy_lane);
+        }
+        if constexpr (c == C_CARRY) cy_store(cy0, cy2, (PH + 2) % 3, cy_dst, cy_lane);
+#endif
+        if constexpr (c == C_RELU1 && !CARRY) c1_relu(c1, it + 2, std::integral_constant<int, 1>{});
         if constexpr (c == C_XSTORE) x_store((it + 3) & 1);
-        if constexpr (c == C_STORE1) c1_store(c1, (PH + 2) % 3, std::integral_constant<int, 1>{});
+        if constexpr (c == C_STORE1 && !CARRY) c1_store(c1, (PH + 2) % 3, std::integral_constant<int, 1>{});
         if constexpr (c == S_RELU0) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) acc0[e] = relu1(acc0[e], rlim);
@@ -499,9 +626,12 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
       xfok[k] = (e < NX) && f >= 0 && f < W;
       xoff[k] = (long long)(row - 3) * a.sxt + (long long)(xfok[k] ? f : 0) * a.sxf;
     }
-    const int vf = vf0 - 2 + r;
+    const int vf = vf0 - 2 + CS + r;
     c1_fok0 = vf >= 0 && vf < W;
     c1_fok1 = vf0 + 30 + (r & 1) < W;
+#if DFA_C123_CARRY
+    cy_on = vf0 != 0;
+#endif
     const int vcol = vf0 - 1 + r;
     col_ok = vcol >= 0 && vcol < W;
   };

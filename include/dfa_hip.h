@@ -79,6 +79,10 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *   "persist123"    1 (default) = where fuse_blocks123 applies, the fused kernel runs as one persistent workgroup per CU that
  *                   walks a contiguous range of (utterance, strip) units and stages the next unit under the tail of the current
  *                   one (static ranges, no communication between workgroups); 0 = one workgroup per unit.  Bit-identical results
+ *   "carry_a1"      1 (default) = where persist123 applies, every workgroup's range is a whole number of utterances (B * strips
+ *                   a multiple of the CU count, the quotient a multiple of the strips per utterance) and T is short enough for
+ *                   the side buffer to fit LDS, a strip takes its two left a1 halo columns from the strip before it instead of
+ *                   computing them again; 0 = the persist123 kernel everywhere.  Bit-identical results
  *   "time_split"    -1 (default) = CNN2D eval forward splits the time axis over workgroups when the batch alone cannot fill
  *                   the chip (B * strips below the resident-workgroup count, e.g. the reference's predict batch of 32), 0 =
  *                   never, n > 0 = force n segments (at most 4).  Logits and embeddings are bit-identical for every setting and
@@ -461,6 +465,13 @@ int dfa_ctx_timing_read(dfa_ctx* ctx, int slot, float* total_ms, int* count);
  * (MI355X_MICROARCH.md, DVFS give-back), so roofline fractions are reported both against the nominal peak and at this clock.
  * ghz_min / ghz_max may be NULL. */
 int dfa_ctx_clock_read(dfa_ctx* ctx, double* ghz_median, double* ghz_min, double* ghz_max, int* workgroups);
+/* Which kernel ran blocks 1-3 of the LAST dfa_cnn2d_forward of this context (read-only; ctx NULL: DFA_E_NULL_PTR):
+ * DFA_CONV123_NONE = separate kernels, _PER_UNIT = conv123_fused, _PERSIST = conv123_persist, _CARRY = conv123_carry. */
+#define DFA_CONV123_NONE 0
+#define DFA_CONV123_PER_UNIT 1
+#define DFA_CONV123_PERSIST 2
+#define DFA_CONV123_CARRY 3
+int dfa_ctx_last_conv123_form(const dfa_ctx* ctx);
 /* Raw copy of the first n (<= 2048) 64-bit words of the probe buffer the "clock_probe" kernels stamp (diagnostics: the fused CNN1D
  * kernel writes, per workgroup b < 128, words 8b..8b+3 = s_memtime at start / after layer 1 / after layer 2 / at the end and
  * 8b+5, 8b+6 = s_memrealtime at start / end).  Synchronises on the context's stream. */
