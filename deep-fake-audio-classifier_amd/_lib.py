@@ -116,6 +116,7 @@ SYMBOLS = [
     ("dfa_ctx_timing_reset", C.c_int, [C.c_void_p]),
     ("dfa_ctx_timing_read", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     ("dfa_ctx_last_conv123_form", C.c_int, [C.c_void_p]),
+    ("dfa_ctx_last_conv123_phase", C.c_int, [C.c_void_p]),
     ("dfa_ctx_debug_read", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]),
     ("dfa_ctx_clock_read", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int)]),
@@ -237,6 +238,10 @@ class Context:
         """Blocks 1-3 of the last CNN2D eval forward: 0 = separate kernels, 1 = one workgroup per unit, 2 = persistent,
         3 = persistent with carried a1 columns (dfa_ctx_last_conv123_form)."""
         return int(self.lib.dfa_ctx_last_conv123_form(self.handle))
+
+    def last_conv123_phase(self) -> int:
+        """1 if the last CNN2D eval forward ran the de-phased build of the carry form (option "phase123"), else 0."""
+        return int(self.lib.dfa_ctx_last_conv123_phase(self.handle))
 
     def clock_read(self):
         """(median, min, max GHz, workgroups) of the last bf16 CNN2D block-3 launch run with set_option("clock_probe", 1)."""

@@ -272,6 +272,7 @@ const Option kOptions[] = {
     {"block3_m16", &dfa_ctx::block3_m16, OPT_FLAG}, {"fuse_conv1", &dfa_ctx::fuse_conv1, OPT_FLAG},
     {"fuse_blocks123", &dfa_ctx::fuse_blocks123, OPT_FLAG}, {"persist123", &dfa_ctx::persist123, OPT_FLAG},
     {"lds_pipe", &dfa_ctx::lds_pipe, OPT_FLAG}, {"carry_a1", &dfa_ctx::carry_a1, OPT_FLAG},
+    {"phase123", &dfa_ctx::phase123, OPT_FLAG},
 };
 }  // namespace
 
@@ -352,6 +353,7 @@ int dfa_ctx_clock_read(dfa_ctx* ctx, double* ghz_median, double* ghz_min, double
 }
 
 int dfa_ctx_last_conv123_form(const dfa_ctx* ctx) { return ctx ? ctx->last_conv123_form : DFA_E_NULL_PTR; }
+int dfa_ctx_last_conv123_phase(const dfa_ctx* ctx) { return ctx ? ctx->last_conv123_phase : DFA_E_NULL_PTR; }
 
 int dfa_ctx_debug_read(dfa_ctx* ctx, long long* host_words, int n) {
   if (!ctx || !host_words) return DFA_E_NULL_PTR;
@@ -491,7 +493,15 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   const bool carry123 = fused123 && ctx->persist123 && ctx->carry_a1 && grid123 > 0 && nunits123 % grid123 == 0 &&
                         (nunits123 / grid123) % nstrips30 == 0 && conv123_carry_lds_bytes(T) <= (size_t)160 * 1024;
   ctx->last_conv123_form = carry123 ? DFA_CONV123_CARRY : fused123 ? (ctx->persist123 ? DFA_CONV123_PERSIST : DFA_CONV123_PER_UNIT) : DFA_CONV123_NONE;
-  if (carry123) {
+  // the carry form with the consumers' step barrier behind fragment read 35 and the consumers at s_setprio 1
+  // (conv123_phase.hip): the same form, the same conditions, bit-identical results
+  ctx->last_conv123_phase = carry123 && ctx->phase123;
+  if (carry123 && ctx->phase123) {
+    ScopedSlot ts(ctx, 2);
+    DFA_HIP_CHECK(ctx, launch_conv123_phase(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
+                                            m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
+                                            ctx->num_cus, s, ctx->lds_pipe));
+  } else if (carry123) {
     ScopedSlot ts(ctx, 2);
     DFA_HIP_CHECK(ctx, launch_conv123_carry(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
                                             m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,

@@ -1,13 +1,14 @@
-// conv123_body.h -- the producer and consumer units of the CNN2D blocks 1-3 kernels, one text for three kernels:
+// conv123_body.h -- the producer and consumer units of the CNN2D blocks 1-3 kernels, one text for four kernels:
 //   conv123_fused.hip    one workgroup per (utterance, 30-column strip) unit            (PERSIST = false)
 //   conv123_persist.hip  one workgroup per CU walking a contiguous range of units        (PERSIST = true)
 //   conv123_carry.hip    the persistent form, two a1 columns carried from strip to strip (PERSIST = true, CARRY = true)
+//   conv123_phase.hip    the carry form, consumers' step barrier behind read 35, consumers at s_setprio 1 (DFA_C123_CBAR / _PRIO)
 // The roles, the column bookkeeping and the per-step schedule are described at the top of conv123_fused.hip; the unit
 // boundary of the persistent form at the top of conv123_persist.hip, the carried columns at the top of conv123_carry.hip.
 // With PERSIST = false every `if constexpr (PERSIST)` below drops out and the functions are the per-unit kernel's bodies;
 // with CARRY = false every `CARRY` term is a constant and the producers are those of the two older kernels.
 #ifndef DFA_CONV123_BODY_SCOPE
-#error "conv123_body.h holds kernel bodies: include it only from conv123_fused.hip, conv123_persist.hip and conv123_carry.hip"
+#error "conv123_body.h holds kernel bodies: include it only from conv123_fused.hip, conv123_persist.hip, conv123_carry.hip and conv123_phase.hip"
 #endif
 #ifndef DFA_CONV123_BODY_H
 #define DFA_CONV123_BODY_H
@@ -22,7 +23,15 @@
 #ifndef DFA_C123_PRIO
 #define DFA_C123_PRIO 0   // s_setprio 1 on one role: 0 = neither, 1 = consumers, 2 = producers
 #endif
-// CARRY, set by conv123_carry.hip alone.  A macro behind the constant: what only the carry form needs (lane constants, lambdas)
+// The fragment-read index behind which the CONSUMERS' step barrier stands (the producers' stays behind their read 4).  Consumer
+// iteration `it` holds barrier #(it + 2) of its unit.  Its reads 0 .. 35 are ring block it and row 0 of block it + 1 = a2 rows
+// 2 it - 1 .. 2 it + 1, which the producers wrote before #(it + 1): legal on either side of #(it + 2).  Reads 36 .. 47 are row
+// 1 of block it + 1 = a2 row 2 it + 2, written in [#(it + 1), #(it + 2)): they must stay behind the barrier.  Hence <= 35
+// (tests/test_phase123_cpu.py walks every value).
+#ifndef DFA_C123_CBAR
+#define DFA_C123_CBAR 4
+#endif
+// CARRY, set by conv123_carry.hip and conv123_phase.hip alone.  A macro behind the constant: what only the carry form needs (lane constants, lambdas)
 // is not declared at all in the two older kernels, whose instruction streams an unused lambda already disturbs.
 #ifndef DFA_C123_CARRY
 #define DFA_C123_CARRY 0
@@ -756,7 +765,8 @@ __device__ __forceinline__ void c123_consumer(const Conv123Args& a, char* smem, 
     f32x4_t acc0[2][2], acc1[2][2];
     constexpr int NR = 4 * 3 * 2 * 2;
     constexpr int C_RELU0 = 36 + 3;
-    constexpr int S_BAR = 4;
+    constexpr int S_BAR = DFA_C123_CBAR;
+    static_assert(0 <= S_BAR && S_BAR <= 35, "reads 36 .. 47 are the a2 row the producers write in the interval this barrier ends");
     u32x4_t xbuf[PF3];
     auto step = [&](auto s_c) {
       constexpr int s = decltype(s_c)::value;

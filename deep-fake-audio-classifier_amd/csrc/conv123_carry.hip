@@ -1,5 +1,6 @@
 // conv123_carry.hip -- conv123_persist.hip with the two a1 halo columns on the left of a strip carried over from the strip
-// before it instead of computed again (context option "carry_a1", the default where its conditions hold: api.hip).
+// before it instead of computed again (context option "carry_a1", the default where its conditions hold: api.hip; with
+// option "phase123" at its default the dispatcher runs this form as built by conv123_phase.hip, with 0 this file's kernel).
 //
 // Why.  A strip owns 30 output columns, f0 .. f0 + 29.  Block 2 needs the a1 columns f0 - 2 .. f0 + 31 = ring slots 0 .. 33,
 // and block 1 makes them with 32-column MFMA tiles: in the two older kernels tile 0 = slots 0 .. 31 and tile 1 = slots 32, 33,

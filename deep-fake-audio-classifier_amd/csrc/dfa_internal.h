@@ -145,6 +145,8 @@ struct dfa_ctx {
   int fuse_blocks123 = 1;      // bf16 mode, fuse_conv1 && block3_m16, no time split: blocks 1-3 + time mean in one kernel (conv123_fused.hip)
   int persist123 = 1;          // where blocks 1-3 are fused: 1 = one workgroup per CU over a contiguous range of units (conv123_persist.hip), 0 = one workgroup per unit
   int carry_a1 = 1;            // where persist123 applies and every workgroup's range is a whole number of utterances: the two left a1 halo columns of a strip come from the strip before it (conv123_carry.hip), 0 = conv123_persist.hip
+  int phase123 = 1;            // where the carry form runs: its de-phased build (consumers' step barrier behind fragment read 35, consumers at s_setprio 1: conv123_phase.hip), 0 = conv123_carry.hip
+  int last_conv123_phase = 0;  // 1 = the last dfa_cnn2d_forward ran conv123_phase.hip (dfa_ctx_last_conv123_phase)
   int last_conv123_form = 0;   // blocks 1-3 of the last dfa_cnn2d_forward: DFA_CONV123_* (dfa_ctx_last_conv123_form)
   int num_cus = 0;             // hipDeviceAttributeMultiprocessorCount of `device`, asked once in dfa_ctx_create (grid of the persistent kernel)
   int lds_pipe = 1;            // 1 = asm-pipelined LDS fragment reads where instantiated, 0 = compiler-scheduled twins (test hook)
@@ -545,6 +547,11 @@ hipError_t launch_conv123_carry(const void* x, int x_dtype, int64_t sb, int64_t 
                                 const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
                                 int num_cus, hipStream_t s, int pipe = 1);
 size_t conv123_carry_lds_bytes(int T);
+// the carry form with the roles' step edges moved apart (same arguments, conditions and LDS bytes): conv123_phase.hip
+hipError_t launch_conv123_phase(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
+                                const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
+                                const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
+                                int num_cus, hipStream_t s, int pipe = 1);
 hipError_t launch_cnn2d_block2(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);
 hipError_t launch_cnn2d_block3(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);
 struct ConvTArgs;

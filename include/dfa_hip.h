@@ -83,6 +83,9 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *                   a multiple of the CU count, the quotient a multiple of the strips per utterance) and T is short enough for
  *                   the side buffer to fit LDS, a strip takes its two left a1 halo columns from the strip before it instead of
  *                   computing them again; 0 = the persist123 kernel everywhere.  Bit-identical results
+ *   "phase123"      1 (default) = where carry_a1 applies, the build of that kernel whose consumer waves hold their step barrier
+ *                   late in their operand reads and run at raised issue priority, so that the MFMA-free parts of the two
+ *                   roles' steps do not coincide; 0 = the carry_a1 kernel as it was.  Bit-identical results
  *   "time_split"    -1 (default) = CNN2D eval forward splits the time axis over workgroups when the batch alone cannot fill
  *                   the chip (B * strips below the resident-workgroup count, e.g. the reference's predict batch of 32), 0 =
  *                   never, n > 0 = force n segments (at most 4).  Logits and embeddings are bit-identical for every setting and
@@ -472,6 +475,9 @@ int dfa_ctx_clock_read(dfa_ctx* ctx, double* ghz_median, double* ghz_min, double
 #define DFA_CONV123_PERSIST 2
 #define DFA_CONV123_CARRY 3
 int dfa_ctx_last_conv123_form(const dfa_ctx* ctx);
+/* 1 if blocks 1-3 of the LAST dfa_cnn2d_forward ran the "phase123" build of the carry form (the form above is then
+ * DFA_CONV123_CARRY: it is that form), else 0; ctx NULL: DFA_E_NULL_PTR. */
+int dfa_ctx_last_conv123_phase(const dfa_ctx* ctx);
 /* Raw copy of the first n (<= 2048) 64-bit words of the probe buffer the "clock_probe" kernels stamp (diagnostics: the fused CNN1D
  * kernel writes, per workgroup b < 128, words 8b..8b+3 = s_memtime at start / after layer 1 / after layer 2 / at the end and
  * 8b+5, 8b+6 = s_memrealtime at start / end).  Synchronises on the context's stream. */
