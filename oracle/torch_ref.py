@@ -248,7 +248,8 @@ def state_after_adamw_step(sd, grads, stats, lr=1e-3, weight_decay=0.01, momentu
     return out
 
 
-def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue"):
+def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue", dtype=torch.float64, return_stats=False,
+                            return_margins=False):
     """One ConvAutoencoder training forward/backward (src/train_cae.py:58-82 over src/model_cae.py:32-125 in train mode, loss =
     MSELoss(recon, x)) restated with the ROUNDING POINTS of the product's bf16 training mode (csrc/cae_train_api.hip):
       encoder block 1   fp32 convolution from the bf16 features, z1 never stored (statistics of the unrounded z1); its pooled
@@ -263,13 +264,19 @@ def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue"):
     (The product's ConvTranspose2d DATA gradient multiplies by the unrounded fp32 weights; here the rounded ones are used in both
     directions -- a 2^-9 relative difference per weight, below the bf16 storage of the result.)  Everything else is float64
     autograd.  emulate=None removes every rounding: the result must equal the reference's autograd goldens.
-    Returns (loss, {parameter name: gradient})."""
-    f64 = torch.float64
+    Returns (loss, {parameter name: gradient}).  With emulate=None only: return_stats=True or return_margins=True append the
+    train-mode reconstruction [B,T,F] and the latent map; return_stats=True then appends {BatchNorm prefix: (batch mean, biased
+    batch variance, element count)} as `state_after_adamw_step` takes it, return_margins=True {BatchNorm prefix: smallest
+    |BatchNorm output| of that layer}; dtype is the arithmetic the step runs in (torch.float32: the same restatement in fp32)."""
+    f64 = dtype
     on = emulate == "bf16"
     if emulate not in (None, "bf16"):
         raise ValueError(emulate)
     if stats not in ("epilogue", "stored"):
         raise ValueError(stats)
+    if on and (return_stats or return_margins or dtype != torch.float64):
+        raise ValueError("dtype, return_stats and return_margins belong to the unrounded restatement (emulate=None)")
+    batch_stats, margins = {}, {}
     P = {k: _t(sd, k).to(f64).clone().requires_grad_(True) for k in sd
          if k.endswith(("weight", "bias")) and not k.endswith(("running_mean", "running_var"))}
     store = _StoreBF16.apply if on else (lambda t: t)
@@ -285,7 +292,10 @@ def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue"):
         zs = z if (zu is None or stats == "stored") else z + (zu - z).detach()
         mean = zs.mean(dim=(0, 2, 3), keepdim=True)
         var = zs.var(dim=(0, 2, 3), unbiased=False, keepdim=True)
-        return (z - mean) / torch.sqrt(var + 1e-5) * P[pfx + ".weight"][None, :, None, None] + P[pfx + ".bias"][None, :, None, None]
+        batch_stats[pfx] = (mean.detach().flatten().float(), var.detach().flatten().float(), zs.numel() // zs.shape[1])
+        out = (z - mean) / torch.sqrt(var + 1e-5) * P[pfx + ".weight"][None, :, None, None] + P[pfx + ".bias"][None, :, None, None]
+        margins[pfx] = float(out.detach().abs().min())
+        return out
 
     def stored(z):              # pre-BN output kept in bf16 (forward value rounded), dz in bf16
         return rnd(rgrad(z))
@@ -296,7 +306,7 @@ def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue"):
     for c, b in ((4, 5), (8, 9), (12, 13)):
         zu = F.conv2d(h, wq(f"encoder.{c}.weight"), P[f"encoder.{c}.bias"], padding=1)
         h = store(F.avg_pool2d(F.relu(bn(stored(zu), f"encoder.{b}", zu if c != 12 else None)), 2))
-    d = h
+    d = latent = h
     for c, b, opad in ((0, 1, (0, 0)), (3, 4, (0, 1)), (6, 7, (0, 0))):
         zu = F.conv_transpose2d(d, wq(f"decoder.{c}.weight"), P[f"decoder.{c}.bias"], stride=2, output_padding=opad)
         d = store(F.relu(bn(stored(zu), f"decoder.{b}", zu)))
@@ -308,7 +318,10 @@ def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue"):
         r = r[:, :, :T, :]
     loss = F.mse_loss(r.squeeze(1), xb)
     loss.backward()
-    return float(loss.detach()), {k: v.grad.float() for k, v in P.items()}
+    out = (float(loss.detach()), {k: v.grad.float() for k, v in P.items()})
+    if return_stats or return_margins:
+        out += (r.detach().squeeze(1).float(), latent.detach().float())
+    return out + ((batch_stats,) if return_stats else ()) + ((margins,) if return_margins else ())
 
 
 @torch.no_grad()
