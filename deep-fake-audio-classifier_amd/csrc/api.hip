@@ -486,36 +486,18 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   const bool fused123 = fused12 && ctx->block3_m16 && ctx->fuse_blocks123 && ctx->time_split <= 0 && B * nstrips30 >= 512 &&
                         seg_iters_for((pl.H1 + 3) / 4, B * nstrips30, 512, 6, ctx->time_split) == 0 &&
                         seg_iters_for(niter3, B * nstrips30, 512, chunk3, ctx->time_split) == 0;
-  // ... and where every workgroup's range is a whole number of utterances (it starts at strip 0: the range formula of
-  // conv123_persist.hip with no remainder) and the side buffer fits the CU's LDS, the form that carries two a1 columns from
-  // strip to strip instead of computing them twice (conv123_carry.hip)
-  const int nunits123 = B * nstrips30, grid123 = std::min(nunits123, ctx->num_cus);
-  const bool carry123 = fused123 && ctx->persist123 && ctx->carry_a1 && grid123 > 0 && nunits123 % grid123 == 0 &&
-                        (nunits123 / grid123) % nstrips30 == 0 && conv123_carry_lds_bytes(T) <= (size_t)160 * 1024;
-  ctx->last_conv123_form = carry123 ? DFA_CONV123_CARRY : fused123 ? (ctx->persist123 ? DFA_CONV123_PERSIST : DFA_CONV123_PER_UNIT) : DFA_CONV123_NONE;
-  // the carry form with the consumers' step barrier behind fragment read 35 and the consumers at s_setprio 1
-  // (conv123_phase.hip): the same form, the same conditions, bit-identical results
-  ctx->last_conv123_phase = carry123 && ctx->phase123;
-  if (carry123 && ctx->phase123) {
+  // ... in the form conv123_plan chooses: per unit, persistent, persistent with two a1 columns carried from strip to strip, and
+  // that last form with the roles' step edges moved apart (the same form, bit-identical results: the value reported stays CARRY)
+  const Conv123Plan p123 = fused123 ? conv123_plan(B, T, F, ctx->num_cus, ctx->persist123, ctx->carry_a1, ctx->phase123) : Conv123Plan{};
+  ctx->last_conv123_form = p123.form;
+  ctx->last_conv123_phase = p123.phase;
+  if (fused123) {
     ScopedSlot ts(ctx, 2);
-    DFA_HIP_CHECK(ctx, launch_conv123_phase(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
-                                            m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
-                                            ctx->num_cus, s, ctx->lds_pipe));
-  } else if (carry123) {
-    ScopedSlot ts(ctx, 2);
-    DFA_HIP_CHECK(ctx, launch_conv123_carry(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
-                                            m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
-                                            ctx->num_cus, s, ctx->lds_pipe));
-  } else if (fused123 && ctx->persist123) {      // one workgroup per CU walks a contiguous range of the same units (conv123_persist.hip)
-    ScopedSlot ts(ctx, 2);
-    DFA_HIP_CHECK(ctx, launch_conv123_persist(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
-                                              m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
-                                              ctx->num_cus, s, ctx->lds_pipe));
-  } else if (fused123) {
-    ScopedSlot ts(ctx, 2);
-    DFA_HIP_CHECK(ctx, launch_conv123_fused(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias,
-                                            m.c3_m16, m.c3.bias, emb, B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr,
-                                            s, ctx->lds_pipe));
+    const Conv123Args a = c123_args(x, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, m.c3_m16, m.c3.bias, emb,
+                                    B, T, F, chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr);
+    const auto launch = p123.phase ? launch_conv123_phase : p123.form == DFA_CONV123_CARRY ? launch_conv123_carry :
+                        p123.form == DFA_CONV123_PERSIST ? launch_conv123_persist : launch_conv123_fused;
+    DFA_HIP_CHECK(ctx, launch(a, x_dtype, ctx->num_cus, s, ctx->lds_pipe));
   } else if (fused12) {
     ScopedSlot ts(ctx, 1);
     const int seg12 = seg_iters_for((pl.H1 + 3) / 4, B * nstrips30, 512, 6, ctx->time_split);

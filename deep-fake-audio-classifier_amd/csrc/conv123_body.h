@@ -39,22 +39,6 @@
 
 namespace dfa {
 
-struct Conv123Args {
-  const void* x;            // features (bf16 or fp32: template argument TX), element strides below (any layout)
-  long long sxb, sxt, sxf;
-  const uint4* c1pack;      // [4][64] block-1 A operands (pack_conv1_mfma_kernel)
-  const float* c1bias;      // [32]  0.5 * folded bias
-  const uint4* wpack2;      // block 2 image [2][9][2][64] (pool factor folded)
-  const float* bias2;       // [64]
-  const uint4* wpack3;      // block 3 image in the 16x16x32 order [4][9][2][2][64]
-  const float* bias3;       // [128]
-  float* emb;               // [B][128][F] fp32 time mean
-  float inv_h;
-  int B, T, F, H1, H2, nstrips;
-  int chunk_iters;          // canonical chunks of the time mean (conv3_m16.hip)
-  long long* clock_stamps;  // held-clock probe (ConvArgs::clock_stamps), null = off
-};
-
 namespace c123 {
 // consumer region (LDS offset 0): a2 ring 4 blocks x 2 rows x 32 slots x 128 B, block-3 bias, running time-mean totals
 constexpr int CPB = 128, CSP = 32, CROWB = CSP * CPB, CBR = 2, CNB = 4, NT = 256;
@@ -62,7 +46,7 @@ constexpr int CRING_BYTES = CNB * CBR * CROWB;
 constexpr int CBIAS_OFF = CRING_BYTES, TOT_OFF = CBIAS_OFF + 128 * 4, TOT_BYTES = NT * 64;
 // producer region: a1 ring 3 blocks x 4 rows x 36 slots x 64 B, block-2 bias, 2 feature-window buffers, store sink
 constexpr int P_OFF = TOT_OFF + TOT_BYTES;
-constexpr int PB = 64, SP = 36, ROWB = SP * PB, BR = 4, NKG = 2, PF = 4, SW = 30;
+constexpr int PB = 64, SP = 36, ROWB = SP * PB, BR = 4, NKG = 2, PF = 4;   // (SW, the strip width: conv123_host.h)
 constexpr int RING_BYTES = 3 * BR * ROWB;
 constexpr int BIAS2_OFF = RING_BYTES, XW_OFF = BIAS2_OFF + 64 * 4;
 constexpr int XROWS = 10, XW_ROWB = SP * 8, XW_BYTES = XROWS * XW_ROWB;
@@ -83,20 +67,6 @@ static_assert(SIDE_OFF % 16 == 0, "");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert(P_OFF + RING_BYTES < 65536 + P_OFF, "");
 }  // namespace c123
-
-// host: the arguments both launchers pass (launch_conv123_fused / launch_conv123_persist, same parameters)
-static inline Conv123Args c123_args(const void* x, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack, const float* c1bias,
-                                    const uint4* wpack2, const float* bias2, const uint4* wpack3, const float* bias3, float* emb, int B,
-                                    int T, int F, int chunk_iters, long long* clock_stamps) {
-  Conv123Args a{};
-  a.x = x; a.sxb = sb; a.sxt = st; a.sxf = sf;
-  a.c1pack = c1pack; a.c1bias = c1bias; a.wpack2 = wpack2; a.bias2 = bias2; a.wpack3 = wpack3; a.bias3 = bias3; a.emb = emb;
-  a.B = B; a.T = T; a.F = F; a.H1 = T / 2; a.H2 = a.H1 / 2; a.nstrips = (F + c123::SW - 1) / c123::SW;
-  a.inv_h = 1.0f / (float)a.H2;
-  a.chunk_iters = chunk_iters;
-  a.clock_stamps = clock_stamps;
-  return a;
-}
 
 // The persistent kernel's main loops are as tight on registers as the per-unit kernel's (254 of 256), and whatever the code
 // between two units computes from loop-invariant lane numbers alone the compiler computes before the loop over units and
@@ -943,6 +913,59 @@ __device__ __forceinline__ void c123_consumer(const Conv123Args& a, char* smem, 
 #ifdef DFA_STAMPS
   stamps.write(4 + nsl, lane, (PERSIST ? u_end : stamp_u0 + 1) - stamp_u0);
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------------------- the frame
+// What a workgroup of each of the four kernels does around the two roles: blockIdx -> XCD -> logical workgroup lw, its unit
+// range [u0, u1) in the per-unit kernel's order (the strips of an utterance back to back), the first unit's (b, f0), and the
+// roles by wave number (not parity): waves 0-3 and 4-7 land one of each on every SIMD.  Ranges: !PERSIST the one unit lw;
+// PERSIST q or q + 1 units, q = units / grid, the first units % grid workgroups one more (conv123_persist.hip); CARRY q
+// units, because conv123_plan lets that form run only where nothing remains and q is a multiple of nstrips (strip = 0).
+template <typename TX, bool PIPE, bool PERSIST>
+__device__ __forceinline__ void c123_workgroup(const Conv123Args& a, char* smem) {
+  using namespace c123;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lw = xcd_logical_workgroup();
+  int u0 = lw, u1 = lw + 1;
+  if constexpr (PERSIST && CARRY) {
+    const int uq = (a.B * a.nstrips) / (int)gridDim.x;
+    u0 = lw * uq; u1 = u0 + uq;
+  } else if constexpr (PERSIST) {
+    const int nwg = gridDim.x, nunits = a.B * a.nstrips;
+    const int uq = nunits / nwg, urem = nunits - uq * nwg;
+    u0 = lw * uq + min(lw, urem); u1 = u0 + uq + (lw < urem ? 1 : 0);   // nwg <= nunits: never empty
+  }
+  const int b = u0 / a.nstrips, strip = u0 - b * a.nstrips;
+  const int f0 = strip * SW;
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+  const int niter3 = (a.H2 + 1) / 2;
+  if (wave < 4) c123_producer<TX, PIPE, PERSIST>(a, smem, lds0, tid, wave, b, f0, niter3, u0, u1);
+  else c123_consumer<PIPE, PERSIST>(a, smem, lds0, tid - 256, wave - 4, b, f0, niter3, u0, u1);
+}
+
+// ---------------------------------------------------------------------------------------------------------- host
+// the instantiation of a form's kernel K for the feature type and the pipelined / compiler-scheduled build
+typedef void (*C123Kernel)(Conv123Args);
+#define DFA_C123_KERNEL(K, x_dtype, pipe)                                                                           \
+  ((x_dtype) == DFA_DTYPE_BF16 ? ((pipe) ? (C123Kernel)K<bf16_t, true> : (C123Kernel)K<bf16_t, false>)             \
+                               : ((pipe) ? (C123Kernel)K<float, true> : (C123Kernel)K<float, false>))
+// The launch of every form: grid and dynamic LDS bytes from conv123_plan, asked for this form alone.  Where the plan answers
+// another form, this one's conditions do not hold (for the carry form: a range that began inside an utterance would read a
+// side-buffer entry nobody wrote) and nothing is launched.
+static hipError_t c123_launch(C123Kernel kern, int form, const char* tag, const Conv123Args& a, int num_cus, hipStream_t s) {
+  const Conv123Plan p = conv123_plan(a.B, a.T, a.F, num_cus, form != DFA_CONV123_PER_UNIT, form == DFA_CONV123_CARRY, 0);
+  if (p.form != form || p.grid < 1) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  if (e != hipSuccess) return e;       // (per device: set on every launch, it is cheap)
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), p.lds, s, a);
+#ifdef DFA_STAMPS
+  {
+    static int calls = 0;      // seconds of back-to-back launches: the clock has settled (tools/gpu_stamps.py)
+    if (++calls == 4000) c123_print_stamps(tag, p.grid);
+  }
+#endif
+  return hipGetLastError();
 }
 
 }  // namespace dfa

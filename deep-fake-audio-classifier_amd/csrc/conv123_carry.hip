@@ -1,5 +1,5 @@
 // conv123_carry.hip -- conv123_persist.hip with the two a1 halo columns on the left of a strip carried over from the strip
-// before it instead of computed again (context option "carry_a1", the default where its conditions hold: api.hip; with
+// before it instead of computed again (context option "carry_a1", the default where its conditions hold: conv123_plan below; with
 // option "phase123" at its default the dispatcher runs this form as built by conv123_phase.hip, with 0 this file's kernel).
 //
 // Why.  A strip owns 30 output columns, f0 .. f0 + 29.  Block 2 needs the a1 columns f0 - 2 .. f0 + 31 = ring slots 0 .. 33,
@@ -41,56 +41,25 @@ namespace dfa {
 // PIPE = false is the compiler-scheduled twin, as in conv123_fused.hip
 template <typename TX, bool PIPE>
 __global__ __launch_bounds__(512, 1) void conv123_carry_kernel(Conv123Args a) {
-  using namespace c123;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7, xi = bid >> 3;
-  const int lw = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + xi;
-  const int uq = (a.B * a.nstrips) / nwg;                  // the launcher: no remainder, a multiple of nstrips
-  const int u0 = lw * uq, u1 = u0 + uq;
-  const int b = u0 / a.nstrips, strip = u0 - b * a.nstrips;    // strip = 0
-  const int f0 = strip * SW;
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-  const int niter3 = (a.H2 + 1) / 2;
-  if (wave < 4) c123_producer<TX, PIPE, true>(a, smem, lds0, tid, wave, b, f0, niter3, u0, u1);
-  else c123_consumer<PIPE, true>(a, smem, lds0, tid - 256, wave - 4, b, f0, niter3, u0, u1);
+  c123_workgroup<TX, PIPE, true>(a, smem);
 }
 
-// dynamic LDS of the kernel for T frames; the dispatcher compares it with the CU's 160 KiB
-size_t conv123_carry_lds_bytes(int T) {
-  const int niter3 = (T / 2 / 2 + 1) / 2;
-  return (size_t)c123::LDS_BYTES + (size_t)c123::side_bytes(niter3);
+hipError_t launch_conv123_carry(const Conv123Args& a, int x_dtype, int num_cus, hipStream_t s, int pipe) {
+  return c123_launch(DFA_C123_KERNEL(conv123_carry_kernel, x_dtype, pipe), DFA_CONV123_CARRY, "conv123 carry", a, num_cus, s);
 }
 
-template <typename TX, bool PIPE>
-static hipError_t launch_conv123_carry_t(const Conv123Args& a, int num_cus, hipStream_t s) {
-  const int nunits = a.B * a.nstrips;
-  const size_t lds = conv123_carry_lds_bytes(a.T);
-  // (the dispatcher's conditions, checked again: a range that began inside an utterance would read an entry nobody wrote)
-  if (nunits < num_cus || nunits % num_cus != 0 || (nunits / num_cus) % a.nstrips != 0 || lds > 160 * 1024) return hipErrorInvalidValue;
-  auto kern = conv123_carry_kernel<TX, PIPE>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;       // (per device: set on every launch, it is cheap)
-  hipLaunchKernelGGL(kern, dim3(num_cus), dim3(512), lds, s, a);
-#ifdef DFA_STAMPS
-  {
-    static int calls = 0;      // seconds of back-to-back launches: the clock has settled (tools/gpu_stamps.py)
-    if (++calls == 4000) c123_print_stamps("conv123 carry", num_cus);
-  }
-#endif
-  return hipGetLastError();
-}
-
-hipError_t launch_conv123_carry(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
-                                const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
-                                int num_cus, hipStream_t s, int pipe) {
-  if (num_cus < 1) return hipErrorInvalidValue;
-  const Conv123Args a = c123_args(x, sb, st, sf, c1pack, c1bias, wpack2, bias2, wpack3, bias3, emb, B, T, F, chunk_iters, clock_stamps);
-  if (x_dtype == DFA_DTYPE_BF16) return pipe ? launch_conv123_carry_t<bf16_t, true>(a, num_cus, s) : launch_conv123_carry_t<bf16_t, false>(a, num_cus, s);
-  return pipe ? launch_conv123_carry_t<float, true>(a, num_cus, s) : launch_conv123_carry_t<float, false>(a, num_cus, s);
+// Which form runs blocks 1-3, for a shape the dispatcher fuses (api.hip) and the three options, and with what grid and dynamic
+// LDS bytes: the one statement of the grid rule and of the carry form's conditions, asked by the dispatcher and by every entry.
+Conv123Plan conv123_plan(int B, int T, int F, int num_cus, int persist123, int carry_a1, int phase123) {
+  const int nstrips = (F + c123::SW - 1) / c123::SW, nunits = B * nstrips, niter3 = (T / 2 / 2 + 1) / 2;
+  if (!persist123) return {DFA_CONV123_PER_UNIT, 0, nunits, (size_t)c123::LDS_BYTES};
+  const int grid = std::min(nunits, num_cus);      // one workgroup per CU, or per unit where there are fewer (< 1: the entry refuses)
+  // carry: every range is a whole number of utterances (it starts at strip 0), and the side buffer fits the CU's 160 KiB
+  const size_t lds_carry = (size_t)c123::LDS_BYTES + (size_t)c123::side_bytes(niter3);
+  if (!carry_a1 || grid < 1 || nunits % grid != 0 || (nunits / grid) % nstrips != 0 || lds_carry > (size_t)160 * 1024)
+    return {DFA_CONV123_PERSIST, 0, grid, (size_t)c123::LDS_BYTES};
+  return {DFA_CONV123_CARRY, phase123 != 0, grid, lds_carry};
 }
 
 }  // namespace dfa

@@ -31,44 +31,12 @@ namespace dfa {
 // PIPE = false is the compiler-scheduled twin (plain LDS loads and stores, same arithmetic): bit-identical output
 template <typename TX, bool PIPE>
 __global__ __launch_bounds__(512, 1) void conv123_fused_kernel(Conv123Args a) {
-  using namespace c123;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7, xi = bid >> 3;
-  const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + xi;
-  const int b = logical / a.nstrips, strip = logical - b * a.nstrips;
-  const int f0 = strip * SW;
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-  const int niter3 = (a.H2 + 1) / 2;
-  // roles by wave number (not parity): waves 0-3 and 4-7 land one of each on every SIMD
-  if (wave < 4) c123_producer<TX, PIPE, false>(a, smem, lds0, tid, wave, b, f0, niter3, logical, logical + 1);
-  else c123_consumer<PIPE, false>(a, smem, lds0, tid - 256, wave - 4, b, f0, niter3, logical, logical + 1);
+  c123_workgroup<TX, PIPE, false>(a, smem);
 }
 
-template <typename TX, bool PIPE>
-static hipError_t launch_conv123_t(const Conv123Args& a, hipStream_t s) {
-  auto kern = conv123_fused_kernel<TX, PIPE>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, c123::LDS_BYTES);
-  if (e != hipSuccess) return e;       // (per device: set on every launch, it is cheap)
-  hipLaunchKernelGGL(kern, dim3(a.B * a.nstrips), dim3(512), c123::LDS_BYTES, s, a);
-#ifdef DFA_STAMPS
-  {
-    static int calls = 0;      // seconds of back-to-back launches: the clock has settled (tools/gpu_stamps.py)
-    if (++calls == 4000) c123_print_stamps("conv123", a.B * a.nstrips);
-  }
-#endif
-  return hipGetLastError();
-}
-
-hipError_t launch_conv123_fused(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
-                                const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
-                                hipStream_t s, int pipe) {
-  const Conv123Args a = c123_args(x, sb, st, sf, c1pack, c1bias, wpack2, bias2, wpack3, bias3, emb, B, T, F, chunk_iters, clock_stamps);
-  if (x_dtype == DFA_DTYPE_BF16) return pipe ? launch_conv123_t<bf16_t, true>(a, s) : launch_conv123_t<bf16_t, false>(a, s);
-  return pipe ? launch_conv123_t<float, true>(a, s) : launch_conv123_t<float, false>(a, s);
+hipError_t launch_conv123_fused(const Conv123Args& a, int x_dtype, int num_cus, hipStream_t s, int pipe) {
+  return c123_launch(DFA_C123_KERNEL(conv123_fused_kernel, x_dtype, pipe), DFA_CONV123_PER_UNIT, "conv123", a, num_cus, s);
 }
 
 }  // namespace dfa

@@ -13,9 +13,7 @@
   const int nsl = wave & 1, mg = wave >> 1;
   const int r = lane & 31, h = lane >> 5;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7, xi = bid >> 3;
-  const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + xi;
+  const int logical = xcd_logical_workgroup();
   const int u = logical / a.nstrips, strip = logical - u * a.nstrips;
   const int b = RAGGED ? __builtin_amdgcn_readfirstlane(rt.tab[rt.B + u]) : u;
   const int f0 = strip * SW;

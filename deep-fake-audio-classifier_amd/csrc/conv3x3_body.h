@@ -19,11 +19,7 @@
   const int mg = (MG == 1) ? 0 : wave / NSL;
   const int r = lane & 31, h = lane >> 5;
 
-  // XCD-aware block order: blocks with equal blockIdx.x % 8 share an XCD (and its L2); hand each XCD a
-  // contiguous range of (utterance, strip) ids so the strips that share halo columns meet in one L2.
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7, xi = bid >> 3;
-  const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + xi;
+  const int logical = xcd_logical_workgroup();   // XCD-aware block order (dfa_device.h)
   // RAGGED: workgroup slot u -> utterance through the dispatch order of the table (longest first, dealt over the eight XCD
   // ranges); H is the utterance's own height at this layer (T_b >> hshift), a.H the batch maximum that fixes the row pitch of
   // the input and of the output.  Rows at or past H stage from the zero page, as rows past the image always did.

@@ -60,9 +60,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_split_kernel(ConvArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = lane & 15, q = lane >> 4;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7, xi = bid >> 3;
-  const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + xi;
+  const int logical = xcd_logical_workgroup();
   const int b = logical / a.nstrips, strip = logical - b * a.nstrips;
   const int f0 = strip * SW;
   const int H = a.H, W = a.W;

@@ -48,6 +48,14 @@ __device__ __forceinline__ float relu_limit() {
 }
 __device__ __forceinline__ float relu1(float x, float lim) { return __builtin_amdgcn_fmed3f(x, 0.f, lim); }
 
+// ---- XCD-aware workgroup order.  Workgroups with equal blockIdx.x % 8 share an XCD (and its L2): each XCD gets a contiguous
+// range of logical workgroup numbers, so that neighbouring (utterance, strip) ids, which share halo columns, meet in one L2.
+__device__ __forceinline__ int xcd_logical_workgroup() {
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7, xi = bid >> 3;
+  return (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + xi;
+}
+
 // ---- loads and stores between storage (float / bf16_t) and float registers
 // one element
 __device__ __forceinline__ float ld1(const float* p) { return *p; }

@@ -11,6 +11,7 @@
 
 #include "../../include/dfa_hip.h"
 #include "conv3x3_mfma.h"
+#include "conv123_host.h"
 #include "rng.h"
 
 namespace dfa {
@@ -531,27 +532,7 @@ hipError_t launch_conv12_fused(const void* x, int x_dtype, int64_t sb, int64_t s
 hipError_t launch_conv12_ragged(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
                                 const float* c1bias, const uint4* wpack2, const float* bias2, void* a2, int B, int T_max,
                                 int F, const int* tab, hipStream_t s, int pipe = 1, int seg_iters = 0);
-hipError_t launch_conv123_fused(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
-                                const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
-                                hipStream_t s, int pipe = 1);
-// the same units, one persistent workgroup per CU (grid = min(units, num_cus)): conv123_persist.hip
-hipError_t launch_conv123_persist(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                  const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
-                                  const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
-                                  int num_cus, hipStream_t s, int pipe = 1);
-// the persistent form with two a1 columns carried from strip to strip (grid = num_cus; every range a whole number of
-// utterances): conv123_carry.hip.  conv123_carry_lds_bytes: its dynamic LDS for T frames
-hipError_t launch_conv123_carry(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
-                                const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
-                                int num_cus, hipStream_t s, int pipe = 1);
-size_t conv123_carry_lds_bytes(int T);
-// the carry form with the roles' step edges moved apart (same arguments, conditions and LDS bytes): conv123_phase.hip
-hipError_t launch_conv123_phase(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                const float* c1bias, const uint4* wpack2, const float* bias2, const uint4* wpack3,
-                                const float* bias3, float* emb, int B, int T, int F, int chunk_iters, long long* clock_stamps,
-                                int num_cus, hipStream_t s, int pipe = 1);
+// (blocks 1-3 in one kernel, conv123_*.hip: conv123_host.h)
 hipError_t launch_cnn2d_block2(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);
 hipError_t launch_cnn2d_block3(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);
 struct ConvTArgs;

@@ -7,10 +7,9 @@ fits LDS."""
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from conv123_common import CARRY, NONE, PATTERNS, PER_UNIT, PERSIST, _ctx, _cus, _model, _niter3, _restore_options, _run, _same, _x  # noqa: F401 (_restore_options: autouse)
 
-PATTERNS = [0xFFFF, 0x7FC0, 0x7F80]
-NONE, PER_UNIT, PERSIST, CARRY = 0, 1, 2, 3
+pytestmark = pytest.mark.gpu
 
 # conv123_body.h, namespace c123: the kernel's LDS without the side buffer, and the side buffer's bytes per a1 ring block
 CRING_BYTES = 4 * 2 * 32 * 128
@@ -21,72 +20,8 @@ SIDE_BLKB = 4 * 2 * 64
 LDS_CAP = 160 * 1024
 
 
-def _niter3(T):
-    return (T // 2 // 2 + 1) // 2
-
-
 def _fits(T):
     return LDS_BYTES + (_niter3(T) + 2) * SIDE_BLKB <= LDS_CAP
-
-
-def _ctx():
-    from dfa_amd import _lib
-    return _lib.Context.get(torch.device("cuda"))
-
-
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-@pytest.fixture(autouse=True)
-def _restore_options():
-    yield
-    ctx = _ctx()
-    ctx.set_option("fuse_blocks123", 1)
-    ctx.set_option("persist123", 1)
-    ctx.set_option("carry_a1", 1)
-    ctx.set_option("lds_pipe", 1)
-
-
-_MODELS = {}
-
-
-def _model(F):
-    if F not in _MODELS:
-        from dfa_amd.model import CNN2D
-        torch.manual_seed(5)
-        m = CNN2D(in_features=F, precision="bf16").to("cuda")
-        with torch.no_grad():
-            for i in m._BN_IDX:
-                m.conv[i].running_mean.normal_(0, 0.3)
-                m.conv[i].running_var.uniform_(0.5, 2.0)
-            m.classifier.weight.mul_(20.0)
-        _MODELS[F] = m.eval()
-    return _MODELS[F]
-
-
-def _x(B, T, F, seed=11, dtype=torch.bfloat16, strided=True):
-    gen = torch.Generator().manual_seed(seed)
-    stored = torch.randn(B, F, T, generator=gen) * 3.2 - 0.07
-    if strided:
-        return stored.to("cuda").to(dtype).transpose(1, 2)          # [B, T, F] view of a [B, F, T] tensor
-    return stored.transpose(1, 2).contiguous().to("cuda").to(dtype)
-
-
-def _run(m, x, form=None, **opts):
-    ctx = _ctx()
-    for k in ("fuse_blocks123", "persist123", "carry_a1", "lds_pipe"):
-        ctx.set_option(k, opts.get(k, 1))
-    lg, emb = m(x, return_embedding=True)
-    torch.cuda.synchronize()
-    if form is not None:
-        assert ctx.last_conv123_form() == form, (ctx.last_conv123_form(), form, opts)
-    return lg.clone(), emb.clone()
-
-
-def _same(got, want, what):
-    assert torch.equal(got[0], want[0]), (what, "logits", (got[0] - want[0]).abs().max().item())
-    assert torch.equal(got[1], want[1]), (what, "embeddings", (got[1] - want[1]).abs().max().item())
 
 
 def _identity(B, T, F, **xkw):

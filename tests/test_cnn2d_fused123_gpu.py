@@ -4,51 +4,9 @@ the dispatcher takes it, its compiler-scheduled twin must equal the pipelined bu
 import pytest
 import torch
 
+from conv123_common import PATTERNS, _ctx, _model, _restore_options, _run, _slots, _x  # noqa: F401 (_restore_options: autouse)
+
 pytestmark = pytest.mark.gpu
-
-PATTERNS = [0xFFFF, 0x7FC0, 0x7F80]
-
-
-def _ctx():
-    from dfa_amd import _lib
-    return _lib.Context.get(torch.device("cuda"))
-
-
-@pytest.fixture(autouse=True)
-def _restore_options():
-    yield
-    ctx = _ctx()
-    ctx.set_option("fuse_blocks123", 1)
-    ctx.set_option("lds_pipe", 1)
-
-
-def _model(F):
-    from dfa_amd.model import CNN2D
-    torch.manual_seed(5)
-    m = CNN2D(in_features=F, precision="bf16").to("cuda")
-    with torch.no_grad():
-        for i in m._BN_IDX:
-            m.conv[i].running_mean.normal_(0, 0.3)
-            m.conv[i].running_var.uniform_(0.5, 2.0)
-        m.classifier.weight.mul_(20.0)
-    return m.eval()
-
-
-def _x(B, T, F, seed=11, dtype=torch.bfloat16, strided=True):
-    gen = torch.Generator().manual_seed(seed)
-    stored = torch.randn(B, F, T, generator=gen) * 3.2 - 0.07
-    if strided:
-        return stored.to("cuda").to(dtype).transpose(1, 2)          # [B, T, F] view of a [B, F, T] tensor
-    return stored.transpose(1, 2).contiguous().to("cuda").to(dtype)
-
-
-def _run(m, x, **opts):
-    ctx = _ctx()
-    for k, v in opts.items():
-        ctx.set_option(k, v)
-    lg, emb = m(x, return_embedding=True)
-    torch.cuda.synchronize()
-    return lg.clone(), emb.clone()
 
 
 @pytest.mark.parametrize("B,T,F,dtype,strided", [
@@ -87,16 +45,6 @@ def test_fused123_ignores_stale_lds():
         _ctx().set_option("poison_lds", pat)
         got = _run(m, x)
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), hex(pat)
-
-
-def _slots(m, x):
-    ctx = _ctx()
-    ctx.timing_reset()
-    ctx.timing(True)
-    m(x)
-    torch.cuda.synchronize()
-    ctx.timing(False)
-    return [ctx.timing_read(s)[1] for s in range(4)]
 
 
 def test_fused123_dispatch():

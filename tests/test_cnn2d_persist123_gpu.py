@@ -5,58 +5,9 @@ must not matter, and nothing may leak from one unit of a workgroup's range into 
 import pytest
 import torch
 
+from conv123_common import PATTERNS, _ctx, _model, _probe_workgroups, _restore_options, _run, _same, _slots, _x  # noqa: F401 (_restore_options: autouse)
+
 pytestmark = pytest.mark.gpu
-
-PATTERNS = [0xFFFF, 0x7FC0, 0x7F80]
-
-
-def _ctx():
-    from dfa_amd import _lib
-    return _lib.Context.get(torch.device("cuda"))
-
-
-@pytest.fixture(autouse=True)
-def _restore_options():
-    yield
-    ctx = _ctx()
-    ctx.set_option("fuse_blocks123", 1)
-    ctx.set_option("persist123", 1)
-    ctx.set_option("lds_pipe", 1)
-    ctx.set_option("clock_probe", 0)
-
-
-def _model(F):
-    from dfa_amd.model import CNN2D
-    torch.manual_seed(5)
-    m = CNN2D(in_features=F, precision="bf16").to("cuda")
-    with torch.no_grad():
-        for i in m._BN_IDX:
-            m.conv[i].running_mean.normal_(0, 0.3)
-            m.conv[i].running_var.uniform_(0.5, 2.0)
-        m.classifier.weight.mul_(20.0)
-    return m.eval()
-
-
-def _x(B, T, F, seed=11, dtype=torch.bfloat16, strided=True):
-    gen = torch.Generator().manual_seed(seed)
-    stored = torch.randn(B, F, T, generator=gen) * 3.2 - 0.07
-    if strided:
-        return stored.to("cuda").to(dtype).transpose(1, 2)          # [B, T, F] view of a [B, F, T] tensor
-    return stored.transpose(1, 2).contiguous().to("cuda").to(dtype)
-
-
-def _run(m, x, **opts):
-    ctx = _ctx()
-    for k, v in opts.items():
-        ctx.set_option(k, v)
-    lg, emb = m(x, return_embedding=True)
-    torch.cuda.synchronize()
-    return lg.clone(), emb.clone()
-
-
-def _same(got, want, what):
-    assert torch.equal(got[0], want[0]), (what, "logits", (got[0] - want[0]).abs().max().item())
-    assert torch.equal(got[1], want[1]), (what, "embeddings", (got[1] - want[1]).abs().max().item())
 
 
 SHAPES = [
@@ -148,26 +99,6 @@ def test_persist123_no_leak_between_units(B, T, F, victim, fill):
     assert torch.equal(got[0][keep], base[0][keep]), (got[0][keep] - base[0][keep]).abs().max().item()
     assert torch.equal(got[1][keep], base[1][keep])
     assert not torch.isfinite(got[1][victim]).all() or not torch.equal(got[1][victim], base[1][victim])
-
-
-def _slots(m, x):
-    ctx = _ctx()
-    ctx.timing_reset()
-    ctx.timing(True)
-    m(x)
-    torch.cuda.synchronize()
-    ctx.timing(False)
-    return [ctx.timing_read(s)[1] for s in range(4)]
-
-
-def _probe_workgroups(m, x):
-    ctx = _ctx()
-    ctx.set_option("clock_probe", 1)
-    m(x)
-    torch.cuda.synchronize()
-    n = ctx.clock_read()[3]
-    ctx.set_option("clock_probe", 0)
-    return n
 
 
 def test_persist123_dispatch():

@@ -1,30 +1,18 @@
 """CPU checks of conv123_persist.hip (CNN2D blocks 1-3, one persistent workgroup per CU): the static LDS-pipeline check of
 the compiled gfx950 assembly, the register budget (two waves per SIMD, no scratch), the range assignment, and a host model
 of the schedule across the boundary between two units of a workgroup."""
-import importlib.util
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "deep-fake-audio-classifier_amd", "csrc")
+from conv123_common import CSRC, _checker, _compiled, _pipelined_fit_two_waves_per_simd
+
 SRC = os.path.join(CSRC, "conv123_persist.hip")
 
 
-def _checker():
-    spec = importlib.util.spec_from_file_location("check_lds_pipeline", os.path.join(ROOT, "tools", "check_lds_pipeline.py"))
-    chk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(chk)
-    if not os.path.exists(chk.HIPCC):
-        pytest.skip("hipcc not available")
-    return chk
-
-
 def test_persist123_lds_pipeline_static_check():
-    chk = _checker()
-    asm = chk.compile_to_asm(SRC)
+    chk, asm = _checker(), _compiled(SRC)[0]
     kernels, nreads, violations = chk.check_asm(asm)
     assert not violations, violations[:5]
     assert nreads > 0
@@ -32,30 +20,10 @@ def test_persist123_lds_pipeline_static_check():
     assert nm > 0 and not v2, v2[:5]
 
 
-def test_persist123_registers_fit_two_waves_per_simd(tmp_path):
+def test_persist123_registers_fit_two_waves_per_simd():
     """512 threads, one workgroup per CU: <= 256 VGPRs per wave (arch + acc) and no scratch in the pipelined kernels.
     (The compiler-scheduled twins are a test hook: they may spill a little.)"""
-    chk = _checker()
-    out = subprocess.run([chk.HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--offload-device-only", "-c", SRC,
-                          "-o", str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, cwd=CSRC)
-    assert out.returncode == 0, out.stderr[-2000:]
-    usage, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
-    assert not any("conv123_fused_kernel" in k for k in usage), list(usage)     # its own kernels, under its own name
-    piped = {k: v for k, v in usage.items() if "conv123_persist_kernel" in k and "Lb1E" in k}
-    assert len(piped) == 2, usage
-    for k, v in piped.items():
-        assert v["VGPRs"] + v["AGPRs"] <= 256, (k, v)
-        assert v["ScratchSize [bytes/lane]"] == 0, (k, v)
+    _pipelined_fit_two_waves_per_simd(_compiled(SRC)[1], "conv123_persist_kernel")     # its own kernels, under its own name
 
 
 def _ranges(nunits, nwg):

@@ -6,15 +6,14 @@ before the interval of its last read, and that the two roles execute the same nu
 and every CBAR = 0 .. 35.  CBAR = 36 must fail (read 36 is the first of a row the producers write in that interval), in the
 model and in the header's static_assert.  conv123_phase.hip, the kernel built with CBAR = 35, is put through the static
 LDS-pipeline check and the register budget."""
-import importlib.util
 import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "deep-fake-audio-classifier_amd", "csrc")
+from conv123_common import CSRC, _checker, _compiled, _pipelined_fit_two_waves_per_simd
+
 SRC = os.path.join(CSRC, "conv123_carry.hip")
 PHASE_SRC = os.path.join(CSRC, "conv123_phase.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -155,43 +154,25 @@ def test_phase123_header_refuses_a_barrier_behind_read_35(cbar, ok):
         assert "static assertion failed" in out.stderr and "S_BAR" in out.stderr, out.stderr[-2000:]
 
 
-def test_phase123_static_check_and_registers(tmp_path):
+def test_phase123_static_check_and_registers():
     """conv123_phase.hip (barrier behind read 35, consumers at priority 1): four kernels, counted waits and operand
     provenance hold, <= 256 VGPRs (arch + acc) and no scratch in the two pipelined kernels.  The position moves no LDS
     operation, only the barrier between them."""
-    spec = importlib.util.spec_from_file_location("check_lds_pipeline", os.path.join(ROOT, "tools", "check_lds_pipeline.py"))
-    chk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(chk)
-    asm_path = tmp_path / "k.s"
-    out = subprocess.run([_hipcc(), "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-device-only", "-S",
-                          PHASE_SRC, "-o", str(asm_path), "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, cwd=CSRC)
-    assert out.returncode == 0, out.stderr[-2000:]
-    asm = asm_path.read_text()
+    chk, (asm, usage) = _checker(), _compiled(PHASE_SRC)
     kernels, nreads, violations = chk.check_asm(asm)
     assert kernels == 4 and nreads > 0 and not violations, violations[:5]
     nk, nm, v2 = chk.check_operand_provenance(asm)
     assert nm > 0 and not v2, v2[:5]
     assert asm.count("s_setprio 1") >= 4 and "conv123_carry_kernel" not in asm      # its own kernels, the consumers raised
-    usage, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
-    assert all("conv123_phase_kernel" in k for k in usage), list(usage)
-    piped = {k: v for k, v in usage.items() if "Lb1E" in k}
-    assert len(piped) == 2, usage
-    for k, v in piped.items():
-        assert v["VGPRs"] + v["AGPRs"] <= 256, (k, v)
-        assert v["ScratchSize [bytes/lane]"] == 0, (k, v)
+    _pipelined_fit_two_waves_per_simd(usage, "conv123_phase_kernel")
 
 
 def test_phase123_file_sets_the_last_legal_position():
     text = open(PHASE_SRC).read()
     assert re.search(r"^#define DFA_C123_CBAR 35$", text, re.M) and re.search(r"^#define DFA_C123_PRIO 1$", text, re.M)
-    assert re.search(r"^#define DFA_C123_CARRY 1$", text, re.M) and "conv123_carry_lds_bytes(a.T)" in text
+    assert re.search(r"^#define DFA_C123_CARRY 1$", text, re.M)
+    # ... and its LDS bytes are the carry form's, side buffer included: both files launch through c123_launch as DFA_CONV123_CARRY,
+    # which takes grid and bytes from conv123_plan, and neither sizes or launches anything itself
+    for t in (text, open(SRC).read()):
+        assert re.search(r"return c123_launch\(DFA_C123_KERNEL\(conv123_\w+_kernel, x_dtype, pipe\), DFA_CONV123_CARRY, ", t)
+        assert "hipLaunchKernelGGL" not in t and "MaxDynamicSharedMemorySize" not in t

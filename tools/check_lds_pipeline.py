@@ -59,15 +59,32 @@ def per_file_flags(path):
     return []
 
 
-def compile_to_asm(path):
+def compile_to_asm(path, remarks=False):
+    """the gfx950 assembly of the file as the Makefile builds it; remarks: (assembly, the compiler's resource-usage remarks)"""
     with tempfile.NamedTemporaryFile(suffix=".s", delete=False) as f:
         out = f.name
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only",
+    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(os.path.abspath(path))] + per_file_flags(path) + ["-o", out, path]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    err = subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True).stderr
     text = open(out).read()
     os.unlink(out)
-    return text
+    return (text, err) if remarks else text
+
+
+def resource_usage(path):
+    """(assembly, {kernel: {"VGPRs", "AGPRs", "ScratchSize [bytes/lane]"}}) of the file, from one compilation"""
+    text, err = compile_to_asm(path, remarks=True)
+    usage, name = {}, None
+    for line in err.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+            continue
+        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
+        if m and name:
+            usage[name][m.group(1)] = int(m.group(2))
+    return text, usage
 
 
 def check_asm(text):
