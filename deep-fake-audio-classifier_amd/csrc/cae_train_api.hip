@@ -59,7 +59,7 @@ CaeTrainPlan plan_cae_train(int B, int T, int F, int prec) {
   p.rec = take(1024 * 4);
   size_t pb = (size_t)kWgradWGs * ((size_t)128 * 64 * 9 + 256) * 4;
   pb = std::max(pb, (size_t)kGemmSplit * 256 * 512 * 4);
-  pb = std::max(pb, ((size_t)conv1_train_blocks(B, T, F) + 64) * 320 * 4);
+  pb = std::max(pb, ((size_t)conv1_train_blocks(B, T, F) + 64) * 352 * 4);   // [32][11] records + the second reduction level (as train_api.hip)
   int ppb;
   pb = std::max(pb, (size_t)cl_stats_blocks((size_t)B * T * F, &ppb) * 256 * 2 * 4);
   pb = std::max(pb, (size_t)cae_dec4_bwd_blocks() * 132 * 4);
@@ -311,7 +311,10 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
     float* xf = (float*)(ws + pl.xf);
     void* dx = (l == 0) ? ws + pl.de[3] : ws + pl.dd[l - 1];
     if (bf && ctx->cae_dgrad_mfma && convt_dgrad_bf16_supports(Cin, Cout)) {   // bf16 matrix cores, bf16 result in place
-      DFA_HIP_CHECK(ctx, launch_convt_dgrad_bf16(ws + pl.zp, wq, xf, dx, P, Cin, Cout, s));   // (xf: scratch for the bf16 weight fragments)
+      // the bf16 weight fragments (Cin * 4 Cout * 2 bytes, at most half of pl.dwq) go to pl.dwq, which is free until this layer's
+      // weight gradient below.  (pl.xf holds P * Cin floats: on a small batch the fragments would run past it, over raw, the
+      // BatchNorm statistics and the head of wq, which the pack kernel is still reading.)
+      DFA_HIP_CHECK(ctx, launch_convt_dgrad_bf16(ws + pl.zp, wq, ws + pl.dwq, dx, P, Cin, Cout, s));
     } else {
       DFA_HIP_CHECK(ctx, launch_gemm_f32(bf, ws + pl.zp, 4 * Cout, 1, 0, wq, 1, 4 * Cout, xf, (int)P, Cin, 4 * Cout, 1, s));
       DFA_HIP_CHECK(ctx, launch_cast_from_f32(prec, xf, dx, (size_t)P * Cin, s));
