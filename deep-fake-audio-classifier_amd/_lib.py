@@ -117,6 +117,8 @@ SYMBOLS = [
     ("dfa_ctx_timing_read", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     ("dfa_ctx_last_conv123_form", C.c_int, [C.c_void_p]),
     ("dfa_ctx_last_conv123_phase", C.c_int, [C.c_void_p]),
+    ("dfa_cnn2d_forward_plan", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                         C.POINTER(C.c_longlong), C.c_int]),
     ("dfa_ctx_debug_read", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]),
     ("dfa_ctx_clock_read", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int)]),
@@ -138,6 +140,23 @@ def load():
                 fn.restype, fn.argtypes = res, args
             _lib = lib
     return _lib
+
+
+CNN2D_PLAN_FIELDS = ("H1", "H2", "a1_off", "a2_off", "emb_off", "slabs", "tab_off", "tab_words", "total", "path", "form", "phase",
+                     "grid", "lds", "seg12", "seg3", "chunk3", "nseg3", "split3")
+CNN2D_PLAN_OPTIONS = ("time_split", "fuse_conv1", "block3_m16", "fuse_blocks123", "persist123", "carry_a1", "phase123")
+CNN2D_PATH_CONV1, CNN2D_PATH_CONV12, CNN2D_PATH_CONV123 = 0, 1, 2
+
+
+def cnn2d_forward_plan(ctx_handle, B, T, F, precision, ragged=False, options=None, num_cus=0):
+    """dfa_cnn2d_forward_plan as a tuple in the order of CNN2D_PLAN_FIELDS: for the context's options and CU count, or, with
+    ctx_handle None, for `options` (seven values in the order of CNN2D_PLAN_OPTIONS; None = the defaults) and `num_cus`."""
+    out = (C.c_longlong * len(CNN2D_PLAN_FIELDS))()
+    opts = None if options is None else (C.c_int * len(CNN2D_PLAN_OPTIONS))(*options)
+    n = load().dfa_cnn2d_forward_plan(ctx_handle, B, T, F, precision, int(ragged), opts, num_cus, out, len(out))
+    if n != len(out):
+        raise ValueError(f"dfa_cnn2d_forward_plan([{B}, {T}, {F}]) returned {n}, not {len(out)} fields")
+    return tuple(out)
 
 
 def check(ctx_handle, code):

@@ -20,7 +20,7 @@
 //     global write.
 // MFMA budget per utterance at T = 321 (11 tiles): 3 x 276 + 6 x 48 + 11 x 96 = 2172 issue slots of 64 cycles on the busiest SIMD
 // = 139 k cycles; one utterance per CU.  Shapes it takes: T <= 384 (activations must fit the 160 KB of LDS); anything else runs
-// the three-launch path (api.hip).
+// the three-launch path (cnn1d_api.hip).
 #include "dfa_internal.h"
 #include "conv3x3_mfma.h"
 

@@ -16,7 +16,7 @@
 //   * frame mean and the 128 -> 1 classifier in the epilogue, as in cnn1d_fused.hip: logits[b] is the only global write.
 // LDS: two fp32 slabs + two split images + layer-1 weights during layer 1 (156.5 KB at T = 321), then h1 and h2 over the same space.
 // Takes the reference's storage only (x[b][f][t] contiguous, 16-byte aligned, F % 4 == 0, 3 <= T <= 347 at F = 180: the LDS budget); anything else runs
-// cnn1d_fused.hip / the three-launch path (api.hip).
+// cnn1d_fused.hip / the three-launch path (cnn1d_api.hip).
 // A variable-length batch padded to its longest utterance runs cnn1d_ragged_x3_kernel (dfa_cnn1d_forward_ragged): the same body
 // (cnn1d_x3_body.h) with the utterance's own length from a device table, rows read at the batch's pitch, and utterances longer
 // than one LDS window walked in time segments inside their workgroup.

@@ -49,7 +49,7 @@ hipError_t launch_conv123_carry(const Conv123Args& a, int x_dtype, int num_cus, 
   return c123_launch(DFA_C123_KERNEL(conv123_carry_kernel, x_dtype, pipe), DFA_CONV123_CARRY, "conv123 carry", a, num_cus, s);
 }
 
-// Which form runs blocks 1-3, for a shape the dispatcher fuses (api.hip) and the three options, and with what grid and dynamic
+// Which form runs blocks 1-3, for a shape the dispatcher fuses (cnn2d_api.hip) and the three options, and with what grid and dynamic
 // LDS bytes: the one statement of the grid rule and of the carry form's conditions, asked by the dispatcher and by every entry.
 Conv123Plan conv123_plan(int B, int T, int F, int num_cus, int persist123, int carry_a1, int phase123) {
   const int nstrips = (F + c123::SW - 1) / c123::SW, nunits = B * nstrips, niter3 = (T / 2 / 2 + 1) / 2;

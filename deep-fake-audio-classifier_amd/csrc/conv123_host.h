@@ -1,4 +1,4 @@
-// conv123_host.h -- the host side of the CNN2D blocks 1-3 kernels (conv123_*.hip), shared with the dispatcher in api.hip: the
+// conv123_host.h -- the host side of the CNN2D blocks 1-3 kernels (conv123_*.hip), shared with the dispatcher in cnn2d_api.hip: the
 // kernel arguments, the entry of each form, and the plan that says which form runs.  The kernel bodies are conv123_body.h.
 #pragma once
 #include <hip/hip_runtime.h>

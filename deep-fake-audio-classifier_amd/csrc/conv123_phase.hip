@@ -1,5 +1,5 @@
 // conv123_phase.hip -- conv123_carry.hip with the two roles' step edges moved apart (context option "phase123", the default
-// where the carry form runs: api.hip).  Same arguments, same launch conditions, same LDS layout, same arithmetic instruction
+// where the carry form runs: cnn2d_api.hip).  Same arguments, same launch conditions, same LDS layout, same arithmetic instruction
 // for instruction; the two differences are where the consumers' step barrier stands in their fragment-read stream
 // (DFA_C123_CBAR = 35 instead of 4) and that the consumer waves run at s_setprio 1 (DFA_C123_PRIO = 1).
 //

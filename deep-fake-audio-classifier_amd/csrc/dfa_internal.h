@@ -318,6 +318,11 @@ hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, con
 int stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void* dst);
 // the same with `extra` words the caller supplies behind them: [2B, 2B + extra) (words = 2 B + extra)
 int stage_ragged_lengths_extra(dfa_ctx* ctx, const int32_t* lengths, int B, const int32_t* extra, size_t n_extra, void* dst);
+// cnn2d_api.hip, cnn1d_api.hip, cae_api.hip: the models' planners behind dfa_workspace_bytes and dfa_ragged_workspace_bytes
+// (api.hip), for B, T, F >= 1.  ctx may be null (CNN2D: the plan of the default options); ragged: T = T_max, the table included
+size_t cnn2d_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, int prec, bool ragged);
+size_t cnn1d_workspace_bytes(int B, int T, bool ragged);
+size_t cae_workspace_bytes(int B, int T, int F, int prec);
 // dlq.hip: the DeepfakeDetector layers (one launch each over the tile list) and the pool + head kernel
 struct DlqLayerArgs {
   const float* x;        // layer 1: element (b, c, t) at b sb + c sc + t

@@ -478,6 +478,31 @@ int dfa_ctx_last_conv123_form(const dfa_ctx* ctx);
 /* 1 if blocks 1-3 of the LAST dfa_cnn2d_forward ran the "phase123" build of the carry form (the form above is then
  * DFA_CONV123_CARRY: it is that form), else 0; ctx NULL: DFA_E_NULL_PTR. */
 int dfa_ctx_last_conv123_phase(const dfa_ctx* ctx);
+/* The plan of a CNN2D eval forward of [B, T, F] in `precision` (ragged != 0: of dfa_cnn2d_forward_ragged at T = T_max): the
+ * very function dfa_cnn2d_forward[_ragged] and the two workspace planners read, reported.  Pure host arithmetic.  With a
+ * context: for its options and its device's CU count (`options` and `num_cus` are not read).  Without one: for the seven
+ * values options[] = {time_split, fuse_conv1, block3_m16, fuse_blocks123, persist123, carry_a1, phase123} (NULL = the
+ * defaults -1, 1, 1, 1, 1, 1, 1) and `num_cus` compute units.  Fills the first min(cap, DFA_CNN2D_PLAN_FIELDS) of
+ *    0 H1, 1 H2                      rows after pool 1 / pool 2
+ *    2 a1_off, 3 a2_off, 4 emb_off   workspace regions (bytes)
+ *    5 slabs                         slabs of B * 128 * F floats in the embedding region: 1, or 5 (the reduced embedding and
+ *                                    four chunk slabs of a split block 3)
+ *    6 tab_off, 7 tab_words          ragged: the per-call table behind the regions (4 * B words; uniform: 0 words)
+ *    8 total                         = dfa_workspace_bytes / dfa_ragged_workspace_bytes
+ *    9 path                          DFA_CNN2D_PATH_*
+ *   10 form, 11 phase, 12 grid, 13 lds   path CONV123: DFA_CONV123_*, the de-phased build, workgroups, dynamic LDS bytes; else 0
+ *   14 seg12                         iterations per time segment of the blocks 1+2 kernel (bf16x3 mode: of block 2), 0 = no split
+ *   15 seg3, 16 chunk3, 17 nseg3     block 3: iterations per segment (0 = no split), iterations per canonical chunk of the time
+ *                                    mean (0: the kernel has none), chunk slabs in use (1 = none).  Ragged: seg3 is the kernel's
+ *                                    0 / 1 switch, chunk3 / nseg3 those of an utterance of T_max frames
+ *   18 split3                        ragged: block 3 writes chunk slabs
+ * of `fields` (may be NULL) and returns DFA_CNN2D_PLAN_FIELDS; 0 for B, T or F < 1. */
+#define DFA_CNN2D_PATH_CONV1 0   /* conv1, block 2, block 3 */
+#define DFA_CNN2D_PATH_CONV12 1  /* blocks 1+2 in one kernel, block 3 */
+#define DFA_CNN2D_PATH_CONV123 2 /* blocks 1-3 in one kernel */
+#define DFA_CNN2D_PLAN_FIELDS 19
+int dfa_cnn2d_forward_plan(const dfa_ctx* ctx, int B, int T, int F, int precision, int ragged, const int* options, int num_cus,
+                           long long* fields, int cap);
 /* Raw copy of the first n (<= 2048) 64-bit words of the probe buffer the "clock_probe" kernels stamp (diagnostics: the fused CNN1D
  * kernel writes, per workgroup b < 128, words 8b..8b+3 = s_memtime at start / after layer 1 / after layer 2 / at the end and
  * 8b+5, 8b+6 = s_memrealtime at start / end).  Synchronises on the context's stream. */

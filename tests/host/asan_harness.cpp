@@ -33,6 +33,23 @@ int main() {
           }
           EXPECT(dfa_workspace_bytes(nullptr, model, 0, T, F, prec) == 0);
         }
+  // ---- the CNN2D forward plan, null context and null options: its total is the planners', a split block 3 has its slabs
+  for (int prec = 0; prec < 3; ++prec)
+    for (int ragged = 0; ragged < 2; ++ragged)
+      for (int T : Ts)
+        for (int F : Fs)
+          for (int B : Bs) {
+            long long f[DFA_CNN2D_PLAN_FIELDS + 1];
+            f[DFA_CNN2D_PLAN_FIELDS] = -7;
+            EXPECT(dfa_cnn2d_forward_plan(nullptr, B, T, F, prec, ragged, nullptr, 256, f, DFA_CNN2D_PLAN_FIELDS) == DFA_CNN2D_PLAN_FIELDS);
+            EXPECT(f[DFA_CNN2D_PLAN_FIELDS] == -7);
+            const size_t n = ragged ? dfa_ragged_workspace_bytes(nullptr, DFA_MODEL_CNN2D, B, T, F, prec)
+                                    : dfa_workspace_bytes(nullptr, DFA_MODEL_CNN2D, B, T, F, prec);
+            EXPECT((size_t)f[8] == n);
+            EXPECT((f[15] == 0 && f[18] == 0) || f[5] > 1);
+            EXPECT(f[17] >= 1 && f[17] <= 4);
+          }
+  EXPECT(dfa_cnn2d_forward_plan(nullptr, 0, 16, 180, DFA_PREC_BF16, 0, nullptr, 256, nullptr, 0) == 0);
   for (int prec = 0; prec < 2; ++prec)
     for (int T : Ts)
       for (int F : Fs) {

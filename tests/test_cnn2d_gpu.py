@@ -349,3 +349,56 @@ def test_cnn2d_pipelined_lds_reads_match_compiler_scheduled_twins(golden):
         ctx.set_option("lds_pipe", 1)
         ctx.set_option("fuse_conv1", 1)
         ctx.set_option("block3_m16", 1)
+
+
+def test_cnn2d_forward_runs_what_its_plan_says():
+    """dfa_cnn2d_forward_plan is the plan dfa_cnn2d_forward reads, so what a forward launches is what the entry reports for the
+    context: the timing slots that recorded an event (conv123 runs in slot 2 and leaves slot 1 empty; conv12 is slot 1, conv1
+    slot 0), the conv123 form and its de-phased build.  Four shapes around the rule's edges, each at time_split = -1 and 3; the
+    expectations at -1 are the rule as tests/golden/cnn2d_forward_plan.npz records it (B * ceil(F / 30) = 512 and 516 fuse blocks
+    1-3, 510 does not and a short T does not split either; [2, 130, 36] splits blocks 1+2 into segments of 6 iterations and block 3
+    into its two canonical chunks of 12, through the chunk slabs).  The split is bit-identical by construction (canonical chunks
+    summed in chunk order), and so is conv123 to the two-kernel path: the logits of the two settings must be equal bit for bit."""
+    import conv123_common as c
+    from dfa_amd import _lib as L
+    ctx = c._ctx()
+    names = L.CNN2D_PLAN_FIELDS
+    CONV12, CONV123 = L.CNN2D_PATH_CONV12, L.CNN2D_PATH_CONV123
+    cases = [((512, 8, 5), {}, dict(path=CONV123)),
+             ((86, 33, 180), {}, dict(path=CONV123)),
+             ((86, 33, 180), {"carry_a1": 0}, dict(path=CONV123, form=c.PERSIST, phase=0)),
+             ((86, 33, 180), {"persist123": 0}, dict(path=CONV123, form=c.PER_UNIT, phase=0)),
+             ((85, 33, 180), {}, dict(path=CONV12, seg12=0, seg3=0, nseg3=1)),
+             ((2, 130, 36), {}, dict(path=CONV12, seg12=6, seg3=12, chunk3=12, nseg3=2, slabs=5))]
+    assert 86 * 6 == 516 and 85 * 6 == 510
+    try:
+        for (B, T, F), opts, expect in cases:
+            m, x = c._model(F), c._x(B, T, F)
+            for k in c.OPTS:
+                ctx.set_option(k, opts.get(k, 1))
+            logits = {}
+            for split in (-1, 3):
+                ctx.set_option("time_split", split)
+                got = L.cnn2d_forward_plan(ctx.handle, B, T, F, L.PREC_BF16)
+                p = dict(zip(names, got))
+                o = (split, 1, 1, 1, opts.get("persist123", 1), opts.get("carry_a1", 1), 1)
+                assert got == L.cnn2d_forward_plan(None, B, T, F, L.PREC_BF16, False, o, c._cus()), ((B, T, F), opts, split)
+                if split == -1:
+                    assert {k: p[k] for k in expect} == expect, ((B, T, F), opts, p)
+                else:
+                    assert p["path"] == CONV12 and p["slabs"] == 5, ((B, T, F), opts, p)     # a forced split never fuses blocks 1-3
+                ctx.timing_reset()
+                ctx.timing(True)
+                logits[split] = m(x).clone()
+                torch.cuda.synchronize()
+                ctx.timing(False)
+                ran = {s for s in range(4) if ctx.timing_read(s)[1] > 0}
+                assert ran == {CONV12: {1, 2, 3}, CONV123: {2, 3}}[p["path"]], ((B, T, F), opts, split, ran, p)
+                assert (ctx.last_conv123_form(), ctx.last_conv123_phase()) == (p["form"], p["phase"]), ((B, T, F), opts, split, p)
+                assert (p["form"] != c.NONE) == (p["path"] == CONV123)
+            assert torch.equal(logits[-1], logits[3]), ((B, T, F), opts, (logits[-1] - logits[3]).abs().max().item())
+    finally:
+        ctx.timing(False)
+        ctx.set_option("time_split", -1)
+        for k in c.OPTS:
+            ctx.set_option(k, 1)

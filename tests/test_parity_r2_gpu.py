@@ -35,7 +35,7 @@ def _model_from_sd(sd, precision="fp32"):
 
 
 def _a2_view(x, B, T, F):
-    """bf16 a2 [B, T/4, F, 64] left in the workspace by the last bf16-mode forward (layout: api.hip plan_cnn2d)."""
+    """bf16 a2 [B, T/4, F, 64] left in the workspace by the last bf16-mode forward (layout: cnn2d_api.hip cnn2d_forward_plan)."""
     from dfa_amd import _lib
     ws = _lib.Context.get(x.device)._ws
     H1, H2 = T // 2, T // 4

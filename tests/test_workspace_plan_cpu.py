@@ -4,8 +4,10 @@ when the batch or the frame count grows, and a ragged plan must cover the unifor
 
 Which planners read the context.  Read in deep-fake-audio-classifier_amd/csrc/*_api.hip: dfa_cae_ragged_workspace_bytes, dfa_dlq_workspace_bytes and the five
 dfa_*_train*_workspace_bytes ignore it ((void)ctx): a null context exercises them completely.  dfa_workspace_bytes and
-dfa_ragged_workspace_bytes read ONE field for DFA_MODEL_CNN2D, the "time_split" option (`ctx ? ctx->time_split : -1`): with a null
-context they give the automatic plan, which reserves the chunk slabs of a split time axis for small batches only.  The plan of a
+dfa_ragged_workspace_bytes (api.hip) hand it to the model's planner, and only the CNN2D's reads it (cnn2d_api.hip: the byte count
+of cnn2d_forward_plan, in which ONE of the context's options counts, "time_split"; a null context plans with the defaults, so
+-1): with a null context they give the automatic plan, which reserves the chunk slabs of a split time axis for small batches only
+(every field of that plan: tests/test_cnn2d_plan_cpu.py).  The plan of a
 FORCED split (time_split > 0 on a large batch) needs a live context and is therefore exercised on the GPU only
 (test_workspace_bounds_gpu.py, test_train_shapes_gpu.py::test_forced_time_split_at_full_batch_stays_inside_the_workspace).
 

@@ -1,6 +1,7 @@
 """A/B two builds of the library (separate processes, alternating): DFA_LIB=<file name under lib/>; DFA_AB_MODE=train times the
 bf16 training step instead of the eval forward, DFA_AB_MODE=train1d the CNN1D's (fp32) uniform training step, DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
-z-score fused) at [256, 321, 180]."""
+z-score fused) at [256, 321, 180].  The eval forward runs at [DFA_AB_B, 321, 180] (default 256) and prints the median round's
+ms per call, its timing slots 0-3 and a checksum of the logits."""
 import os, sys, time, torch
 sys.path.insert(0, os.getcwd())
 from dfa_amd import _lib
@@ -74,7 +75,8 @@ if os.environ.get("DFA_AB_MODE") == "cae":
 dev = torch.device("cuda", 0)
 g = torch.Generator().manual_seed(1234)
 PREC = os.environ.get("DFA_AB_PREC", "bf16")
-x = (torch.randn(256, 180, 321, generator=g) * 3.2 - 0.07).to(device=dev, dtype=torch.bfloat16 if PREC == "bf16" else torch.float32).transpose(1, 2)
+B = int(os.environ.get("DFA_AB_B", "256"))     # eval forward: the batch size ([B, 321, 180]; 1 = the host's time per call shows)
+x = (torch.randn(B, 180, 321, generator=g) * 3.2 - 0.07).to(device=dev, dtype=torch.bfloat16 if PREC == "bf16" else torch.float32).transpose(1, 2)
 ctx = _lib.Context.get(dev)
 model = bench.build_model(torch, dev, PREC)
 for _ in range(10): model(x)
@@ -87,4 +89,4 @@ for rnd in range(5):
     ctx.timing(False)
     sl = [ctx.timing_read(s) for s in range(4)]
     out.append((round(dt * 1e3, 4), [round(ms / max(n, 1), 4) for ms, n in sl]))
-print(name, sorted(out)[len(out)//2], flush=True)
+print(name, "B", B, sorted(out)[len(out)//2], "checksum %.9g" % float(model(x).double().sum()), flush=True)
