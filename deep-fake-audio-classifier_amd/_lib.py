@@ -117,6 +117,7 @@ SYMBOLS = [
     ("dfa_ctx_timing_read", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     ("dfa_ctx_last_conv123_form", C.c_int, [C.c_void_p]),
     ("dfa_ctx_last_conv123_phase", C.c_int, [C.c_void_p]),
+    ("dfa_ctx_last_conv123_cls", C.c_int, [C.c_void_p]),
     ("dfa_cnn2d_forward_plan", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                          C.POINTER(C.c_longlong), C.c_int]),
     ("dfa_ctx_debug_read", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]),
@@ -261,6 +262,10 @@ class Context:
     def last_conv123_phase(self) -> int:
         """1 if the last CNN2D eval forward ran the de-phased build of the carry form (option "phase123"), else 0."""
         return int(self.lib.dfa_ctx_last_conv123_phase(self.handle))
+
+    def last_conv123_cls(self) -> int:
+        """1 if the last CNN2D eval forward computed the logits inside the blocks 1-3 kernel (option "cls123"), else 0."""
+        return int(self.lib.dfa_ctx_last_conv123_cls(self.handle))
 
     def clock_read(self):
         """(median, min, max GHz, workgroups) of the last bf16 CNN2D block-3 launch run with set_option("clock_probe", 1)."""

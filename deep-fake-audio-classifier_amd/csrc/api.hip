@@ -168,7 +168,7 @@ const Option kOptions[] = {
     {"block3_m16", &dfa_ctx::block3_m16, OPT_FLAG}, {"fuse_conv1", &dfa_ctx::fuse_conv1, OPT_FLAG},
     {"fuse_blocks123", &dfa_ctx::fuse_blocks123, OPT_FLAG}, {"persist123", &dfa_ctx::persist123, OPT_FLAG},
     {"lds_pipe", &dfa_ctx::lds_pipe, OPT_FLAG}, {"carry_a1", &dfa_ctx::carry_a1, OPT_FLAG},
-    {"phase123", &dfa_ctx::phase123, OPT_FLAG},
+    {"phase123", &dfa_ctx::phase123, OPT_FLAG}, {"cls123", &dfa_ctx::cls123, OPT_FLAG},
 };
 }  // namespace
 
@@ -216,6 +216,7 @@ int dfa_ctx_timing_read(dfa_ctx* ctx, int slot, float* total_ms, int* count) {
   float sum = 0.f;
   for (int i = 0; i < t.used; ++i) {
     DFA_HIP_CHECK(ctx, hipEventSynchronize(t.stop[i]));
+    if (t.empty[i]) continue;   // a stage that launched nothing: the record counts, its duration is 0
     float ms = 0.f;
     DFA_HIP_CHECK(ctx, hipEventElapsedTime(&ms, t.start[i], t.stop[i]));
     sum += ms;
@@ -250,6 +251,7 @@ int dfa_ctx_clock_read(dfa_ctx* ctx, double* ghz_median, double* ghz_min, double
 
 int dfa_ctx_last_conv123_form(const dfa_ctx* ctx) { return ctx ? ctx->last_conv123_form : DFA_E_NULL_PTR; }
 int dfa_ctx_last_conv123_phase(const dfa_ctx* ctx) { return ctx ? ctx->last_conv123_phase : DFA_E_NULL_PTR; }
+int dfa_ctx_last_conv123_cls(const dfa_ctx* ctx) { return ctx ? ctx->last_conv123_cls : DFA_E_NULL_PTR; }
 
 int dfa_ctx_debug_read(dfa_ctx* ctx, long long* host_words, int n) {
   if (!ctx || !host_words) return DFA_E_NULL_PTR;

@@ -2,6 +2,7 @@
 // parameter binding, weight preparation, and the ONE plan every caller reads (cnn2d_forward_plan below; dfa_cnn2d_forward_plan
 // reports it): which kernels a forward runs, how it segments the time axis, where things live in the workspace.  The paths:
 //   conv123 (blocks 1-3 + time mean in one kernel, conv123_*.hip)                                            ->  linear
+//           (conv123_cls.hip, where the phase form runs: the linear head inside that kernel, no launch behind it)
 //   conv12 (blocks 1+2, conv12_fused.hip)  ->  block 3 (+BN+ReLU+mean_T)                   [->  emb_reduce]  ->  linear
 //   conv1 (+BN+ReLU+pool)  ->  block 2 MFMA conv (+BN+ReLU+pool)  ->  block 3 MFMA conv    [->  emb_reduce]  ->  linear
 #include <algorithm>
@@ -228,6 +229,7 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   TraceRange trace_("dfa_cnn2d_forward");
   if (!ctx) return DFA_E_NULL_PTR;
   Cnn2dState& m = ctx->cnn2d;
+  ctx->last_conv123_cls = 0;     // (also where a check below refuses the call)
   DFA_TRY(cnn2d_forward_front(ctx, false, x && logits && workspace, x_dtype, B, T, F));
   const int prec = m.prepared_prec;
   const Cnn2dForwardPlan pl = plan_for(ctx, B, T, F, prec, false);
@@ -240,13 +242,22 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   // (the de-phased build is the carry form with the roles' step edges moved apart: bit-identical results, the value reported stays CARRY)
   ctx->last_conv123_form = pl.p123.form;
   ctx->last_conv123_phase = pl.p123.phase;
+  // The phase form with the classifier head inside (conv123_cls.hip): wherever the phase form runs, unless linear1_kernel would
+  // take its scalar path (weights or embedding not 16-byte aligned), which the kernel does not reproduce.  Same plan, same
+  // form and phase reported; the head runs in the kernel where that build has it (conv123_cls_in_kernel: the shipped one does).
+  const float* const cls_w = m.p[18];
+  const bool cls123 = pl.path == DFA_CNN2D_PATH_CONV123 && pl.p123.phase && ctx->cls123 && (((uintptr_t)cls_w | (uintptr_t)emb) & 15) == 0;
+  bool head_done = false;
   if (pl.path == DFA_CNN2D_PATH_CONV123) {
     ScopedSlot ts(ctx, 2);
-    const Conv123Args a = c123_args(x, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, m.c3_m16, m.c3.bias, emb,
+    Conv123Args a = c123_args(x, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, m.c3_m16, m.c3.bias, emb,
                                     B, T, F, pl.chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr);
-    const auto launch = pl.p123.phase ? launch_conv123_phase : pl.p123.form == DFA_CONV123_CARRY ? launch_conv123_carry :
+    if (cls123) { a.cls_w = cls_w; a.cls_b = m.p[19]; a.logits = logits; a.cls_K = 128 * F; }
+    const auto launch = cls123 ? launch_conv123_cls : pl.p123.phase ? launch_conv123_phase : pl.p123.form == DFA_CONV123_CARRY ? launch_conv123_carry :
                         pl.p123.form == DFA_CONV123_PERSIST ? launch_conv123_persist : launch_conv123_fused;
     DFA_HIP_CHECK(ctx, launch(a, x_dtype, ctx->num_cus, s, ctx->lds_pipe));
+    head_done = cls123 && conv123_cls_in_kernel();
+    ctx->last_conv123_cls = head_done ? 1 : 0;
   } else if (pl.path == DFA_CNN2D_PATH_CONV12) {
     ScopedSlot ts(ctx, 1);
     DFA_HIP_CHECK(ctx, launch_conv12_fused(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, a2,
@@ -284,7 +295,8 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
     }
   }
   {
-    ScopedSlot ts(ctx, 3);
+    ScopedSlot ts(ctx, 3);      // one record per forward, also where the head ran inside the blocks 1-3 kernel: then of 0 ms
+    if (head_done) { ts.nothing_launched(); return DFA_OK; }
     if (pl.nseg3 > 1) {   // chunk slabs 1 .. nseg3 of the workspace region -> the embedding (slab 0 of the region, or the caller's buffer)
       const size_t n = (size_t)B * 128 * F;
       DFA_HIP_CHECK(ctx, launch_emb_reduce((const float*)(ws + pl.emb_off) + n, pl.nseg3, n, n, 1.0f / (float)pl.H2, emb, s));

@@ -3,12 +3,14 @@
 //   conv123_persist.hip  one workgroup per CU walking a contiguous range of units        (PERSIST = true)
 //   conv123_carry.hip    the persistent form, two a1 columns carried from strip to strip (PERSIST = true, CARRY = true)
 //   conv123_phase.hip    the carry form, consumers' step barrier behind read 35, consumers at s_setprio 1 (DFA_C123_CBAR / _PRIO)
+//   conv123_cls.hip      the phase form, classifier head at the end of the workgroup (DFA_C123_CLS; build option
+//                        DFA_C123_LATE_EMIT: time mean stored under the next unit's step 0)
 // The roles, the column bookkeeping and the per-step schedule are described at the top of conv123_fused.hip; the unit
 // boundary of the persistent form at the top of conv123_persist.hip, the carried columns at the top of conv123_carry.hip.
 // With PERSIST = false every `if constexpr (PERSIST)` below drops out and the functions are the per-unit kernel's bodies;
 // with CARRY = false every `CARRY` term is a constant and the producers are those of the two older kernels.
 #ifndef DFA_CONV123_BODY_SCOPE
-#error "conv123_body.h holds kernel bodies: include it only from conv123_fused.hip, conv123_persist.hip, conv123_carry.hip and conv123_phase.hip"
+#error "conv123_body.h holds kernel bodies: include it only from the conv123_*.hip kernel files"
 #endif
 #ifndef DFA_CONV123_BODY_H
 #define DFA_CONV123_BODY_H
@@ -35,6 +37,23 @@
 // is not declared at all in the two older kernels, whose instruction streams an unused lambda already disturbs.
 #ifndef DFA_C123_CARRY
 #define DFA_C123_CARRY 0
+#endif
+// Set by conv123_cls.hip alone (PERSIST consumers; the argument for both stands at the top of that file).
+// LATE_EMIT: the time-mean stores of a unit follow the first idle barrier of the next unit instead of preceding it, so that
+// the producers' step 0 does not wait for them.  EMIT_PRIO0: those stores run at s_setprio 0 (a measured variant).
+// CLS (CARRY only: a workgroup owns whole utterances): after its last unit the workgroup's consumer waves compute the
+// classifier head of its utterances from the emb rows they have just stored, as linear1_kernel (linear.hip) would.
+#ifndef DFA_C123_LATE_EMIT
+#define DFA_C123_LATE_EMIT 0
+#endif
+#ifndef DFA_C123_EMIT_PRIO0
+#define DFA_C123_EMIT_PRIO0 0
+#endif
+#ifndef DFA_C123_CLS
+#define DFA_C123_CLS 0
+#endif
+#if DFA_C123_CLS && !DFA_C123_CARRY
+#error "DFA_C123_CLS needs the carry form: a workgroup's range must be whole utterances"
 #endif
 
 namespace dfa {
@@ -184,6 +203,9 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
 #ifdef DFA_STAMPS
   C123Stamps stamps;
   const int stamp_u0 = u;
+#endif
+#if DFA_C123_CLS
+  const int cls_u0 = u;
 #endif
 
   uint4 w[9][NKG];
@@ -674,12 +696,73 @@ __device__ __forceinline__ void c123_producer(const Conv123Args& a, char* smem, 
     barrier();
     barrier();                 // idle step niter3 + 1 of the last unit
     C123_STAMP(3);
+#if DFA_C123_CLS
+    // the consumers' classifier barriers (c123_classifier): one, then one per utterance of the range
+    for (int k = (u_end - cls_u0) / a.nstrips; k >= 0; --k) __syncthreads();
+#endif
   }
 #ifdef DFA_STAMPS
   stamps.write(wave, lane, (PERSIST ? u_end : stamp_u0 + 1) - stamp_u0);
 #endif
 #undef DFA_C123_PRODUCER_STEPS
 }
+
+#if DFA_C123_CLS
+// ---------------------------------------------------------------------------------------------------------- classifier
+// logits[bb] for the utterances [b0, b1) of the workgroup, by its four consumer waves, behind the last time-mean stores of the
+// last unit: linear1_kernel's operation sequence (linear.hip) with the consumer thread number in the role of its thread
+// number -- one fmaf chain per thread over the float4 words ctid + 256 k (x, y, z, w in that order), the same shuffle tree,
+// the same ((p0 + p1) + (p2 + p3)) + bias -- so the logits are the bits the separate launch gives.  The launcher takes this
+// kernel only where emb rows and weights are 16-byte aligned (K = 128 F is a multiple of 4: no scalar tail).
+// Visibility.  The emb rows were stored by these four waves, each lane its own words, and are read across waves: every wave
+// waits for its stores (release at workgroup scope = vmcnt(0); the waves of a workgroup share the CU's vector L1, which
+// the stores write through), all meet at a workgroup barrier, then acquire.  No other workgroup reads or writes these rows.
+// Barriers: 1 + (b1 - b0), all eight waves (the producers execute the same number before they return: c123_producer).
+// The partial sums alternate between two sets of four words of the block-3 bias area (read by the consumers alone, last in
+// front of their last step barrier): the writers of utterance i + 2 have passed the barrier of utterance i + 1, which thread
+// 0 reaches only after it has read the words of utterance i.
+// The lane number is a fresh one (c123_fresh_lane): no address below is computed before the loop over units.
+__device__ __forceinline__ void c123_classifier(const Conv123Args& a, char* smem, int cwave, int b0, int b1) {
+  using namespace c123;
+  constexpr int NB = 8;                            // float4 pairs in flight per thread
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // the time-mean stores of the last unit (and every LDS read)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  const int clane = c123_fresh_lane(), ctid = cwave * 64 + clane;
+  float* const part = (float*)(smem + CBIAS_OFF);
+  const int K4 = a.cls_K >> 2;
+  const float4* const w4 = reinterpret_cast<const float4*>(a.cls_w);
+  for (int bb = b0; bb < b1; ++bb) {
+    const float4* const e4 = reinterpret_cast<const float4*>(a.emb + (size_t)bb * a.cls_K);
+    float acc = 0.f;
+    for (int j0 = ctid; j0 < K4; j0 += 256 * NB) {
+      float4 ev[NB], wv[NB];
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        const int j = j0 + 256 * k, jc = j < K4 ? j : j0;      // (past the end: a word this thread owns anyway, not used)
+        ev[k] = e4[jc];
+        wv[k] = w4[jc];
+      }
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        float t = acc;
+        t = fmaf(ev[k].x, wv[k].x, t);
+        t = fmaf(ev[k].y, wv[k].y, t);
+        t = fmaf(ev[k].z, wv[k].z, t);
+        t = fmaf(ev[k].w, wv[k].w, t);
+        acc = (j0 + 256 * k < K4) ? t : acc;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    float* const pp = part + 4 * ((bb - b0) & 1);
+    if (clane == 0) pp[cwave] = acc;
+    __syncthreads();
+    if (ctid == 0) a.logits[bb] = ((pp[0] + pp[1]) + (pp[2] + pp[3])) + a.cls_b[0];
+  }
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------------------- consumers
 // conv3_m16_meant_kernel's eval unit on the 4-block ring the producers fill.  Barrier count: 4 (prologue) + 2 (idle steps)
@@ -866,9 +949,33 @@ __device__ __forceinline__ void c123_consumer(const Conv123Args& a, char* smem, 
     C123_STAMP(4);
   } else {
     const int bid = blockIdx.x;
+#if DFA_C123_LATE_EMIT || DFA_C123_CLS
+    const int u_first = u;
+#endif
     long long sum_c = 0, sum_r = 0;               // the probe reports the main loops of all units of the workgroup
     for (;;) {
+#if DFA_C123_LATE_EMIT
+      // The time mean of the unit before this one goes out between the two idle barriers, under the producers' step 0 (which
+      // stands behind the first of them), and the totals are zeroed behind it: this lane's own LDS words, long before the
+      // first flush of this unit.  Ring row -1 was zeroed behind N1, both idle barriers before its first reader.
+      barrier();                                  // idle step 0
+      if (u != u_first) {
+        C123_STAMP(1);
+        int pl = p, ql = q;
+        asm volatile("" : "+v"(pl), "+v"(ql));
+        if (DFA_C123_EMIT_PRIO0 && DFA_C123_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        DFA_C123_EMIT(pl, ql)
+        if (DFA_C123_EMIT_PRIO0 && DFA_C123_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+        C123_STAMP(4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tot[k * NT] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        b = u / a.nstrips;
+        f0 = (u - b * a.nstrips) * SW;
+      }
+      barrier();                                  // idle step 1
+#else
       barrier(); barrier();                       // idle steps 0, 1
+#endif
       C123_STAMP(1);
       next_flush = min(niter, chunk);
       if (probe) {
@@ -889,6 +996,11 @@ __device__ __forceinline__ void c123_consumer(const Conv123Args& a, char* smem, 
       if (!last) {
         barrier();
         *(uint4*)(smem + ctid * 16) = make_uint4(0u, 0u, 0u, 0u);
+#if DFA_C123_LATE_EMIT
+        C123_STAMP(4);
+        ++u;                                      // (b, f0) stay the finished unit's until its time mean is out: loop top
+        continue;
+#endif
       }
       // the time mean of unit (b, f0) -> emb.  (The lane numbers go through an empty asm so that no address of these
       // stores is computed before the loop over units and kept across the main loop, which has no register to spare.)
@@ -907,6 +1019,10 @@ __device__ __forceinline__ void c123_consumer(const Conv123Args& a, char* smem, 
       a.clock_stamps[2 * bid] = sum_c;
       a.clock_stamps[2 * bid + 1] = sum_r;
     }
+#if DFA_C123_CLS
+    c123_classifier(a, smem, nsl, u_first / a.nstrips, u_end / a.nstrips);
+    C123_STAMP(4);
+#endif
   }
 #undef DFA_C123_CONSUMER_STEPS
 #undef DFA_C123_EMIT

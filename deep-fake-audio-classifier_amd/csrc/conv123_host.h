@@ -22,6 +22,11 @@ struct Conv123Args {
   int B, T, F, H1, H2, nstrips;
   int chunk_iters;          // canonical chunks of the time mean (conv3_m16.hip)
   long long* clock_stamps;  // held-clock probe (ConvArgs::clock_stamps), null = off
+  // conv123_cls.hip alone (appended: the offsets above are those of the four older kernels); set by the dispatcher, null / 0 elsewhere
+  const float* cls_w;       // [K] classifier weights, 16-byte aligned
+  const float* cls_b;       // [1]
+  float* logits;            // [B]
+  int cls_K;                // 128 * F
 };
 static inline Conv123Args c123_args(const void* x, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack, const float* c1bias,
                                     const uint4* wpack2, const float* bias2, const uint4* wpack3, const float* bias3, float* emb, int B,
@@ -42,6 +47,11 @@ hipError_t launch_conv123_fused(const Conv123Args& a, int x_dtype, int num_cus, 
 hipError_t launch_conv123_persist(const Conv123Args& a, int x_dtype, int num_cus, hipStream_t s, int pipe);
 hipError_t launch_conv123_carry(const Conv123Args& a, int x_dtype, int num_cus, hipStream_t s, int pipe);
 hipError_t launch_conv123_phase(const Conv123Args& a, int x_dtype, int num_cus, hipStream_t s, int pipe);
+// the phase form with, where conv123_cls_in_kernel() answers 1 (the shipped build), the classifier head at the end of every
+// workgroup: a.cls_w, a.cls_b, a.logits, a.cls_K must be set, cls_w
+// and emb 16-byte aligned, and the caller launches no linear1_kernel behind it (conv123_cls.hip)
+hipError_t launch_conv123_cls(const Conv123Args& a, int x_dtype, int num_cus, hipStream_t s, int pipe);
+int conv123_cls_in_kernel();
 // which form runs for these dimensions and options: form = DFA_CONV123_*, phase = the de-phased build of the carry form, grid
 // workgroups of 512 threads, lds bytes of dynamic LDS.  (Defined in conv123_carry.hip: the LDS layout constants it needs are
 // conv123_body.h's, which only the kernel files may include.)

@@ -24,6 +24,7 @@ constexpr int kEventsPerSlot = 256;
 
 struct SlotTimer {
   std::vector<hipEvent_t> start, stop;
+  std::vector<char> empty;   // 1 = the record stands for a stage that launched nothing: it counts, with zero duration (ScopedSlot::nothing_launched)
   int used = 0;
 };
 
@@ -147,6 +148,8 @@ struct dfa_ctx {
   int persist123 = 1;          // where blocks 1-3 are fused: 1 = one workgroup per CU over a contiguous range of units (conv123_persist.hip), 0 = one workgroup per unit
   int carry_a1 = 1;            // where persist123 applies and every workgroup's range is a whole number of utterances: the two left a1 halo columns of a strip come from the strip before it (conv123_carry.hip), 0 = conv123_persist.hip
   int phase123 = 1;            // where the carry form runs: its de-phased build (consumers' step barrier behind fragment read 35, consumers at s_setprio 1: conv123_phase.hip), 0 = conv123_carry.hip
+  int cls123 = 1;              // where the phase form runs: conv123_cls.hip (classifier head inside the kernel, no linear1_kernel launch), 0 = conv123_phase.hip + linear1_kernel.  Not a plan option: the plan's values do not depend on it
+  int last_conv123_cls = 0;    // 1 = the last dfa_cnn2d_forward computed the logits inside the blocks 1-3 kernel (dfa_ctx_last_conv123_cls)
   int last_conv123_phase = 0;  // 1 = the last dfa_cnn2d_forward ran conv123_phase.hip (dfa_ctx_last_conv123_phase)
   int last_conv123_form = 0;   // blocks 1-3 of the last dfa_cnn2d_forward: DFA_CONV123_* (dfa_ctx_last_conv123_form)
   int num_cus = 0;             // hipDeviceAttributeMultiprocessorCount of `device`, asked once in dfa_ctx_create (grid of the persistent kernel)
@@ -224,13 +227,18 @@ struct ScopedSlot {
       if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
       t.start.push_back(a);
       t.stop.push_back(b);
+      t.empty.push_back(0);
     }
     idx = t.used++;
+    t.empty[idx] = 0;
     (void)hipEventRecord(t.start[idx], ctx->stream);
   }
   ~ScopedSlot() {
     if (idx >= 0) (void)hipEventRecord(ctx->slots[slot].stop[idx], ctx->stream);
   }
+  // the stage this slot times ran inside another kernel and launched nothing of its own: callers still find one record per
+  // call in the slot, and dfa_ctx_timing_read adds exactly 0 ms for it
+  void nothing_launched() { if (idx >= 0) ctx->slots[slot].empty[idx] = 1; }
 };
 
 // ---- launch prototypes (one translation unit each, see Makefile) ---------------------------------

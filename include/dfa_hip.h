@@ -86,6 +86,11 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *   "phase123"      1 (default) = where carry_a1 applies, the build of that kernel whose consumer waves hold their step barrier
  *                   late in their operand reads and run at raised issue priority, so that the MFMA-free parts of the two
  *                   roles' steps do not coincide; 0 = the carry_a1 kernel as it was.  Bit-identical results
+ *   "cls123"        1 (default) = where phase123 applies and the classifier weights and the embedding are 16-byte aligned, the
+ *                   build of that kernel which computes the
+ *                   logits at the end of each workgroup, from the embedding rows it has just written: no linear1_kernel launch
+ *                   (timing slot 3 keeps its one record per forward, of exactly 0 ms: no launch in it).  0 = the phase123 kernel and the separate classifier launch.  Bit-identical
+ *                   logits and embeddings.  Not one of the plan's options: dfa_cnn2d_forward_plan answers the same either way
  *   "time_split"    -1 (default) = CNN2D eval forward splits the time axis over workgroups when the batch alone cannot fill
  *                   the chip (B * strips below the resident-workgroup count, e.g. the reference's predict batch of 32), 0 =
  *                   never, n > 0 = force n segments (at most 4).  Logits and embeddings are bit-identical for every setting and
@@ -478,6 +483,10 @@ int dfa_ctx_last_conv123_form(const dfa_ctx* ctx);
 /* 1 if blocks 1-3 of the LAST dfa_cnn2d_forward ran the "phase123" build of the carry form (the form above is then
  * DFA_CONV123_CARRY: it is that form), else 0; ctx NULL: DFA_E_NULL_PTR. */
 int dfa_ctx_last_conv123_phase(const dfa_ctx* ctx);
+/* 1 if the LAST dfa_cnn2d_forward computed the logits inside the blocks 1-3 kernel (option "cls123"; form and phase above
+ * read DFA_CONV123_CARRY and 1: it is that kernel with the classifier head at its end), 0 if linear1_kernel was launched or
+ * the call was refused; ctx NULL: DFA_E_NULL_PTR. */
+int dfa_ctx_last_conv123_cls(const dfa_ctx* ctx);
 /* The plan of a CNN2D eval forward of [B, T, F] in `precision` (ragged != 0: of dfa_cnn2d_forward_ragged at T = T_max): the
  * very function dfa_cnn2d_forward[_ragged] and the two workspace planners read, reported.  Pure host arithmetic.  With a
  * context: for its options and its device's CU count (`options` and `num_cus` are not read).  Without one: for the seven

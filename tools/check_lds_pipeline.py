@@ -5,7 +5,9 @@ them with counted `s_waitcnt lgkmcnt(N)`.  Between the read and the wait the com
 already hold the data; if register pressure makes it copy or spill such a register (v_accvgpr_write, scratch_store,
 v_mov ...) before the wait, it moves stale data.  This script compiles a .hip file to gfx950 assembly and verifies, per
 kernel, that no instruction touches the destination of an in-flight asm read before a wait has retired it, and that
-no asm read is in flight across a loop back-edge (forward skips are covered by the linear scan).
+no asm read is carried around a loop: forward skips are covered by the linear scan, and a backward branch taken with reads in
+flight (a join block or the top of a rotated loop placed above the branch) is followed from its target, with the state at the
+branch, until those reads have been retired.
 
 Second rule (round 2): MATRIX-OPERAND PROVENANCE.  The wrong sums round 1 recorded for the pipelined one-wave-per-SIMD fp32
 ACCIN kernel were traced (tools/gpu_accin_probe2.py + the ISA) to a register-allocation miscompile of hipcc (ROCm 7.2), not
@@ -87,78 +89,169 @@ def resource_usage(path):
     return text, usage
 
 
+class _Lds:
+    """issue-ordered outstanding operations of a wave: `queue` LDS ops (is_asm_read, dest regs, line no), `vqueue` vector-memory
+    ops (vmcnt retires them in order): (is_asm_load, dest regs, line no)"""
+    def __init__(self, queue=(), vqueue=(), in_asm=False):
+        self.queue, self.vqueue, self.in_asm = list(queue), list(vqueue), in_asm
+
+    def copy(self):
+        return _Lds(self.queue, self.vqueue, self.in_asm)
+
+    def inflight(self):
+        return set().union(*[q[1] for q in self.queue if q[0]]) if self.queue else set()
+
+    def vinflight(self):
+        return set().union(*[q[1] for q in self.vqueue if q[0]]) if self.vqueue else set()
+
+
+def _clean(raw):
+    return raw.split(";")[0].strip() if not raw.strip().startswith(";;#") else raw.strip()
+
+
+def _step(st, kernel, ln, line, violations):
+    """one instruction (not a label, branch, kernel header or s_endpgm) against the state; returns the asm reads it issued"""
+    if line.startswith(";;#ASMSTART"):
+        st.in_asm = True
+        return 0
+    if line.startswith(";;#ASMEND"):
+        st.in_asm = False
+        return 0
+    inflight, vinflight = st.inflight(), st.vinflight()
+    m = LGKM.search(line)
+    if line.startswith("s_waitcnt"):
+        mv = VMC.search(line)
+        if mv:
+            n = int(mv.group(1))
+            st.vqueue = st.vqueue[len(st.vqueue) - n:] if n else []
+        if m:
+            n = int(m.group(1))
+            st.queue = st.queue[len(st.queue) - n:] if n < len(st.queue) else st.queue
+            if n == 0:
+                st.queue = []
+        return 0
+    if line.startswith("s_barrier"):
+        return 0
+    touched = regs_of(line)
+    if st.in_asm and line.startswith("buffer_load"):     # asm global -> register load (wgrad_mfma.hip): same contract, on vmcnt
+        dest = regs_of(line.split(",")[0])
+        if dest & (vinflight | inflight):
+            violations.append((kernel, ln, "asm buffer load overwrites an in-flight destination: " + line))
+        if (regs_of(",".join(line.split(",")[1:])) & (vinflight | inflight)):
+            violations.append((kernel, ln, "asm buffer load reads an in-flight destination: " + line))
+        st.vqueue.append((True, dest, ln))
+        return 1
+    if touched & vinflight:
+        violations.append((kernel, ln, "touches an in-flight buffer-load destination: " + line))
+    if line.startswith(VMEM_OPS):
+        st.vqueue.append((False, set(), ln))
+    if st.in_asm and line.startswith("ds_read"):
+        dest = regs_of(line.split(",")[0])
+        if dest & inflight:
+            violations.append((kernel, ln, "asm read overwrites an in-flight destination: " + line))
+        st.queue.append((True, dest, ln))
+        return 1
+    if touched & inflight:
+        violations.append((kernel, ln, "touches an in-flight LDS destination: " + line))
+    if line.startswith("ds_"):
+        st.queue.append((False, set(), ln))
+    return 0
+
+
+FOLLOW_LINES = 4000   # a followed path retires its reads within one step of a main loop; far below this
+
+
+def _skips_to_join(lines, i, target):
+    """lines[i - 1] is `s_cbranch_execz target`: True if it is the skip of an exec-masked block whose other end is an unconditional
+    `s_branch target` -- an `if` whose join block was placed above it.  The masked block holds LDS stores the counted waits include
+    and the kernels keep its mask non-empty, so the path is the one through the block (as for a forward skip, where the linear
+    scan assumes the same) and the s_branch carries the state to the join."""
+    for raw in lines[i:i + 60]:
+        line = _clean(raw)
+        if line.endswith(":") and not line.startswith(";;#"):
+            return False
+        if line.startswith("s_branch"):
+            return line.split()[-1] == target
+        if line.startswith("s_cbranch") or line.startswith("s_endpgm"):
+            return False
+    return False
+
+
+def _follow(lines, label_at, kernel, start, st, seen, violations, origin):
+    """The taken path of a BACKWARD branch that has asm LDS reads in flight (block placement puts a join block, or the top of a
+    rotated loop, above the branch): walk it from the target with the state at the branch until every such read has been
+    retired.  Forward conditional branches are passed as in the linear scan, forward unconditional ones are taken; a second
+    backward branch is followed in turn, and a label met twice with reads still in flight is a loop that carries them."""
+    i, budget = start, FOLLOW_LINES
+    while i < len(lines) and budget > 0:
+        raw = lines[i]
+        line = _clean(raw)
+        i += 1
+        budget -= 1
+        if not line or (line.endswith(":") and not line.startswith(";;#")):
+            continue
+        if raw.startswith("_Z") or line.startswith("s_endpgm"):
+            return
+        if line.startswith("s_cbranch") or line.startswith("s_branch"):
+            target = line.split()[-1]
+            t = label_at.get(target)
+            if t is not None and t < i:                # backward again
+                if line.startswith("s_cbranch_execz") and _skips_to_join(lines, i, target):
+                    continue
+                if target in seen:
+                    violations.append((kernel, origin, "asm LDS read in flight around a loop (followed from here to line %d): %s" % (i, line)))
+                    return
+                _follow(lines, label_at, kernel, t, st.copy(), seen | {target}, violations, origin)
+                if line.startswith("s_branch"):
+                    return
+            elif line.startswith("s_branch") and t is not None:
+                i = t
+            continue
+        _step(st, kernel, i, line, violations)
+        if not st.inflight():
+            return
+    violations.append((kernel, origin, "asm LDS read in flight across a backward branch and not retired within %d lines of its target" % FOLLOW_LINES))
+
+
 def check_asm(text):
     """returns (kernels checked, asm reads seen, list of violations)"""
     violations, kernels, nreads = [], 0, 0
-    kernel, queue, in_asm, labels = None, [], False, set()   # queue: issue-ordered LDS ops, entries = (is_asm_read, dest regs, line no)
-    vqueue = []   # issue-ordered vector-memory ops (vmcnt retires them in order): (is_asm_load, dest regs, line no)
-    for ln, raw in enumerate(text.split("\n"), 1):
-        line = raw.split(";")[0].strip() if not raw.strip().startswith(";;#") else raw.strip()
+    lines = text.split("\n")
+    label_at = {}
+    for i, raw in enumerate(lines):
+        line = _clean(raw)
+        if line.endswith(":") and not line.startswith(";;#"):
+            label_at[line[:-1]] = i
+    kernel, st, labels = None, _Lds(), set()
+    for ln, raw in enumerate(lines, 1):
+        line = _clean(raw)
         if raw.startswith("_Z") and raw.rstrip().split(";")[0].rstrip().endswith(":"):
-            kernel, queue, vqueue, labels = raw.split(":")[0], [], [], set()
+            kernel, st, labels = raw.split(":")[0], _Lds(), set()
             kernels += 1
             continue
         if kernel is None or not line:
             continue
-        if line.startswith(";;#ASMSTART"):
-            in_asm = True
+        if line.startswith("s_endpgm"):            # one exit of possibly several: what follows is reached by branches only
+            st = _Lds()
             continue
-        if line.startswith(";;#ASMEND"):
-            in_asm = False
-            continue
-        if line.startswith("s_endpgm"):
+        if line.startswith(".Lfunc_end"):
             kernel = None
             continue
-        inflight = set().union(*[q[1] for q in queue if q[0]]) if queue else set()
-        vinflight = set().union(*[q[1] for q in vqueue if q[0]]) if vqueue else set()
-        if line.endswith(":"):                      # label: a forward skip lands here, the linear scan covers both paths
+        if line.endswith(":") and not line.startswith(";;#"):   # label: a forward skip lands here, the linear scan covers both paths
             labels.add(line[:-1])
             continue
         if line.startswith("s_cbranch") or line.startswith("s_branch"):
-            if inflight and line.split()[-1] in labels:   # backward branch (loop): nothing may be in flight
-                violations.append((kernel, ln, "asm LDS read in flight across a loop back-edge: " + line))
-            if vinflight and line.split()[-1] in labels:
+            target = line.split()[-1]
+            if st.inflight() and target in labels and line.startswith("s_cbranch_execz") and _skips_to_join(lines, ln, target):
+                continue
+            if st.inflight() and target in labels:     # backward branch: a loop, or a block placed above its predecessor
+                _follow(lines, label_at, kernel, label_at[target], st.copy(), {target}, violations, ln)
+                if line.startswith("s_branch"):        # nothing falls through: the state went with the branch
+                    st.queue = [(False, set(), q[2]) for q in st.queue]
+            if st.vinflight() and target in labels:
                 violations.append((kernel, ln, "asm buffer load in flight across a loop back-edge: " + line))
             continue
-        m = LGKM.search(line)
-        if line.startswith("s_waitcnt"):
-            mv = VMC.search(line)
-            if mv:
-                n = int(mv.group(1))
-                vqueue = vqueue[len(vqueue) - n:] if n else []
-            if m:
-                n = int(m.group(1))
-                queue = queue[len(queue) - n:] if n < len(queue) else queue
-                if n == 0:
-                    queue = []
-            continue
-        if line.startswith("s_barrier"):
-            continue
-        touched = regs_of(line)
-        if in_asm and line.startswith("buffer_load"):     # asm global -> register load (wgrad_mfma.hip): same contract, on vmcnt
-            dest = regs_of(line.split(",")[0])
-            if dest & (vinflight | inflight):
-                violations.append((kernel, ln, "asm buffer load overwrites an in-flight destination: " + line))
-            if (regs_of(",".join(line.split(",")[1:])) & (vinflight | inflight)):
-                violations.append((kernel, ln, "asm buffer load reads an in-flight destination: " + line))
-            vqueue.append((True, dest, ln))
-            nreads += 1
-            continue
-        if touched & vinflight:
-            violations.append((kernel, ln, "touches an in-flight buffer-load destination: " + line))
-        if line.startswith(VMEM_OPS):
-            vqueue.append((False, set(), ln))
-        if in_asm and line.startswith("ds_read"):
-            dest = regs_of(line.split(",")[0])
-            if dest & inflight:
-                violations.append((kernel, ln, "asm read overwrites an in-flight destination: " + line))
-            queue.append((True, dest, ln))
-            nreads += 1
-            continue
-        if touched & inflight:
-            violations.append((kernel, ln, "touches an in-flight LDS destination: " + line))
-        if line.startswith("ds_"):
-            queue.append((False, set(), ln))
+        nreads += _step(st, kernel, ln, line, violations)
     return kernels, nreads, violations
 
 
