@@ -78,6 +78,7 @@ SYMBOLS = [
                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_size_t]),
     ("dfa_cae_train_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dfa_cae_train_plan", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int]),
     ("dfa_cae_forward_train", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                         C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_size_t]),
@@ -158,6 +159,35 @@ def cnn2d_forward_plan(ctx_handle, B, T, F, precision, ragged=False, options=Non
     if n != len(out):
         raise ValueError(f"dfa_cnn2d_forward_plan([{B}, {T}, {F}]) returned {n}, not {len(out)} fields")
     return tuple(out)
+
+
+class CaeTrainPlan:
+    """dfa_cae_train_plan as named fields (the order of include/dfa_hip.h): H, W, Hd, Wd, the byte offsets e, z, zd, d, dd, dzd, de,
+    dz (tuples; z[0] = dz[0] = -1), zp, xf, raw, stats, sums, wq, dwq, rec, partial, partial_bytes, total, elem, and per BatchNorm
+    layer C, mean, var, invstd."""
+    _GROUPS = (("H", 5), ("W", 5), ("Hd", 4), ("Wd", 4), ("e", 4), ("z", 4), ("zd", 3), ("d", 3), ("dd", 3), ("dzd", 3), ("de", 4),
+               ("dz", 4), ("zp", 0), ("xf", 0), ("raw", 0), ("stats", 0), ("sums", 0), ("wq", 0), ("dwq", 0), ("rec", 0), ("partial", 0),
+               ("partial_bytes", 0), ("total", 0), ("elem", 0), ("C", 7), ("mean", 7), ("var", 7), ("invstd", 7))
+    NFIELDS = sum(max(n, 1) for _, n in _GROUPS)
+
+    def __init__(self, fields):
+        self.fields = tuple(fields)
+        i = 0
+        for name, n in self._GROUPS:
+            setattr(self, name, self.fields[i] if n == 0 else self.fields[i:i + n])
+            i += max(n, 1)
+
+
+def cae_train_plan(ctx_handle, B, T, F, precision):
+    """The workspace layout of a ConvAutoencoder training step (dfa_cae_train_plan); a refused shape or precision raises as the
+    step itself would (the message needs a context)."""
+    out = (C.c_longlong * CaeTrainPlan.NFIELDS)()
+    n = load().dfa_cae_train_plan(ctx_handle, B, T, F, precision, out, len(out))
+    if n < 0:
+        check(ctx_handle, n)
+    if n != len(out):
+        raise ValueError(f"dfa_cae_train_plan([{B}, {T}, {F}]) returned {n}, not {len(out)} fields")
+    return CaeTrainPlan(out)
 
 
 def check(ctx_handle, code):

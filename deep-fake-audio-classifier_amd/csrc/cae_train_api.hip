@@ -107,9 +107,49 @@ Conv1Train conv1_block(CaeState& m, const void* x, int x_dtype, int64_t sb, int6
   return c;
 }
 
+// the plan of a step, or the refusal of its precision or shape (what dfa_cae_forward_train and dfa_cae_train_plan both answer)
+int checked_plan(dfa_ctx* ctx, int B, int T, int F, int precision, CaeTrainPlan* pl) {
+  if (precision != DFA_PREC_F32 && precision != DFA_PREC_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "unknown precision %d", precision);
+  if (B < 1 || T < 16) return fail(ctx, DFA_E_BAD_SHAPE, "need B >= 1 and T >= 16 (got %d, %d)", B, T);
+  *pl = plan_cae_train(B, T, F, precision);
+  if (!pl->ok) return fail(ctx, DFA_E_BAD_SHAPE, "F=%d: decoder would rebuild %d columns (needs F = 16*(F/16)+4)", F, pl->Wd[3]);
+  return DFA_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dfa_cae_train_plan(dfa_ctx* ctx, int B, int T, int F, int precision, long long* fields, int cap) {
+  CaeTrainPlan pl;
+  DFA_TRY(checked_plan(ctx, B, T, F, precision, &pl));
+  long long v[DFA_CAE_TRAIN_PLAN_FIELDS];
+  int n = 0;
+  auto put = [&](long long x) { v[n++] = x; };
+  for (int l = 0; l < 5; ++l) put(pl.H[l]);
+  for (int l = 0; l < 5; ++l) put(pl.W[l]);
+  for (int l = 0; l < 4; ++l) put(pl.Hd[l]);
+  for (int l = 0; l < 4; ++l) put(pl.Wd[l]);
+  for (int l = 0; l < 4; ++l) put((long long)pl.e[l]);
+  for (int l = 0; l < 4; ++l) put(l ? (long long)pl.z[l] : -1);      // block 1's pre-BN output is never stored
+  for (int l = 0; l < 3; ++l) put((long long)pl.zd[l]);
+  for (int l = 0; l < 3; ++l) put((long long)pl.d[l]);
+  for (int l = 0; l < 3; ++l) put((long long)pl.dd[l]);
+  for (int l = 0; l < 3; ++l) put((long long)pl.dzd[l]);
+  for (int l = 0; l < 4; ++l) put((long long)pl.de[l]);
+  for (int l = 0; l < 4; ++l) put(l ? (long long)pl.dz[l] : -1);
+  for (size_t off : {pl.zp, pl.xf, pl.raw, pl.stats, pl.sums, pl.wq, pl.dwq, pl.rec, pl.partial, pl.partial_bytes, pl.total}) put((long long)off);
+  put(precision == DFA_PREC_BF16 ? 2 : 4);
+  for (int l = 0; l < 7; ++l) put(l < 4 ? kEC[l] : kDC[l - 4]);
+  for (int k = 0; k < 3; ++k)       // mean, biased variance, inverse standard deviation: where bn_stats puts them
+    for (int l = 0; l < 7; ++l) {
+      const int C = l < 4 ? kEC[l] : kDC[l - 4];
+      put((long long)(pl.stats + ((size_t)3 * kBnOff[l] + (size_t)k * C) * sizeof(float)));
+    }
+  static_assert(DFA_CAE_TRAIN_PLAN_FIELDS == 18 + 28 + 11 + 1 + 7 + 21, "field table of dfa_cae_train_plan");
+  for (int i = 0; fields && i < cap && i < DFA_CAE_TRAIN_PLAN_FIELDS; ++i) fields[i] = v[i];
+  return DFA_CAE_TRAIN_PLAN_FIELDS;
+}
 
 size_t dfa_cae_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, int precision) {
   (void)ctx;
@@ -128,10 +168,8 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
   if (!x || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x and workspace must be non-null");
   if (!recon && !mse) return fail(ctx, DFA_E_NULL_PTR, "give recon, mse or both (the decoder's last kernel needs an output)");
   if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
-  if (precision != DFA_PREC_F32 && precision != DFA_PREC_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "unknown precision %d", precision);
-  if (B < 1 || T < 16) return fail(ctx, DFA_E_BAD_SHAPE, "need B >= 1 and T >= 16 (got %d, %d)", B, T);
-  const CaeTrainPlan pl = plan_cae_train(B, T, F, precision);
-  if (!pl.ok) return fail(ctx, DFA_E_BAD_SHAPE, "F=%d: decoder would rebuild %d columns (needs F = 16*(F/16)+4)", F, pl.Wd[3]);
+  CaeTrainPlan pl;
+  DFA_TRY(checked_plan(ctx, B, T, F, precision, &pl));
   DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total, false, "train "));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int prec = precision;

@@ -360,6 +360,39 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
 int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
                      int64_t stride_f, const float* drecon, float* const* grads, int ngrads, void* workspace,
                      size_t workspace_bytes);
+/* The workspace layout of a training step of [B, T, F] in `precision`: the very plan dfa_cae_forward_train, dfa_cae_backward and
+ * dfa_cae_train_workspace_bytes read, reported.  Pure host arithmetic; ctx may be NULL (it only receives the refusal's text).
+ * Every activation is channels-last, [B][H][W][C], of `elem` bytes per element (bf16 or fp32); offsets are bytes from the
+ * workspace's start.  After one forward_train + backward every region below still holds what the step stored in it.
+ * Fills the first min(cap, DFA_CAE_TRAIN_PLAN_FIELDS) of
+ *    0-4   H[0..4]      rows of x and of the pooled encoder outputs e[0..3] (H[l+1] = H[l] / 2)
+ *    5-9   W[0..4]      their columns
+ *   10-13  Hd[0..3]     rows of the decoder outputs d[0..2] and of the uncropped reconstruction
+ *   14-17  Wd[0..3]     their columns (Wd[1] includes the output_padding column)
+ *   18-21  e[0..3]      pooled encoder outputs                         [B][H[l+1]][W[l+1]][32 << l]
+ *   22-25  z[0..3]      encoder pre-BatchNorm outputs, z[0] = -1 (block 1's is recomputed, never stored)   [B][H[l]][W[l]][32 << l]
+ *   26-28  zd[0..2]     decoder pre-BatchNorm outputs                  [B][Hd[l]][Wd[l]][128 >> l]
+ *   29-31  d[0..2]      decoder block outputs                          as zd
+ *   32-34  dd[0..2]     gradients of d                                 as zd
+ *   35-37  dzd[0..2]    gradients of zd (written only with option cae_bwd_fold = 0)   as zd
+ *   38-41  de[0..3]     gradients of e                                 as e
+ *   42-45  dz[0..3]     gradients of z, dz[0] = -1                     as z
+ *   46 zp               the ConvTranspose2d gradient GEMMs' patch-major dzd: [B * Hd[l]/2 * Win][2][2][Cout], rewritten per layer
+ *   47 xf, 48 raw       fp32 scratch of the fp32 GEMM path / of the split convolutions
+ *   49 stats, 50 sums   the BatchNorm statistics block and the backward's (sum dy, sum dy * xhat) block
+ *   51 wq, 52 dwq       ConvTranspose2d weights / weight gradients as [Cin][4 Cout] matrices
+ *   53 rec              decoder block 4's and encoder block 1's gradient records
+ *   54 partial, 55 partial_bytes   the per-workgroup records of every reduction
+ *   56 total            = dfa_cae_train_workspace_bytes
+ *   57 elem             bytes per stored activation element (2 or 4)
+ *   58-64  C[0..6]      channels of the seven BatchNorm layers in the order encoder.{1,5,9,13}, decoder.{1,4,7}
+ *   65-71  mean[0..6]   byte offset of each layer's float[C] batch mean
+ *   72-78  var[0..6]    ... of its biased batch variance
+ *   79-85  invstd[0..6] ... of its 1 / sqrt(var + 1e-5)
+ * of `fields` (may be NULL) and returns DFA_CAE_TRAIN_PLAN_FIELDS.  A precision or shape the step refuses returns the step's own
+ * error code (negative) and leaves its message in ctx. */
+#define DFA_CAE_TRAIN_PLAN_FIELDS 86
+int dfa_cae_train_plan(dfa_ctx* ctx, int B, int T, int F, int precision, long long* fields, int cap);
 
 /* anomaly scores of a variable-length (ragged) batch in five launches: utterance b is x[b, :lengths[b], :] and mse[b] is, bit for
  * bit, the mse dfa_cae_forward gives x[b:b+1, :lengths[b], :] alone (layer heights T_b/2, T_b/4, T_b/8, T_b/16, zero

@@ -249,7 +249,7 @@ def state_after_adamw_step(sd, grads, stats, lr=1e-3, weight_decay=0.01, momentu
 
 
 def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue", dtype=torch.float64, return_stats=False,
-                            return_margins=False):
+                            return_margins=False, unrounded_grads=False):
     """One ConvAutoencoder training forward/backward (src/train_cae.py:58-82 over src/model_cae.py:32-125 in train mode, loss =
     MSELoss(recon, x)) restated with the ROUNDING POINTS of the product's bf16 training mode (csrc/cae_train_api.hip):
       encoder block 1   fp32 convolution from the bf16 features, z1 never stored (statistics of the unrounded z1); its pooled
@@ -267,7 +267,8 @@ def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue", dtype=torch
     Returns (loss, {parameter name: gradient}).  With emulate=None only: return_stats=True or return_margins=True append the
     train-mode reconstruction [B,T,F] and the latent map; return_stats=True then appends {BatchNorm prefix: (batch mean, biased
     batch variance, element count)} as `state_after_adamw_step` takes it, return_margins=True {BatchNorm prefix: smallest
-    |BatchNorm output| of that layer}; dtype is the arithmetic the step runs in (torch.float32: the same restatement in fp32)."""
+    |BatchNorm output| of that layer}; dtype is the arithmetic the step runs in (torch.float32: the same restatement in fp32).
+    unrounded_grads=True returns the gradients in `dtype` instead of float32 (for comparisons below fp32's resolution)."""
     f64 = dtype
     on = emulate == "bf16"
     if emulate not in (None, "bf16"):
@@ -318,7 +319,7 @@ def cae_train_step_emulated(sd, x, emulate="bf16", stats="epilogue", dtype=torch
         r = r[:, :, :T, :]
     loss = F.mse_loss(r.squeeze(1), xb)
     loss.backward()
-    out = (float(loss.detach()), {k: v.grad.float() for k, v in P.items()})
+    out = (float(loss.detach()), {k: (v.grad if unrounded_grads else v.grad.float()) for k, v in P.items()})
     if return_stats or return_margins:
         out += (r.detach().squeeze(1).float(), latent.detach().float())
     return out + ((batch_stats,) if return_stats else ()) + ((margins,) if return_margins else ())

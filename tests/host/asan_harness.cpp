@@ -64,6 +64,34 @@ int main() {
           p2 = a; pc = c; p1 = d;
         }
       }
+  // ---- the auto-encoder's training plan: null context, null array, short array; its total is the planner's, a refused shape is
+  //      refused by both, every region lies inside the workspace
+  for (int prec = 0; prec < 2; ++prec)
+    for (int T : Ts)
+      for (int F : Fs)
+        for (int B : Bs) {
+          long long f[DFA_CAE_TRAIN_PLAN_FIELDS + 1];
+          for (long long& v : f) v = -7;
+          const size_t n = dfa_cae_train_workspace_bytes(nullptr, B, T, F, prec);
+          const int rc = dfa_cae_train_plan(nullptr, B, T, F, prec, f, DFA_CAE_TRAIN_PLAN_FIELDS);
+          EXPECT(rc == dfa_cae_train_plan(nullptr, B, T, F, prec, nullptr, 0));
+          if (n == 0 || F < 16) {       // (the byte planner also refuses F < 16, which no F = 16k + 4 is)
+            EXPECT(rc == DFA_E_BAD_SHAPE && f[0] == -7);
+            continue;
+          }
+          EXPECT(rc == DFA_CAE_TRAIN_PLAN_FIELDS && f[DFA_CAE_TRAIN_PLAN_FIELDS] == -7);
+          EXPECT((size_t)f[56] == n && f[0] == T && f[5] == F && f[17] == F && f[57] == (prec ? 2 : 4));
+          for (int i = 18; i < 55; ++i) EXPECT(f[i] == -1 || (f[i] >= 0 && f[i] % 256 == 0 && f[i] < f[56]));
+          EXPECT(f[22] == -1 && f[42] == -1 && f[54] + f[55] <= f[56]);
+          for (int l = 0; l < 7; ++l) EXPECT(f[65 + l] >= f[49] && f[79 + l] + 4 * f[58 + l] <= f[49] + 704 * 3 * 4);
+          long long s3[4] = {-7, -7, -7, -7};
+          EXPECT(dfa_cae_train_plan(nullptr, B, T, F, prec, s3, 3) == DFA_CAE_TRAIN_PLAN_FIELDS);
+          EXPECT(s3[0] == T && s3[2] == T / 4 && s3[3] == -7);
+        }
+  EXPECT(dfa_cae_train_plan(nullptr, 0, 16, 20, DFA_PREC_BF16, nullptr, 0) == DFA_E_BAD_SHAPE);
+  EXPECT(dfa_cae_train_plan(nullptr, 1, 15, 20, DFA_PREC_BF16, nullptr, 0) == DFA_E_BAD_SHAPE);
+  EXPECT(dfa_cae_train_plan(nullptr, 1, 16, 21, DFA_PREC_BF16, nullptr, 0) == DFA_E_BAD_SHAPE);
+  EXPECT(dfa_cae_train_plan(nullptr, 1, 16, 20, 7, nullptr, 0) == DFA_E_BAD_DTYPE);
   // ---- tables and null-context paths
   for (int code = 1; code > -12; --code) EXPECT(dfa_error_name(code) != nullptr && strlen(dfa_error_name(code)) > 0);
   for (int model = -1; model < 5; ++model)
