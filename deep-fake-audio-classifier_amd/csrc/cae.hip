@@ -156,9 +156,11 @@ __global__ void cae_latent_export_kernel(const T* __restrict__ lat, float* __res
   out[i] = ld1(lat + ((size_t)b * HW + p) * C + c);
 }
 
-hipError_t launch_cae_enc1(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu,
-                           const float* sigma, const float* w1, const float* b1, void* out, int prec, int B, int T, int F,
+hipError_t launch_cae_enc1(const FeatView& v, const float* mu, const float* sigma, const float* w1, const float* b1, void* out, int prec,
                            hipStream_t s) {
+  const void* x = v.x;
+  const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
+  const int64_t sb = v.sb, st = v.st, sf = v.sf;
   const int Ho = T / 2, Wo = F / 2;
   dim3 grid((Wo + E1_TJ - 1) / E1_TJ, (Ho + E1_TI - 1) / E1_TI, B), block(256);
   if (x_dtype == DFA_DTYPE_F32 && prec == DFA_PREC_F32)
@@ -184,9 +186,12 @@ hipError_t launch_cae_opad_col(void* out, const float* bias, int prec, int rows,
 
 int cae_dec4_blocks(int T, int W3) { return (((T + 1) / 2) * W3 + 255) / 256; }
 
-hipError_t launch_cae_dec4_mse(const void* d3, int prec, const float* w4, const float* b4, const void* x, int x_dtype,
-                               int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma, float* recon,
-                               float* partial, float* mse, int B, int H3, int W3, int T, int F, hipStream_t s) {
+hipError_t launch_cae_dec4_mse(const void* d3, int prec, const HeadParams& head, const FeatView& v, const float* mu, const float* sigma,
+                               float* recon, float* partial, float* mse, int H3, int W3, hipStream_t s) {
+  const float *w4 = head.w, *b4 = head.b;
+  const void* x = v.x;
+  const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
+  const int64_t sb = v.sb, st = v.st, sf = v.sf;
   const int nblk = cae_dec4_blocks(T, W3);
   dim3 grid(nblk, B), block(256);
   if (prec == DFA_PREC_F32 && x_dtype == DFA_DTYPE_F32)

@@ -113,35 +113,28 @@ int dfa_cae_prepare(dfa_ctx* ctx, int precision) {
     m.enc[l].bias = (float*)(base + eb[l]); m.enc[l].wpack = (uint4*)(base + ew[l]);
     m.dec[l].bias = (float*)(base + db[l]); m.dec[l].wpack = (uint4*)(base + dw[l]);
   }
-  const float* const* p = m.p;
+  const HeadParams head = head_params(m.p, kCaeLayers, 0);
   hipStream_t s = ctx->stream;
-  DFA_HIP_CHECK(ctx, launch_fold_conv1(p[0], p[1], p[2], p[3], p[4], p[5], m.w1, m.b1, 32, s));
-  for (int l = 0; l < 2; ++l) {
-    const float* const* q = p + 6 * (l + 1);
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(q[0], q[1], q[2], q[3], q[4], q[5], ecin[l], 0, ecin[l], ecout[l], precision, m.enc[l].wpack, m.enc[l].bias, s, 1, 0.25f));
+  DFA_HIP_CHECK(ctx, launch_fold_conv1(layer_params(m.p, 0), m.w1, m.b1, 32, s));
+  for (int l = 0; l < 2; ++l)
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(layer_params(m.p, l + 1), ecin[l], 0, ecin[l], ecout[l], precision, m.enc[l].wpack, m.enc[l].bias, s, 0.25f));
+  const LayerParams e4 = layer_params(m.p, 3);
+  if (precision == DFA_PREC_BF16) {
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(e4, 128, 0, 128, 256, precision, m.enc[2].wpack, m.enc[2].bias, s, 0.25f));
+  } else {  // two Cin halves, see conv3x3_inst_cae.hip
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(e4, 128, 0, 64, 256, precision, m.enc[2].wpack, m.enc[2].bias, s, 0.25f));
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(e4, 128, 64, 64, 256, precision, m.enc[2].wpack + (size_t)(256 / 32) * 9 * 8 * 64, m.enc[2].bias, s, 0.25f));
   }
-  {
-    const float* const* q = p + 18;
-    if (precision == DFA_PREC_BF16) {
-      DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(q[0], q[1], q[2], q[3], q[4], q[5], 128, 0, 128, 256, precision, m.enc[2].wpack, m.enc[2].bias, s, 1, 0.25f));
-    } else {  // two Cin halves, see conv3x3_inst_cae.hip
-      DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(q[0], q[1], q[2], q[3], q[4], q[5], 128, 0, 64, 256, precision, m.enc[2].wpack, m.enc[2].bias, s, 1, 0.25f));
-      DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(q[0], q[1], q[2], q[3], q[4], q[5], 128, 64, 64, 256, precision,
-                                                  m.enc[2].wpack + (size_t)(256 / 32) * 9 * 8 * 64, m.enc[2].bias, s, 1, 0.25f));
-    }
-  }
-  for (int l = 0; l < 3; ++l) {
-    const float* const* q = p + 24 + 6 * l;
-    DFA_HIP_CHECK(ctx, launch_fold_pack_convt2x2(q[0], q[1], q[2], q[3], q[4], q[5], dcin[l], dcout[l], precision, m.dec[l].wpack, m.dec[l].bias, s));
-  }
+  for (int l = 0; l < 3; ++l)
+    DFA_HIP_CHECK(ctx, launch_fold_pack_convt2x2(layer_params(m.p, kCaeDec0 + l), dcin[l], dcout[l], precision, m.dec[l].wpack, m.dec[l].bias, s));
   m.opad_cst = (float*)(base + cst_off);
   m.c1pack = (uint4*)(base + c1p_off);
   m.c1bias = (float*)(base + c1p_off + 6 * 64 * 16);
   DFA_HIP_CHECK(ctx, launch_pack_cae_enc1_mfma(m.w1, m.b1, m.c1pack, m.c1bias, s));
   m.dec4pack = (uint4*)(base + d4p_off);
-  DFA_HIP_CHECK(ctx, launch_pack_cae_dec4(p[42], m.dec4pack, s));
+  DFA_HIP_CHECK(ctx, launch_pack_cae_dec4(head.w, m.dec4pack, s));
   if (precision == DFA_PREC_BF16)   // the constants the fused decoder uses for the columns grown from block 2's output_padding column
-    DFA_HIP_CHECK(ctx, launch_cae_opad_consts(m.dec[1].bias, m.dec[2].wpack, m.dec[2].bias, p[42], p[43], m.opad_cst, s));
+    DFA_HIP_CHECK(ctx, launch_cae_opad_consts(m.dec[1].bias, m.dec[2].wpack, m.dec[2].bias, head.w, head.b, m.opad_cst, s));
   m.prepared_prec = precision;
   return DFA_OK;
 }
@@ -157,6 +150,8 @@ int dfa_cae_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int 
   const CaePlan pl = plan_cae(B, T, F, prec);
   if (!pl.ok) return cae_refuse_F(ctx, F, pl);
   DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total));
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
+  const HeadParams head = head_params(m.p, kCaeLayers, 0);
   char* ws = (char*)workspace;
   const CaeBuffers bf = cae_buffers(ws, pl);
   void* const* e = bf.e;
@@ -164,9 +159,9 @@ int dfa_cae_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int 
   hipStream_t s = ctx->stream;
   { ScopedSlot ts(ctx, 8);
     if (prec == DFA_PREC_BF16 && ctx->cae_enc1_mfma && F <= 1022)    // block 1 on the matrix cores (hi + lo bf16 operands)
-      DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma(x, x_dtype, stride_b, stride_t, stride_f, mu, sigma, m.c1pack, m.c1bias, e[0], B, T, F, s));
+      DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma(v, mu, sigma, m.c1pack, m.c1bias, e[0], s));
     else
-      DFA_HIP_CHECK(ctx, launch_cae_enc1(x, x_dtype, stride_b, stride_t, stride_f, mu, sigma, m.w1, m.b1, e[0], prec, B, T, F, s)); }
+      DFA_HIP_CHECK(ctx, launch_cae_enc1(v, mu, sigma, m.w1, m.b1, e[0], prec, s)); }
   for (int l = 0; l < 3; ++l) {
     ScopedSlot ts(ctx, 9 + l);
     const ConvArgs a = cae_enc_args(ctx, pl, bf, l, B);
@@ -176,13 +171,12 @@ int dfa_cae_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int 
     DFA_HIP_CHECK(ctx, err);
   }
   if (latent) DFA_HIP_CHECK(ctx, launch_cae_latent_export(e[3], prec, latent, B, pl.H[4] * pl.W[4], 256, s));
-  if (prec == DFA_PREC_BF16 && ctx->cae_dec_fused && cae_dec_fused_supports(T, F, stride_t, stride_f)) {   // decoder + squared error in one kernel: d1, d2, d3 never leave the CU (slot 12)
+  if (prec == DFA_PREC_BF16 && ctx->cae_dec_fused && cae_dec_fused_supports(v)) {   // decoder + squared error in one kernel: d1, d2, d3 never leave the CU (slot 12)
     if (recon || mse) {
       ScopedSlot ts(ctx, 12);
       float* partial = (float*)(ws + pl.part_off);
-      DFA_HIP_CHECK(ctx, launch_cae_dec_fused(e[3], m.dec[0].wpack, m.dec[0].bias, m.dec[1].wpack, m.dec[1].bias, m.dec[2].wpack, m.dec[2].bias,
-                                              m.p[42], m.p[43], m.dec4pack, m.opad_cst, x, x_dtype, stride_b, stride_t, stride_f, mu, sigma, recon, partial,
-                                              B, pl.H[4], pl.W[4], T, F, s, ctx->clock_probe ? ctx->clock_buf : nullptr));
+      DFA_HIP_CHECK(ctx, launch_cae_dec_fused(e[3], m.dec, head, m.dec4pack, m.opad_cst, v, mu, sigma, recon, partial, pl.H[4], pl.W[4], s,
+                                              ctx->clock_probe ? ctx->clock_buf : nullptr));
       if (mse) DFA_HIP_CHECK(ctx, launch_cae_mse_finalize(partial, cae_dec_fused_tiles(pl.H[4], pl.W[4]), 1.0f / ((float)T * (float)F), mse, B, s));
     }
     return DFA_OK;
@@ -200,8 +194,7 @@ int dfa_cae_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int 
   }
   if (recon || mse) {
     ScopedSlot ts(ctx, 15);
-    DFA_HIP_CHECK(ctx, launch_cae_dec4_mse(d[2], prec, m.p[42], m.p[43], x, x_dtype, stride_b, stride_t, stride_f, mu, sigma,
-                                           recon, (float*)(ws + pl.part_off), mse, B, pl.Hd[2], pl.Wd[2], T, F, s));
+    DFA_HIP_CHECK(ctx, launch_cae_dec4_mse(d[2], prec, head, v, mu, sigma, recon, (float*)(ws + pl.part_off), mse, pl.Hd[2], pl.Wd[2], s));
   }
   return DFA_OK;
 }
@@ -231,7 +224,8 @@ int dfa_cae_score_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_
   if (!ctx->cae_dec_fused || !ctx->cae_enc1_mfma || !ctx->cae_enc_dma || !ctx->lds_pipe)   // the uniform forward would run other kernels
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score needs the default options cae_dec_fused=1, cae_enc1_mfma=1, "
                 "cae_enc_dma=1 and lds_pipe=1");
-  if (F > 1022 || !cae_dec_fused_supports(T_max, F, stride_t, stride_f))
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T_max, F};
+  if (F > 1022 || !cae_dec_fused_supports(v))
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged auto-encoder score needs F <= 1022, non-negative strides and 32-bit element "
                 "offsets inside an utterance (F=%d, stride_t=%lld, stride_f=%lld)", F, (long long)stride_t, (long long)stride_f);
   DFA_TRY(refuse_capture(ctx, "score"));
@@ -250,8 +244,7 @@ int dfa_cae_score_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_
   const RaggedTab rt{dtab, B};
   const CaeBuffers bf = cae_buffers(ws, pl);
   { ScopedSlot ts(ctx, 8);
-    DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma_ragged(x, x_dtype, stride_b, stride_t, stride_f, mu, sigma, m.c1pack, m.c1bias, bf.e[0], B, T_max, F,
-                                                   dtab, s)); }
+    DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma_ragged(v, mu, sigma, m.c1pack, m.c1bias, bf.e[0], dtab, s)); }
   for (int l = 0; l < 3; ++l) {
     ScopedSlot ts(ctx, 9 + l);
     DFA_HIP_CHECK(ctx, launch_cae_enc_ragged(l, cae_enc_args(ctx, pl, bf, l, B), rt, s));
@@ -259,9 +252,8 @@ int dfa_cae_score_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_
   {
     ScopedSlot ts(ctx, 12);
     float* partial = (float*)(ws + pl.part_off);
-    DFA_HIP_CHECK(ctx, launch_cae_dec_fused_ragged(bf.e[3], m.dec[0].wpack, m.dec[0].bias, m.dec[1].wpack, m.dec[1].bias, m.dec[2].wpack,
-                                                   m.dec[2].bias, m.p[42], m.p[43], m.dec4pack, m.opad_cst, x, x_dtype, stride_b, stride_t,
-                                                   stride_f, mu, sigma, partial, B, pl.H[4], pl.W[4], T_max, F, dtab, s));
+    DFA_HIP_CHECK(ctx, launch_cae_dec_fused_ragged(bf.e[3], m.dec, head_params(m.p, kCaeLayers, 0), m.dec4pack, m.opad_cst, v, mu, sigma, partial,
+                                                   pl.H[4], pl.W[4], dtab, s));
     DFA_HIP_CHECK(ctx, launch_cae_mse_finalize_ragged(partial, cae_dec_fused_tiles(pl.H[4], pl.W[4]), dtab, mse, B, s));
   }
   return DFA_OK;

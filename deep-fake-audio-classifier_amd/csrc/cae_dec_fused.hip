@@ -150,22 +150,30 @@ hipError_t launch_cae_opad_consts(const float* b2, const uint4* wp3, const float
 }
 
 // the kernel addresses x inside one utterance with unsigned 32-bit element offsets
-bool cae_dec_fused_supports(int T, int F, int64_t st, int64_t sf) {
-  return st >= 0 && sf >= 0 && F <= cdf::ZS_MAXF && (int64_t)(T - 1) * st + (int64_t)(F - 1) * sf < ((int64_t)1 << 31);
+bool cae_dec_fused_supports(const FeatView& v) {
+  return v.st >= 0 && v.sf >= 0 && v.F <= cdf::ZS_MAXF && (int64_t)(v.T - 1) * v.st + (int64_t)(v.F - 1) * v.sf < ((int64_t)1 << 31);
+}
+// what both launches below fill alike: the packed decoder blocks, block 4, the features and their z-score
+static CaeDecFusedArgs cae_dec_fused_args(const void* lat, const PackedConv* dec, const HeadParams& head, const uint4* w4pack, const float* cst,
+                                          const FeatView& v, const float* mu, const float* sigma, float* partial, int H4, int W4) {
+  CaeDecFusedArgs a{};
+  a.w4pack = w4pack;
+  a.lat = (const bf16_t*)lat; a.wp1 = dec[0].wpack; a.wp2 = dec[1].wpack; a.wp3 = dec[2].wpack;
+  a.b1 = dec[0].bias; a.b2 = dec[1].bias; a.b3 = dec[2].bias; a.w4 = head.w; a.b4 = head.b; a.cst = cst;
+  a.x = v.x; a.x_bf16 = v.dtype == DFA_DTYPE_BF16 ? 1 : 0; a.sb = v.sb; a.st = v.st; a.sf = v.sf; a.mu = mu; a.sigma = sigma;
+  a.partial = partial; a.H4 = H4; a.W4 = W4; a.T = v.T; a.F = v.F; a.ntile = cae_dec_fused_tiles(H4, W4);
+  return a;
 }
 
 int cae_dec_fused_tiles(int H4, int W4) { return (H4 * W4 + cdf::NP - 1) / cdf::NP; }
 
-hipError_t launch_cae_dec_fused(const void* lat, const uint4* wp1, const float* b1, const uint4* wp2, const float* b2, const uint4* wp3,
-                                const float* b3, const float* w4, const float* b4, const uint4* w4pack, const float* cst, const void* x,
-                                int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma, float* recon,
-                                float* partial, int B, int H4, int W4, int T, int F, hipStream_t s, long long* stamps) {
-  CaeDecFusedArgs a{};
-  a.w4pack = w4pack;
+hipError_t launch_cae_dec_fused(const void* lat, const PackedConv* dec, const HeadParams& head, const uint4* w4pack, const float* cst,
+                                const FeatView& v, const float* mu, const float* sigma, float* recon, float* partial, int H4, int W4,
+                                hipStream_t s, long long* stamps) {
+  const int B = v.B;
+  CaeDecFusedArgs a = cae_dec_fused_args(lat, dec, head, w4pack, cst, v, mu, sigma, partial, H4, W4);
   a.stamps = stamps;
-  a.lat = (const bf16_t*)lat; a.wp1 = wp1; a.wp2 = wp2; a.wp3 = wp3; a.b1 = b1; a.b2 = b2; a.b3 = b3; a.w4 = w4; a.b4 = b4; a.cst = cst;
-  a.x = x; a.x_bf16 = x_dtype == DFA_DTYPE_BF16 ? 1 : 0; a.sb = sb; a.st = st; a.sf = sf; a.mu = mu; a.sigma = sigma;
-  a.recon = recon; a.partial = partial; a.H4 = H4; a.W4 = W4; a.T = T; a.F = F; a.ntile = cae_dec_fused_tiles(H4, W4);
+  a.recon = recon;
   auto go = [&](auto kern) -> hipError_t {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, cdf::LDS_BYTES);
     if (e != hipSuccess) return e;     // (per device: set on every launch, it is cheap)
@@ -177,16 +185,11 @@ hipError_t launch_cae_dec_fused(const void* lat, const uint4* wp1, const float* 
 }
 
 // ragged batch, score only: H4 / T = those of the padded batch (pitches and grid extent); tab = the device table, [0, B) the lengths
-hipError_t launch_cae_dec_fused_ragged(const void* lat, const uint4* wp1, const float* b1, const uint4* wp2, const float* b2,
-                                       const uint4* wp3, const float* b3, const float* w4, const float* b4, const uint4* w4pack,
-                                       const float* cst, const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu,
-                                       const float* sigma, float* partial, int B, int H4, int W4, int T, int F, const int* tab,
+hipError_t launch_cae_dec_fused_ragged(const void* lat, const PackedConv* dec, const HeadParams& head, const uint4* w4pack, const float* cst,
+                                       const FeatView& v, const float* mu, const float* sigma, float* partial, int H4, int W4, const int* tab,
                                        hipStream_t s) {
-  CaeDecFusedArgs a{};
-  a.w4pack = w4pack;
-  a.lat = (const bf16_t*)lat; a.wp1 = wp1; a.wp2 = wp2; a.wp3 = wp3; a.b1 = b1; a.b2 = b2; a.b3 = b3; a.w4 = w4; a.b4 = b4; a.cst = cst;
-  a.x = x; a.x_bf16 = x_dtype == DFA_DTYPE_BF16 ? 1 : 0; a.sb = sb; a.st = st; a.sf = sf; a.mu = mu; a.sigma = sigma;
-  a.partial = partial; a.H4 = H4; a.W4 = W4; a.T = T; a.F = F; a.ntile = cae_dec_fused_tiles(H4, W4);
+  const int B = v.B;
+  const CaeDecFusedArgs a = cae_dec_fused_args(lat, dec, head, w4pack, cst, v, mu, sigma, partial, H4, W4);
   const RaggedTab rt{tab, B};
   auto go = [&](auto kern) -> hipError_t {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, cdf::LDS_BYTES);

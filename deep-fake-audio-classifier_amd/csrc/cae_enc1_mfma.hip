@@ -80,8 +80,11 @@ __global__ __launch_bounds__(256) void cae_enc1_mfma_ragged_kernel(const TX* __r
 int cae_enc1_mfma_pitch(int F) { return (F + 2 + 31) / 32 * 32 + 1; }
 size_t cae_enc1_mfma_lds(int F) { return ((size_t)e1m::XR * cae_enc1_mfma_pitch(F) + 2 * (size_t)F) * sizeof(float); }   // x rows + the z-score table
 
-hipError_t launch_cae_enc1_mfma(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma,
-                                const uint4* c1pack, const float* c1bias, void* out, int B, int T, int F, hipStream_t s) {
+hipError_t launch_cae_enc1_mfma(const FeatView& v, const float* mu, const float* sigma, const uint4* c1pack, const float* c1bias, void* out,
+                                hipStream_t s) {
+  const void* x = v.x;
+  const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
+  const int64_t sb = v.sb, st = v.st, sf = v.sf;
   const int Ho = T / 2, Wo = F / 2, pitch = cae_enc1_mfma_pitch(F);
   static const int dbg = getenv("DFA_E1_DBG") ? atoi(getenv("DFA_E1_DBG")) : 0;   // diagnostic phase skipping (timing only)
   const size_t lds = cae_enc1_mfma_lds(F);
@@ -99,9 +102,11 @@ hipError_t launch_cae_enc1_mfma(const void* x, int x_dtype, int64_t sb, int64_t 
 }
 
 // ragged batch: T = the padded length (grid extent, output row pitch); tab = the device table, [0, B) the lengths
-hipError_t launch_cae_enc1_mfma_ragged(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma,
-                                       const uint4* c1pack, const float* c1bias, void* out, int B, int T, int F, const int* tab,
-                                       hipStream_t s) {
+hipError_t launch_cae_enc1_mfma_ragged(const FeatView& v, const float* mu, const float* sigma, const uint4* c1pack, const float* c1bias,
+                                       void* out, const int* tab, hipStream_t s) {
+  const void* x = v.x;
+  const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
+  const int64_t sb = v.sb, st = v.st, sf = v.sf;
   const int Ho = T / 2, Wo = F / 2, pitch = cae_enc1_mfma_pitch(F);
   const size_t lds = cae_enc1_mfma_lds(F);
   const RaggedTab rt{tab, B};

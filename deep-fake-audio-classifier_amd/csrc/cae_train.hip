@@ -188,7 +188,8 @@ hipError_t launch_cae_dec4_bwd(int prec, const void* d3, const float* w4, const 
   MseSrc mse{};
   if (!drecon) {
     if (!mse_args) return hipErrorInvalidValue;
-    mse.x = mse_args->x; mse.x_bf16 = mse_args->x_bf16; mse.sb = mse_args->sb; mse.st = mse_args->st; mse.sf = mse_args->sf;
+    const FeatView& v = mse_args->v;
+    mse.x = v.x; mse.x_bf16 = v.dtype == DFA_DTYPE_BF16 ? 1 : 0; mse.sb = v.sb; mse.st = v.st; mse.sf = v.sf;
     mse.b4 = 0.f; mse.scale = 2.0f / ((float)B * (float)T * (float)F);
     mse.b4_dev = mse_args->b4_dev;
   }
@@ -239,11 +240,10 @@ __global__ __launch_bounds__(256) void mse_finish_kernel(const float* __restrict
   }
   if (threadIdx.x == 0) loss[0] = (float)(red[0] * inv_n);
 }
-hipError_t launch_mse_fwd_bwd(const float* recon, const void* x, int x_bf16, int64_t sb, int64_t st, int64_t sf, int B, int T, int F,
-                              float* partial, float* loss, float* drecon, hipStream_t s) {
-  const size_t n = (size_t)B * T * F;
-  hipLaunchKernelGGL(mse_fwd_bwd_kernel, dim3(kMseBlocks), dim3(256), 0, s, recon, x, x_bf16, sb, st, sf, T, F, n, (float)(2.0 / (double)n),
-                     partial, drecon);
+hipError_t launch_mse_fwd_bwd(const float* recon, const FeatView& v, float* partial, float* loss, float* drecon, hipStream_t s) {
+  const size_t n = (size_t)v.B * v.T * v.F;
+  hipLaunchKernelGGL(mse_fwd_bwd_kernel, dim3(kMseBlocks), dim3(256), 0, s, recon, v.x, v.dtype == DFA_DTYPE_BF16 ? 1 : 0, v.sb, v.st, v.sf, v.T,
+                     v.F, n, (float)(2.0 / (double)n), partial, drecon);
   if (loss) hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, partial, kMseBlocks, 1.0 / (double)n, loss);
   return hipGetLastError();
 }

@@ -87,22 +87,21 @@ BnStats stat_of(char* ws, const CaeTrainPlan& pl, int layer, int C) { return bn_
 float* sums_of(char* ws, const CaeTrainPlan& pl, int layer) { return bn_sums(ws + pl.sums, kBnOff[layer]); }
 
 // statistics of a stored pre-BN output in a pass of their own
-int finalize_stats(dfa_ctx* ctx, int prec, const void* z, size_t npix, int C, const BnStats& st, float* partial, float* rm,
-                   float* rv, float momentum) {
+int finalize_stats(dfa_ctx* ctx, int prec, const void* z, size_t npix, int C, const BnStats& st, float* partial, const RunningStats& run,
+                   float momentum) {
   int ppb;
   const int nblk = cl_stats_blocks(npix, &ppb);
   DFA_HIP_CHECK(ctx, launch_cl_stats(prec, z, partial, npix, C, ctx->stream));
-  return finalize_bn_stats(ctx, partial, nblk, C, (double)npix, st, rm, rv, momentum);
+  return finalize_bn_stats(ctx, partial, nblk, C, (double)npix, st, run, momentum);
 }
 
 // encoder block 1 of a step: what conv1_train_stats (forward) and conv1_train_backward (backward, da = de[0]) take.  The matrix-core
 // passes keep XX | Xs and their [32][11] record behind the decoder-block-4 record in pl.rec; the two-pass record is pl.rec itself
-Conv1Train conv1_block(CaeState& m, const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, int B, int T, int F, char* ws,
-                       const CaeTrainPlan& pl, bool mfma) {
+Conv1Train conv1_block(CaeState& m, const FeatView& v, char* ws, const CaeTrainPlan& pl, bool mfma) {
   float* rec = (float*)(ws + pl.rec);
   Conv1Train c{};             // (no dropout, no augmentation, single-level synchronised statistics)
-  c.x = x; c.x_dtype = x_dtype; c.sb = sb; c.st = st; c.sf = sf; c.B = B; c.T = T; c.F = F; c.prec = m.train_prec; c.poolw = 2;
-  c.p = m.p; c.fw = m.tw1; c.fb = m.tb1; c.partial = (float*)(ws + pl.partial); c.xxs = rec + 512; c.c1rec = mfma ? rec + 640 : rec;
+  c.v = v; c.prec = m.train_prec; c.poolw = 2;
+  c.p = layer_params(m.p, 0); c.fw = m.tw1; c.fb = m.tb1; c.partial = (float*)(ws + pl.partial); c.xxs = rec + 512; c.c1rec = mfma ? rec + 640 : rec;
   c.sums = sums_of(ws, pl, 0); c.stats = stat_of(ws, pl, 0, 32); c.da = ws + pl.de[0];
   return c;
 }
@@ -192,74 +191,74 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
       m.tdec[l].bias = (float*)(b + db[l]); m.tdec[l].wpack = (uint4*)(b + dw[l]);
     }
   }
-  const float* const* p = m.p;
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
+  const LayerParams e2 = layer_params(m.p, 1), e3 = layer_params(m.p, 2), e4 = layer_params(m.p, 3);
   hipStream_t s = ctx->stream;
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
   const int nkg = (prec == DFA_PREC_BF16) ? 4 : 8;
   // ---- weight images (weights move every step)
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[6], p[7], nullptr, nullptr, nullptr, nullptr, 32, 0, 32, 64, prec, m.tenc[0].wpack, m.tenc[0].bias, s, 0));
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[12], p[13], nullptr, nullptr, nullptr, nullptr, 64, 0, 64, 128, prec, m.tenc[1].wpack, m.tenc[1].bias, s, 0));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e2), 32, 0, 32, 64, prec, m.tenc[0].wpack, m.tenc[0].bias, s));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e3), 64, 0, 64, 128, prec, m.tenc[1].wpack, m.tenc[1].bias, s));
   m.train_enc4_wide = (prec == DFA_PREC_BF16 && ctx->cae_enc4_wide) ? 1 : 0;
   if (m.train_enc4_wide) {   // one 128-input-channel image (the eval forward's layout)
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[18], p[19], nullptr, nullptr, nullptr, nullptr, 128, 0, 128, 256, prec, m.tenc[2].wpack, m.tenc[2].bias, s, 0));
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e4), 128, 0, 128, 256, prec, m.tenc[2].wpack, m.tenc[2].bias, s));
   } else {
   for (int hlf = 0; hlf < 2; ++hlf)
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[18], p[19], nullptr, nullptr, nullptr, nullptr, 128, 64 * hlf, 64, 256, prec,
-                                                m.tenc[2].wpack + (size_t)hlf * (256 / 32) * 9 * nkg * 64, m.tenc[2].bias, s, 0));
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e4), 128, 64 * hlf, 64, 256, prec,
+                                                m.tenc[2].wpack + (size_t)hlf * (256 / 32) * 9 * nkg * 64, m.tenc[2].bias, s));
   }
   // bf16 mode: the 64 -> 32 and 128 -> 64 data gradients on the 16x16x32 kernels of conv_split.hip, one launch each (as the CNN2D's;
   // the 32x32x16 forms ran the first with one channel slice per workgroup -- 0.31 ms -- and the second as two launches chained
   // through fp32 partial sums)
   m.train_dgrad_m16 = (prec == DFA_PREC_BF16 && ctx->dgrad_m16) ? 1 : 0;
-  DFA_TRY(pack_dgrad_images(ctx, p[6], p[12], prec, m.train_dgrad_m16, m.tdg[0], m.tdg[1]));
+  DFA_TRY(pack_dgrad_images(ctx, e2.w, e3.w, prec, m.train_dgrad_m16, m.tdg[0], m.tdg[1]));
   if (m.train_enc4_wide) {
     for (int c = 0; c < 2; ++c)
-      DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(p[18], 128, 256, 128 * c, 128, prec, m.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * 8 * 64, m.tdg[2].bias, s));
+      DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(e4.w, 128, 256, 128 * c, 128, prec, m.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * 8 * 64, m.tdg[2].bias, s));
   } else {
   for (int c = 0; c < 4; ++c)
-    DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(p[18], 128, 256, 64 * c, 64, prec, m.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * nkg * 64, m.tdg[2].bias, s));
+    DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(e4.w, 128, 256, 64 * c, 64, prec, m.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * nkg * 64, m.tdg[2].bias, s));
   }
-  for (int l = 0; l < 3; ++l) {
-    const float* const* q = p + 24 + 6 * l;
-    DFA_HIP_CHECK(ctx, launch_fold_pack_convt2x2(q[0], q[1], nullptr, nullptr, nullptr, nullptr, kDCin[l], kDC[l], prec, m.tdec[l].wpack, m.tdec[l].bias, s, 0));
-  }
+  for (int l = 0; l < 3; ++l)
+    DFA_HIP_CHECK(ctx, launch_fold_pack_convt2x2(raw_conv(layer_params(m.p, kCaeDec0 + l)), kDCin[l], kDC[l], prec, m.tdec[l].wpack, m.tdec[l].bias, s));
   m.train_prec = prec; m.train_B = B; m.train_T = T;
-  auto rmv = [&](int pi) { return update_running_stats ? (float*)p[pi] : nullptr; };
+  const bool upd = update_running_stats != 0;
   // ---- encoder block 1 (pre-BN output recomputed from x: statistics pass, fold, fused eval kernel)
   {
     // bf16 mode on bf16 features (F even): the statistics pass (with the 9 x 9 tap moments the fused backward algebra needs) and
     // the backward pass on the matrix cores (train_conv1_mfma.hip, as the CNN2D's block 1), the forward on cae_enc1_mfma.hip
     // (synchronised BatchNorm: the backward needs the layer's sums before the weight gradient is formed -> the two-pass vector path)
     m.train_c1_mfma = (ctx->conv1_mfma && !ctx->bn_sync.fn && prec == DFA_PREC_BF16 && x_dtype == DFA_DTYPE_BF16 && F <= 224 && !(F & 1) && T >= 4) ? 1 : 0;
-    DFA_TRY(conv1_train_stats(ctx, conv1_block(m, x, x_dtype, stride_b, stride_t, stride_f, B, T, F, ws, pl, m.train_c1_mfma), m.train_c1_mfma,
-                              m.train_c1_mfma, rmv(4), rmv(5), momentum));
+    DFA_TRY(conv1_train_stats(ctx, conv1_block(m, v, ws, pl, m.train_c1_mfma), m.train_c1_mfma, m.train_c1_mfma, upd, momentum));
     if (m.train_c1_mfma && ctx->cae_enc1_mfma) {
       uint4* tpack = (uint4*)(ws + pl.wq);                // this step's three-term A operands (pl.wq is free until the decoder's backward)
       float* tbias = (float*)(ws + pl.wq) + 6 * 64 * 4;
       DFA_HIP_CHECK(ctx, launch_pack_cae_enc1_mfma(m.tw1, m.tb1, tpack, tbias, s));
-      DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma(x, x_dtype, stride_b, stride_t, stride_f, nullptr, nullptr, tpack, tbias, ws + pl.e[0], B, T, F, s));
+      DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma(v, nullptr, nullptr, tpack, tbias, ws + pl.e[0], s));
     } else {
-      DFA_HIP_CHECK(ctx, launch_cae_enc1(x, x_dtype, stride_b, stride_t, stride_f, nullptr, nullptr, m.tw1, m.tb1, ws + pl.e[0], prec, B, T, F, s));
+      DFA_HIP_CHECK(ctx, launch_cae_enc1(v, nullptr, nullptr, m.tw1, m.tb1, ws + pl.e[0], prec, s));
     }
   }
   // ---- encoder blocks 2-4
   for (int l = 1; l < 4; ++l) {
+    const LayerParams q = layer_params(m.p, l);
     ConvArgs a = conv_args(ws + pl.e[l - 1], m.tenc[l - 1], ws + pl.z[l], B, pl.H[l], pl.W[l], kEC[l], ctx);
     const bool epi_stats = ctx->cae_conv_stats && l < 3;         // (block 4: conv3x3_inst_cae_train.hip)
     a.stats_partial = epi_stats ? partial : nullptr;             // one [COUT][2] record per (sample, 32-column strip)
     DFA_HIP_CHECK(ctx, launch_cae_train_fwd(prec, kEC[l - 1], a, (float*)(ws + pl.raw), s, m.train_enc4_wide));
     BnStats st = stat_of(ws, pl, l, kEC[l]);
     const size_t npix = (size_t)B * pl.H[l] * pl.W[l];
-    int rc = epi_stats ? finalize_bn_stats(ctx, partial, B * ((pl.W[l] + 31) / 32), kEC[l], (double)npix, st, rmv(6 * l + 4), rmv(6 * l + 5), momentum)
-                                 : finalize_stats(ctx, prec, ws + pl.z[l], npix, kEC[l], st, partial, rmv(6 * l + 4), rmv(6 * l + 5), momentum);
+    const RunningStats run = running_stats(q, upd);
+    int rc = epi_stats ? finalize_bn_stats(ctx, partial, B * ((pl.W[l] + 31) / 32), kEC[l], (double)npix, st, run, momentum)
+                                 : finalize_stats(ctx, prec, ws + pl.z[l], npix, kEC[l], st, partial, run, momentum);
     if (rc != DFA_OK) return rc;
-    DFA_HIP_CHECK(ctx, launch_bn_relu_pool(prec, 2, ws + pl.z[l], st.mean, st.invstd, p[6 * l + 2], p[6 * l + 3], ws + pl.e[l], B, pl.H[l], pl.W[l], kEC[l], s));
+    DFA_HIP_CHECK(ctx, launch_bn_relu_pool(prec, 2, ws + pl.z[l], bn_apply(st, q), ws + pl.e[l], B, pl.H[l], pl.W[l], kEC[l], s));
   }
   if (latent) DFA_HIP_CHECK(ctx, launch_cae_latent_export(ws + pl.e[3], prec, latent, B, pl.H[4] * pl.W[4], 256, s));
   // ---- decoder blocks 1-3: raw ConvTranspose2d -> statistics -> BN + ReLU
   for (int l = 0; l < 3; ++l) {
-    const float* const* q = p + 24 + 6 * l;
+    const LayerParams q = layer_params(m.p, kCaeDec0 + l);
     ConvTArgs a{};
     a.in = (l == 0) ? ws + pl.e[3] : ws + pl.d[l - 1];
     a.wpack = m.tdec[l].wpack; a.bias = m.tdec[l].bias; a.out = ws + pl.zd[l];
@@ -268,17 +267,18 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
     a.stats_partial = ctx->cae_conv_stats ? partial : nullptr;   // one [COUT][2] record per workgroup (the padding column's share in record 0)
     DFA_HIP_CHECK(ctx, launch_cae_dec(prec, kDCin[l], a, s));
     if (l == 1) DFA_HIP_CHECK(ctx, launch_cae_opad_col(ws + pl.zd[1], m.tdec[1].bias, prec, B * pl.Hd[1], pl.Wd[1], 64, s, 1));
-    BnStats st = stat_of(ws, pl, 4 + l, kDC[l]);
+    BnStats st = stat_of(ws, pl, kCaeDec0 + l, kDC[l]);
     const size_t npix = (size_t)B * pl.Hd[l] * pl.Wd[l];
+    const RunningStats run = running_stats(q, upd);
     int rc = ctx->cae_conv_stats ? finalize_bn_stats(ctx, partial, cae_dec_stats_records(prec, kDCin[l], (long)B * a.H * a.W), kDC[l], (double)npix, st,
-                                                    rmv(24 + 6 * l + 4), rmv(24 + 6 * l + 5), momentum, partial + pl.partial_bytes / 8)
-                                 : finalize_stats(ctx, prec, ws + pl.zd[l], npix, kDC[l], st, partial, rmv(24 + 6 * l + 4), rmv(24 + 6 * l + 5), momentum);
+                                                    run, momentum, partial + pl.partial_bytes / 8)
+                                 : finalize_stats(ctx, prec, ws + pl.zd[l], npix, kDC[l], st, partial, run, momentum);
     if (rc != DFA_OK) return rc;
-    DFA_HIP_CHECK(ctx, launch_bn_relu_pool(prec, 1, ws + pl.zd[l], st.mean, st.invstd, q[2], q[3], ws + pl.d[l], B, pl.Hd[l], pl.Wd[l], kDC[l], s));
+    DFA_HIP_CHECK(ctx, launch_bn_relu_pool(prec, 1, ws + pl.zd[l], bn_apply(st, q), ws + pl.d[l], B, pl.Hd[l], pl.Wd[l], kDC[l], s));
   }
   // ---- decoder block 4 + zero time padding (+ per-sample MSE)
-  DFA_HIP_CHECK(ctx, launch_cae_dec4_mse(ws + pl.d[2], prec, p[42], p[43], x, x_dtype, stride_b, stride_t, stride_f, nullptr, nullptr, recon,
-                                         partial, mse, B, pl.Hd[2], pl.Wd[2], T, F, s));
+  DFA_HIP_CHECK(ctx, launch_cae_dec4_mse(ws + pl.d[2], prec, head_params(m.p, kCaeLayers, 0), v, nullptr, nullptr, recon, partial, mse, pl.Hd[2],
+                                         pl.Wd[2], s));
   return DFA_OK;
 }
 
@@ -290,10 +290,12 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
   CaeState& m = ctx->cae;
   const int prec = m.train_prec;
   CaeTrainPlan pl;
-  DFA_TRY(check_backward(ctx, {"dfa_cae_backward", "dfa_cae_forward_train", "the auto-encoder", 30, nullptr, false},
+  DFA_TRY(check_backward(ctx, {"dfa_cae_backward", "dfa_cae_forward_train", "the auto-encoder", kCaeGrads, nullptr, false},
                          m.train_packed && m.train_B == B && m.train_T == T, x, x_dtype, drecon, grads, ngrads, workspace, workspace_bytes,
                          [&] { return (pl = plan_cae_train(B, T, F, prec)).total; }));
-  const float* const* p = m.p;
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
+  const HeadParams head = head_params(m.p, kCaeLayers, 0);
+  const HeadGrads gh = head_grads(grads, kCaeLayers, 0);
   hipStream_t s = ctx->stream;
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
@@ -308,43 +310,45 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
   // ---- decoder block 4
   // drecon == NULL: the loss is MSELoss(recon, x) (src/train_cae.py:67-68) and its gradient 2 (recon - x) / (B T F) is formed inside
   // the kernel from the saved d3 and x -- neither recon nor drecon has to exist in memory
-  MseArgs ma{x, x_dtype == DFA_DTYPE_BF16 ? 1 : 0, stride_b, stride_t, stride_f, p[43]};
-  DFA_HIP_CHECK(ctx, launch_cae_dec4_bwd(prec, ws + pl.d[2], p[42], drecon, ws + pl.dd[2], partial, B, pl.Hd[2], pl.Wd[2], T, F, s, drecon ? nullptr : &ma));
+  MseArgs ma{v, head.b};
+  DFA_HIP_CHECK(ctx, launch_cae_dec4_bwd(prec, ws + pl.d[2], head.w, drecon, ws + pl.dd[2], partial, B, pl.Hd[2], pl.Wd[2], T, F, s, drecon ? nullptr : &ma));
   DFA_HIP_CHECK(ctx, launch_reduce_partials(partial, cae_dec4_bwd_blocks(), 132, 1.0f, rec, s, nullptr));
-  DFA_HIP_CHECK(ctx, hipMemcpyAsync(grads[28], rec, 128 * 4, hipMemcpyDeviceToDevice, s));
-  DFA_HIP_CHECK(ctx, hipMemcpyAsync(grads[29], rec + 128, 4, hipMemcpyDeviceToDevice, s));
+  DFA_HIP_CHECK(ctx, hipMemcpyAsync(gh.dw, rec, 128 * 4, hipMemcpyDeviceToDevice, s));
+  DFA_HIP_CHECK(ctx, hipMemcpyAsync(gh.db, rec + 128, 4, hipMemcpyDeviceToDevice, s));
   // ---- decoder blocks 3, 2, 1
   for (int l = 2; l >= 0; --l) {
-    const float* const* q = p + 24 + 6 * l;
+    const LayerParams q = layer_params(m.p, kCaeDec0 + l);
+    const LayerGrads g = layer_grads(grads, kCaeDec0 + l);
     const int Hin = pl.Hd[l] / 2, Win = (l == 1) ? (pl.Wd[l] - 1) / 2 : pl.Wd[l] / 2;
     const int Cin = kDCin[l], Cout = kDC[l];
     const long P = (long)B * Hin * Win;
-    BnStats st = stat_of(ws, pl, 4 + l, Cout);
-    float* sm = sums_of(ws, pl, 4 + l);
+    BnStats st = stat_of(ws, pl, kCaeDec0 + l, Cout);
+    float* sm = sums_of(ws, pl, kCaeDec0 + l);
+    const BnApply bn = bn_apply(st, q);
     if (ctx->cae_bwd_fold) {
       // one apply pass writes dz patch-major (what the two gradient GEMMs read) and leaves the records of its channel sums = the
       // ConvTranspose2d bias gradient (over ALL output pixels, the output_padding column included): dzd itself is never stored
       dfa::BnBwdFold fold{ws + pl.zp, Win, partial, 0};
-      DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], st.mean, st.invstd, q[2], q[3], nullptr, ws + pl.dd[l], partial, sm,
-                                       nullptr, B, pl.Hd[l], pl.Wd[l], Cout, nodrop, s, scratch2, sync, &fold));
-      DFA_HIP_CHECK(ctx, launch_split_sums(sm, grads[16 + 4 * l + 2], grads[16 + 4 * l + 3], Cout, s));
-      DFA_HIP_CHECK(ctx, launch_reduce_partials(partial, fold.nrec, Cout, 1.0f, grads[16 + 4 * l + 1], s, scratch2));
+      DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], bn, nullptr, ws + pl.dd[l], partial, sm, nullptr, B, pl.Hd[l], pl.Wd[l],
+                                       Cout, nodrop, s, scratch2, sync, &fold));
+      DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, Cout, s));
+      DFA_HIP_CHECK(ctx, launch_reduce_partials(partial, fold.nrec, Cout, 1.0f, g.db, s, scratch2));
     } else {
-    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], st.mean, st.invstd, q[2], q[3], nullptr, ws + pl.dd[l], partial, sm,
-                                     ws + pl.dzd[l], B, pl.Hd[l], pl.Wd[l], Cout, nodrop, s, scratch2, sync));
-    DFA_HIP_CHECK(ctx, launch_split_sums(sm, grads[16 + 4 * l + 2], grads[16 + 4 * l + 3], Cout, s));
+    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], bn, nullptr, ws + pl.dd[l], partial, sm, ws + pl.dzd[l], B, pl.Hd[l],
+                                     pl.Wd[l], Cout, nodrop, s, scratch2, sync));
+    DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, Cout, s));
     {  // ConvTranspose2d bias gradient = channel sums of dz over ALL output pixels (the output_padding column included)
       int ppb;
       const size_t npix = (size_t)B * pl.Hd[l] * pl.Wd[l];
       const int nblk = cl_stats_blocks(npix, &ppb);
       DFA_HIP_CHECK(ctx, launch_cl_stats(prec, ws + pl.dzd[l], partial, npix, Cout, s));
       DFA_HIP_CHECK(ctx, launch_reduce_partials(partial, nblk, Cout * 2, 1.0f, scratch_c, s, scratch2));
-      DFA_HIP_CHECK(ctx, launch_split_sums(scratch_c, scratch_c + 512, grads[16 + 4 * l + 1], Cout, s));
+      DFA_HIP_CHECK(ctx, launch_split_sums(scratch_c, scratch_c + 512, g.db, Cout, s));
     }
     DFA_HIP_CHECK(ctx, launch_pixel_unshuffle(prec, ws + pl.dzd[l], ws + pl.zp, B, Hin, Win, pl.Wd[l], Cout, s));
     }
     float* wq = (float*)(ws + pl.wq);
-    DFA_HIP_CHECK(ctx, launch_convt_w_to_q(q[0], wq, Cin, Cout, s));
+    DFA_HIP_CHECK(ctx, launch_convt_w_to_q(q.w, wq, Cin, Cout, s));
     // data gradient: dX[P x Cin] = Zp[P x 4Cout] . Wq^T
     float* xf = (float*)(ws + pl.xf);
     void* dx = (l == 0) ? ws + pl.de[3] : ws + pl.dd[l - 1];
@@ -367,22 +371,23 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
       DFA_HIP_CHECK(ctx, launch_gemm_f32(bf, xin, 1, Cin, bf, ws + pl.zp, 4 * Cout, 1, partial, Cin, 4 * Cout, (int)P, kGemmSplit, s));
     }
     DFA_HIP_CHECK(ctx, launch_reduce_partials(partial, nparts, Cin * 4 * Cout, 1.0f, dwq, s, nullptr));
-    DFA_HIP_CHECK(ctx, launch_convt_q_to_w(dwq, grads[16 + 4 * l], Cin, Cout, s));
+    DFA_HIP_CHECK(ctx, launch_convt_q_to_w(dwq, g.dw, Cin, Cout, s));
   }
   // ---- encoder blocks 4, 3, 2
   for (int l = 3; l >= 1; --l) {
     BnStats st = stat_of(ws, pl, l, kEC[l]);
     float* sm = sums_of(ws, pl, l);
-    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL22, ws + pl.z[l], st.mean, st.invstd, p[6 * l + 2], p[6 * l + 3], nullptr, ws + pl.de[l], partial, sm,
+    const LayerGrads g = layer_grads(grads, l);
+    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL22, ws + pl.z[l], bn_apply(st, layer_params(m.p, l)), nullptr, ws + pl.de[l], partial, sm,
                                      ws + pl.dz[l], B, pl.H[l], pl.W[l], kEC[l], nodrop, s, scratch2, sync));
-    DFA_HIP_CHECK(ctx, launch_split_sums(sm, grads[4 * l + 2], grads[4 * l + 3], kEC[l], s));
+    DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, kEC[l], s));
     if (l == 3) {
       for (int co = 0; co < 2; ++co)
         for (int ci = 0; ci < 2; ++ci)
-          DFA_HIP_CHECK(ctx, launch_wgrad3x3_window(prec, 64, 128, 128, 256, 64 * ci, 128 * co, ws + pl.dz[3], ws + pl.e[2], partial, grads[12],
-                                                    ci == 0 ? grads[13] : nullptr, B, pl.H[3], pl.W[3], kWgradWGs, s));
+          DFA_HIP_CHECK(ctx, launch_wgrad3x3_window(prec, 64, 128, 128, 256, 64 * ci, 128 * co, ws + pl.dz[3], ws + pl.e[2], partial, g.dw,
+                                                    ci == 0 ? g.db : nullptr, B, pl.H[3], pl.W[3], kWgradWGs, s));
     } else {
-      DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, kEC[l - 1], kEC[l], ws + pl.dz[l], ws + pl.e[l - 1], partial, grads[4 * l], grads[4 * l + 1], B,
+      DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, kEC[l - 1], kEC[l], ws + pl.dz[l], ws + pl.e[l - 1], partial, g.dw, g.db, B,
                                          pl.H[l], pl.W[l], kWgradWGs, s));
     }
     const ConvArgs a = conv_args(ws + pl.dz[l], m.tdg[l - 1], ws + pl.de[l - 1], B, pl.H[l], pl.W[l], kEC[l - 1], ctx);
@@ -392,7 +397,7 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
   }
   // ---- encoder block 1 (z1 recomputed from x; upstream through the 2x2 average pool): matrix-core pass + algebra, or two vector passes
   const bool c1_mfma = m.train_c1_mfma && ctx->conv1_mfma;
-  return conv1_train_backward(ctx, conv1_block(m, x, x_dtype, stride_b, stride_t, stride_f, B, T, F, ws, pl, c1_mfma), c1_mfma, false, sync, grads);
+  return conv1_train_backward(ctx, conv1_block(m, v, ws, pl, c1_mfma), c1_mfma, false, sync, layer_grads(grads, 0));
 }
 
 int dfa_mse_fwd_bwd(dfa_ctx* ctx, const float* recon, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
@@ -405,8 +410,8 @@ int dfa_mse_fwd_bwd(dfa_ctx* ctx, const float* recon, const void* x, int x_dtype
   if (B < 1 || T < 1 || F < 1) return fail(ctx, DFA_E_BAD_SHAPE, "need B, T, F >= 1 (got %d, %d, %d)", B, T, F);
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (!ctx->mse_partial) DFA_HIP_CHECK(ctx, hipMalloc((void**)&ctx->mse_partial, kMseBlocks * sizeof(float)));
-  DFA_HIP_CHECK(ctx, launch_mse_fwd_bwd(recon, x, x_dtype == DFA_DTYPE_BF16 ? 1 : 0, stride_b, stride_t, stride_f, B, T, F, ctx->mse_partial,
-                                        loss, drecon, ctx->stream));
+  DFA_HIP_CHECK(ctx, launch_mse_fwd_bwd(recon, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T, F}, ctx->mse_partial, loss, drecon,
+                                        ctx->stream));
   return DFA_OK;
 }
 

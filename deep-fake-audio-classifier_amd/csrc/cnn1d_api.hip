@@ -8,9 +8,7 @@ using namespace dfa;
 
 namespace {
 
-struct Cnn1dPlan {
-  size_t h1_off, h2_off, pooled_off, total;
-};
+struct Cnn1dPlan { size_t h1_off, h2_off, pooled_off, total; };
 
 Cnn1dPlan plan_cnn1d(int B, int T) {
   Cnn1dPlan p;
@@ -77,8 +75,7 @@ int dfa_cnn1d_prepare(dfa_ctx* ctx) {
   for (int l = 0; l < 3; ++l) {
     m.w[l] = (float*)((char*)m.packed + off[l]);
     m.b[l] = (float*)((char*)m.packed + boff[l]);
-    const float* const* q = m.p + 6 * l;
-    DFA_HIP_CHECK(ctx, launch_fold_conv1d(q[0], q[1], q[2], q[3], q[4], q[5], m.w[l], m.b[l], cin[l], cout[l], ctx->stream));
+    DFA_HIP_CHECK(ctx, launch_fold_conv1d(layer_params(m.p, l), m.w[l], m.b[l], cin[l], cout[l], ctx->stream));
     m.wp[l] = (float*)((char*)m.packed + poff[l]);
     DFA_HIP_CHECK(ctx, launch_pack_cnn1d_fused(m.w[l], m.wp[l], cin[l], cout[l], l, ctx->stream));
     m.wx[l] = (char*)m.packed + xoff[l];
@@ -99,18 +96,20 @@ int dfa_cnn1d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   char* ws = (char*)workspace;
   float *h1 = (float*)(ws + pl.h1_off), *h2 = (float*)(ws + pl.h2_off), *pooled = (float*)(ws + pl.pooled_off);
   hipStream_t s = ctx->stream;
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
+  const HeadParams head = head_params(m.p, kCnn1dLayers, 0);
   // (the fused kernel addresses an utterance's elements with 32-bit offsets)
   const bool off32 = stride_t >= 0 && stride_f >= 0 && (int64_t)(F - 1) * stride_f + (int64_t)(T - 1) * stride_t < ((int64_t)1 << 31);
-  if (ctx->cnn1d_fused == 1 && cnn1d_fused_x3_supports(x, stride_b, stride_t, stride_f, T, F)) {   // split-bf16 matrix cores (slot 4)
+  if (ctx->cnn1d_fused == 1 && cnn1d_fused_x3_supports(v)) {   // split-bf16 matrix cores (slot 4)
     ScopedSlot ts(ctx, 4);
-    DFA_HIP_CHECK(ctx, launch_cnn1d_fused_x3((const float*)x, m.wx[0], m.b[0], m.wx[1], m.b[1], m.wx[2], m.b[2], m.p[18], m.p[19], logits, B, T, F,
+    DFA_HIP_CHECK(ctx, launch_cnn1d_fused_x3((const float*)x, m.wx[0], m.b[0], m.wx[1], m.b[1], m.wx[2], m.b[2], head.w, head.b, logits, B, T, F,
                                              s, ctx->clock_probe ? ctx->clock_buf : nullptr));
     return DFA_OK;
   }
   if (ctx->cnn1d_fused && cnn1d_fused_supports(T) && off32) {   // one kernel, one global write per utterance (timing slot 4)
     ScopedSlot ts(ctx, 4);
-    DFA_HIP_CHECK(ctx, launch_cnn1d_fused((const float*)x, stride_b, stride_t, stride_f, m.wp[0], m.b[0], m.wp[1], m.b[1], m.wp[2], m.b[2],
-                                          m.p[18], m.p[19], logits, B, T, F, s, ctx->clock_probe ? ctx->clock_buf : nullptr));
+    DFA_HIP_CHECK(ctx, launch_cnn1d_fused(v, m.wp[0], m.b[0], m.wp[1], m.b[1], m.wp[2], m.b[2], head.w, head.b, logits, s,
+                                          ctx->clock_probe ? ctx->clock_buf : nullptr));
     return DFA_OK;
   }
   { ScopedSlot ts(ctx, 4);
@@ -120,7 +119,7 @@ int dfa_cnn1d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   { ScopedSlot ts(ctx, 6);
     DFA_HIP_CHECK(ctx, launch_conv1d(h2, (int64_t)64 * T, T, 1, m.w[2], m.b[2], pooled, B, 64, 128, T, true, s)); }
   { ScopedSlot ts(ctx, 7);
-    DFA_HIP_CHECK(ctx, launch_linear(pooled, m.p[18], m.p[19], logits, B, 128, s)); }
+    DFA_HIP_CHECK(ctx, launch_linear(pooled, head.w, head.b, logits, B, 128, s)); }
   return DFA_OK;
 }
 
@@ -150,8 +149,9 @@ int dfa_cnn1d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, cnn1d_workspace_bytes(B, T_max, true)));
   DFA_TRY(stage_ragged_lengths(ctx, lengths, B, workspace));
   ScopedSlot ts(ctx, 4);
+  const HeadParams head = head_params(m.p, kCnn1dLayers, 0);
   DFA_HIP_CHECK(ctx, launch_cnn1d_ragged_x3((const float*)x, stride_b, stride_f, (const int*)workspace, m.wx[0], m.b[0], m.wx[1], m.b[1], m.wx[2],
-                                            m.b[2], m.p[18], m.p[19], logits, B, T_max, F, ctx->stream,
+                                            m.b[2], head.w, head.b, logits, B, T_max, F, ctx->stream,
                                             ctx->clock_probe ? ctx->clock_buf : nullptr));
   return DFA_OK;
 }

@@ -387,16 +387,17 @@ bool cnn1d_fused_supports(int T) {   // layer 1 gives a wave at most MAXT1 tiles
   return T >= 3 && (T + c1f::TW - 1) / c1f::TW <= 4 * c1f::MAXT1 && cnn1d_fused_lds_bytes(T) <= 160 * 1024;
 }
 
-hipError_t launch_cnn1d_fused(const float* x, int64_t sb, int64_t st, int64_t sf, const float* wp1, const float* b1, const float* wp2,
-                              const float* b2, const float* wp3, const float* b3, const float* cw, const float* cb, float* logits, int B,
-                              int T, int F, hipStream_t s, long long* stamps) {
+// v: float32 features (the entry point has refused every other dtype)
+hipError_t launch_cnn1d_fused(const FeatView& v, const float* wp1, const float* b1, const float* wp2, const float* b2, const float* wp3,
+                              const float* b3, const float* cw, const float* cb, float* logits, hipStream_t s, long long* stamps) {
+  const int B = v.B, T = v.T, F = v.F;
   Cnn1dFusedArgs a{};
   a.stamps = stamps;
-  a.x = x; a.sb = sb; a.st = st; a.sf = sf;
+  a.x = (const float*)v.x; a.sb = v.sb; a.st = v.st; a.sf = v.sf;
   a.wp1 = wp1; a.b1 = b1; a.wp2 = wp2; a.b2 = b2; a.wp3 = wp3; a.b3 = b3; a.cw = cw; a.cb = cb; a.logits = logits;
   a.T = T; a.F = F; a.NT = (T + c1f::TW - 1) / c1f::TW; a.pitch = 32 * a.NT + 8; a.ncp1 = cnn1d_fused_ncp_pad(F, 0);
   const size_t lds = cnn1d_fused_lds_bytes(T);
-  auto kern = (st == 1) ? cnn1d_fused_kernel<true> : cnn1d_fused_kernel<false>;
+  auto kern = (v.st == 1) ? cnn1d_fused_kernel<true> : cnn1d_fused_kernel<false>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, s, a);

@@ -548,10 +548,11 @@ hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const fl
   return mt == 2 ? go(conv1d_x3_kernel<2, 2>) : go(conv1d_x3_kernel<1, 2>);
 }
 
-bool cnn1d_fused_x3_supports(const void* x, int64_t sb, int64_t st, int64_t sf, int T, int F) {
+bool cnn1d_fused_x3_supports(const FeatView& v) {
+  const int T = v.T, F = v.F;
   // (a slab of 16 channels = 4 T float4 must fit the 3 x 512 loads of a trip: T <= 384)
   if (T < 3 || T > 384 || (T + 31) / 32 > c1x::NW * c1x::MAXT1 || F < 1 || (F & 3)) return false;
-  if (st != 1 || sf != T || sb != (int64_t)F * T || ((uintptr_t)x & 15)) return false;
+  if (v.st != 1 || v.sf != T || v.sb != (int64_t)F * T || ((uintptr_t)v.x & 15)) return false;
   int offB, total, sl;
   cnn1d_x3_layout(T, F, 0, &offB, &total, &sl);
   return total <= 160 * 1024;

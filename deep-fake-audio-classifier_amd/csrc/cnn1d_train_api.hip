@@ -47,12 +47,12 @@ float* sums1d(char* ws, const Train1dPlan& pl, int l) { return bn_sums(ws + pl.s
 // sits behind the uniform plan in the workspace; the backward reads it from there.
 size_t ragged1d_tab_bytes(int B) { return align_up((size_t)2 * B * sizeof(int32_t), 256); }
 
-// lengths == nullptr: the uniform step
-int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
-                             int64_t stride_t, int64_t stride_f, const int32_t* lengths, float p_drop, uint64_t seed, uint64_t offset,
-                             float momentum, int update_running_stats, float* logits, void* workspace,
-                             size_t workspace_bytes) {
+// lengths == nullptr: the uniform step.  v: the entry point's arguments as they came, checked here
+int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* lengths, float p_drop, uint64_t seed, uint64_t offset,
+                             float momentum, int update_running_stats, float* logits, void* workspace, size_t workspace_bytes) {
   Cnn1dState& m = ctx->cnn1d;
+  const float* x = (const float*)v.x;       // (float32: refused below otherwise)
+  const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
   const AugCfg armed = m.aug_armed;     // one-shot: consumed here, also by a call that fails its checks below
   m.aug_armed = AugCfg{};
   m.train_aug = AugCfg{};
@@ -107,17 +107,18 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
     for (int i = 0; i < 5; ++i) m.wx3[i] = base + off[i];
     m.wx3_F = F;
   }
-  const float* const* p = m.p;
+  const LayerParams layer[3] = {layer_params(m.p, 0), layer_params(m.p, 1), layer_params(m.p, 2)};
+  const HeadParams head = head_params(m.p, kCnn1dLayers, 0);
   hipStream_t s = ctx->stream;
   const int x3 = ctx->cnn1d_train_x3, terms = (x3 == 3) ? 2 : 3;
   // the fp32 data-gradient images are only read by the vector-ALU fallback (T > 384, option 0)
   const bool dgrad_x3 = x3 && conv1d_x3_supports((const float*)workspace, (int64_t)128 * T, T, 1, (const float*)workspace, T, 128, 64, terms) &&
                         conv1d_x3_supports((const float*)workspace, (int64_t)64 * T, T, 1, (const float*)workspace, T, 64, 32, terms);
   if (!dgrad_x3) {
-    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(p[6], m.wt[0], m.zero_bias, 32, 64, s));
-    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(p[12], m.wt[1], m.zero_bias, 64, 128, s));
+    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[1].w, m.wt[0], m.zero_bias, 32, 64, s));
+    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[2].w, m.wt[1], m.zero_bias, 64, 128, s));
   }
-  if (x3) DFA_HIP_CHECK(ctx, launch_pack_conv1d_train_all(p[0], p[6], p[12], m.wx3, F, terms, m.zero_bias, s));   // all five images, one launch
+  if (x3) DFA_HIP_CHECK(ctx, launch_pack_conv1d_train_all(layer[0].w, layer[1].w, layer[2].w, m.wx3, F, terms, m.zero_bias, s));   // all five images, one launch
   m.train_x3 = x3;
   DropCfg dc = drop_cfg(p_drop, seed, offset);
   m.train_drop = dc; m.train_B = B; m.train_T = T;
@@ -128,72 +129,71 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   const int nch = cm_chunks(B);
   for (int l = 0; l < 3; ++l) {
     float* z = (float*)(ws + pl.z[l]);
-    const float* const* q = p + 6 * l;
+    const LayerParams& q = layer[l];
     if (l == 0) {
-      if (x3 && conv1d_x3_supports((const float*)x, stride_b, stride_f, stride_t, z, T, F, 32, terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3((const float*)x, stride_b, m.wx3[0], q[1], z, B, F, 32, T, terms, s, x3, aug, lens));
+      if (x3 && conv1d_x3_supports(x, v.sb, v.sf, v.st, z, T, F, 32, terms))
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(x, v.sb, m.wx3[0], q.b, z, B, F, 32, T, terms, s, x3, aug, lens));
       else
-        DFA_HIP_CHECK(ctx, launch_conv1d((const float*)x, stride_b, stride_f, stride_t, q[0], q[1], z, B, F, 32, T, false, s, false, aug, lens));
+        DFA_HIP_CHECK(ctx, launch_conv1d(x, v.sb, v.sf, v.st, q.w, q.b, z, B, F, 32, T, false, s, false, aug, lens));
     } else {
       const float* hin = (const float*)(ws + pl.h[l - 1]);
       if (x3 && conv1d_x3_supports(hin, (int64_t)Cin[l] * T, T, 1, z, T, Cin[l], C[l], terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3(hin, (int64_t)Cin[l] * T, m.wx3[l], q[1], z, B, Cin[l], C[l], T, terms, s, x3));
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(hin, (int64_t)Cin[l] * T, m.wx3[l], q.b, z, B, Cin[l], C[l], T, terms, s, x3));
       else
-        DFA_HIP_CHECK(ctx, launch_conv1d(hin, (int64_t)Cin[l] * T, T, 1, q[0], q[1], z, B, Cin[l], C[l], T, false, s, false));
+        DFA_HIP_CHECK(ctx, launch_conv1d(hin, (int64_t)Cin[l] * T, T, 1, q.w, q.b, z, B, Cin[l], C[l], T, false, s, false));
     }
     BnStats st = st1d(ws, pl, l);
     const bool shifted = !ctx->bn_sync.fn;       // sums of z - z[0][c][0]: see cm_stats_body
     DFA_HIP_CHECK(ctx, launch_cm_stats(z, partial, B, C[l], T, s, lens, shifted));
-    DFA_TRY(finalize_bn_stats(ctx, partial, nch, C[l], frames, st, update_running_stats ? (float*)q[4] : nullptr,
-                              update_running_stats ? (float*)q[5] : nullptr, momentum, nullptr, shifted ? z : nullptr, T));
+    DFA_TRY(finalize_bn_stats(ctx, partial, nch, C[l], frames, st, running_stats(q, update_running_stats), momentum, nullptr, shifted ? z : nullptr, T));
     if (l < 2) {
       dc.layer = 1 + l;
-      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_drop(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.h[l]), B, C[l], T, dc, s, lens));
+      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_drop(z, bn_apply(st, q), (float*)(ws + pl.h[l]), B, C[l], T, dc, s, lens));
     } else {
-      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_meant(z, st.mean, st.invstd, q[2], q[3], (float*)(ws + pl.pooled), B, 128, T, s, lens));
+      DFA_HIP_CHECK(ctx, launch_cm_bn_relu_meant(z, bn_apply(st, q), (float*)(ws + pl.pooled), B, 128, T, s, lens));
     }
   }
-  DFA_HIP_CHECK(ctx, launch_linear((const float*)(ws + pl.pooled), p[18], p[19], logits, B, 128, s));
+  DFA_HIP_CHECK(ctx, launch_linear((const float*)(ws + pl.pooled), head.w, head.b, logits, B, 128, s));
   return DFA_OK;
 }
 
 // ragged = which of the two entry points this is: it must be the one whose forward is in flight
-int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b, int64_t stride_t,
-                        int64_t stride_f, const float* dlogits, float* const* grads, int ngrads, void* workspace,
+int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const FeatView& v, const float* dlogits, float* const* grads, int ngrads, void* workspace,
                         size_t workspace_bytes) {
   Cnn1dState& m = ctx->cnn1d;
+  const int B = v.B, T = v.T, F = v.F;
   Train1dPlan pl;
   DFA_TRY(check_backward(ctx, {ragged ? "dfa_cnn1d_backward_ragged" : "dfa_cnn1d_backward",
-                               ragged ? "dfa_cnn1d_forward_train_ragged" : "dfa_cnn1d_forward_train", "cnn1d", 14, "dlogits", true},
-                         m.train_packed && m.train_B == B && m.train_T == T && m.train_ragged == ragged, x, x_dtype, dlogits, grads, ngrads,
+                               ragged ? "dfa_cnn1d_forward_train_ragged" : "dfa_cnn1d_forward_train", "cnn1d", kCnn1dGrads, "dlogits", true},
+                         m.train_packed && m.train_B == B && m.train_T == T && m.train_ragged == ragged, v.x, v.dtype, dlogits, grads, ngrads,
                          workspace, workspace_bytes, [&] { return (pl = plan_train1d(B, T, F)).total + (ragged ? ragged1d_tab_bytes(B) : 0); }));
   if (ragged && ctx->bn_sync.fn)
     return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed)");
   char* ws = (char*)workspace;
   const int* lens = ragged ? (const int*)(ws + pl.total) : nullptr;     // the table the forward left behind the plan
   float* partial = (float*)(ws + pl.partial);
-  const float* const* p = m.p;
+  const HeadGrads gh = head_grads(grads, kCnn1dLayers, 0);
   hipStream_t s = ctx->stream;
   DropCfg dc = m.train_drop;
   const int C[3] = {32, 64, 128}, Cin[3] = {F, 32, 64};
   float* dpooled = (float*)(ws + pl.dpooled);
-  DFA_HIP_CHECK(ctx, launch_linear_bwd(dlogits, p[18], (const float*)(ws + pl.pooled), dpooled, grads[12], grads[13], B, 128, s));
+  DFA_HIP_CHECK(ctx, launch_linear_bwd(dlogits, head_params(m.p, kCnn1dLayers, 0).w, (const float*)(ws + pl.pooled), dpooled, gh.dw, gh.db, B, 128, s));
   for (int l = 2; l >= 0; --l) {
-    const float* const* q = p + 6 * l;
+    const LayerGrads g = layer_grads(grads, l);
     BnStats st = st1d(ws, pl, l);
     float* sm = sums1d(ws, pl, l);
     float* dz = (float*)(ws + pl.dz[l]);
     const float* up = (l == 2) ? dpooled : (const float*)(ws + pl.dh[l]);
     dc.layer = 1 + l;
-    DFA_HIP_CHECK(ctx, launch_cm_bn_bwd(l == 2 ? 0 : 1, (const float*)(ws + pl.z[l]), st.mean, st.invstd, q[2], q[3], up, partial, sm, dz,
+    DFA_HIP_CHECK(ctx, launch_cm_bn_bwd(l == 2 ? 0 : 1, (const float*)(ws + pl.z[l]), bn_apply(st, layer_params(m.p, l)), up, partial, sm, dz,
                                         B, C[l], T, dc, s, ctx->bn_sync.fn ? &ctx->bn_sync : nullptr, lens, m.train_frames));
-    DFA_HIP_CHECK(ctx, launch_split_sums(sm, grads[4 * l + 2], grads[4 * l + 3], C[l], s));
+    DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, C[l], s));
     if (l == 0) {
-      DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)x, stride_b, stride_f, stride_t, partial, grads[0], grads[1], B, F, 32, T, s,
+      DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)v.x, v.sb, v.sf, v.st, partial, g.dw, g.db, B, F, 32, T, s,
                                              m.train_aug.on ? &m.train_aug : nullptr, m.train_x3, lens));
     } else {
-      DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)(ws + pl.h[l - 1]), (int64_t)Cin[l] * T, T, 1, partial, grads[4 * l],
-                                             grads[4 * l + 1], B, Cin[l], C[l], T, s, nullptr, m.train_x3));
+      DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)(ws + pl.h[l - 1]), (int64_t)Cin[l] * T, T, 1, partial, g.dw,
+                                             g.db, B, Cin[l], C[l], T, s, nullptr, m.train_x3));
       // data gradient: dh[l-1] = conv1d(dz; W'[Cin][Cout][3]) -- a Conv1d with Cout input channels, Cin output channels
       float* dh = (float*)(ws + pl.dh[l - 1]);
       const int terms = (m.train_x3 == 3) ? 2 : 3;
@@ -222,7 +222,7 @@ int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
                             size_t workspace_bytes) {
   TraceRange trace_("dfa_cnn1d_forward_train");
   if (!ctx) return DFA_E_NULL_PTR;
-  return cnn1d_forward_train_impl(ctx, x, x_dtype, B, T, F, stride_b, stride_t, stride_f, nullptr, p_drop, seed, offset, momentum,
+  return cnn1d_forward_train_impl(ctx, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T, F}, nullptr, p_drop, seed, offset, momentum,
                                   update_running_stats, logits, workspace, workspace_bytes);
 }
 
@@ -231,7 +231,7 @@ int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
                        size_t workspace_bytes) {
   TraceRange trace_("dfa_cnn1d_backward");
   if (!ctx) return DFA_E_NULL_PTR;
-  return cnn1d_backward_impl(ctx, 0, x, x_dtype, B, T, F, stride_b, stride_t, stride_f, dlogits, grads, ngrads, workspace, workspace_bytes);
+  return cnn1d_backward_impl(ctx, 0, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T, F}, dlogits, grads, ngrads, workspace, workspace_bytes);
 }
 
 size_t dfa_cnn1d_train_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F) {
@@ -250,7 +250,7 @@ int dfa_cnn1d_forward_train_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int
     ctx->cnn1d.aug_armed = AugCfg{};      // one-shot, as in every forward_train
     return fail(ctx, DFA_E_NULL_PTR, "lengths must be non-null");
   }
-  return cnn1d_forward_train_impl(ctx, x, x_dtype, B, T_max, F, stride_b, stride_t, stride_f, lengths, p_drop, seed, offset, momentum,
+  return cnn1d_forward_train_impl(ctx, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T_max, F}, lengths, p_drop, seed, offset, momentum,
                                   update_running_stats, logits, workspace, workspace_bytes);
 }
 
@@ -259,7 +259,8 @@ int dfa_cnn1d_backward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, i
                               size_t workspace_bytes) {
   TraceRange trace_("dfa_cnn1d_backward_ragged");
   if (!ctx) return DFA_E_NULL_PTR;
-  return cnn1d_backward_impl(ctx, 1, x, x_dtype, B, T_max, F, stride_b, stride_t, stride_f, dlogits, grads, ngrads, workspace, workspace_bytes);
+  return cnn1d_backward_impl(ctx, 1, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T_max, F}, dlogits, grads, ngrads, workspace,
+                             workspace_bytes);
 }
 
 }  // extern "C"

@@ -205,20 +205,20 @@ int dfa_cnn2d_prepare(dfa_ctx* ctx, int precision) {
   m.c1pack = (uint4*)(wp + w2_bytes + w3_bytes);
   m.c1bias = (float*)(wp + w2_bytes + w3_bytes + 4 * 64 * 16);
   m.c3_m16 = (uint4*)(wp + w2_bytes + w3_bytes + 4 * 64 * 16 + 256);
-  const float* const* p = m.p;
-  DFA_HIP_CHECK(ctx, launch_fold_conv1(p[0], p[1], p[2], p[3], p[4], p[5], m.w1, m.b1, 32, ctx->stream));
+  const LayerParams l1 = layer_params(m.p, 0), l2 = layer_params(m.p, 1), l3 = layer_params(m.p, 2);
+  DFA_HIP_CHECK(ctx, launch_fold_conv1(l1, m.w1, m.b1, 32, ctx->stream));
   DFA_HIP_CHECK(ctx, launch_pack_conv1_mfma(m.w1, m.b1, m.c1pack, m.c1bias, ctx->stream));
   if (precision == DFA_PREC_BF16X3) {
     // hi/lo split images (conv_split.hip): the same byte counts as the fp32 images, so they live in the same regions
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_split(p[6], p[7], p[8], p[9], p[10], p[11], 32, 64, m.c2.wpack, m.c2.bias, 0.5f, ctx->stream));
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_split(p[12], p[13], p[14], p[15], p[16], p[17], 64, 128, m.c3.wpack, m.c3.bias, 1.0f, ctx->stream));
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_split(l2, 32, 64, m.c2.wpack, m.c2.bias, 0.5f, ctx->stream));
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_split(l3, 64, 128, m.c3.wpack, m.c3.bias, 1.0f, ctx->stream));
     m.prepared_prec = precision;
     return DFA_OK;
   }
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[6], p[7], p[8], p[9], p[10], p[11], 32, 0, 32, 64, precision, m.c2.wpack, m.c2.bias, ctx->stream, 1, 0.5f));
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[12], p[13], p[14], p[15], p[16], p[17], 64, 0, 64, 128, precision, m.c3.wpack, m.c3.bias, ctx->stream));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(l2, 32, 0, 32, 64, precision, m.c2.wpack, m.c2.bias, ctx->stream, 0.5f));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(l3, 64, 0, 64, 128, precision, m.c3.wpack, m.c3.bias, ctx->stream));
   if (precision == DFA_PREC_BF16)
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_m16(p[12], p[13], p[14], p[15], p[16], p[17], 64, 128, m.c3_m16, ctx->stream));
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_m16(l3, 64, 128, m.c3_m16, ctx->stream));
   m.prepared_prec = precision;
   return DFA_OK;
 }
@@ -234,6 +234,8 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   const int prec = m.prepared_prec;
   const Cnn2dForwardPlan pl = plan_for(ctx, B, T, F, prec, false);
   DFA_TRY(cnn2d_forward_buffers(ctx, workspace, workspace_bytes, pl.total, embedding));
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
+  const HeadParams head = head_params(m.p, kCnn2dLayers, 0);
   char* ws = (char*)workspace;
   void* a1 = ws + pl.a1_off;
   void* a2 = ws + pl.a2_off;
@@ -245,14 +247,13 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
   // The phase form with the classifier head inside (conv123_cls.hip): wherever the phase form runs, unless linear1_kernel would
   // take its scalar path (weights or embedding not 16-byte aligned), which the kernel does not reproduce.  Same plan, same
   // form and phase reported; the head runs in the kernel where that build has it (conv123_cls_in_kernel: the shipped one does).
-  const float* const cls_w = m.p[18];
-  const bool cls123 = pl.path == DFA_CNN2D_PATH_CONV123 && pl.p123.phase && ctx->cls123 && (((uintptr_t)cls_w | (uintptr_t)emb) & 15) == 0;
+  const bool cls123 = pl.path == DFA_CNN2D_PATH_CONV123 && pl.p123.phase && ctx->cls123 && (((uintptr_t)head.w | (uintptr_t)emb) & 15) == 0;
   bool head_done = false;
   if (pl.path == DFA_CNN2D_PATH_CONV123) {
     ScopedSlot ts(ctx, 2);
-    Conv123Args a = c123_args(x, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, m.c3_m16, m.c3.bias, emb,
-                                    B, T, F, pl.chunk3, ctx->clock_probe ? ctx->clock_buf : nullptr);
-    if (cls123) { a.cls_w = cls_w; a.cls_b = m.p[19]; a.logits = logits; a.cls_K = 128 * F; }
+    Conv123Args a = c123_args(v, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, m.c3_m16, m.c3.bias, emb, pl.chunk3,
+                              ctx->clock_probe ? ctx->clock_buf : nullptr);
+    if (cls123) { a.cls_w = head.w; a.cls_b = head.b; a.logits = logits; a.cls_K = 128 * F; }
     const auto launch = cls123 ? launch_conv123_cls : pl.p123.phase ? launch_conv123_phase : pl.p123.form == DFA_CONV123_CARRY ? launch_conv123_carry :
                         pl.p123.form == DFA_CONV123_PERSIST ? launch_conv123_persist : launch_conv123_fused;
     DFA_HIP_CHECK(ctx, launch(a, x_dtype, ctx->num_cus, s, ctx->lds_pipe));
@@ -260,11 +261,10 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
     ctx->last_conv123_cls = head_done ? 1 : 0;
   } else if (pl.path == DFA_CNN2D_PATH_CONV12) {
     ScopedSlot ts(ctx, 1);
-    DFA_HIP_CHECK(ctx, launch_conv12_fused(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, a2,
-                                           B, T, F, s, ctx->lds_pipe, pl.seg12));
+    DFA_HIP_CHECK(ctx, launch_conv12_fused(v, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, a2, s, ctx->lds_pipe, pl.seg12));
   } else {
     { ScopedSlot ts(ctx, 0);
-      DFA_HIP_CHECK(ctx, launch_conv1(x, x_dtype, stride_b, stride_t, stride_f, m.w1, m.b1, a1, prec, B, T, F, s)); }
+      DFA_HIP_CHECK(ctx, launch_conv1(v, m.w1, m.b1, a1, prec, s)); }
     ScopedSlot ts(ctx, 1);
     ConvArgs a{};
     a.in = a1; a.wpack = m.c2.wpack; a.bias = m.c2.bias; a.out = a2; a.emb = nullptr;
@@ -301,7 +301,7 @@ int dfa_cnn2d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, in
       const size_t n = (size_t)B * 128 * F;
       DFA_HIP_CHECK(ctx, launch_emb_reduce((const float*)(ws + pl.emb_off) + n, pl.nseg3, n, n, 1.0f / (float)pl.H2, emb, s));
     }
-    DFA_HIP_CHECK(ctx, launch_linear(emb, m.p[18], m.p[19], logits, B, 128 * F, s));
+    DFA_HIP_CHECK(ctx, launch_linear(emb, head.w, head.b, logits, B, 128 * F, s));
   }
   return DFA_OK;
 }
@@ -324,6 +324,8 @@ int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   DFA_TRY(refuse_capture(ctx, "forward"));
   const Cnn2dForwardPlan pl = plan_for(ctx, B, T_max, F, prec, true);
   DFA_TRY(cnn2d_forward_buffers(ctx, workspace, workspace_bytes, pl.total, embedding));
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T_max, F};
+  const HeadParams head = head_params(m.p, kCnn2dLayers, 0);
   char* ws = (char*)workspace;
   const int* dtab = (const int*)(ws + pl.tab_off);
   hipStream_t s = ctx->stream;
@@ -343,8 +345,7 @@ int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
   float* emb = embedding ? embedding : (float*)(ws + pl.emb_off);
   {   // blocks 1 + 2 (timing slot 1)
     ScopedSlot ts(ctx, 1);
-    DFA_HIP_CHECK(ctx, launch_conv12_ragged(x, x_dtype, stride_b, stride_t, stride_f, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, a2,
-                                            B, T_max, F, dtab, s, ctx->lds_pipe, pl.seg12));
+    DFA_HIP_CHECK(ctx, launch_conv12_ragged(v, m.c1pack, m.c1bias, m.c2.wpack, m.c2.bias, a2, dtab, s, ctx->lds_pipe, pl.seg12));
   }
   {   // block 3 + time mean (slot 2): split = one workgroup per chunk
     ScopedSlot ts(ctx, 2);
@@ -365,7 +366,7 @@ int dfa_cnn2d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
       const size_t n = (size_t)B * 128 * F;
       DFA_HIP_CHECK(ctx, launch_emb_reduce_ragged((const float*)(ws + pl.emb_off) + n, n, 128 * F, dtab, B, emb, s));
     }
-    DFA_HIP_CHECK(ctx, launch_linear(emb, m.p[18], m.p[19], logits, B, 128 * F, s));
+    DFA_HIP_CHECK(ctx, launch_linear(emb, head.w, head.b, logits, B, 128 * F, s));
   }
   return DFA_OK;
 }

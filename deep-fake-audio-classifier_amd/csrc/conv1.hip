@@ -155,9 +155,11 @@ __global__ __launch_bounds__(256) void conv1_bn_relu_poolh2_kernel(const TX* __r
   }
 }
 
-hipError_t launch_conv1(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* w1,
-                        const float* b1, void* out, int out_prec, int B, int T, int F, hipStream_t s,
+hipError_t launch_conv1(const FeatView& v, const float* w1, const float* b1, void* out, int out_prec, hipStream_t s,
                         const DropCfg* drop, const AugCfg* augp) {
+  const void* x = v.x;
+  const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
+  const int64_t sb = v.sb, st = v.st, sf = v.sf;
   DropCfg dc{};
   if (drop) dc = *drop;
   AugCfg aug{};

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "launch_views.h"
+
 namespace dfa {
 
 namespace c123 { constexpr int SW = 30; }   // output columns of a unit = an (utterance, strip) pair
@@ -28,13 +30,13 @@ struct Conv123Args {
   float* logits;            // [B]
   int cls_K;                // 128 * F
 };
-static inline Conv123Args c123_args(const void* x, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack, const float* c1bias,
-                                    const uint4* wpack2, const float* bias2, const uint4* wpack3, const float* bias3, float* emb, int B,
-                                    int T, int F, int chunk_iters, long long* clock_stamps) {
+static inline Conv123Args c123_args(const FeatView& v, const uint4* c1pack, const float* c1bias, const uint4* wpack2, const float* bias2,
+                                    const uint4* wpack3, const float* bias3, float* emb, int chunk_iters, long long* clock_stamps) {
+  const int T = v.T, F = v.F;
   Conv123Args a{};
-  a.x = x; a.sxb = sb; a.sxt = st; a.sxf = sf;
+  a.x = v.x; a.sxb = v.sb; a.sxt = v.st; a.sxf = v.sf;
   a.c1pack = c1pack; a.c1bias = c1bias; a.wpack2 = wpack2; a.bias2 = bias2; a.wpack3 = wpack3; a.bias3 = bias3; a.emb = emb;
-  a.B = B; a.T = T; a.F = F; a.H1 = T / 2; a.H2 = a.H1 / 2; a.nstrips = (F + c123::SW - 1) / c123::SW;
+  a.B = v.B; a.T = T; a.F = F; a.H1 = T / 2; a.H2 = a.H1 / 2; a.nstrips = (F + c123::SW - 1) / c123::SW;
   a.inv_h = 1.0f / (float)a.H2;
   a.chunk_iters = chunk_iters;
   a.clock_stamps = clock_stamps;

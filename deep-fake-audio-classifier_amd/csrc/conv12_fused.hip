@@ -126,29 +126,29 @@ static hipError_t launch_conv12_ragged_t(const Conv12Args& a, const RaggedTab& r
 }
 
 // ragged batch: x is [B, T_max, F] (strided), a2 is [B][T_max/4][F][64] with utterance b's rows 0 .. T_b/4 - 1 written
-hipError_t launch_conv12_ragged(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                const float* c1bias, const uint4* wpack2, const float* bias2, void* a2, int B, int T_max,
-                                int F, const int* tab, hipStream_t s, int pipe, int seg_iters) {
+hipError_t launch_conv12_ragged(const FeatView& v, const uint4* c1pack, const float* c1bias, const uint4* wpack2, const float* bias2, void* a2,
+                                const int* tab, hipStream_t s, int pipe, int seg_iters) {
+  const int B = v.B;
   Conv12Args a{};
   a.seg_iters = seg_iters;
-  a.x = x; a.sxb = sb; a.sxt = st; a.sxf = sf;
+  a.x = v.x; a.sxb = v.sb; a.sxt = v.st; a.sxf = v.sf;
   a.c1pack = c1pack; a.c1bias = c1bias; a.wpack = wpack2; a.bias = bias2; a.out = (bf16_t*)a2;
-  a.B = B; a.T = T_max; a.F = F; a.H1 = T_max / 2; a.nstrips = (F + c12::SW - 1) / c12::SW;
+  a.B = B; a.T = v.T; a.F = v.F; a.H1 = v.T / 2; a.nstrips = (v.F + c12::SW - 1) / c12::SW;
   const RaggedTab rt{tab, B};
-  if (x_dtype == DFA_DTYPE_BF16) return pipe ? launch_conv12_ragged_t<bf16_t, true>(a, rt, B, s) : launch_conv12_ragged_t<bf16_t, false>(a, rt, B, s);
+  if (v.dtype == DFA_DTYPE_BF16) return pipe ? launch_conv12_ragged_t<bf16_t, true>(a, rt, B, s) : launch_conv12_ragged_t<bf16_t, false>(a, rt, B, s);
   return pipe ? launch_conv12_ragged_t<float, true>(a, rt, B, s) : launch_conv12_ragged_t<float, false>(a, rt, B, s);
 }
 
-hipError_t launch_conv12_fused(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                               const float* c1bias, const uint4* wpack2, const float* bias2, void* a2, int B, int T,
-                               int F, hipStream_t s, int pipe, int seg_iters) {
+hipError_t launch_conv12_fused(const FeatView& v, const uint4* c1pack, const float* c1bias, const uint4* wpack2, const float* bias2, void* a2,
+                               hipStream_t s, int pipe, int seg_iters) {
+  const int B = v.B;
   Conv12Args a{};
   a.seg_iters = seg_iters;
-  a.x = x; a.sxb = sb; a.sxt = st; a.sxf = sf;
+  a.x = v.x; a.sxb = v.sb; a.sxt = v.st; a.sxf = v.sf;
   a.c1pack = c1pack; a.c1bias = c1bias; a.wpack = wpack2; a.bias = bias2; a.out = (bf16_t*)a2;
-  a.B = B; a.T = T; a.F = F; a.H1 = T / 2; a.nstrips = (F + c12::SW - 1) / c12::SW;
+  a.B = B; a.T = v.T; a.F = v.F; a.H1 = v.T / 2; a.nstrips = (v.F + c12::SW - 1) / c12::SW;
   hipError_t le;
-  if (x_dtype == DFA_DTYPE_BF16) le = pipe ? launch_conv12_t<bf16_t, true>(a, B, s) : launch_conv12_t<bf16_t, false>(a, B, s);
+  if (v.dtype == DFA_DTYPE_BF16) le = pipe ? launch_conv12_t<bf16_t, true>(a, B, s) : launch_conv12_t<bf16_t, false>(a, B, s);
   else le = pipe ? launch_conv12_t<float, true>(a, B, s) : launch_conv12_t<float, false>(a, B, s);
   if (le != hipSuccess) return le;
 #ifdef DFA_STAMPS

@@ -116,10 +116,9 @@ __global__ void fold_conv1d_kernel(const float* __restrict__ w, const float* __r
   if (i < cout) bf[i] = (b[i] - mean[i]) * (g[i] / sqrtf(var[i] + kBnEps)) + beta[i];
 }
 
-hipError_t launch_fold_conv1d(const float* w, const float* b, const float* g, const float* beta, const float* mean,
-                              const float* var, float* wf, float* bf, int cin, int cout, hipStream_t s) {
+hipError_t launch_fold_conv1d(const LayerParams& lp, float* wf, float* bf, int cin, int cout, hipStream_t s) {
   const int n = cout * cin * 3;
-  hipLaunchKernelGGL(fold_conv1d_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, b, g, beta, mean, var, wf, bf, cin,
+  hipLaunchKernelGGL(fold_conv1d_kernel, dim3((n + 255) / 256), dim3(256), 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, wf, bf, cin,
                      cout);
   return hipGetLastError();
 }

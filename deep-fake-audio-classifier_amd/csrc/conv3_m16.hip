@@ -85,12 +85,10 @@ __global__ void fold_pack_conv3x3_m16_kernel(const float* __restrict__ w, const 
   wpack[i] = *reinterpret_cast<const uint4*>(v);
 }
 
-hipError_t launch_fold_pack_conv3x3_m16(const float* w, const float* b, const float* g, const float* beta,
-                                        const float* mean, const float* var, int cin, int cout, uint4* wpack,
-                                        hipStream_t s, int fold) {
+hipError_t launch_fold_pack_conv3x3_m16(const LayerParams& lp, int cin, int cout, uint4* wpack, hipStream_t s) {
   const int total = (cout / 32) * 9 * 2 * 2 * 64;
-  hipLaunchKernelGGL(fold_pack_conv3x3_m16_kernel, dim3((total + 255) / 256), dim3(256), 0, s, w, b, g, beta, mean, var,
-                     cin, cout, wpack, fold);
+  hipLaunchKernelGGL(fold_pack_conv3x3_m16_kernel, dim3((total + 255) / 256), dim3(256), 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar,
+                     cin, cout, wpack, folds(lp) ? 1 : 0);
   return hipGetLastError();
 }
 

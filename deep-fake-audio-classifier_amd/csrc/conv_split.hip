@@ -415,13 +415,11 @@ __global__ void fold_pack_conv3x3_split_kernel(const float* __restrict__ w, cons
   wpack[i] = *reinterpret_cast<const uint4*>(v);
 }
 
-hipError_t launch_fold_pack_conv3x3_split(const float* w, const float* b, const float* g, const float* beta,
-                                          const float* mean, const float* var, int cin, int cout, uint4* wpack,
-                                          float* bias, float post_scale, hipStream_t s) {
+hipError_t launch_fold_pack_conv3x3_split(const LayerParams& lp, int cin, int cout, uint4* wpack, float* bias, float post_scale, hipStream_t s) {
   int total = (cout / 16) * 9 * (cin / 32) * 2 * 64;
   if (total < cout) total = cout;
-  hipLaunchKernelGGL(fold_pack_conv3x3_split_kernel, dim3((total + 255) / 256), dim3(256), 0, s, w, b, g, beta, mean, var,
-                     cin, cout, wpack, bias, post_scale);
+  hipLaunchKernelGGL(fold_pack_conv3x3_split_kernel, dim3((total + 255) / 256), dim3(256), 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean,
+                     lp.rvar, cin, cout, wpack, bias, post_scale);
   return hipGetLastError();
 }
 

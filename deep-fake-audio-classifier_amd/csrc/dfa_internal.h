@@ -12,6 +12,7 @@
 #include "../../include/dfa_hip.h"
 #include "conv3x3_mfma.h"
 #include "conv123_host.h"
+#include "launch_views.h"
 #include "rng.h"
 
 namespace dfa {
@@ -32,6 +33,17 @@ struct PackedConv {
   uint4* wpack = nullptr;  // [COUT/32][9][CIN/KG][64]
   float* bias = nullptr;   // [COUT]
 };
+
+// Every model's parameter array p is `layers` conv + BatchNorm layers of six pointers, then the head's (w, b) pairs; its gradient array
+// four per layer, then the head's (launch_views.h: layer_params, layer_grads, head_params, head_grads -- the only indexing of either).
+// CNN2D, CNN1D: three blocks + the linear head.  Auto-encoder: encoder blocks 1-4 = layers 0-3, decoder blocks 1-3 = layers 4-6, decoder
+// block 4 (no BatchNorm) = the head.  DeepfakeDetector: three layers + head.0 and head.3
+constexpr int kCnn2dLayers = 3, kCnn1dLayers = 3, kCaeLayers = 7, kCaeDec0 = 4, kDlqLayers = 3;
+constexpr int kCnn2dGrads = n_grads(kCnn2dLayers, 1), kCnn1dGrads = n_grads(kCnn1dLayers, 1), kCaeGrads = n_grads(kCaeLayers, 1),
+              kDlqGrads = n_grads(kDlqLayers, 2);
+static_assert(DFA_CNN2D_NPARAMS == n_params(kCnn2dLayers, 1) && DFA_CNN1D_NPARAMS == n_params(kCnn1dLayers, 1) &&
+              DFA_CAE_NPARAMS == n_params(kCaeLayers, 1) && DFA_DLQ_NPARAMS == n_params(kDlqLayers, 2), "parameter arrays: 6 per layer + the head");
+static_assert(kCnn2dGrads == 14 && kCnn1dGrads == 14 && kCaeGrads == 30 && kDlqGrads == 16, "gradient arrays (dfa_hip.h): 4 per layer + the head");
 
 struct Cnn2dState {
   const float* p[DFA_CNN2D_NPARAMS] = {nullptr};
@@ -242,26 +254,23 @@ struct ScopedSlot {
 };
 
 // ---- launch prototypes (one translation unit each, see Makefile) ---------------------------------
+// The caller's features come as a FeatView, a layer's six parameters as a LayerParams (raw_conv(layer): its convolution alone, no
+// BatchNorm folded), a BatchNorm layer's mean / invstd / gamma / beta as a BnApply: launch_views.h.  A launcher unpacks them into
+// its kernel's own arguments; the channel-major launchers of the CNN1D training path and the DeepfakeDetector keep their strides.
 // pack.hip
-hipError_t launch_fold_conv1(const float* w, const float* b, const float* g, const float* beta, const float* mean,
-                             const float* var, float* w1, float* b1, int cout, hipStream_t s);
-hipError_t launch_fold_pack_conv3x3(const float* w, const float* b, const float* g, const float* beta,
-                                    const float* mean, const float* var, int cin_total, int cin_off, int cin, int cout,
-                                    int prec, uint4* wpack, float* bias, hipStream_t s, int fold = 1,
-                                    float post_scale = 1.0f);
+hipError_t launch_fold_conv1(const LayerParams& lp, float* w1, float* b1, int cout, hipStream_t s);
+hipError_t launch_fold_pack_conv3x3(const LayerParams& lp, int cin_total, int cin_off, int cin, int cout, int prec, uint4* wpack,
+                                    float* bias, hipStream_t s, float post_scale = 1.0f);
 hipError_t launch_pack_conv3x3_dgrad(const float* w, int cin, int cout, int co_off, int co_n, int prec, uint4* wpack,
                                      float* bias, hipStream_t s);
-hipError_t launch_fold_pack_convt2x2(const float* w, const float* b, const float* g, const float* beta,
-                                     const float* mean, const float* var, int cin, int cout, int prec, uint4* wpack,
-                                     float* bias, hipStream_t s, int fold = 1);
+hipError_t launch_fold_pack_convt2x2(const LayerParams& lp, int cin, int cout, int prec, uint4* wpack, float* bias, hipStream_t s);
 // gemm_f32.hip
 hipError_t launch_gemm_tn_bf16(const void* X, const void* Z, float* partial, size_t partial_floats, int M, int N, int K,
                                int* nparts, hipStream_t s);
 hipError_t launch_gemm_f32(int a_bf16, const void* A, int64_t sam, int64_t sak, int b_bf16, const void* Bm, int64_t sbk,
                            int64_t sbn, float* C, int M, int N, int K, int ksplit, hipStream_t s);
 // conv1.hip
-hipError_t launch_conv1(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* w1,
-                        const float* b1, void* out, int out_prec, int B, int T, int F, hipStream_t s,
+hipError_t launch_conv1(const FeatView& v, const float* w1, const float* b1, void* out, int out_prec, hipStream_t s,
                         const DropCfg* drop = nullptr, const AugCfg* aug = nullptr);
 // linear.hip
 hipError_t launch_linear(const float* emb, const float* w, const float* bias, float* logits, int B, int K,
@@ -269,29 +278,25 @@ hipError_t launch_linear(const float* emb, const float* w, const float* bias, fl
 hipError_t launch_emb_reduce(const float* parts, int nparts, size_t stride, size_t n, float inv_h, float* out, hipStream_t s);
 hipError_t launch_emb_reduce_ragged(const float* parts, size_t stride, int per_b, const int* tab, int B, float* out, hipStream_t s);
 // conv1d.hip
-hipError_t launch_fold_conv1d(const float* w, const float* b, const float* g, const float* beta, const float* mean,
-                              const float* var, float* wf, float* bf, int cin, int cout, hipStream_t s);
+hipError_t launch_fold_conv1d(const LayerParams& lp, float* wf, float* bf, int cin, int cout, hipStream_t s);
 // cae_enc1_mfma.hip: auto-encoder block 1 (conv 1 -> 32 + ReLU + 2 x 2 pool) on the matrix cores, bf16 mode
-hipError_t launch_cae_enc1_mfma(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma,
-                                const uint4* c1pack, const float* c1bias, void* out, int B, int T, int F, hipStream_t s);
-hipError_t launch_cae_enc1_mfma_ragged(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma,
-                                       const uint4* c1pack, const float* c1bias, void* out, int B, int T, int F, const int* tab,
-                                       hipStream_t s);
+hipError_t launch_cae_enc1_mfma(const FeatView& v, const float* mu, const float* sigma, const uint4* c1pack, const float* c1bias, void* out,
+                                hipStream_t s);
+hipError_t launch_cae_enc1_mfma_ragged(const FeatView& v, const float* mu, const float* sigma, const uint4* c1pack, const float* c1bias,
+                                       void* out, const int* tab, hipStream_t s);
 hipError_t launch_pack_cae_enc1_mfma(const float* w1, const float* b1, uint4* pack, float* bias, hipStream_t s);
 // cae_dec_fused.hip: the auto-encoder's decoder + per-sample squared error as one kernel (bf16 mode)
 int cae_dec_fused_tiles(int H4, int W4);
 hipError_t launch_cae_opad_consts(const float* b2, const uint4* wp3, const float* b3, const float* w4, const float* b4, float* cst,
                                   hipStream_t s);
-hipError_t launch_cae_dec_fused(const void* lat, const uint4* wp1, const float* b1, const uint4* wp2, const float* b2, const uint4* wp3,
-                                const float* b3, const float* w4, const float* b4, const uint4* w4pack, const float* cst, const void* x,
-                                int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma, float* recon,
-                                float* partial, int B, int H4, int W4, int T, int F, hipStream_t s, long long* stamps = nullptr);
-hipError_t launch_cae_dec_fused_ragged(const void* lat, const uint4* wp1, const float* b1, const uint4* wp2, const float* b2,
-                                       const uint4* wp3, const float* b3, const float* w4, const float* b4, const uint4* w4pack,
-                                       const float* cst, const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu,
-                                       const float* sigma, float* partial, int B, int H4, int W4, int T, int F, const int* tab,
+// dec = the three packed decoder blocks (CaeState::dec), head = decoder block 4
+hipError_t launch_cae_dec_fused(const void* lat, const PackedConv* dec, const HeadParams& head, const uint4* w4pack, const float* cst,
+                                const FeatView& v, const float* mu, const float* sigma, float* recon, float* partial, int H4, int W4,
+                                hipStream_t s, long long* stamps = nullptr);
+hipError_t launch_cae_dec_fused_ragged(const void* lat, const PackedConv* dec, const HeadParams& head, const uint4* w4pack, const float* cst,
+                                       const FeatView& v, const float* mu, const float* sigma, float* partial, int H4, int W4, const int* tab,
                                        hipStream_t s);
-bool cae_dec_fused_supports(int T, int F, int64_t st, int64_t sf);
+bool cae_dec_fused_supports(const FeatView& v);
 hipError_t launch_pack_cae_dec4(const float* w4, uint4* pack, hipStream_t s);
 hipError_t launch_cae_mse_finalize(const float* partial, int nblk, float inv_n, float* mse, int B, hipStream_t s);
 hipError_t launch_cae_mse_finalize_ragged(const float* partial, int nblk, const int* tab, float* mse, int B, hipStream_t s);
@@ -300,14 +305,13 @@ int cnn1d_fused_ncp_pad(int cin, int layer);
 size_t cnn1d_fused_pack_floats(int cin, int cout, int layer);
 bool cnn1d_fused_supports(int T);
 hipError_t launch_pack_cnn1d_fused(const float* wf, float* wp, int cin, int cout, int layer, hipStream_t s);
-hipError_t launch_cnn1d_fused(const float* x, int64_t sb, int64_t st, int64_t sf, const float* wp1, const float* b1, const float* wp2,
-                              const float* b2, const float* wp3, const float* b3, const float* cw, const float* cb, float* logits, int B,
-                              int T, int F, hipStream_t s, long long* stamps = nullptr);
+hipError_t launch_cnn1d_fused(const FeatView& v, const float* wp1, const float* b1, const float* wp2, const float* b2, const float* wp3,
+                              const float* b3, const float* cw, const float* cb, float* logits, hipStream_t s, long long* stamps = nullptr);
 // cnn1d_fused_x3.hip: the same forward on the bf16 matrix cores with hi + lo bf16 operands (fp32-grade accuracy)
 int cnn1d_x3_nks(int cin);
 size_t cnn1d_x3_pack_bytes(int cin, int cout);
 hipError_t launch_pack_cnn1d_x3(const float* wf, void* wx, int cin, int cout, hipStream_t s);
-bool cnn1d_fused_x3_supports(const void* x, int64_t sb, int64_t st, int64_t sf, int T, int F);
+bool cnn1d_fused_x3_supports(const FeatView& v);
 // ragged form (cnn1d_ragged_x3_kernel): x = the batch padded to T_max, element (b, f, t) at b stride_b + f stride_f + t;
 // tab = device table, [0, B) lengths, [B, 2B) dispatch order
 hipError_t launch_cnn1d_ragged_x3(const float* x, int64_t stride_b, int64_t stride_f, const int* tab, const void* w1, const float* b1,
@@ -351,7 +355,7 @@ struct DlqLayerArgs {
 };
 int dlq_nks(int cin);
 size_t dlq_pack_bytes(int cin, int taps);
-hipError_t launch_dlq_pack(const float* const* p6, int cin, int taps, void* wp, float* bias, hipStream_t s);
+hipError_t launch_dlq_pack(const LayerParams& lp, int cin, int taps, void* wp, float* bias, hipStream_t s);
 hipError_t launch_dlq_layer(int layer, const DlqLayerArgs& a, int ntiles, hipStream_t s);
 hipError_t launch_dlq_layer_train(int layer, int mode, const DlqLayerArgs& a, int ntiles, hipStream_t s);
 hipError_t launch_dlq_finish(const float* part, const int* tab, const float* w0, const float* b0, const float* w3, const float* b3, float* logits,
@@ -364,8 +368,7 @@ struct DlqPackJobs {
 hipError_t launch_dlq_train_pack(const float* w1, const float* w2, const float* w3, void* const* dst, int in_ch, hipStream_t s);
 hipError_t launch_dlq_bn_finalize(const float* rec, int ntiles, int tpu, int T_max, float* mean, float* var, float* invstd, float* rm, float* rv,
                                   float momentum, hipStream_t s);
-hipError_t launch_dlq_bn_act(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta, void* h,
-                             unsigned char* keep_out, long long N, const DropCfg& dc, hipStream_t s);
+hipError_t launch_dlq_bn_act(const float* z, const BnApply& bn, void* h, unsigned char* keep_out, long long N, const DropCfg& dc, hipStream_t s);
 struct DlqHeadArgs {       // layer 3's BN + GELU + dropout, the pool, the head; forward and backward
   const float *z3, *mean, *invstd, *gamma, *beta;   // layer 3
   const int* lens;
@@ -381,8 +384,7 @@ hipError_t launch_dlq_pool_head(const DlqHeadArgs& a, int B, hipStream_t s);
 hipError_t launch_dlq_head_bwd(const DlqHeadArgs& a, int B, float* dw0, float* db0, float* dw3, float* db3, hipStream_t s);
 hipError_t launch_dlq_dy3(const DlqHeadArgs& a, int B, int tpu, float* dy, float* rec, hipStream_t s);
 int dlq_dz_blocks(long long N);
-hipError_t launch_dlq_dz(const float* dy, const float* z, const float* mean, const float* invstd, const float* gamma, const float* sums, void* dz,
-                         float* dbrec, long long N, hipStream_t s);
+hipError_t launch_dlq_dz(const float* dy, const float* z, const BnApply& bn, const float* sums, void* dz, float* dbrec, long long N, hipStream_t s);
 struct DlqWgradArgs {
   const uint4* dz;       // [N] split pixels
   const uint4* h;        // the source as split pixels, or
@@ -402,12 +404,10 @@ int cm_chunks(int B);
 int conv1d_wgrad_chunks(int B);
 // lens (device, [B]) != null selects the ragged twins: utterance b owns frames [0, lens[b]) of the T the batch is padded to
 hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens = nullptr, bool shifted = false);
-hipError_t launch_cm_bn_relu_drop(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                  const float* beta, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s, const int* lens = nullptr);
-hipError_t launch_cm_bn_relu_meant(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                   const float* beta, float* pooled, int B, int C, int T, hipStream_t s, const int* lens = nullptr);
-hipError_t launch_cm_bn_bwd(int src, const float* z, const float* mean, const float* invstd, const float* gamma,
-                            const float* beta, const float* up, float* partial, float* sums, float* dz, int B, int C,
+hipError_t launch_cm_bn_relu_drop(const float* z, const BnApply& bn, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s,
+                                  const int* lens = nullptr);
+hipError_t launch_cm_bn_relu_meant(const float* z, const BnApply& bn, float* pooled, int B, int C, int T, hipStream_t s, const int* lens = nullptr);
+hipError_t launch_cm_bn_bwd(int src, const float* z, const BnApply& bn, const float* up, float* partial, float* sums, float* dz, int B, int C,
                             int T, const DropCfg& dc, hipStream_t s, const BnSync* sync = nullptr, const int* lens = nullptr, double n_valid = 0.0);
 bool conv1d_x3_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms);
 hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int Cout, int T,
@@ -420,15 +420,13 @@ hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int
                                float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug = nullptr, int x3 = 0, const int* lens = nullptr);
 hipError_t launch_conv1d_dgrad_pack(const float* w, float* wt, float* zero_bias, int cin, int cout, hipStream_t s);
 // cae.hip
-hipError_t launch_cae_enc1(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* mu,
-                           const float* sigma, const float* w1, const float* b1, void* out, int prec, int B, int T, int F,
+hipError_t launch_cae_enc1(const FeatView& v, const float* mu, const float* sigma, const float* w1, const float* b1, void* out, int prec,
                            hipStream_t s);
 hipError_t launch_cae_opad_col(void* out, const float* bias, int prec, int rows, int Wo, int C, hipStream_t s,
                                int no_relu = 0);
 int cae_dec4_blocks(int T, int W3);
-hipError_t launch_cae_dec4_mse(const void* d3, int prec, const float* w4, const float* b4, const void* x, int x_dtype,
-                               int64_t sb, int64_t st, int64_t sf, const float* mu, const float* sigma, float* recon,
-                               float* partial, float* mse, int B, int H3, int W3, int T, int F, hipStream_t s);
+hipError_t launch_cae_dec4_mse(const void* d3, int prec, const HeadParams& head, const FeatView& v, const float* mu, const float* sigma,
+                               float* recon, float* partial, float* mse, int H3, int W3, hipStream_t s);
 hipError_t launch_cae_latent_export(const void* lat, int prec, float* out, int B, int HW, int C, hipStream_t s);
 // train_elem.hip / train_conv1.hip / wgrad_mfma.hip
 // the `mode` of launch_conv1_train and the `src` of launch_bn_bwd (described at their kernels)
@@ -441,29 +439,24 @@ hipError_t launch_reduce_partials(const float* partial, int nparts, int n, float
                                   float* scratch = nullptr);
 hipError_t launch_reduce_partials_strided(const float* partial, int nparts, int stride, int off, int n, float* out,
                                           hipStream_t s);
-hipError_t launch_bn_relu_pool_drop(int prec, const void* z, const float* mean, const float* invstd, const float* gamma,
-                                    const float* beta, void* out, int B, int H, int W, int C, const DropCfg& dc,
+hipError_t launch_bn_relu_pool_drop(int prec, const void* z, const BnApply& bn, void* out, int B, int H, int W, int C, const DropCfg& dc,
                                     hipStream_t s);
 int cl_stats_blocks(size_t npix, int* pix_per_block);
 hipError_t launch_cl_stats(int prec, const void* z, float* partial, size_t npix, int C, hipStream_t s);
-hipError_t launch_bn_relu_pool(int prec, int pool, const void* z, const float* mean, const float* invstd,
-                               const float* gamma, const float* beta, void* out, int B, int H, int W, int C,
-                               hipStream_t s);
-hipError_t launch_bn_relu_meant(int prec, const void* z, const float* mean, const float* invstd, const float* gamma,
-                                const float* beta, float* emb, int B, int H, int W, int C, hipStream_t s, float* msum = nullptr);
-hipError_t launch_bn_bwd_meant_saved(int prec, const void* z, const float* mean, const float* invstd, const float* gamma,
-                                     const float* beta, const float* demb, const float* msum, float* partial, float* sums,
-                                     void* dz, int B, int H, int W, int C, hipStream_t s, const BnSync* sync = nullptr);
+hipError_t launch_bn_relu_pool(int prec, int pool, const void* z, const BnApply& bn, void* out, int B, int H, int W, int C, hipStream_t s);
+hipError_t launch_bn_relu_meant(int prec, const void* z, const BnApply& bn, float* emb, int B, int H, int W, int C, hipStream_t s,
+                                float* msum = nullptr);
+hipError_t launch_bn_bwd_meant_saved(int prec, const void* z, const BnApply& bn, const float* demb, const float* msum, float* partial,
+                                     float* sums, void* dz, int B, int H, int W, int C, hipStream_t s, const BnSync* sync = nullptr);
 hipError_t launch_linear_bwd(const float* dlogits, const float* w, const float* emb, float* demb, float* dw, float* db,
                              int B, int K, hipStream_t s, int tc = 0, int tw = 0);
 int bn_bwd_blocks(int B, int H, int W, int* pix_per_block);
 // SRC_DIRECT apply pass that writes dz patch-major (the pixel-unshuffled operand of a ConvTranspose2d(k2, s2) layer's gradient GEMMs,
 // Wh input columns) and leaves [nrec][C] records of its channel sums in bias_partial (train_elem.hip bn_bwd_apply_unshuffle_kernel)
 struct BnBwdFold { void* zp; int Wh; float* bias_partial; int nrec; };
-hipError_t launch_bn_bwd(int prec, int src, const void* z, const float* mean, const float* invstd, const float* gamma,
-                         const float* beta, const float* demb, const void* da, float* partial, float* sums, void* dz,
-                         int B, int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch = nullptr, const BnSync* sync = nullptr,
-                         BnBwdFold* fold = nullptr);
+hipError_t launch_bn_bwd(int prec, int src, const void* z, const BnApply& bn, const float* demb, const void* da, float* partial, float* sums,
+                         void* dz, int B, int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch = nullptr,
+                         const BnSync* sync = nullptr, BnBwdFold* fold = nullptr);
 // sums[C][2] -> dbeta = S1, dgamma = S2 (C <= 256); the conv1 weight-gradient record [32][10] -> dW1[32][9], db1[32]
 hipError_t launch_split_sums(const float* sums, float* dgamma, float* dbeta, int C, hipStream_t s);
 hipError_t launch_split_c1(const float* rec, float* dw, float* db, hipStream_t s);
@@ -475,15 +468,16 @@ int conv1_train_blocks(int B, int T, int F);
 // train_conv1_mfma.hip: the block-1 train passes on the matrix cores (bf16 features, no folded augmentation)
 enum { C1X_STATS = 0, C1X_FWD = 1, C1X_BWD = 2 };
 int conv1_mfma_blocks(int B, int T, int F);
-hipError_t launch_conv1_mfma(int mode, const void* x, int64_t sb, int64_t st, int64_t sf, const float* w, const float* bias,
-                             void* a1, const void* da1, float* partial, int B, int T, int F, const DropCfg& dc, hipStream_t s, int poolw = 1);
-hipError_t launch_conv1_train(int mode, const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* w,
-                              const float* bconv, const float* mean, const float* invstd, const float* gamma,
-                              const float* beta, const float* sums, const void* da1, int prec, float* partial, int B,
-                              int T, int F, const DropCfg& dc, hipStream_t s, int poolw = 1, const AugCfg* aug = nullptr, float inv_n_scale = 1.0f);
-hipError_t launch_conv1_bwd_finalize(const float* rec, const float* xxs, const float* w, const float* bconv, const float* mean,
-                                     const float* invstd, const float* gamma, double n, float* dw, float* db, float* dgamma,
-                                     float* dbeta, hipStream_t s, int derive_s2 = 0);
+// (v: bf16 features.)  The passes of one block 1 (train_host.h: Conv1Train); poolw = the pool behind the block, 1 in the statistics passes
+hipError_t launch_conv1_mfma(int mode, const FeatView& v, const float* w, const float* bias, void* a1, const void* da1, float* partial,
+                             const DropCfg& dc, int poolw, hipStream_t s);
+// bn: null terms in the statistics passes.  sums, inv_n_scale: the (S1, S2) C1M_WGRAD forms dz1 from, and 1 / world where they are the
+// synchronised ones (1 otherwise)
+hipError_t launch_conv1_train(int mode, const FeatView& v, const float* w, const float* bconv, const BnApply& bn, const float* sums,
+                              const void* da1, int prec, float* partial, const DropCfg& dc, int poolw, const AugCfg* aug, float inv_n_scale,
+                              hipStream_t s);
+hipError_t launch_conv1_bwd_finalize(const float* rec, const float* xxs, const LayerParams& lp, const BnApply& bn, double n, const LayerGrads& g,
+                                     hipStream_t s, int derive_s2 = 0);
 // cae_train.hip
 hipError_t launch_pixel_unshuffle(int prec, const void* dz, void* zp, int B, int H, int W, int Wo, int C, hipStream_t s);
 hipError_t launch_convt_w_to_q(const float* w, float* wq, int cin, int cout, hipStream_t s);
@@ -491,17 +485,14 @@ hipError_t launch_convt_q_to_w(const float* dwq, float* dw, int cin, int cout, h
 int cae_dec4_bwd_blocks();
 // MSE form of the decoder-block-4 backward (drecon == nullptr): the upstream gradient 2 (recon - x) / (B T F) is formed in the kernel
 struct MseArgs {
-  const void* x;
-  int x_bf16;
-  int64_t sb, st, sf;
+  FeatView v;              // x
   const float* b4_dev;
 };
 hipError_t launch_cae_dec4_bwd(int prec, const void* d3, const float* w4, const float* drecon, void* dd3, float* partial,
                                int B, int H3, int W3, int T, int F, hipStream_t s, const MseArgs* mse_args = nullptr);
 // loss = mean((recon - x)^2), drecon = 2 (recon - x) / n  (src/train_cae.py:67-68,203); partial: >= kMseBlocks floats of scratch
 constexpr int kMseBlocks = 1024;
-hipError_t launch_mse_fwd_bwd(const float* recon, const void* x, int x_bf16, int64_t sb, int64_t st, int64_t sf, int B, int T, int F,
-                              float* partial, float* loss, float* drecon, hipStream_t s);
+hipError_t launch_mse_fwd_bwd(const float* recon, const FeatView& v, float* partial, float* loss, float* drecon, hipStream_t s);
 bool convt_dgrad_bf16_supports(int Cin, int Cout);
 hipError_t launch_convt_dgrad_bf16(const void* zp, const float* wq, void* wfrag, void* dx, long P, int Cin, int Cout, hipStream_t s);
 hipError_t launch_cast_from_f32(int prec, const float* src, void* dst, size_t n, hipStream_t s);
@@ -513,8 +504,7 @@ hipError_t launch_wgrad3x3_window(int prec, int cin, int cout, int cin_total, in
 hipError_t launch_wgrad3x3(int prec, int cin, int cout, const void* dz, const void* a, float* partial, float* dw,
                            float* db, int B, int H, int W, int nwg, hipStream_t s);
 // conv3x3_inst_*.hip
-hipError_t launch_fold_pack_conv3x3_m16(const float* w, const float* b, const float* g, const float* beta, const float* mean,
-                                        const float* var, int cin, int cout, uint4* wpack, hipStream_t s, int fold = 1);
+hipError_t launch_fold_pack_conv3x3_m16(const LayerParams& lp, int cin, int cout, uint4* wpack, hipStream_t s);
 hipError_t launch_train_fwd2(int prec, const ConvArgs& a, hipStream_t s);
 hipError_t launch_train_fwd3(int prec, const ConvArgs& a, hipStream_t s);
 hipError_t launch_train_dgrad3(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s);
@@ -523,9 +513,7 @@ hipError_t launch_cae_train_fwd(int prec, int cin, const ConvArgs& a, float* raw
 hipError_t launch_cae_dgrad4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide);
 hipError_t launch_train_fwd3_m16(const ConvArgs& a, hipStream_t s, int pipe = 1);
 // conv_split.hip (DFA_PREC_BF16X3)
-hipError_t launch_fold_pack_conv3x3_split(const float* w, const float* b, const float* g, const float* beta, const float* mean,
-                                          const float* var, int cin, int cout, uint4* wpack, float* bias, float post_scale,
-                                          hipStream_t s);
+hipError_t launch_fold_pack_conv3x3_split(const LayerParams& lp, int cin, int cout, uint4* wpack, float* bias, float post_scale, hipStream_t s);
 hipError_t launch_cnn2d_block2_split(const ConvArgs& a, hipStream_t s, int pipe = 1);
 hipError_t launch_cnn2d_block3_split(const ConvArgs& a, hipStream_t s, int pipe = 1);
 hipError_t launch_pack_conv3x3_dgrad_m16(const float* w, int cin, int cout, uint4* wpack, float* bias, hipStream_t s);
@@ -539,12 +527,10 @@ void set_train_conv_variant(int v);
 int train_conv_variant();   // conv3x3_inst_train.hip (process-wide test hook)
 void set_wgrad_variant(int v);   // wgrad_mfma.hip: bf16 weight-gradient kernel selection (process-wide test hook)
 hipError_t launch_pack_conv1_mfma(const float* w1, const float* b1, uint4* c1pack, float* c1bias, hipStream_t s);
-hipError_t launch_conv12_fused(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack, const float* c1bias,
-                               const uint4* wpack2, const float* bias2, void* a2, int B, int T, int F, hipStream_t s, int pipe = 1,
-                               int seg_iters = 0);
-hipError_t launch_conv12_ragged(const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const uint4* c1pack,
-                                const float* c1bias, const uint4* wpack2, const float* bias2, void* a2, int B, int T_max,
-                                int F, const int* tab, hipStream_t s, int pipe = 1, int seg_iters = 0);
+hipError_t launch_conv12_fused(const FeatView& v, const uint4* c1pack, const float* c1bias, const uint4* wpack2, const float* bias2, void* a2,
+                               hipStream_t s, int pipe = 1, int seg_iters = 0);
+hipError_t launch_conv12_ragged(const FeatView& v, const uint4* c1pack, const float* c1bias, const uint4* wpack2, const float* bias2, void* a2,
+                                const int* tab, hipStream_t s, int pipe = 1, int seg_iters = 0);
 // (blocks 1-3 in one kernel, conv123_*.hip: conv123_host.h)
 hipError_t launch_cnn2d_block2(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);
 hipError_t launch_cnn2d_block3(int prec, const ConvArgs& a, hipStream_t s, int dma = -1, int pipe = 1);

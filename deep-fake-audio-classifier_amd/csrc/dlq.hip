@@ -60,10 +60,10 @@ __global__ void dlq_pack_kernel(const float* __restrict__ w, const float* __rest
 
 int dlq_nks(int cin) { return (cin + 15) / 16; }
 size_t dlq_pack_bytes(int cin, int taps) { return (size_t)taps * dlq_nks(cin) * 4 * 6 * 64 * 16; }
-hipError_t launch_dlq_pack(const float* const* p6, int cin, int taps, void* wp, float* bias, hipStream_t s) {
+hipError_t launch_dlq_pack(const LayerParams& lp, int cin, int taps, void* wp, float* bias, hipStream_t s) {
   const int total = taps * dlq_nks(cin) * 8 * 64;
-  hipLaunchKernelGGL(dlq_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p6[0], p6[1], p6[2], p6[3], p6[4], p6[5], (uint4*)wp, bias, cin,
-                     taps, dlq_nks(cin));
+  hipLaunchKernelGGL(dlq_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, (uint4*)wp, bias,
+                     cin, taps, dlq_nks(cin));
   return hipGetLastError();
 }
 

@@ -60,7 +60,7 @@ int dfa_dlq_prepare(dfa_ctx* ctx) {
   for (int l = 0; l < 3; ++l) {
     m.w[l] = (char*)m.packed + woff[l];
     m.b[l] = (float*)((char*)m.packed + boff[l]);
-    DFA_HIP_CHECK(ctx, launch_dlq_pack(m.p + 6 * l, cin[l], taps[l], m.w[l], m.b[l], ctx->stream));
+    DFA_HIP_CHECK(ctx, launch_dlq_pack(layer_params(m.p, l), cin[l], taps[l], m.w[l], m.b[l], ctx->stream));
   }
   m.prepared = true;
   return DFA_OK;
@@ -131,7 +131,8 @@ int dfa_dlq_forward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, in
   }
   {
     ScopedSlot ts(ctx, 7);
-    DFA_HIP_CHECK(ctx, launch_dlq_finish(a.part, a.tab, m.p[18], m.p[19], m.p[20], m.p[21], logits, pooled, B, s));
+    const HeadParams h0 = head_params(m.p, kDlqLayers, 0), h3 = head_params(m.p, kDlqLayers, 1);
+    DFA_HIP_CHECK(ctx, launch_dlq_finish(a.part, a.tab, h0.w, h0.b, h3.w, h3.b, logits, pooled, B, s));
   }
   return DFA_OK;
 }

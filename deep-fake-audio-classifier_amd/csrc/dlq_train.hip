@@ -136,9 +136,9 @@ __global__ __launch_bounds__(256) void dlq_bn_act_kernel(const float* __restrict
   }
 }
 
-hipError_t launch_dlq_bn_act(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta, void* h,
-                             unsigned char* keep_out, long long N, const DropCfg& dc, hipStream_t s) {
-  hipLaunchKernelGGL(dlq_bn_act_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, s, z, mean, invstd, gamma, beta, (uint4*)h, keep_out, N, dc);
+hipError_t launch_dlq_bn_act(const float* z, const BnApply& bn, void* h, unsigned char* keep_out, long long N, const DropCfg& dc, hipStream_t s) {
+  hipLaunchKernelGGL(dlq_bn_act_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, s, z, bn.mean, bn.invstd, bn.gamma, bn.beta, (uint4*)h, keep_out,
+                     N, dc);
   return hipGetLastError();
 }
 
@@ -348,9 +348,8 @@ __global__ __launch_bounds__(256) void dlq_dz_kernel(const float* __restrict__ d
 }
 
 int dlq_dz_blocks(long long N) { return (int)((N + 63) / 64); }
-hipError_t launch_dlq_dz(const float* dy, const float* z, const float* mean, const float* invstd, const float* gamma, const float* sums, void* dz,
-                         float* dbrec, long long N, hipStream_t s) {
-  hipLaunchKernelGGL(dlq_dz_kernel, dim3(dlq_dz_blocks(N)), dim3(256), 0, s, dy, z, mean, invstd, gamma, sums, (uint4*)dz, dbrec, N);
+hipError_t launch_dlq_dz(const float* dy, const float* z, const BnApply& bn, const float* sums, void* dz, float* dbrec, long long N, hipStream_t s) {
+  hipLaunchKernelGGL(dlq_dz_kernel, dim3(dlq_dz_blocks(N)), dim3(256), 0, s, dy, z, bn.mean, bn.invstd, bn.gamma, sums, (uint4*)dz, dbrec, N);
   return hipGetLastError();
 }
 

@@ -45,6 +45,17 @@ DlqTrainPlan plan_dlq_train(int B, int T_max, int in_ch) {
 
 BnStats st_dlq(char* ws, const DlqTrainPlan& pl, int l) { return bn_stats(ws + pl.stats, HID * l, HID); }
 
+// what launch_dlq_pool_head, launch_dlq_head_bwd and launch_dlq_dy3 share: layer 3's terms, the head's two pairs, the pool's buffers
+DlqHeadArgs head_args(const DlqState& m, char* ws, const DlqTrainPlan& pl) {
+  DlqHeadArgs h{};
+  const BnApply bn = bn_apply(st_dlq(ws, pl, 2), layer_params(m.p, 2));
+  const HeadParams h0 = head_params(m.p, kDlqLayers, 0), h3 = head_params(m.p, kDlqLayers, 1);
+  h.z3 = (const float*)(ws + pl.z[2]); h.mean = bn.mean; h.invstd = bn.invstd; h.gamma = bn.gamma; h.beta = bn.beta;
+  h.w0 = h0.w; h.b0 = h0.b; h.w3 = h3.w; h.b3 = h3.b;
+  h.pooled = (float*)(ws + pl.pooled); h.pvar = (float*)(ws + pl.pvar); h.u = (float*)(ws + pl.u);
+  return h;
+}
+
 int check_dlq_shape(dfa_ctx* ctx, int B, int T_max, int in_ch) {
   if (B < 1) return fail(ctx, DFA_E_BAD_SHAPE, "batch must be >= 1 (got B=%d)", B);
   if (T_max < 1) return fail(ctx, DFA_E_BAD_SHAPE, "T_max must be >= 1 (got %d)", T_max);
@@ -100,12 +111,11 @@ int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_
     m.tw_in_ch = in_ch;
   }
   DFA_TRY(stage_ragged_lengths(ctx, lengths, B, workspace));
-  const float* const* p = m.p;
   char* ws = (char*)workspace;
   const long long N = (long long)B * T_max;
   {
     ScopedSlot ts(ctx, 8);
-    DFA_HIP_CHECK(ctx, launch_dlq_train_pack(p[0], p[6], p[12], m.tw, in_ch, s));
+    DFA_HIP_CHECK(ctx, launch_dlq_train_pack(layer_params(m.p, 0).w, layer_params(m.p, 1).w, layer_params(m.p, 2).w, m.tw, in_ch, s));
   }
   DropCfg dc = drop_cfg(p_drop, seed, offset);
   DlqLayerArgs a{};
@@ -114,31 +124,28 @@ int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_
   a.B = B; a.T_max = T_max; a.tpu = pl.tpu;
   a.rec = (float*)(ws + pl.rec);
   for (int l = 0; l < 3; ++l) {
-    const float* const* q = p + 6 * l;
+    const LayerParams q = layer_params(m.p, l);
     BnStats st = st_dlq(ws, pl, l);
+    const RunningStats run = running_stats(q, update_running_stats);
     {
       ScopedSlot ts(ctx, 9);
       a.hin = l ? (const uint4*)(ws + pl.h[l - 1]) : nullptr;
-      a.w = (const uint4*)m.tw[l]; a.bias = q[1];
+      a.w = (const uint4*)m.tw[l]; a.bias = q.b;
       a.C = l ? HID : in_ch; a.nks = dlq_nks(a.C);
       a.zout = (float*)(ws + pl.z[l]);
       DFA_HIP_CHECK(ctx, launch_dlq_layer_train(l + 1, 1, a, pl.ntiles, s));
     }
     ScopedSlot ts(ctx, 10);
-    DFA_HIP_CHECK(ctx, launch_dlq_bn_finalize(a.rec, pl.ntiles, pl.tpu, T_max, st.mean, st.var, st.invstd, update_running_stats ? (float*)q[4] : nullptr,
-                                              update_running_stats ? (float*)q[5] : nullptr, momentum, s));
+    DFA_HIP_CHECK(ctx, launch_dlq_bn_finalize(a.rec, pl.ntiles, pl.tpu, T_max, st.mean, st.var, st.invstd, run.mean, run.var, momentum, s));
     if (l < 2) {
       dc.layer = 1 + l;
-      DFA_HIP_CHECK(ctx, launch_dlq_bn_act(a.zout, st.mean, st.invstd, q[2], q[3], ws + pl.h[l], keep_out ? keep_out + (size_t)l * N * HID : nullptr, N, dc, s));
+      DFA_HIP_CHECK(ctx, launch_dlq_bn_act(a.zout, bn_apply(st, q), ws + pl.h[l], keep_out ? keep_out + (size_t)l * N * HID : nullptr, N, dc, s));
     }
   }
   {
     ScopedSlot ts(ctx, 10);
-    BnStats st = st_dlq(ws, pl, 2);
-    DlqHeadArgs h{};
-    h.z3 = (const float*)(ws + pl.z[2]); h.mean = st.mean; h.invstd = st.invstd; h.gamma = p[14]; h.beta = p[15];
-    h.lens = a.tab; h.w0 = p[18]; h.b0 = p[19]; h.w3 = p[20]; h.b3 = p[21];
-    h.pooled = (float*)(ws + pl.pooled); h.pvar = (float*)(ws + pl.pvar); h.u = (float*)(ws + pl.u); h.logits = logits;
+    DlqHeadArgs h = head_args(m, ws, pl);
+    h.lens = a.tab; h.logits = logits;
     h.keep3 = keep_out ? keep_out + (size_t)2 * N * HID : nullptr;
     h.keep4 = keep_out ? keep_out + (size_t)3 * N * HID : nullptr;
     h.T_max = T_max;
@@ -157,7 +164,7 @@ int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, i
   if (!ctx) return DFA_E_NULL_PTR;
   DlqState& m = ctx->dlq;
   DlqTrainPlan pl;
-  DFA_TRY(check_backward(ctx, {"dfa_dlq_backward", "dfa_dlq_forward_train", "the DeepfakeDetector", 16, "dlogits", false},
+  DFA_TRY(check_backward(ctx, {"dfa_dlq_backward", "dfa_dlq_forward_train", "the DeepfakeDetector", kDlqGrads, "dlogits", false},
                          m.train_packed && m.train_B > 0 && m.train_B == B && m.train_T == T_max && m.in_ch == in_ch, x, DFA_DTYPE_F32, dlogits,
                          grads, ngrads, workspace, workspace_bytes, [&] { return (pl = plan_dlq_train(B, T_max, in_ch)).total; }));
   DFA_TRY(check_channel_major(ctx, "DeepfakeDetector training step", "stride_c", x, stride_b, stride_c, T_max));
@@ -166,7 +173,6 @@ int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, i
                                         "BatchNorm (dfa_ctx_set_bn_sync is armed)");
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const float* const* p = m.p;
   char* ws = (char*)workspace;
   const long long N = (long long)B * T_max;
   const int* lens = (const int*)(ws + pl.tab);       // the table the forward left
@@ -178,27 +184,25 @@ int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, i
   DropCfg dc = m.train_drop;
   {
     ScopedSlot ts(ctx, 11);
-    BnStats st = st_dlq(ws, pl, 2);
-    DlqHeadArgs h{};
-    h.z3 = (const float*)(ws + pl.z[2]); h.mean = st.mean; h.invstd = st.invstd; h.gamma = p[14]; h.beta = p[15];
-    h.lens = lens; h.w0 = p[18]; h.b0 = p[19]; h.w3 = p[20]; h.b3 = p[21];
-    h.pooled = (float*)(ws + pl.pooled); h.pvar = (float*)(ws + pl.pvar); h.u = (float*)(ws + pl.u);
+    const HeadGrads g0 = head_grads(grads, kDlqLayers, 0), g3 = head_grads(grads, kDlqLayers, 1);
+    DlqHeadArgs h = head_args(m, ws, pl);
+    h.lens = lens;
     h.dlogits = dlogits; h.du = (float*)(ws + pl.du); h.dpooled = (float*)(ws + pl.dpooled);
     h.T_max = T_max;
     dc.layer = 3;
     h.drop = dc;
-    DFA_HIP_CHECK(ctx, launch_dlq_head_bwd(h, B, grads[12], grads[13], grads[14], grads[15], s));
+    DFA_HIP_CHECK(ctx, launch_dlq_head_bwd(h, B, g0.dw, g0.db, g3.dw, g3.db, s));
     DFA_HIP_CHECK(ctx, launch_dlq_dy3(h, B, pl.tpu, dy, rec, s));
   }
   for (int l = 2; l >= 0; --l) {
-    const float* const* q = p + 6 * l;
-    BnStats st = st_dlq(ws, pl, l);
+    const BnApply bn = bn_apply(st_dlq(ws, pl, l), layer_params(m.p, l));
+    const LayerGrads g = layer_grads(grads, l);
     {
       ScopedSlot ts(ctx, 11);
       DFA_HIP_CHECK(ctx, launch_reduce_partials(rec, pl.ntiles, 2 * HID, 1.0f, sums, s, scratch));
-      DFA_HIP_CHECK(ctx, launch_split_sums(sums, grads[4 * l + 2], grads[4 * l + 3], HID, s));
-      DFA_HIP_CHECK(ctx, launch_dlq_dz(dy, (const float*)(ws + pl.z[l]), st.mean, st.invstd, q[2], sums, ws + pl.dz, dbrec, N, s));
-      DFA_HIP_CHECK(ctx, launch_reduce_partials(dbrec, dlq_dz_blocks(N), HID, 1.0f, grads[4 * l + 1], s, scratch));
+      DFA_HIP_CHECK(ctx, launch_split_sums(sums, g.dgamma, g.dbeta, HID, s));
+      DFA_HIP_CHECK(ctx, launch_dlq_dz(dy, (const float*)(ws + pl.z[l]), bn, sums, ws + pl.dz, dbrec, N, s));
+      DFA_HIP_CHECK(ctx, launch_reduce_partials(dbrec, dlq_dz_blocks(N), HID, 1.0f, g.db, s, scratch));
     }
     {
       ScopedSlot ts(ctx, 13);
@@ -207,16 +211,16 @@ int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, i
       w.lens = lens; w.partial = (float*)(ws + pl.partial); w.N = N; w.T_max = T_max;
       if (l == 0) { w.x = (const float*)x; w.sb = stride_b; w.sc = stride_c; w.C = in_ch; w.taps = 5; }
       else { w.h = (const uint4*)(ws + pl.h[l - 1]); w.C = HID; w.taps = 3; }
-      DFA_HIP_CHECK(ctx, launch_dlq_wgrad(w, grads[4 * l], s));
+      DFA_HIP_CHECK(ctx, launch_dlq_wgrad(w, g.dw, s));
     }
     if (l > 0) {        // dy of the layer below: the 256 -> 256 k3 layer kernel on the data-gradient image, dz as its input
       ScopedSlot ts(ctx, 12);
-      BnStats sb = st_dlq(ws, pl, l - 1);
+      const BnApply below = bn_apply(st_dlq(ws, pl, l - 1), layer_params(m.p, l - 1));
       DlqLayerArgs a{};
       a.tab = lens; a.B = B; a.T_max = T_max; a.tpu = pl.tpu; a.C = HID; a.nks = 16;
       a.hin = (const uint4*)(ws + pl.dz); a.w = (const uint4*)m.tw[l == 2 ? 3 : 4];
       a.zout = dy; a.rec = rec;
-      a.zprev = (const float*)(ws + pl.z[l - 1]); a.st_mean = sb.mean; a.st_invstd = sb.invstd; a.gamma = p[6 * (l - 1) + 2]; a.beta = p[6 * (l - 1) + 3];
+      a.zprev = (const float*)(ws + pl.z[l - 1]); a.st_mean = below.mean; a.st_invstd = below.invstd; a.gamma = below.gamma; a.beta = below.beta;
       dc.layer = l;
       a.drop = dc;
       DFA_HIP_CHECK(ctx, launch_dlq_layer_train(2, 2, a, pl.ntiles, s));

@@ -62,27 +62,25 @@ __global__ void fold_pack_conv3x3_kernel(const float* __restrict__ w, const floa
   wpack[i] = *reinterpret_cast<const uint4*>(v);
 }
 
-hipError_t launch_fold_conv1(const float* w, const float* b, const float* g, const float* beta, const float* mean,
-                             const float* var, float* w1, float* b1, int cout, hipStream_t s) {
+hipError_t launch_fold_conv1(const LayerParams& lp, float* w1, float* b1, int cout, hipStream_t s) {
   const int n = cout * 9;
-  hipLaunchKernelGGL(fold_conv1_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, b, g, beta, mean, var, w1, b1,
+  hipLaunchKernelGGL(fold_conv1_kernel, dim3((n + 255) / 256), dim3(256), 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, w1, b1,
                      cout);
   return hipGetLastError();
 }
 
-hipError_t launch_fold_pack_conv3x3(const float* w, const float* b, const float* g, const float* beta,
-                                    const float* mean, const float* var, int cin_total, int cin_off, int cin, int cout,
-                                    int prec, uint4* wpack, float* bias, hipStream_t s, int fold, float post_scale) {
-  const int kg = (prec == DFA_PREC_BF16) ? 16 : 8;
+hipError_t launch_fold_pack_conv3x3(const LayerParams& lp, int cin_total, int cin_off, int cin, int cout, int prec, uint4* wpack,
+                                    float* bias, hipStream_t s, float post_scale) {
+  const int kg = (prec == DFA_PREC_BF16) ? 16 : 8, fold = folds(lp) ? 1 : 0;
   int total = (cout / 32) * 9 * (cin / kg) * 64;
   if (total < cout) total = cout;
   dim3 grid((total + 255) / 256), block(256);
   if (prec == DFA_PREC_BF16)
-    hipLaunchKernelGGL(fold_pack_conv3x3_kernel<bf16_t>, grid, block, 0, s, w, b, g, beta, mean, var, cin_total, cin_off,
-                       cin, cout, wpack, bias, fold, post_scale);
+    hipLaunchKernelGGL(fold_pack_conv3x3_kernel<bf16_t>, grid, block, 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, cin_total,
+                       cin_off, cin, cout, wpack, bias, fold, post_scale);
   else
-    hipLaunchKernelGGL(fold_pack_conv3x3_kernel<float>, grid, block, 0, s, w, b, g, beta, mean, var, cin_total, cin_off, cin,
-                       cout, wpack, bias, fold, post_scale);
+    hipLaunchKernelGGL(fold_pack_conv3x3_kernel<float>, grid, block, 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, cin_total,
+                       cin_off, cin, cout, wpack, bias, fold, post_scale);
   return hipGetLastError();
 }
 
@@ -116,19 +114,17 @@ __global__ void fold_pack_convt2x2_kernel(const float* __restrict__ w, const flo
   wpack[i] = *reinterpret_cast<const uint4*>(v);
 }
 
-hipError_t launch_fold_pack_convt2x2(const float* w, const float* b, const float* g, const float* beta,
-                                     const float* mean, const float* var, int cin, int cout, int prec, uint4* wpack,
-                                     float* bias, hipStream_t s, int fold) {
-  const int kg = (prec == DFA_PREC_BF16) ? 16 : 8;
+hipError_t launch_fold_pack_convt2x2(const LayerParams& lp, int cin, int cout, int prec, uint4* wpack, float* bias, hipStream_t s) {
+  const int kg = (prec == DFA_PREC_BF16) ? 16 : 8, fold = folds(lp) ? 1 : 0;
   int total = (4 * cout / 32) * (cin / kg) * 64;
   if (total < cout) total = cout;
   dim3 grid((total + 255) / 256), block(256);
   if (prec == DFA_PREC_BF16)
-    hipLaunchKernelGGL(fold_pack_convt2x2_kernel<bf16_t>, grid, block, 0, s, w, b, g, beta, mean, var, cin, cout, wpack,
-                       bias, fold);
+    hipLaunchKernelGGL(fold_pack_convt2x2_kernel<bf16_t>, grid, block, 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, cin, cout,
+                       wpack, bias, fold);
   else
-    hipLaunchKernelGGL(fold_pack_convt2x2_kernel<float>, grid, block, 0, s, w, b, g, beta, mean, var, cin, cout, wpack,
-                       bias, fold);
+    hipLaunchKernelGGL(fold_pack_convt2x2_kernel<float>, grid, block, 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, cin, cout,
+                       wpack, bias, fold);
   return hipGetLastError();
 }
 

@@ -55,12 +55,11 @@ BnStats stat_ptrs(char* ws, const TrainPlan& pl, int layer) { return bn_stats(ws
 float* sums_ptr(char* ws, const TrainPlan& pl, int layer) { return bn_sums(ws + pl.sums, kBnOff[layer]); }
 
 // block 1 of a step: what conv1_train_stats (forward) and conv1_train_backward (backward, da = da1) take
-Conv1Train conv1_block(Cnn2dState& m, const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, int B, int T, int F, char* ws,
-                       const TrainPlan& pl, const DropCfg& dc) {
+Conv1Train conv1_block(Cnn2dState& m, const FeatView& v, char* ws, const TrainPlan& pl, const DropCfg& dc) {
   float* c1rec = (float*)(ws + pl.sums) + 2 * (32 + 64 + 128);      // [32][11] record, then XX[9][9] | Xs[9]
   Conv1Train c{};
-  c.x = x; c.x_dtype = x_dtype; c.sb = sb; c.st = st; c.sf = sf; c.B = B; c.T = T; c.F = F; c.prec = m.train_prec; c.poolw = 1;
-  c.drop = dc; c.aug = m.train_aug.on ? &m.train_aug : nullptr; c.p = m.p; c.fw = m.tw1; c.fb = m.tb1;
+  c.v = v; c.prec = m.train_prec; c.poolw = 1;
+  c.drop = dc; c.aug = m.train_aug.on ? &m.train_aug : nullptr; c.p = layer_params(m.p, 0); c.fw = m.tw1; c.fb = m.tb1;
   c.partial = (float*)(ws + pl.partial); c.stats_scratch = true; c.xxs = c1rec + 352; c.c1rec = c1rec;
   c.sums = sums_ptr(ws, pl, 0); c.stats = stat_ptrs(ws, pl, 0); c.da = ws + pl.da1;
   return c;
@@ -113,27 +112,24 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
     m.t2.wpack = (uint4*)(base + t2); m.t3.wpack = (uint4*)(base + t3);
     m.d2.wpack = (uint4*)(base + d2); m.d3.wpack = (uint4*)(base + d3);
   }
-  const float* const* p = m.p;
+  const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
+  const LayerParams l2 = layer_params(m.p, 1), l3 = layer_params(m.p, 2);
+  const HeadParams head = head_params(m.p, kCnn2dLayers, 0);
   hipStream_t s = ctx->stream;
   const int prec = precision;
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[6], p[7], nullptr, nullptr, nullptr, nullptr, 32, 0, 32, 64, prec, m.t2.wpack, m.t2.bias, s, 0));
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(p[12], p[13], nullptr, nullptr, nullptr, nullptr, 64, 0, 64, 128, prec, m.t3.wpack, m.t3.bias, s, 0));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(l2), 32, 0, 32, 64, prec, m.t2.wpack, m.t2.bias, s));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(l3), 64, 0, 64, 128, prec, m.t3.wpack, m.t3.bias, s));
   // bf16: the 16x16x32 image of the same raw weights, in the unused second half of the (fp32-sized) t3 buffer
   uint4* t3_m16 = (uint4*)((char*)m.t3.wpack + (size_t)128 * 64 * 9 * 2);
   const bool fwd3_m16 = prec == DFA_PREC_BF16 && train_conv_variant() != 1;   // 2: pipelined, 0: its compiler-scheduled twin
   if (fwd3_m16)
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_m16(p[12], p[13], nullptr, nullptr, nullptr, nullptr, 64, 128, t3_m16, s, 0));
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_m16(raw_conv(l3), 64, 128, t3_m16, s));
   m.train_dgrad_m16 = (prec == DFA_PREC_BF16 && ctx->dgrad_m16) ? 1 : 0;
-  DFA_TRY(pack_dgrad_images(ctx, p[6], p[12], prec, m.train_dgrad_m16, m.d2, m.d3));
+  DFA_TRY(pack_dgrad_images(ctx, l2.w, l3.w, prec, m.train_dgrad_m16, m.d2, m.d3));
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
   DropCfg dc = drop_cfg(p_drop, seed, offset);
   m.train_drop = dc; m.train_prec = prec; m.train_B = B; m.train_T = T;
-  float* rm[3] = {nullptr, nullptr, nullptr}; float* rv[3] = {nullptr, nullptr, nullptr};
-  if (update_running_stats) {
-    rm[0] = (float*)p[4]; rv[0] = (float*)p[5]; rm[1] = (float*)p[10]; rv[1] = (float*)p[11];
-    rm[2] = (float*)p[16]; rv[2] = (float*)p[17];
-  }
   // ---- block 1
   // augmentation armed by dfa_cnn2d_set_train_augment: one-shot, folded into the three kernels that read x
   m.train_aug = armed;
@@ -145,13 +141,12 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   // (the backward reads da1 with the dropout keep mask already applied by the 16x16x32 data-gradient kernel)
   m.train_c1_mfma = (ctx->conv1_mfma && m.train_c1_fused && prec == DFA_PREC_BF16 && x_dtype == DFA_DTYPE_BF16 && !aug && F <= 224 &&
                      (dc.thresh == 0 || m.train_dgrad_m16)) ? 1 : 0;
-  DFA_TRY(conv1_train_stats(ctx, conv1_block(m, x, x_dtype, stride_b, stride_t, stride_f, B, T, F, ws, pl, dc), m.train_c1_mfma, m.train_c1_fused,
-                            rm[0], rv[0], momentum));
+  DFA_TRY(conv1_train_stats(ctx, conv1_block(m, v, ws, pl, dc), m.train_c1_mfma, m.train_c1_fused, update_running_stats != 0, momentum));
   dc.layer = 1;
   if (m.train_c1_mfma)
-    DFA_HIP_CHECK(ctx, launch_conv1_mfma(C1X_FWD, x, stride_b, stride_t, stride_f, m.tw1, m.tb1, ws + pl.a1, nullptr, nullptr, B, T, F, dc, s));
+    DFA_HIP_CHECK(ctx, launch_conv1_mfma(C1X_FWD, v, m.tw1, m.tb1, ws + pl.a1, nullptr, nullptr, dc, 1, s));
   else
-  DFA_HIP_CHECK(ctx, launch_conv1(x, x_dtype, stride_b, stride_t, stride_f, m.tw1, m.tb1, ws + pl.a1, prec, B, T, F, s, &dc, aug));
+    DFA_HIP_CHECK(ctx, launch_conv1(v, m.tw1, m.tb1, ws + pl.a1, prec, s, &dc, aug));
   // ---- block 2
   const int nstrips = (F + 31) / 32;
   {
@@ -160,9 +155,9 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
     DFA_HIP_CHECK(ctx, launch_train_fwd2(prec, a, s));
   }
   BnStats s2 = stat_ptrs(ws, pl, 1);
-  DFA_TRY(finalize_bn_stats(ctx, partial, B * nstrips, 64, (double)B * pl.H1 * F, s2, rm[1], rv[1], momentum, partial + (size_t)B * nstrips * 128));
+  DFA_TRY(finalize_bn_stats(ctx, partial, B * nstrips, 64, (double)B * pl.H1 * F, s2, running_stats(l2, update_running_stats), momentum, partial + (size_t)B * nstrips * 128));
   dc.layer = 2;
-  DFA_HIP_CHECK(ctx, launch_bn_relu_pool_drop(prec, ws + pl.z2, s2.mean, s2.invstd, p[8], p[9], ws + pl.a2, B, pl.H1, F, 64, dc, s));
+  DFA_HIP_CHECK(ctx, launch_bn_relu_pool_drop(prec, ws + pl.z2, bn_apply(s2, l2), ws + pl.a2, B, pl.H1, F, 64, dc, s));
   // ---- block 3
   {
     ConvArgs a = conv_args(ws + pl.a2, m.t3, ws + pl.z3, B, pl.H2, F, 128, ctx);
@@ -176,11 +171,11 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   }
   BnStats s3 = stat_ptrs(ws, pl, 2);
   const int np3 = B * (fwd3_m16 ? (F + 29) / 30 : nstrips);   // conv3_m16 owns 30 columns per strip
-  DFA_TRY(finalize_bn_stats(ctx, partial, np3, 128, (double)B * pl.H2 * F, s3, rm[2], rv[2], momentum, partial + (size_t)np3 * 256));
+  DFA_TRY(finalize_bn_stats(ctx, partial, np3, 128, (double)B * pl.H2 * F, s3, running_stats(l3, update_running_stats), momentum, partial + (size_t)np3 * 256));
   float* emb = (float*)(ws + pl.emb);
-  DFA_HIP_CHECK(ctx, launch_bn_relu_meant(prec, ws + pl.z3, s3.mean, s3.invstd, p[14], p[15], emb, B, pl.H2, F, 128, s, (float*)(ws + pl.msum)));
+  DFA_HIP_CHECK(ctx, launch_bn_relu_meant(prec, ws + pl.z3, bn_apply(s3, l3), emb, B, pl.H2, F, 128, s, (float*)(ws + pl.msum)));
   if (embedding) DFA_HIP_CHECK(ctx, hipMemcpyAsync(embedding, emb, (size_t)B * 128 * F * 4, hipMemcpyDeviceToDevice, s));
-  DFA_HIP_CHECK(ctx, launch_linear(emb, p[18], p[19], logits, B, 128 * F, s));
+  DFA_HIP_CHECK(ctx, launch_linear(emb, head.w, head.b, logits, B, 128 * F, s));
   return DFA_OK;
 }
 
@@ -192,12 +187,14 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
   Cnn2dState& m = ctx->cnn2d;
   const int prec = m.train_prec;
   TrainPlan pl;
-  DFA_TRY(check_backward(ctx, {"dfa_cnn2d_backward", "dfa_cnn2d_forward_train", "cnn2d", 14, "dlogits", false},
+  DFA_TRY(check_backward(ctx, {"dfa_cnn2d_backward", "dfa_cnn2d_forward_train", "cnn2d", kCnn2dGrads, "dlogits", false},
                          m.train_packed && m.train_B == B && m.train_T == T, x, x_dtype, dlogits, grads, ngrads, workspace, workspace_bytes,
                          [&] { return (pl = plan_train(B, T, F, prec)).total; }));
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
-  const float* const* p = m.p;
+  const LayerParams l2 = layer_params(m.p, 1), l3 = layer_params(m.p, 2);
+  const LayerGrads g2 = layer_grads(grads, 1), g3 = layer_grads(grads, 2);
+  const HeadGrads gh = head_grads(grads, kCnn2dLayers, 0);
   hipStream_t s = ctx->stream;
   DropCfg dc = m.train_drop;
   BnStats s2 = stat_ptrs(ws, pl, 1), s3 = stat_ptrs(ws, pl, 2);
@@ -205,23 +202,23 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
   float* demb = (float*)(ws + pl.demb);
   const dfa::BnSync* sync = ctx->bn_sync.fn ? &ctx->bn_sync : nullptr;     // synchronised BatchNorm (dfa_ctx_set_bn_sync)
   // classifier
-  DFA_HIP_CHECK(ctx, launch_linear_bwd(dlogits, p[18], (const float*)(ws + pl.emb), demb, grads[12], grads[13], B, 128 * F, s, 128, F));
+  DFA_HIP_CHECK(ctx, launch_linear_bwd(dlogits, head_params(m.p, kCnn2dLayers, 0).w, (const float*)(ws + pl.emb), demb, gh.dw, gh.db, B, 128 * F, s, 128, F));
   // block 3: BN backward (upstream = mean_T then Linear), weight gradient, data gradient
-  DFA_HIP_CHECK(ctx, launch_bn_bwd_meant_saved(prec, ws + pl.z3, s3.mean, s3.invstd, p[14], p[15], demb, (const float*)(ws + pl.msum), partial,
+  DFA_HIP_CHECK(ctx, launch_bn_bwd_meant_saved(prec, ws + pl.z3, bn_apply(s3, l3), demb, (const float*)(ws + pl.msum), partial,
                                                sm3, ws + pl.dz3, B, pl.H2, F, 128, s, sync));
-  DFA_HIP_CHECK(ctx, launch_split_sums(sm3, grads[10], grads[11], 128, s));
-  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 64, 128, ws + pl.dz3, ws + pl.a2, partial, grads[8], grads[9], B, pl.H2, F, kWgradWGs, s));
+  DFA_HIP_CHECK(ctx, launch_split_sums(sm3, g3.dgamma, g3.dbeta, 128, s));
+  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 64, 128, ws + pl.dz3, ws + pl.a2, partial, g3.dw, g3.db, B, pl.H2, F, kWgradWGs, s));
   DFA_HIP_CHECK(ctx, launch_dgrad3(m.train_dgrad_m16, prec, conv_args(ws + pl.dz3, m.d3, ws + pl.da2, B, pl.H2, F, 64, ctx), (float*)(ws + pl.raw), s));
   // block 2
   dc.layer = 2;
   {
     int ppb_;
     float* scratch2 = partial + (size_t)bn_bwd_blocks(B, pl.H1, F, &ppb_) * 64 * 2;
-    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL, ws + pl.z2, s2.mean, s2.invstd, p[8], p[9], nullptr, ws + pl.da2, partial, sm2, ws + pl.dz2,
+    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL, ws + pl.z2, bn_apply(s2, l2), nullptr, ws + pl.da2, partial, sm2, ws + pl.dz2,
                                      B, pl.H1, F, 64, dc, s, scratch2, sync));
   }
-  DFA_HIP_CHECK(ctx, launch_split_sums(sm2, grads[6], grads[7], 64, s));
-  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 32, 64, ws + pl.dz2, ws + pl.a1, partial, grads[4], grads[5], B, pl.H1, F, kWgradWGs, s));
+  DFA_HIP_CHECK(ctx, launch_split_sums(sm2, g2.dgamma, g2.dbeta, 64, s));
+  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 32, 64, ws + pl.dz2, ws + pl.a1, partial, g2.dw, g2.db, B, pl.H1, F, kWgradWGs, s));
   {
     ConvArgs a = conv_args(ws + pl.dz2, m.d2, ws + pl.da1, B, pl.H1, F, 32, ctx);
     if (m.train_c1_mfma) { a.drop = dc; a.drop.layer = 1; }   // keep mask of a1's dropout where da1 is produced (idempotent for the vector kernel)
@@ -229,8 +226,8 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
   }
   // block 1 (z1 recomputed from x; conv1_mfma may be cleared between forward and backward: the vector kernel reads the same state)
   dc.layer = 1;
-  return conv1_train_backward(ctx, conv1_block(m, x, x_dtype, stride_b, stride_t, stride_f, B, T, F, ws, pl, dc),
-                              m.train_c1_mfma && ctx->conv1_mfma, m.train_c1_fused, sync, grads);
+  return conv1_train_backward(ctx, conv1_block(m, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T, F}, ws, pl, dc),
+                              m.train_c1_mfma && ctx->conv1_mfma, m.train_c1_fused, sync, layer_grads(grads, 0));
 }
 
 // shared by the CNN2D and CNN1D entry points: validate, copy the keep mask into the context's double buffer, fill `armed`

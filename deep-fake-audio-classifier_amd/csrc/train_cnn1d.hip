@@ -437,25 +437,26 @@ hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, 
   else hipLaunchKernelGGL(cm_stats_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, (int)shifted);
   return hipGetLastError();
 }
-hipError_t launch_cm_bn_relu_drop(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                  const float* beta, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s, const int* lens) {
+hipError_t launch_cm_bn_relu_drop(const float* z, const BnApply& bn, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s,
+                                  const int* lens) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t n = (size_t)B * C * T;
   const dim3 grid((unsigned)((n + 255) / 256));
   if (lens) hipLaunchKernelGGL(cm_bn_relu_drop_ragged_kernel, grid, dim3(256), 0, s, z, mean, invstd, gamma, beta, h, C, T, n, dc, lens);
   else hipLaunchKernelGGL(cm_bn_relu_drop_kernel, grid, dim3(256), 0, s, z, mean, invstd, gamma, beta, h, C, T, n, dc);
   return hipGetLastError();
 }
-hipError_t launch_cm_bn_relu_meant(const float* z, const float* mean, const float* invstd, const float* gamma,
-                                   const float* beta, float* pooled, int B, int C, int T, hipStream_t s, const int* lens) {
+hipError_t launch_cm_bn_relu_meant(const float* z, const BnApply& bn, float* pooled, int B, int C, int T, hipStream_t s, const int* lens) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const int rows = B * C;
   if (lens) hipLaunchKernelGGL(cm_bn_relu_meant_ragged_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, z, mean, invstd, gamma, beta, pooled, C, T, rows, lens);
   else hipLaunchKernelGGL(cm_bn_relu_meant_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, z, mean, invstd, gamma, beta, pooled, C, T, rows);
   return hipGetLastError();
 }
 // lens != null: the ragged twins, n_valid = the batch's frame count (sum of the lengths)
-hipError_t launch_cm_bn_bwd(int src, const float* z, const float* mean, const float* invstd, const float* gamma,
-                            const float* beta, const float* up, float* partial, float* sums, float* dz, int B, int C,
+hipError_t launch_cm_bn_bwd(int src, const float* z, const BnApply& bn, const float* up, float* partial, float* sums, float* dz, int B, int C,
                             int T, const DropCfg& dc, hipStream_t s, const BnSync* sync, const int* lens, double n_valid) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const int nch = cm_chunks(B), bchunk = (B + nch - 1) / nch;
   const size_t n = (size_t)B * C * T;
   float inv_n = (float)(1.0 / (lens ? n_valid : (double)B * T));

@@ -238,21 +238,23 @@ __global__ void conv1_bwd_finalize_kernel(const float* __restrict__ rec, const f
   }
 }
 
-hipError_t launch_conv1_bwd_finalize(const float* rec, const float* xxs, const float* w, const float* bconv, const float* mean,
-                                     const float* invstd, const float* gamma, double n, float* dw, float* db, float* dgamma,
-                                     float* dbeta, hipStream_t s, int derive_s2) {
-  hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(320), 0, s, rec, xxs, w, bconv, mean, invstd, gamma, n, dw, db,
-                     dgamma, dbeta, derive_s2);
+hipError_t launch_conv1_bwd_finalize(const float* rec, const float* xxs, const LayerParams& lp, const BnApply& bn, double n, const LayerGrads& g,
+                                     hipStream_t s, int derive_s2) {
+  hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(320), 0, s, rec, xxs, lp.w, lp.b, bn.mean, bn.invstd, bn.gamma, n, g.dw, g.db,
+                     g.dgamma, g.dbeta, derive_s2);
   return hipGetLastError();
 }
 
 constexpr int C1T_GY = 4;  // row-tile walkers per (utterance, column strip)
 int conv1_train_blocks(int B, int T, int F) { (void)T; return B * C1T_GY * ((F + C1T_C - 1) / C1T_C); }
 
-hipError_t launch_conv1_train(int mode, const void* x, int x_dtype, int64_t sb, int64_t st, int64_t sf, const float* w,
-                              const float* bconv, const float* mean, const float* invstd, const float* gamma,
-                              const float* beta, const float* sums, const void* da1, int prec, float* partial, int B,
-                              int T, int F, const DropCfg& dc, hipStream_t s, int poolw, const AugCfg* augp, float inv_n_scale) {
+hipError_t launch_conv1_train(int mode, const FeatView& v, const float* w, const float* bconv, const BnApply& bn, const float* sums,
+                              const void* da1, int prec, float* partial, const DropCfg& dc, int poolw, const AugCfg* augp, float inv_n_scale,
+                              hipStream_t s) {
+  const void* x = v.x;
+  const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
+  const int64_t sb = v.sb, st = v.st, sf = v.sf;
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   AugCfg aug{};
   if (augp) aug = *augp;
   dim3 grid((F + C1T_C - 1) / C1T_C, C1T_GY, B), block(256);

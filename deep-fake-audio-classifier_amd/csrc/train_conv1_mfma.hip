@@ -356,12 +356,13 @@ int conv1_mfma_blocks(int B, int T, int F) {
   return B * ((np + rows - 1) / rows);
 }
 
-hipError_t launch_conv1_mfma(int mode, const void* x, int64_t sb, int64_t st, int64_t sf, const float* w, const float* bias,
-                             void* a1, const void* da1, float* partial, int B, int T, int F, const DropCfg& dc, hipStream_t s, int poolw) {
+hipError_t launch_conv1_mfma(int mode, const FeatView& v, const float* w, const float* bias, void* a1, const void* da1, float* partial,
+                             const DropCfg& dc, int poolw, hipStream_t s) {
+  const int B = v.B, T = v.T, F = v.F;
   C1xArgs a{};
   if (poolw != 1 && (poolw != 2 || mode != C1X_BWD || (F & 1))) return hipErrorInvalidValue;   // the 2x2 form exists for the backward pass (STATS is pool-free)
   a.poolw = poolw;
-  a.x = (const bf16_t*)x; a.sb = sb; a.st = st; a.sf = sf;
+  a.x = (const bf16_t*)v.x; a.sb = v.sb; a.st = v.st; a.sf = v.sf;
   a.w = w; a.b = bias; a.a1 = (bf16_t*)a1; a.da1 = (const bf16_t*)da1; a.partial = partial;
   a.T = T; a.F = F; a.Ho = T / 2; a.FP = (F + 31) / 32 * 32;
   a.rows_per_wg = conv1_mfma_rows_per_wg(B, T, F);

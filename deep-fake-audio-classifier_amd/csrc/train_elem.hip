@@ -800,9 +800,9 @@ hipError_t launch_reduce_wgrad_record(const float* partial, int nparts, int stri
   return hipGetLastError();
 }
 
-hipError_t launch_bn_relu_pool_drop(int prec, const void* z, const float* mean, const float* invstd, const float* gamma,
-                                    const float* beta, void* out, int B, int H, int W, int C, const DropCfg& dc,
+hipError_t launch_bn_relu_pool_drop(int prec, const void* z, const BnApply& bn, void* out, int B, int H, int W, int C, const DropCfg& dc,
                                     hipStream_t s) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t total = (size_t)B * (H / 2) * W * (C / 8);
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
   if (prec == DFA_PREC_BF16)
@@ -829,9 +829,8 @@ hipError_t launch_cl_stats(int prec, const void* z, float* partial, size_t npix,
   return hipGetLastError();
 }
 
-hipError_t launch_bn_relu_pool(int prec, int pool, const void* z, const float* mean, const float* invstd,
-                               const float* gamma, const float* beta, void* out, int B, int H, int W, int C,
-                               hipStream_t s) {
+hipError_t launch_bn_relu_pool(int prec, int pool, const void* z, const BnApply& bn, void* out, int B, int H, int W, int C, hipStream_t s) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t total = (size_t)B * (H / pool) * (W / pool) * (C / 8);
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
   if (prec == DFA_PREC_BF16) {
@@ -844,8 +843,9 @@ hipError_t launch_bn_relu_pool(int prec, int pool, const void* z, const float* m
   return hipGetLastError();
 }
 
-hipError_t launch_bn_relu_meant(int prec, const void* z, const float* mean, const float* invstd, const float* gamma,
-                                const float* beta, float* emb, int B, int H, int W, int C, hipStream_t s, float* msum) {
+hipError_t launch_bn_relu_meant(int prec, const void* z, const BnApply& bn, float* emb, int B, int H, int W, int C, hipStream_t s,
+                                float* msum) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t total = (size_t)B * W * (C / 8);
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
 #define DFA_BRM(TT, MS) hipLaunchKernelGGL((bn_relu_meant_kernel<TT, MS>), grid, block, 0, s, (const TT*)z, mean, invstd, gamma, beta, emb, msum, B, H, W, C)
@@ -857,9 +857,9 @@ hipError_t launch_bn_relu_meant(int prec, const void* z, const float* mean, cons
 
 // BatchNorm backward of the mean-over-T layer with the reduction taken from the forward's saved sums (msum[B][W][C][2]):
 // reduce (3 floats per position) -> fixed-order second stage -> the usual apply pass (z -> dz).
-hipError_t launch_bn_bwd_meant_saved(int prec, const void* z, const float* mean, const float* invstd, const float* gamma,
-                                     const float* beta, const float* demb, const float* msum, float* partial, float* sums,
-                                     void* dz, int B, int H, int W, int C, hipStream_t s, const BnSync* sync) {
+hipError_t launch_bn_bwd_meant_saved(int prec, const void* z, const BnApply& bn, const float* demb, const float* msum, float* partial,
+                                     float* sums, void* dz, int B, int H, int W, int C, hipStream_t s, const BnSync* sync) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t npos = (size_t)B * W;
   const int PL = 256 / (C / 8);
   const int ppb = 8 * PL;
@@ -912,10 +912,10 @@ int bn_bwd_blocks(int B, int H, int W, int* pix_per_block) {
 
 // sums: [C][2] (S1 = dbeta, S2 = dgamma) written by the reduce stage; dz may alias nothing.  scratch: 64 * C * 2 floats for the
 // two-level reduction of the block records (nullptr: one level)
-hipError_t launch_bn_bwd(int prec, int src, const void* z, const float* mean, const float* invstd, const float* gamma,
-                         const float* beta, const float* demb, const void* da, float* partial, float* sums, void* dz,
-                         int B, int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch, const BnSync* sync,
+hipError_t launch_bn_bwd(int prec, int src, const void* z, const BnApply& bn, const float* demb, const void* da, float* partial, float* sums,
+                         void* dz, int B, int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch, const BnSync* sync,
                          BnBwdFold* fold) {
+  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   int ppb;
   int nblk = bn_bwd_blocks(B, H, W, &ppb);
   if (fold && (src != SRC_DIRECT || (H & 1) || 2 * fold->Wh > W || !fold->zp || !fold->bias_partial)) return hipErrorInvalidValue;
