@@ -3,6 +3,7 @@ missing or a call fails, an exception is raised (ValueError for shape/dtype erro
 mirroring how the reference surfaces torch shape errors and its own ValueErrors)."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import threading
@@ -39,6 +40,7 @@ SYMBOLS = [
     ("dfa_cnn2d_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     ("dfa_cnn2d_train_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dfa_cnn2d_train_plan", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int]),
     ("dfa_cnn2d_forward_train", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                           C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_float,
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -188,6 +190,23 @@ def cae_train_plan(ctx_handle, B, T, F, precision):
     if n != len(out):
         raise ValueError(f"dfa_cae_train_plan([{B}, {T}, {F}]) returned {n}, not {len(out)} fields")
     return CaeTrainPlan(out)
+
+
+CNN2D_TRAIN_PLAN_FIELDS = ("H1", "H2", "elem", "a1", "z2", "a2", "z3", "emb", "demb", "msum", "dz3", "da2", "dz2", "da1", "raw", "stats",
+                           "sums", "partial", "partial_bytes", "total")
+Cnn2dTrainPlan = collections.namedtuple("Cnn2dTrainPlan", CNN2D_TRAIN_PLAN_FIELDS)
+
+
+def cnn2d_train_plan(ctx_handle, B, T, F, precision):
+    """The workspace layout of a CNN2D training step (dfa_cnn2d_train_plan) as named fields in the order of include/dfa_hip.h; a
+    refused shape or precision raises as the step itself would (the message needs a context)."""
+    out = (C.c_longlong * len(CNN2D_TRAIN_PLAN_FIELDS))()
+    n = load().dfa_cnn2d_train_plan(ctx_handle, B, T, F, precision, out, len(out))
+    if n < 0:
+        check(ctx_handle, n)
+    if n != len(out):
+        raise ValueError(f"dfa_cnn2d_train_plan([{B}, {T}, {F}]) returned {n}, not {len(out)} fields")
+    return Cnn2dTrainPlan(*out)
 
 
 def check(ctx_handle, code):

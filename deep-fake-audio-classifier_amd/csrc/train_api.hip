@@ -65,6 +65,18 @@ Conv1Train conv1_block(Cnn2dState& m, const FeatView& v, char* ws, const TrainPl
   return c;
 }
 
+// the plan of a step, or the refusal of its precision or shape (what dfa_cnn2d_forward_train and dfa_cnn2d_train_plan both answer);
+// armed: the forward's one-shot augmentation, refused between the two where it was drawn for another shape
+int checked_plan(dfa_ctx* ctx, int B, int T, int F, int precision, const AugCfg* armed, TrainPlan* pl) {
+  if (precision != DFA_PREC_F32 && precision != DFA_PREC_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "unknown precision %d", precision);
+  if (armed && armed->on && (armed->T != T || armed->F != F))
+    return fail(ctx, DFA_E_BAD_SHAPE, "the armed augmentation was drawn for [T=%d, F=%d], the batch is [T=%d, F=%d]", armed->T, armed->F, T, F);
+  if (B < 1 || T < 4) return fail(ctx, DFA_E_BAD_SHAPE, "need B >= 1 and T >= 4 (got %d, %d)", B, T);
+  if (F < 1) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d: need F >= 1", F);
+  *pl = plan_train(B, T, F, precision);
+  return DFA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -73,6 +85,18 @@ size_t dfa_cnn2d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, 
   (void)ctx;
   if (B < 1 || T < 4 || F < 1) return 0;
   return plan_train(B, T, F, precision).total;
+}
+
+int dfa_cnn2d_train_plan(dfa_ctx* ctx, int B, int T, int F, int precision, long long* fields, int cap) {
+  TrainPlan pl;
+  DFA_TRY(checked_plan(ctx, B, T, F, precision, nullptr, &pl));
+  const long long v[] = {pl.H1, pl.H2, precision == DFA_PREC_BF16 ? 2 : 4,
+                         (long long)pl.a1, (long long)pl.z2, (long long)pl.a2, (long long)pl.z3, (long long)pl.emb, (long long)pl.demb,
+                         (long long)pl.msum, (long long)pl.dz3, (long long)pl.da2, (long long)pl.dz2, (long long)pl.da1, (long long)pl.raw,
+                         (long long)pl.stats, (long long)pl.sums, (long long)pl.partial, (long long)pl.partial_bytes, (long long)pl.total};
+  static_assert(sizeof(v) / sizeof(v[0]) == DFA_CNN2D_TRAIN_PLAN_FIELDS, "field table of dfa_cnn2d_train_plan");
+  for (int i = 0; fields && i < cap && i < DFA_CNN2D_TRAIN_PLAN_FIELDS; ++i) fields[i] = v[i];
+  return DFA_CNN2D_TRAIN_PLAN_FIELDS;
 }
 
 int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
@@ -90,13 +114,10 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn2d_set_params has not been called");
   if (!x || !logits || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, logits and workspace must be non-null");
   if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
-  if (precision != DFA_PREC_F32 && precision != DFA_PREC_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "unknown precision %d", precision);
-  if (armed.on && (armed.T != T || armed.F != F))
-    return fail(ctx, DFA_E_BAD_SHAPE, "the armed augmentation was drawn for [T=%d, F=%d], the batch is [T=%d, F=%d]", armed.T, armed.F, T, F);
-  if (B < 1 || T < 4) return fail(ctx, DFA_E_BAD_SHAPE, "need B >= 1 and T >= 4 (got %d, %d)", B, T);
+  TrainPlan pl;
+  DFA_TRY(checked_plan(ctx, B, T, F, precision, &armed, &pl));
   if (F != m.in_features) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d", F, m.in_features);
   if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(ctx, DFA_E_BAD_SHAPE, "dropout p must be in [0, 1)");
-  const TrainPlan pl = plan_train(B, T, F, precision);
   DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total, true, "train "));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // train-mode weight images: raw convs (BN is its own pass) + data-gradient images; rebuilt every step (weights move)

@@ -210,6 +210,36 @@ size_t dfa_cnn1d_ragged_lds_bytes(int T_max, int F);
 
 /* ---- CNN2D training step (replaces, for src/train.py:71-76, torch autograd over src/model.py:13-39) ------------ */
 size_t dfa_cnn2d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, int precision);
+/* The workspace layout of a training step of [B, T, F] in `precision`: the very plan dfa_cnn2d_forward_train, dfa_cnn2d_backward and
+ * dfa_cnn2d_train_workspace_bytes read, reported.  Pure host arithmetic; ctx may be NULL (it only receives the refusal's text).
+ * Activations are channels-last, [B][H][F][C], of `elem` bytes per element (bf16 or fp32); offsets are bytes from the workspace's
+ * start, each 256-byte aligned, in the order below.  After one forward_train + backward every region but raw and partial still
+ * holds what the step stored in it.  Fills the first min(cap, DFA_CNN2D_TRAIN_PLAN_FIELDS) of
+ *    0 H1, 1 H2    rows of a1 / z2 (T / 2) and of a2 / z3 (H1 / 2)
+ *    2 elem        bytes per stored activation element (2 or 4)
+ *    3 a1          block 1's pooled (and dropped-out) output            [B][H1][F][32]
+ *    4 z2          conv 32 -> 64 pre-BatchNorm output                   [B][H1][F][64]
+ *    5 a2          block 2's pooled (and dropped-out) output            [B][H2][F][64]
+ *    6 z3          conv 64 -> 128 pre-BatchNorm output                  [B][H2][F][128]
+ *    7 emb         mean over time of ReLU(BatchNorm(z3)), the classifier's input      float [B][128][F]
+ *    8 demb        its gradient, transposed for the BatchNorm backward               float [B][F][128]
+ *    9 msum        per (b, f, c) the two time sums block 3's BatchNorm backward reduces from: n = sum_t mask and
+ *                  sx = sum_t mask * xhat, mask = (gamma * xhat + beta > 0), xhat = (z3 - mean) * invstd     float [B][F][128][2]
+ *   10 dz3, 11 da2, 12 dz2, 13 da1   gradients, shaped as z3, a2, z2, a1
+ *   14 raw         fp32 scratch of the two-launch 64 <- 128 data gradient (written only with option dgrad_m16 = 0 or in fp32)
+ *   15 stats       float: per BatchNorm layer mean[C] | biased variance[C] | invstd[C]; the layers (C = 32, 64, 128) follow each
+ *                  other, so layer l's block starts 3 * {0, 32, 96}[l] floats in
+ *   16 sums        float: per layer the backward's [C][2] records (S1 = sum dy = dbeta, S2 = sum dy * xhat = dgamma) at
+ *                  2 * {0, 32, 96}[l] floats (layer 1's only on the two-pass block-1 backward, conv1_bwd_fused = 0 or
+ *                  synchronised BatchNorm); at float 448 block 1's backward record: [32][11] = per channel A[9] = sum dy * x_tap,
+ *                  S1, S2 on the one-pass paths (the matrix-core pass leaves S2 = 0 and derives it), [32][10] = dW[9], db on the
+ *                  two-pass path; at float 800 the tap moments XX[9][9] | Xs[9] of x (one-pass paths only)
+ *   17 partial, 18 partial_bytes   the per-workgroup records of every reduction
+ *   19 total       = dfa_cnn2d_train_workspace_bytes
+ * of `fields` (may be NULL: validate only) and returns DFA_CNN2D_TRAIN_PLAN_FIELDS.  A precision or shape the step refuses returns
+ * the step's own error code (negative) and leaves its message in ctx. */
+#define DFA_CNN2D_TRAIN_PLAN_FIELDS 20
+int dfa_cnn2d_train_plan(dfa_ctx* ctx, int B, int T, int F, int precision, long long* fields, int cap);
 /* train-mode forward: BatchNorm uses batch statistics (and updates running_mean/var in place through the pointers
  * given to dfa_cnn2d_set_params when update_running_stats != 0, momentum 0.1 in the reference); Dropout(p_drop) after
  * pools 1 and 2 with a Philox mask keyed by (seed, offset).  Uses the raw parameters directly (no prepare needed).

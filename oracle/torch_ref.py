@@ -142,7 +142,7 @@ class _RoundGrad(torch.autograd.Function):
 
 
 def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", round_x=True, return_stats=False,
-                              return_margins=False, dtype=torch.float64):
+                              return_margins=False, dtype=torch.float64, unrounded=False):
     """One CNN2D training forward/backward (dropout 0) restated with the ROUNDING POINTS of the product's bf16 training
     mode (src/train.py:71-76 over src/model.py:13-39 in train mode): a1, z2, a2, z3 and their gradients da1, dz2, da2, dz3
     are stored in bf16, the MFMA convolutions of blocks 2 and 3 (forward, data gradient, weight gradient) take bf16
@@ -154,10 +154,12 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
     return_stats=True a fourth item {BatchNorm prefix: (batch mean, biased batch variance, element count)} from which the
     running-statistics update of nn.BatchNorm2d follows (momentum m: (1-m)*old + m*mean, (1-m)*old + m*var*n/(n-1)).
     return_margins=True appends {BatchNorm prefix: smallest |BatchNorm output| of that layer} (how far the nearest ReLU input
-    is from zero); dtype is the arithmetic everything "float64" above runs in (torch.float32: the same restatement in fp32)."""
+    is from zero); dtype is the arithmetic everything "float64" above runs in (torch.float32: the same restatement in fp32);
+    unrounded=True returns logits, gradients and statistics in that arithmetic instead of cast to float32."""
     f64 = dtype
     on = emulate == "bf16"
     stats, margins = {}, {}
+    out_t = (lambda t: t) if unrounded else (lambda t: t.float())
     if emulate not in (None, "bf16"):
         raise ValueError(emulate)
     P = {k: _t(sd, k).to(f64).clone().requires_grad_(True) for k in sd
@@ -170,7 +172,7 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
         za = rgrad(z)
         mean = za.mean(dim=(0, 2, 3), keepdim=True)
         var = za.var(dim=(0, 2, 3), unbiased=False, keepdim=True)
-        stats[pfx] = (mean.detach().flatten().float(), var.detach().flatten().float(), za.numel() // za.shape[1])
+        stats[pfx] = (out_t(mean.detach().flatten()), out_t(var.detach().flatten()), za.numel() // za.shape[1])
         zs = rnd(za)
         out = (zs - mean) / torch.sqrt(var + 1e-5) * P[pfx + ".weight"][None, :, None, None] + P[pfx + ".bias"][None, :, None, None]
         margins[pfx] = float(out.detach().abs().min())
@@ -181,7 +183,7 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
     z1 = F.conv2d(xb, P["conv.0.weight"], P["conv.0.bias"], padding=1)
     m1 = z1.mean(dim=(0, 2, 3), keepdim=True)
     v1 = z1.var(dim=(0, 2, 3), unbiased=False, keepdim=True)
-    stats["conv.1"] = (m1.detach().flatten().float(), v1.detach().flatten().float(), z1.numel() // z1.shape[1])
+    stats["conv.1"] = (out_t(m1.detach().flatten()), out_t(v1.detach().flatten()), z1.numel() // z1.shape[1])
     y1 = (z1 - m1) / torch.sqrt(v1 + 1e-5) * P["conv.1.weight"][None, :, None, None] + P["conv.1.bias"][None, :, None, None]
     margins["conv.1"] = float(y1.detach().abs().min())
     a1 = store(F.avg_pool2d(F.relu(y1), (2, 1)))
@@ -196,7 +198,7 @@ def cnn2d_train_step_emulated(sd, x, y, label_smoothing=0.0, emulate="bf16", rou
     ys = y.to(f64) * (1.0 - label_smoothing) + 0.5 * label_smoothing if label_smoothing > 0 else y.to(f64)
     loss = F.binary_cross_entropy_with_logits(logits, ys)
     loss.backward()
-    out = (logits.detach().float(), float(loss), {k: v.grad.float() for k, v in P.items()})
+    out = (out_t(logits.detach()), float(loss), {k: out_t(v.grad) for k, v in P.items()})
     return out + ((stats,) if return_stats else ()) + ((margins,) if return_margins else ())
 
 

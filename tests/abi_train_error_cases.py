@@ -216,6 +216,8 @@ def _cases():
     add("mse_fwd_bwd/no_loss_no_drecon", "cae", None, lambda r: r.mse(loss=False, drecon=False))
     add("mse_fwd_bwd/x_dtype", "cae", None, lambda r: r.mse(dtype=2))
     add("mse_fwd_bwd/batch_0", "cae", None, lambda r: r.mse(B=0))
+    # the one refusal dfa_cnn2d_train_plan adds to the step's own (which it answers word for word: tests/test_cnn2d_train_stages_gpu.py)
+    add("cnn2d_train_plan/F_0", "cnn2d", None, lambda r: r.lib.dfa_cnn2d_train_plan(r.ctx, B, T, 0, PREC_BF16, None, 0))
     return c
 
 

@@ -120,9 +120,18 @@ def _pool22(t):
     return 0.25 * ((t[:, 0::2, 0::2] + t[:, 1::2, 0::2]) + (t[:, 0::2, 1::2] + t[:, 1::2, 1::2]))
 
 
+def _pool21(t):
+    H2 = t.shape[1] // 2
+    return 0.5 * (t[:, 0:2 * H2:2] + t[:, 1:2 * H2:2])
+
+
+def _pool(t, pool):
+    return _pool22(t) if pool == 2 else _pool21(t) if pool == (2, 1) else t
+
+
 def bn_relu_pool(z, mean, invstd, gamma, beta, pool, dt=F64, mags=False):
     """z [B,H,W,C] (as stored), the layer's statistics and affine parameters -> ReLU(BatchNorm(z)), averaged over 2x2 windows when
-    pool == 2 (floor: a last odd row / column is dropped).
+    pool == 2 and over row pairs when pool == (2, 1) (floor: a last odd row / column is dropped).
     Error of one BatchNorm output y in fp32, for A_y = |z s| + |mean s| + |beta|, s = gamma invstd: s costs one rounding (u A_y on
     the first two terms), shift = beta - mean s two more on its product and one on the difference (<= 3u A_y), the fused
     multiply-add one (u |y| <= u A_y); the same count holds for (z - mean) invstd gamma + beta.  <= 6u A_y, K_BN = 8 leaves room
@@ -130,25 +139,26 @@ def bn_relu_pool(z, mean, invstd, gamma, beta, pool, dt=F64, mags=False):
     z, mean, invstd, gamma, beta = (t.to(dt) for t in (z, mean, invstd, gamma, beta))
     s = gamma * invstd
     r = F.relu((z - mean) * s + beta)
-    out = _pool22(r) if pool == 2 else r
+    out = _pool(r, pool)
     A = None
     if mags:
         a = (z * s).abs() + (mean * s).abs() + beta.abs()
-        A = _pool22(a) if pool == 2 else a
-    return Stage(out, A, K_BN + (4 if pool == 2 else 0))
+        A = _pool(a, pool)
+    return Stage(out, A, K_BN + (4 if pool != 1 else 0))
 
 
-def block1_forward(x, w, b, gamma, beta, mean, invstd, dt=F64, mags=False):
-    """x [B,T,F], the fp32 block-1 parameters and ITS batch statistics -> e[0] = pool(ReLU(BatchNorm(conv(x)))) [B,T/2,F/2,32].
+def block1_forward(x, w, b, gamma, beta, mean, invstd, dt=F64, mags=False, pool=2):
+    """x [B,T,F], the fp32 block-1 parameters and ITS batch statistics -> e[0] = pool(ReLU(BatchNorm(conv(x)))) [B,T/2,F/2,32]
+    (pool = (2, 1): row pairs only, [B,T/2,F,32]).
     The kernels fold the statistics into the weights first (fw = w s, fb = (b - mean) s + beta; three roundings each), then sum
     nine products and the bias (vector path: fused multiply-adds; matrix-core path: the three-term bf16 split of fw, exact to
     2^-24 per product): <= (3 + 10 + 3 + 3) u A_y with A_y = s (sum |x w| + |b| + |mean|) + |beta|; K_BLOCK1 = 24 with the pool."""
     zs = conv3x3(x.unsqueeze(-1), w, b, dt, mags)
-    st = bn_relu_pool(zs.out, mean, invstd, gamma, beta, 2, dt)
+    st = bn_relu_pool(zs.out, mean, invstd, gamma, beta, pool, dt)
     A = None
     if mags:
         s = (gamma.to(dt) * invstd.to(dt)).abs()
-        A = _pool22(s * (zs.A + mean.to(dt).abs()) + beta.to(dt).abs())
+        A = _pool(s * (zs.A + mean.to(dt).abs()) + beta.to(dt).abs(), pool)
     return Stage(st.out, A, K_BLOCK1)
 
 
@@ -193,12 +203,16 @@ def dec4_backward(d2, w, b, x, drecon=None, dt=F64, mags=False):
 
 
 def upstream(da, H, W, src, dt=F64):
-    """the gradient that arrives at a BatchNorm + ReLU output [B,H,W,C]: da itself ("direct": the decoder) or a quarter of da at
-    each of a pooled window's four pixels and zero on a dropped last row / column ("pool22": the encoder)"""
+    """the gradient that arrives at a BatchNorm + ReLU output [B,H,W,C]: da itself ("direct": the decoder), a quarter of da at
+    each of a pooled window's four pixels and zero on a dropped last row / column ("pool22": the encoder), or half of da at each
+    row of a pooled pair and zero on a dropped last row ("pool21")"""
     da = da.to(dt)
     if src == "direct":
         return da
     up = torch.zeros((da.shape[0], H, W, da.shape[3]), dtype=dt)
+    if src == "pool21":
+        up[:, :2 * (H // 2)] = 0.5 * da.repeat_interleave(2, dim=1)
+        return up
     up[:, :2 * (H // 2), :2 * (W // 2)] = 0.25 * da.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
     return up
 
@@ -206,11 +220,12 @@ def upstream(da, H, W, src, dt=F64):
 BnReduce = namedtuple("BnReduce", "S1 S2 slack1 slack2 on amb xh")
 
 
-def bn_bwd_reduce(z, up, mean, invstd, gamma, beta, dt=F64, k_amb=K_BN, terms=None):
+def bn_bwd_reduce(z, up, mean, invstd, gamma, beta, dt=F64, k_amb=K_BN, terms=None, also_open=None):
     """z as stored, `up` = upstream(...) -> S1 = sum dy (dbeta), S2 = sum dy xhat (dgamma) with dy = up where BatchNorm(z) > 0.
     amb marks the elements whose BatchNorm output y lies within k_amb u (|gamma| invstd (|z| + |mean|) + |beta|) of zero -- the
     fp32 rounding of its own terms (`terms`: the caller's own sum of magnitudes, block 1) -- so that an fp32 kernel may take
-    either branch; slack1 / slack2 are what those elements can move the two sums by (sum |up|, sum |up xhat| over them)."""
+    either branch; slack1 / slack2 are what those elements can move the two sums by (sum |up|, sum |up xhat| over them).
+    also_open: elements whose dy the caller cannot state wherever their ReLU is on (a bool mask; and-ed with `on`, or-ed into amb)."""
     z, up, mean, invstd, gamma, beta = (t.to(dt) for t in (z, up, mean, invstd, gamma, beta))
     xh = (z - mean) * invstd
     y = gamma * xh + beta
@@ -219,20 +234,25 @@ def bn_bwd_reduce(z, up, mean, invstd, gamma, beta, dt=F64, k_amb=K_BN, terms=No
     if terms is None:
         terms = gamma.abs() * invstd * (z.abs() + mean.abs()) + beta.abs()
     amb = y.abs() <= k_amb * U * terms.to(dt)
+    if also_open is not None:
+        amb = amb | (also_open & on)
     au = up.abs() * amb
     return BnReduce(dy.sum(dim=(0, 1, 2)), (dy * xh).sum(dim=(0, 1, 2)), au.sum(dim=(0, 1, 2)), (au * xh.abs()).sum(dim=(0, 1, 2)),
                     on, amb, xh)
 
 
-def bn_bwd_apply(z, up, mean, invstd, gamma, beta, S1, S2, dt=F64, mags=False):
+def bn_bwd_apply(z, up, mean, invstd, gamma, beta, S1, S2, dt=F64, mags=False, z_term=None):
     """dz = gamma invstd (dy - S1 / N - xhat S2 / N) with the sums the caller gives (the GPU's own) -> (Stage dz, dz with the ReLU
     decision of every element reversed).  k0 = gamma invstd, k1, k2 one rounding each, xhat two, the bracket three, the product
-    one: K = K_BN of A = |k0| (|up| + |k1| + invstd (|z| + |mean|) |k2|)."""
+    one: K = K_BN of A = |k0| (|up| + |k1| + invstd (|z| + |mean|) |k2|).  z_term: the tensor the xhat of the S2 term is formed
+    from when it is not z (autograd through statistics of the unrounded accumulators; the kernels take z)."""
     z, up, mean, invstd, gamma, beta, S1, S2 = (t.to(dt) for t in (z, up, mean, invstd, gamma, beta, S1, S2))
     N = z.shape[0] * z.shape[1] * z.shape[2]
     k0, k1, k2 = gamma * invstd, S1 / N, S2 / N
     xh = (z - mean) * invstd
     on = (gamma * xh + beta) > 0
+    if z_term is not None:
+        xh = (z_term.to(dt) - mean) * invstd
     off_v = k0 * (-k1 - xh * k2)
     on_v = k0 * (up - k1 - xh * k2)
     A = (k0.abs() * (up.abs() + k1.abs() + invstd * (z.abs() + mean.abs()) * k2.abs())) if mags else None
@@ -285,7 +305,7 @@ def convt_wgrad(a, dzd, dt=F64):
 Block1Bwd = namedtuple("Block1Bwd", "dW db dgamma dbeta slack amb_share db_terms")
 
 
-def block1_backward(x, w, b, gamma, beta, mean, invstd, de0, dt=F64, slack=False):
+def block1_backward(x, w, b, gamma, beta, mean, invstd, de0, dt=F64, slack=False, src="pool22", also_open=None):
     """x [B,T,F], block 1's fp32 parameters and statistics, de[0] [B,T/2,F/2,32] -> the block's four gradients.  Its pre-BatchNorm
     output is recomputed, never stored, so the ReLU decisions are the stage's own: with slack=True the result carries, per
     gradient, what the elements within K_BLOCK1 roundings of zero could move it by (the gradients are linear in dy: the magnitudes
@@ -295,11 +315,11 @@ def block1_backward(x, w, b, gamma, beta, mean, invstd, de0, dt=F64, slack=False
     B, T, Fq = x.shape
     x4 = x.unsqueeze(-1)
     zs = conv3x3(x4, w, b, dt, mags=slack)
-    up = upstream(de0, T, Fq, "pool22", dt)
+    up = upstream(de0, T, Fq, src, dt)
     terms = None
     if slack:
         terms = (gamma * invstd).abs() * (zs.A + mean.abs()) + beta.abs()
-    red = bn_bwd_reduce(zs.out, up, mean, invstd, gamma, beta, dt, K_BLOCK1, terms)
+    red = bn_bwd_reduce(zs.out, up, mean, invstd, gamma, beta, dt, K_BLOCK1, terms, also_open)
     dz = bn_bwd_apply(zs.out, up, mean, invstd, gamma, beta, red.S1, red.S2, dt)[0].out
     dW, db = conv3x3_wgrad(dz, x4, dt)
     sl, share, dbt = None, None, None

@@ -554,7 +554,7 @@ def test_conv1_matrix_core_passes_match_vector_path(golden):
     Checked against the vector-ALU kernels they replace, pass by pass (end to end the two paths differ by bf16 storage noise
     like any two valid implementations -- the emulated-oracle test bounds that):
       statistics  running mean / variance after one step agree to fp32 summation noise;
-      forward     a1 (first region of the train workspace) differs in < 0.2 % of its elements and by at most one bf16 ulp
+      forward     a1 (read out of the train workspace through dfa_cnn2d_train_plan) differs in < 0.2 % of its elements and by at most one bf16 ulp
                   (three bf16 terms carry the fp32 weights exactly; what remains is fp32 accumulation order);
       backward    on the SAME forward state (the option is cleared between two backward calls) every other gradient is
                   bit-identical and dW1, dgamma1, dbeta1 agree up to the handful of pixels whose pre-ReLU value is within fp32
@@ -585,7 +585,8 @@ def test_conv1_matrix_core_passes_match_vector_path(golden):
             xb = xb.contiguous()                       # [B, T, F] storage: the loaders' other stride pattern (stride_t = F, stride_f = 1)
         logits, c, ws = cnn2d_forward_train_raw(model, xb)
         B, T, F = x.shape
-        a1 = ws[: B * (T // 2) * F * 32 * 2].view(torch.bfloat16).clone()
+        pl = _lib.cnn2d_train_plan(c.handle, B, T, F, _lib.PREC_BF16)
+        a1 = ws[pl.a1: pl.a1 + B * pl.H1 * F * 32 * pl.elem].view(torch.bfloat16).clone()
         return model, xb, logits, c, ws, a1
 
     try:
@@ -657,6 +658,7 @@ def test_dropout_mask_statistics(p_drop):
     shifted far into the positive range no ReLU ever clips, so a zero in the stored block-1 / block-2 activations is a dropped
     element.  Keep fraction within 5 sigma of 1 - p for the whole tensor, for each of the eight lanes of a call and for each
     channel; no correlation between neighbours in any direction; a new call draws a new, equally distributed mask."""
+    from dfa_amd import _lib
     from dfa_amd.model import CNN2D
     from dfa_amd.training.train_step import cnn2d_forward_train_raw
     B, T, F = 8, 64, 180
@@ -668,15 +670,12 @@ def test_dropout_mask_statistics(p_drop):
         for i in m._BN_IDX:
             m.conv[i].weight.fill_(0.05)
             m.conv[i].bias.fill_(4.0)
-    H1, H2 = T // 2, T // 4
-    n1, nz2, n2 = B * H1 * F * 32, B * H1 * F * 64, B * H2 * F * 64
-    al = lambda v: (v + 255) // 256 * 256
     masks = []
     for call in range(2):
-        _, _, ws = cnn2d_forward_train_raw(m, x)
-        a1 = ws[:2 * n1].view(torch.bfloat16).view(B, H1, F, 32).float()
-        o2 = al(2 * n1) + al(2 * nz2)
-        a2 = ws[o2:o2 + 2 * n2].view(torch.bfloat16).view(B, H2, F, 64).float()
+        _, c, ws = cnn2d_forward_train_raw(m, x)
+        pl = _lib.cnn2d_train_plan(c.handle, B, T, F, _lib.PREC_BF16)        # where the step stored a1 and a2
+        a1 = ws[pl.a1:pl.a1 + B * pl.H1 * F * 32 * pl.elem].view(torch.bfloat16).view(B, pl.H1, F, 32).float()
+        a2 = ws[pl.a2:pl.a2 + B * pl.H2 * F * 64 * pl.elem].view(torch.bfloat16).view(B, pl.H2, F, 64).float()
         for a in (a1, a2):
             assert torch.isfinite(a).all() and float(a.max()) > 0
             keep = (a != 0).float()
