@@ -69,6 +69,7 @@ SYMBOLS = [
     ("dfa_cnn1d_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                      C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t]),
     ("dfa_cnn1d_train_ragged_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("dfa_cnn1d_train_plan", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int]),
     ("dfa_cnn1d_forward_train_ragged", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                                  C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_uint64, C.c_uint64, C.c_float,
                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -207,6 +208,33 @@ def cnn2d_train_plan(ctx_handle, B, T, F, precision):
     if n != len(out):
         raise ValueError(f"dfa_cnn2d_train_plan([{B}, {T}, {F}]) returned {n}, not {len(out)} fields")
     return Cnn2dTrainPlan(*out)
+
+
+class Cnn1dTrainPlan:
+    """dfa_cnn1d_train_plan as named fields (the order of include/dfa_hip.h): the byte offsets z, h, dz, dh (tuples, one per layer),
+    pooled, dpooled, stats, sums, partial, partial_bytes, lengths (-1: a uniform batch), total."""
+    _GROUPS = (("z", 3), ("h", 2), ("pooled", 0), ("dpooled", 0), ("dz", 3), ("dh", 2), ("stats", 0), ("sums", 0), ("partial", 0),
+               ("partial_bytes", 0), ("lengths", 0), ("total", 0))
+    NFIELDS = sum(max(n, 1) for _, n in _GROUPS)
+
+    def __init__(self, fields):
+        self.fields = tuple(fields)
+        i = 0
+        for name, n in self._GROUPS:
+            setattr(self, name, self.fields[i] if n == 0 else self.fields[i:i + n])
+            i += max(n, 1)
+
+
+def cnn1d_train_plan(ctx_handle, B, T, F, ragged=False):
+    """The workspace layout of a CNN1D training step (dfa_cnn1d_train_plan), of a ragged batch padded to T frames with
+    ragged=True; a refused shape raises as the step itself would (the message needs a context)."""
+    out = (C.c_longlong * Cnn1dTrainPlan.NFIELDS)()
+    n = load().dfa_cnn1d_train_plan(ctx_handle, B, T, F, int(ragged), out, len(out))
+    if n < 0:
+        check(ctx_handle, n)
+    if n != len(out):
+        raise ValueError(f"dfa_cnn1d_train_plan([{B}, {T}, {F}]) returned {n}, not {len(out)} fields")
+    return Cnn1dTrainPlan(out)
 
 
 def check(ctx_handle, code):

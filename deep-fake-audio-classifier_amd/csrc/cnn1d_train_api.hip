@@ -9,7 +9,7 @@ using namespace dfa;
 namespace {
 
 struct Train1dPlan {
-  size_t z[3], h[2], pooled, dpooled, dz[3], dh[2], stats, sums, partial, total;
+  size_t z[3], h[2], pooled, dpooled, dz[3], dh[2], stats, sums, partial, partial_bytes, total;
 };
 
 Train1dPlan plan_train1d(int B, int T, int F) {
@@ -29,9 +29,17 @@ Train1dPlan plan_train1d(int B, int T, int F) {
   const size_t wch = (size_t)conv1d_wgrad_chunks(B);
   pb = std::max(pb, wch * ((size_t)32 * F * 3 + 32) * 4);
   pb = std::max(pb, wch * ((size_t)128 * 64 * 3 + 128) * 4);
+  p.partial_bytes = pb;
   p.partial = take(pb);
   p.total = take.off;
   return p;
+}
+
+// the shape a step refuses (what cnn1d_forward_train_impl and dfa_cnn1d_train_plan both answer, word for word)
+int check_shape1d(dfa_ctx* ctx, int B, int T, bool ragged) {
+  if (B < 1 || T < 1) return fail(ctx, DFA_E_BAD_SHAPE, "B and T must be >= 1 (got %d, %d)", B, T);
+  if (ragged && T < 3) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: a ragged cnn1d batch needs T_max >= 3", T);
+  return DFA_OK;
 }
 
 const int kBnOff[3] = {0, 32, 96}, kBnC[3] = {32, 64, 128};     // BN layer order in the stats / sums blocks: layers 1-3
@@ -59,12 +67,11 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
   if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_set_params has not been called");
   if (!x || !logits || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, logits and workspace must be non-null");
   if (x_dtype != DFA_DTYPE_F32) return fail(ctx, DFA_E_BAD_DTYPE, "cnn1d takes float32 input (got dtype %d)", x_dtype);
-  if (B < 1 || T < 1) return fail(ctx, DFA_E_BAD_SHAPE, "B and T must be >= 1 (got %d, %d)", B, T);
+  DFA_TRY(check_shape1d(ctx, B, T, lengths != nullptr));
   if (F != m.in_features) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d does not match in_features=%d", F, m.in_features);
   if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(ctx, DFA_E_BAD_SHAPE, "dropout p must be in [0, 1)");
   double frames = (double)B * T;             // frames BatchNorm1d counts
   if (lengths) {
-    if (T < 3) return fail(ctx, DFA_E_BAD_SHAPE, "T_max=%d is too short: a ragged cnn1d batch needs T_max >= 3", T);
     DFA_TRY(check_lengths(ctx, lengths, B, 3, T));
     frames = 0.0;
     for (int b = 0; b < B; ++b) frames += (double)lengths[b];
@@ -214,6 +221,20 @@ size_t dfa_cnn1d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F) 
   (void)ctx;
   if (B < 1 || T < 1 || F < 1) return 0;
   return plan_train1d(B, T, F).total;
+}
+
+int dfa_cnn1d_train_plan(dfa_ctx* ctx, int B, int T, int F, int ragged, long long* fields, int cap) {
+  DFA_TRY(check_shape1d(ctx, B, T, ragged != 0));
+  if (F < 1) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d: need F >= 1", F);
+  const Train1dPlan pl = plan_train1d(B, T, F);
+  const long long v[] = {(long long)pl.z[0], (long long)pl.z[1], (long long)pl.z[2], (long long)pl.h[0], (long long)pl.h[1],
+                         (long long)pl.pooled, (long long)pl.dpooled, (long long)pl.dz[0], (long long)pl.dz[1], (long long)pl.dz[2],
+                         (long long)pl.dh[0], (long long)pl.dh[1], (long long)pl.stats, (long long)pl.sums, (long long)pl.partial,
+                         (long long)pl.partial_bytes, ragged ? (long long)pl.total : -1LL,
+                         (long long)(pl.total + (ragged ? ragged1d_tab_bytes(B) : 0))};
+  static_assert(sizeof(v) / sizeof(v[0]) == DFA_CNN1D_TRAIN_PLAN_FIELDS, "field table of dfa_cnn1d_train_plan");
+  for (int i = 0; fields && i < cap && i < DFA_CNN1D_TRAIN_PLAN_FIELDS; ++i) fields[i] = v[i];
+  return DFA_CNN1D_TRAIN_PLAN_FIELDS;
 }
 
 int dfa_cnn1d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,

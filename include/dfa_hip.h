@@ -344,6 +344,27 @@ int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
  * Everything else -- dtype (float32), strides, option cnn1d_train_x3, dropout, running statistics, gradients -- as in the
  * uniform pair. */
 size_t dfa_cnn1d_train_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F);
+/* The workspace layout of a CNN1D training step of [B, T, F] (ragged != 0: of a ragged batch padded to T = T_max): the very plan
+ * the forward_train / backward pairs and the two *_workspace_bytes functions read, reported.  Pure host arithmetic; ctx may be NULL
+ * (it only receives the refusal's text).  Everything is float, channel-major [B][C][T] with C = 32, 64, 128 for layers 1-3; offsets
+ * are bytes from the workspace's start, each 256-byte aligned, in the order below.  After one forward_train + backward every region
+ * but partial still holds what the step stored in it.  Fills the first min(cap, DFA_CNN1D_TRAIN_PLAN_FIELDS) of
+ *    0-2  z[3]      the Conv1d outputs in front of BatchNorm                        [B][C_l][T]
+ *    3-4  h[2]      dropout(ReLU(BatchNorm(z))) of layers 1 and 2                    [B][C_l][T]
+ *    5    pooled    the time mean of ReLU(BatchNorm(z[2])), the classifier's input   [B][128]
+ *    6    dpooled   its gradient                                                    [B][128]
+ *    7-9  dz[3]     the gradients of z                                              [B][C_l][T]
+ *   10-11 dh[2]     the gradients of h                                              [B][C_l][T]
+ *   12    stats     per BatchNorm layer mean[C] | biased variance[C] | invstd[C]; layer l's block starts 3 * {0, 32, 96}[l] floats in
+ *   13    sums      per layer the backward's [C][2] records (S1 = sum dy = dbeta, S2 = sum dy * xhat = dgamma) at 2 * {0, 32, 96}[l]
+ *   14 partial, 15 partial_bytes   the per-chunk records of every reduction
+ *   16    lengths   where the forward leaves the ragged batch's table (int32[B] lengths, then int32[B] unused); -1 when ragged == 0
+ *   17    total     = dfa_cnn1d_train_workspace_bytes, or dfa_cnn1d_train_ragged_workspace_bytes when ragged != 0
+ * of `fields` (may be NULL: validate only) and returns DFA_CNN1D_TRAIN_PLAN_FIELDS.  At a padding frame t >= lengths[b] of a ragged
+ * batch h and dz hold exact zeros; z and dh hold whatever the uniform convolution makes of its zero-padded neighbours (finite, read
+ * by nothing).  A shape the step refuses returns the step's own error code (negative) and leaves its message in ctx. */
+#define DFA_CNN1D_TRAIN_PLAN_FIELDS 18
+int dfa_cnn1d_train_plan(dfa_ctx* ctx, int B, int T, int F, int ragged, long long* fields, int cap);
 int dfa_cnn1d_forward_train_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,
                                    int64_t stride_t, int64_t stride_f, const int32_t* lengths, float p_drop, uint64_t seed,
                                    uint64_t offset, float momentum, int update_running_stats, float* logits, void* workspace,

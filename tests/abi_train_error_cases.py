@@ -218,6 +218,8 @@ def _cases():
     add("mse_fwd_bwd/batch_0", "cae", None, lambda r: r.mse(B=0))
     # the one refusal dfa_cnn2d_train_plan adds to the step's own (which it answers word for word: tests/test_cnn2d_train_stages_gpu.py)
     add("cnn2d_train_plan/F_0", "cnn2d", None, lambda r: r.lib.dfa_cnn2d_train_plan(r.ctx, B, T, 0, PREC_BF16, None, 0))
+    # the same for dfa_cnn1d_train_plan (tests/test_cnn1d_train_stages_gpu.py)
+    add("cnn1d_train_plan/F_0", "cnn1d", None, lambda r: r.lib.dfa_cnn1d_train_plan(r.ctx, B, T, 0, 0, None, 0))
     return c
 
 

@@ -103,9 +103,15 @@ def convt2x2(a, w, b, opad=0, dt=F64, mags=False):
     return Stage(out, A, w.shape[0] + 1)
 
 
-def batch_stats(z, dt=F64):
-    """(mean, biased variance) over batch and pixels of z [B,H,W,C]"""
+def batch_stats(z, dt=F64, valid=None):
+    """(mean, biased variance) over batch and pixels of z [B,H,W,C]; valid (bool, broadcastable to z): over those pixels only (the
+    frames of a ragged batch's utterances; what z holds elsewhere is not read)"""
     z = z.to(dt)
+    if valid is not None:
+        z = torch.where(valid, z, torch.zeros_like(z))
+        n = valid.expand(z.shape).to(dt).sum(dim=(0, 1, 2))
+        mean = z.sum(dim=(0, 1, 2)) / n
+        return mean, torch.where(valid, (z - mean) ** 2, torch.zeros_like(z)).sum(dim=(0, 1, 2)) / n
     mean = z.mean(dim=(0, 1, 2))
     return mean, ((z - mean) ** 2).mean(dim=(0, 1, 2))
 
@@ -220,12 +226,14 @@ def upstream(da, H, W, src, dt=F64):
 BnReduce = namedtuple("BnReduce", "S1 S2 slack1 slack2 on amb xh")
 
 
-def bn_bwd_reduce(z, up, mean, invstd, gamma, beta, dt=F64, k_amb=K_BN, terms=None, also_open=None):
+def bn_bwd_reduce(z, up, mean, invstd, gamma, beta, dt=F64, k_amb=K_BN, terms=None, also_open=None, valid=None):
     """z as stored, `up` = upstream(...) -> S1 = sum dy (dbeta), S2 = sum dy xhat (dgamma) with dy = up where BatchNorm(z) > 0.
     amb marks the elements whose BatchNorm output y lies within k_amb u (|gamma| invstd (|z| + |mean|) + |beta|) of zero -- the
     fp32 rounding of its own terms (`terms`: the caller's own sum of magnitudes, block 1) -- so that an fp32 kernel may take
     either branch; slack1 / slack2 are what those elements can move the two sums by (sum |up|, sum |up xhat| over them).
-    also_open: elements whose dy the caller cannot state wherever their ReLU is on (a bool mask; and-ed with `on`, or-ed into amb)."""
+    also_open: elements whose dy the caller cannot state wherever their ReLU is on (a bool mask; and-ed with `on`, or-ed into amb).
+    valid (bool, broadcastable to z): the elements that belong to the batch (a ragged batch's own frames); `up` is zero at the others,
+    which are no decisions: amb is and-ed with it."""
     z, up, mean, invstd, gamma, beta = (t.to(dt) for t in (z, up, mean, invstd, gamma, beta))
     xh = (z - mean) * invstd
     y = gamma * xh + beta
@@ -236,18 +244,21 @@ def bn_bwd_reduce(z, up, mean, invstd, gamma, beta, dt=F64, k_amb=K_BN, terms=No
     amb = y.abs() <= k_amb * U * terms.to(dt)
     if also_open is not None:
         amb = amb | (also_open & on)
+    if valid is not None:
+        amb = amb & valid
     au = up.abs() * amb
     return BnReduce(dy.sum(dim=(0, 1, 2)), (dy * xh).sum(dim=(0, 1, 2)), au.sum(dim=(0, 1, 2)), (au * xh.abs()).sum(dim=(0, 1, 2)),
                     on, amb, xh)
 
 
-def bn_bwd_apply(z, up, mean, invstd, gamma, beta, S1, S2, dt=F64, mags=False, z_term=None):
+def bn_bwd_apply(z, up, mean, invstd, gamma, beta, S1, S2, dt=F64, mags=False, z_term=None, n=None):
     """dz = gamma invstd (dy - S1 / N - xhat S2 / N) with the sums the caller gives (the GPU's own) -> (Stage dz, dz with the ReLU
     decision of every element reversed).  k0 = gamma invstd, k1, k2 one rounding each, xhat two, the bracket three, the product
     one: K = K_BN of A = |k0| (|up| + |k1| + invstd (|z| + |mean|) |k2|).  z_term: the tensor the xhat of the S2 term is formed
-    from when it is not z (autograd through statistics of the unrounded accumulators; the kernels take z)."""
+    from when it is not z (autograd through statistics of the unrounded accumulators; the kernels take z).  n: the count the
+    statistics ran over when it is not every pixel of z (the frames of a ragged batch)."""
     z, up, mean, invstd, gamma, beta, S1, S2 = (t.to(dt) for t in (z, up, mean, invstd, gamma, beta, S1, S2))
-    N = z.shape[0] * z.shape[1] * z.shape[2]
+    N = z.shape[0] * z.shape[1] * z.shape[2] if n is None else n
     k0, k1, k2 = gamma * invstd, S1 / N, S2 / N
     xh = (z - mean) * invstd
     on = (gamma * xh + beta) > 0
@@ -417,6 +428,7 @@ def run_chain(sd, x, rounding=True, stats="epilogue", dgrad_bf16=True):
 # where it may be taken; eslack: an absolute allowance per element, used where an operand could only be restated);
 # kind "fp32": an fp32 output (slack: absolute allowance per element from ambiguous ReLU decisions or restated operands; scale:
 # the tensor's scale when it is not max |want|)
+# kind "allow": an output held to a derived absolute allowance per element (slack) alone -- worst = max |got - want| / slack, bound 1
 Result = namedtuple("Result", "kind out A K alt amb slack scale", defaults=(None,) * 6)
 
 
@@ -575,6 +587,10 @@ def compare_one(name, res, got, floor_out=None, cap=1.0):
         if res.amb is not None:
             unequal &= ~(res.amb & (bf16(res.alt.to(F64)) == got))
         return Row(name, "bf16", float(ratio.max()), 1.0, float(unequal.double().mean()), amb_share, 0.0, 0.0, 0.0, unequal.numel(), float(acc.max()))
+    if res.kind == "allow":     # a derived per-element allowance (res.slack) and nothing else: no floor, no tolerance on top
+        ratio = (got - want).abs() / res.slack.to(F64).reshape(want.shape).clamp_min(1e-300)
+        ratio = torch.where((got - want).abs() == 0, torch.zeros_like(ratio), ratio)
+        return Row(name, "allow", float(ratio.max()), cap, 0.0, 0.0, 0.0, 0.0, 0.0, ratio.numel())
     scale = res.scale if res.scale is not None else max(float(want.abs().max()), 1e-300)
     emax, el2 = _dev(got, want, scale, res.slack)
     fmax = fl2 = 0.0
@@ -595,7 +611,7 @@ def row_failures(row, cap=1.0):
     """what one stage misses (the unequal share is a criterion of the whole case: `compare`)"""
     bad = []
     if not row.worst <= row.bound:
-        bad.append(f"{row.name}: {'element allowance ratio' if row.kind == 'bf16' else 'max/scale'} {row.worst:.3e} > {row.bound:.3e}"
+        bad.append(f"{row.name}: {'max/scale' if row.kind == 'fp32' else 'element allowance ratio'} {row.worst:.3e} > {row.bound:.3e}"
                    + (f" (floor {row.floor:.2e})" if row.kind == "fp32" else ""))
     if not row.l2 <= row.l2_bound:
         bad.append(f"{row.name}: relative L2 {row.l2:.3e} > {row.l2_bound:.3e}")
