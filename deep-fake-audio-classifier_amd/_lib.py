@@ -110,6 +110,9 @@ SYMBOLS = [
                                         C.c_size_t]),
     ("dfa_dlq_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
                                    C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t]),
+    ("dfa_dlq_gather_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("dfa_dlq_gather_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t]),
     ("dfa_bce_pos_weight_fwd_bwd", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     ("dfa_clip_grad_norm", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]),
     ("dfa_cnn1d_ragged_segments", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),

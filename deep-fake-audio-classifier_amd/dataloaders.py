@@ -288,6 +288,126 @@ class ResidentBatcher:
         return _Epoch()
 
 
+def plan_packed_set(lengths, C: int):
+    """(offsets int64[N], total_floats) of a packed set of N utterances [C, T_i], time fastest: utterance i is C rows of
+    pitch_i = ceil(T_i / 4) * 4 floats from float offset offsets[i], back to back in input order.  Every offset is a multiple of
+    4, so on a 16-byte aligned base every row starts on 16 bytes.  Pure host arithmetic in int64 (a set may exceed 2^31 floats)."""
+    lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if int(C) < 1 or (lens.size and int(lens.min()) < 1):
+        raise ValueError("a packed set needs C >= 1 and every length >= 1")
+    sizes = int(C) * ((lens + 3) // 4 * 4)
+    ends = np.cumsum(sizes, dtype=np.int64)
+    offsets = np.zeros(lens.size, dtype=np.int64)
+    offsets[1:] = ends[:-1]
+    return offsets, (int(ends[-1]) if lens.size else 0)
+
+
+class DlqResidentSet:
+    """A DeepfakeDetector training or dev set held in HBM: the per-utterance [C, T_i] tensors of a
+    features.pkl are uploaded ONCE, packed (plan_packed_set), and `batch(idx, spans)` assembles the padded, optionally
+    SpecAugmented batch of any utterances with one HIP launch (dfa_dlq_gather_batch) in the layout DlqTrainer.step and the eval
+    forward read in place.  Per batch the host sends the table alone: offsets, lengths and mask spans, a few hundred bytes.
+    What ResidentBatcher is to the equal-length models; utterances of unequal lengths and per-sample masks need a kernel.
+
+    offsets / lengths: host numpy arrays (int64 / int32); labels: float32 device tensor, labels_host its numpy copy (or None);
+    set: the packed float32 device buffer (the floats T_i .. pitch_i of a row are unspecified); bytes_resident."""
+
+    def __init__(self, feature_list, labels=None, device="cuda", chunk_utts: int = 1024):
+        from . import _lib
+        self.device = torch.device(device)
+        self.ctx = _lib.Context.get(self.device)               # (raises off the GPU: there is no CPU path)
+        if len(feature_list) == 0:
+            raise ValueError("DlqResidentSet needs at least one utterance")
+        chans = {int(f.shape[0]) for f in feature_list}
+        if len(chans) != 1:
+            raise ValueError(f"utterances must share the feature dimension, got {sorted(chans)}")
+        self.C = chans.pop()
+        self.lengths = np.array([int(f.shape[-1]) for f in feature_list], dtype=np.int32)
+        self.offsets, self.total_floats = plan_packed_set(self.lengths, self.C)
+        dev = torch.device("cuda", self.ctx.index)
+        self.set = torch.empty(self.total_floats, dtype=torch.float32, device=dev)
+        if self.set.data_ptr() % 256:
+            raise RuntimeError("the resident buffer is not 256-byte aligned")
+        n = len(feature_list)
+        ends = np.append(self.offsets[1:], self.total_floats)
+        for lo in range(0, n, max(1, int(chunk_utts))):          # bounded host staging, as ResidentBatcher's
+            hi = min(n, lo + max(1, int(chunk_utts)))
+            base = int(self.offsets[lo])
+            host = torch.zeros(int(ends[hi - 1]) - base, dtype=torch.float32)
+            for i in range(lo, hi):
+                T = int(self.lengths[i])
+                rows = host[int(self.offsets[i]) - base:int(ends[i]) - base].view(self.C, -1)
+                rows[:, :T] = torch.as_tensor(feature_list[i]).float()
+            self.set[base:int(ends[hi - 1])].copy_(host)
+        self.labels_host = None if labels is None else np.asarray(labels, dtype=np.float32).reshape(-1)
+        if self.labels_host is not None and self.labels_host.shape[0] != n:
+            raise ValueError(f"got {self.labels_host.shape[0]} labels for {n} utterances")
+        self.labels = None if labels is None else torch.from_numpy(self.labels_host.copy()).to(dev)
+        self.bytes_resident = self.set.numel() * 4
+        self._x = None          # the batch buffer, grown when needed and reused from batch to batch
+        self._tab = None        # the kernel's per-call table
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    @staticmethod
+    def fits(feature_list, device, fraction: float = 0.5) -> bool:
+        """True when the packed set takes at most `fraction` of the device's currently free memory."""
+        dev = torch.device(device)
+        if dev.type != "cuda" or len(feature_list) == 0:
+            return False
+        _, total = plan_packed_set([int(f.shape[-1]) for f in feature_list], int(feature_list[0].shape[0]))
+        free, _total = torch.cuda.mem_get_info(dev)
+        return total * 4 <= fraction * free
+
+    def batch(self, idx, spans=None, n_tmask: int = 0):
+        """The utterances `idx` (any order, repeats allowed) as (x [b, C, T] float32 device view with rows of T_pad = T rounded up
+        to 4 frames, T the longest of them; lengths int32[b] on the host; y float32[b] on the device, or None without labels).
+        spans: int32 [b, n, 2] = (start, width) per utterance, its n_tmask time spans first, then its channel spans
+        (train_dlqueen.draw_spans), or None.  x is zero behind every utterance and inside the spans.  It lives in ONE buffer owned
+        by the set: the next batch overwrites it, ordered on torch's current stream behind whatever read this one there."""
+        import ctypes as C
+        from . import _lib
+        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+        b = int(idx.shape[0])
+        if b == 0:
+            raise ValueError("an empty batch")
+        if int(idx.min()) < 0 or int(idx.max()) >= len(self):
+            raise IndexError(f"utterance index outside [0, {len(self)})")
+        lengths = np.ascontiguousarray(self.lengths[idx])
+        src = np.ascontiguousarray(self.offsets[idx])
+        n_sp = 0
+        if spans is not None:
+            spans = np.ascontiguousarray(spans, dtype=np.int32)
+            if spans.ndim != 3 or spans.shape[0] != b or spans.shape[2] != 2 or not 0 <= int(n_tmask) <= spans.shape[1]:
+                raise ValueError(f"spans must be int32 [b={b}, n >= n_tmask={n_tmask}, 2], got shape {spans.shape}")
+            n_sp = int(spans.shape[1])
+        n_t = int(n_tmask) if n_sp else 0
+        T = int(lengths.max())
+        T_pad = -(-T // 4) * 4
+        need = b * self.C * T_pad
+        ctx = self.ctx
+        with torch.cuda.device(ctx.index):
+            if self._x is None or self._x.numel() < need:
+                self._x = None
+                self._x = torch.empty(need, dtype=torch.float32, device=self.set.device)
+            nbytes = int(ctx.lib.dfa_dlq_gather_workspace_bytes(b, n_t, n_sp - n_t))
+            if nbytes == 0:
+                raise ValueError(f"{n_sp} spans per utterance: the batch gather takes at most 16")
+            if self._tab is None or self._tab.numel() < nbytes:
+                self._tab = None
+                self._tab = torch.empty(nbytes, dtype=torch.uint8, device=self.set.device)
+            x = self._x[:need].view(b, self.C, T_pad)
+            ctx.use_current_stream()
+            code = ctx.lib.dfa_dlq_gather_batch(ctx.handle, _lib.ptr(self.set), self.total_floats, C.c_void_p(src.ctypes.data),
+                                                C.c_void_p(lengths.ctypes.data), C.c_void_p(spans.ctypes.data) if n_sp else None,
+                                                n_t, n_sp - n_t, b, T, self.C, _lib.ptr(x), self.C * T_pad, T_pad,
+                                                _lib.ptr(self._tab), self._tab.numel())
+            _lib.check(ctx.handle, code)
+            y = None if self.labels is None else self.labels.index_select(0, torch.from_numpy(idx).to(self.set.device))
+        return x[:, :, :T], lengths, y
+
+
 def open_flat(features_path: str, labels_path: str | None, cache_dir: str, rank: int = 0, world: int = 1, tag: str = "set"):
     """(features tensor [N,180,321] zero-copy over a memory-mapped flat file, labels [N] float32 or None, uttids) for the
     data-parallel drivers.  `features_path` is either a flat prefix made by `python -m dfa_amd.ingest` (<prefix>.npy +

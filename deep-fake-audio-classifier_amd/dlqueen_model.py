@@ -146,6 +146,28 @@ def evaluate_eer(model, feature_list, labels, batch_size: int = 32, device="cuda
     return float(eer)
 
 
+@torch.no_grad()
+def run_inference_resident(model, rset, batch_size: int = 32, use_prob: bool = False):
+    """run_inference(..., file_order=True) on a dataloaders.DlqResidentSet: the same file-order batches, assembled on the device
+    by the set's gather and read in place by the forward; the same scores, bit for bit."""
+    model.eval()
+    outs = []
+    for lo in range(0, len(rset), batch_size):
+        x, lengths, _ = rset.batch(np.arange(lo, min(lo + batch_size, len(rset))))
+        outs.append(model(x, lengths))
+    scores = torch.cat(outs) if outs else torch.empty(0, device=rset.device)
+    return torch.sigmoid(scores) if use_prob else scores
+
+
+@torch.no_grad()
+def evaluate_eer_resident(model, rset, labels, batch_size: int = 32) -> float:
+    """evaluate_eer(..., file_order=True) on a resident set"""
+    from .evaluation import calculate_eer
+    scores = run_inference_resident(model, rset, batch_size).cpu().numpy()
+    eer, _thr = calculate_eer(np.asarray(scores, dtype=np.float64), np.asarray(labels))
+    return float(eer)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="DeepfakeDetector (Conv1d + StatsPool) prediction on the MI355X")
     ap.add_argument("--data_dir", default="data")

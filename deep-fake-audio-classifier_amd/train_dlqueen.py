@@ -7,7 +7,11 @@ pos_weight = neg / pos, a WeightedRandomSampler with replacement, batches in SAM
 (the step depends on the batch's composition, so there is no length sorting), per-sample SpecAugment on the host before staging,
 dev EER every epoch (file-order batches, under the EMA weights with --ema), the best state_dict saved with torch.save under the
 reference's keys and shapes (the raw weights, as the reference saves them after restoring from the EMA), early stopping.
-What is not: AMP.  The step is fp32-grade throughout; GradScaler / autocast have no counterpart."""
+What is not: AMP.  The step is fp32-grade throughout; GradScaler / autocast have no counterpart.
+
+--resident (default off): both splits are uploaded once (dataloaders.DlqResidentSet) and every batch is assembled on the device by
+one launch; the host still draws the sampler's order and the SpecAugment masks (draw_spans), so the run is bit for bit the same
+(DESIGN.md section 3.15b)."""
 from __future__ import annotations
 
 import argparse
@@ -41,6 +45,8 @@ def parse_args(argv=None):
     ap.add_argument("--ema", action="store_true")
     ap.add_argument("--ema_decay", type=float, default=0.999)
     ap.add_argument("--patience", type=int, default=6)
+    ap.add_argument("--resident", action="store_true",
+                    help="keep the train and dev sets in GPU memory and assemble every batch there (dataloaders.DlqResidentSet)")
     args = ap.parse_args(argv)
     if args.hidden != 256:
         ap.exit(2, f"--hidden {args.hidden}: the DeepfakeDetector HIP path is built for hidden=256\n")
@@ -50,6 +56,8 @@ def parse_args(argv=None):
         ap.exit(2, "--batch_size must be >= 1\n")
     if not 0.0 <= args.dropout < 1.0:
         ap.exit(2, "--dropout must be in [0, 1)\n")
+    if args.resident and args.specaug and sum(span_counts(args.time_mask_max, args.time_mask_n, args.freq_mask_max, args.freq_mask_n)) > 16:
+        ap.exit(2, "--resident: the batch gather takes at most 16 mask spans per utterance (time_mask_n + freq_mask_n <= 16)\n")
     return args
 
 
@@ -104,6 +112,40 @@ def epoch_batches(feats, labels, order, batch_size, specaug=None, rng=None):
         yield host[:, :, :T], lengths, torch.tensor([float(labels[i]) for i in idx], dtype=torch.float32)
 
 
+def span_counts(time_mask_max, time_mask_n, freq_mask_max, freq_mask_n):
+    """(time spans, channel spans) draw_spans records per sample: a family with max <= 0 or n <= 0 has none"""
+    return (time_mask_n if time_mask_max > 0 and time_mask_n > 0 else 0), (freq_mask_n if freq_mask_max > 0 and freq_mask_n > 0 else 0)
+
+
+def draw_spans(rng, C, T, time_mask_max, time_mask_n, freq_mask_max, freq_mask_n):
+    """spec_augment's masks of one [C, T] sample as spans instead of slice assignments: int32 [n_t + n_f, 2] = (start, width),
+    the time spans first (span_counts).  Consumes rng in exactly spec_augment's order -- per mask w = randint(0, min(max, dim)),
+    the start only when w != 0 -- so one rng drives either; a mask of width 0 is recorded as (0, 0)."""
+    n_t, n_f = span_counts(time_mask_max, time_mask_n, freq_mask_max, freq_mask_n)
+    out = np.zeros((n_t + n_f, 2), dtype=np.int32)
+    for k in range(n_t + n_f):
+        cap, dim = (time_mask_max, T) if k < n_t else (freq_mask_max, C)
+        w = rng.randint(0, min(cap, dim))
+        if w == 0:
+            continue
+        out[k] = (rng.randint(0, max(0, dim - w)), w)
+    return out
+
+
+def resident_epoch_batches(rset, order, batch_size, specaug=None, rng=None):
+    """epoch_batches on a dataloaders.DlqResidentSet: the same triples in the same order, bit for bit, assembled on the device
+    (x [b, C, T] device float32 in the stored layout, lengths int32 [b] on the host, y float32 [b] on the device).  The spans
+    are drawn sample by sample in batch order, as epoch_batches draws its masks: one rng drives both paths identically.  x is
+    the set's one batch buffer: consume a batch before asking for the next."""
+    n_t = span_counts(*specaug)[0] if specaug is not None else 0
+    for lo in range(0, len(order), batch_size):
+        idx = order[lo:lo + batch_size]
+        spans = None
+        if specaug is not None:
+            spans = np.stack([draw_spans(rng, rset.C, int(rset.lengths[i]), *specaug) for i in idx])
+        yield rset.batch(idx, spans, n_t)
+
+
 def train_epoch(trainer, batches, device):
     """mean of the steps' losses (one host read at the end of the epoch)"""
     losses = []
@@ -124,7 +166,8 @@ def _load_split(data_dir, split):
 
 
 def main(argv=None):
-    from .dlqueen_model import DeepfakeDetector, evaluate_eer
+    from .dataloaders import DlqResidentSet
+    from .dlqueen_model import DeepfakeDetector, evaluate_eer, evaluate_eer_resident
     from .training import DlqTrainer
 
     args = parse_args(argv)
@@ -134,6 +177,9 @@ def main(argv=None):
     train_feats, y_train = _load_split(args.data_dir, args.train_split)
     dev_feats, y_dev = _load_split(args.data_dir, args.dev_split)
     pos_weight, _, _ = compute_class_weights(y_train)
+    if args.resident and not DlqResidentSet.fits(list(train_feats) + list(dev_feats), args.device):
+        raise SystemExit(f"--resident: the packed train and dev sets do not fit in half of the free memory of '{args.device}'; "
+                         "run without --resident")
     model = DeepfakeDetector(in_ch=int(train_feats[0].shape[0]), hidden=args.hidden, dropout=args.dropout).to(args.device)
     model._drop_seed, model._drop_offset = int(args.seed) & 0xFFFFFFFFFFFFFFFF, 0
     trainer = DlqTrainer(model, lr=args.lr, weight_decay=args.weight_decay, pos_weight=pos_weight, grad_clip=args.grad_clip,
@@ -142,11 +188,20 @@ def main(argv=None):
     rng = random.Random(args.seed)
     specaug = (args.time_mask_max, args.time_mask_n, args.freq_mask_max, args.freq_mask_n) if args.specaug else None
     best_eer, bad = 1.0, 0
+    if args.resident:           # both splits uploaded once; from here on the host sends indices and mask spans only
+        train_set = DlqResidentSet(train_feats, y_train, device=args.device)
+        dev_set = DlqResidentSet(dev_feats, None, device=args.device)
     for epoch in range(1, args.epochs + 1):
         order = sample_order(y_train, gen)
-        loss = train_epoch(trainer, epoch_batches(train_feats, y_train, order, args.batch_size, specaug, rng), args.device)
+        if args.resident:
+            loss = train_epoch(trainer, resident_epoch_batches(train_set, order, args.batch_size, specaug, rng), args.device)
+        else:
+            loss = train_epoch(trainer, epoch_batches(train_feats, y_train, order, args.batch_size, specaug, rng), args.device)
         with trainer.ema_applied():
-            dev_eer = evaluate_eer(model, dev_feats, y_dev, args.batch_size, device=args.device, file_order=True)
+            if args.resident:
+                dev_eer = evaluate_eer_resident(model, dev_set, y_dev, args.batch_size)
+            else:
+                dev_eer = evaluate_eer(model, dev_feats, y_dev, args.batch_size, device=args.device, file_order=True)
         print(f"Epoch {epoch}: train_loss={loss:.6f} dev EER={dev_eer:.6f}  (lower is better)")
         if dev_eer < best_eer:
             best_eer, bad = dev_eer, 0

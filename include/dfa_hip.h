@@ -523,6 +523,28 @@ int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_
                           int update_running_stats, float* logits, uint8_t* keep_out, void* workspace, size_t workspace_bytes);
 int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, int64_t stride_b, int64_t stride_c,
                      const float* dlogits, float* const* grads, int ngrads /* 16 */, void* workspace, size_t workspace_bytes);
+/* ---- DeepfakeDetector batches from a resident set.  The whole training or dev set lives in ONE device
+ * float32 buffer `set` of set_floats floats: utterance i of [C][T_i], time fastest, is C rows of pitch_i = ceil(T_i / 4) * 4 floats
+ * from float offset off_i, a multiple of 4 (a 16-byte aligned base makes every row 16-byte aligned).  The floats T_i .. pitch_i of a
+ * row are unspecified.  One launch assembles the batch x[B][C][T_pad], T_pad = ceil(T_max / 4) * 4, element (b, c, t) at
+ * x + b stride_b + c stride_c + t, from B utterances of the set, optionally SpecAugmented:
+ *   x[b][c][t] = (t < lengths[b] and t in no time span of b and c in no channel span of b) ? set[src_off[b] + c pitch_b + t] : +0.0f
+ * for every t < T_pad.  It is a select, never a multiply: NaN or Inf inside a masked span, behind lengths[b] or in a row's padding
+ * floats gives an exact +0.0.  Every float of [b][c][0, T_pad) is written (no memset needed), no other float of x is.
+ * src_off: HOST int64[B]; lengths: HOST int32[B], each in [1, T_max]; spans: HOST int32[B][n_tmask + n_fmask][2] = (start, width),
+ *   the n_tmask time spans of an utterance first, then its n_fmask channel spans, half-open [start, start + width), width 0 masks
+ *   nothing; NULL when both counts are 0.  At most 16 spans per utterance (else DFA_E_UNSUPPORTED).
+ * DFA_E_BAD_SHAPE, naming the index: B, C or T_max < 1; lengths[b] outside [1, T_max]; src_off[b] negative, not a multiple of 4 or
+ *   with src_off[b] + C pitch_b > set_floats; a time span with start < 0, width < 0 or start + width > lengths[b]; a channel span
+ *   that leaves [0, C]; x not 16-byte aligned; stride_c or stride_b not a multiple of 4, stride_c < T_pad, or (B > 1) stride_b <
+ *   (C - 1) stride_c + T_pad.
+ * workspace: device, 256-byte aligned, >= the bytes the planner below returns (the per-call table; 0 for B < 1 or more than 16
+ *   spans), else DFA_E_WORKSPACE.  The table goes through the context's pinned staging slots; the launch is on the context's
+ *   stream.  A capturing stream returns DFA_E_UNSUPPORTED (the table is per-call data).  Timing slot: 14. */
+size_t dfa_dlq_gather_workspace_bytes(int B, int n_tmask, int n_fmask);
+int dfa_dlq_gather_batch(dfa_ctx* ctx, const float* set, int64_t set_floats, const int64_t* src_off, const int32_t* lengths,
+                         const int32_t* spans, int n_tmask, int n_fmask, int B, int T_max, int C, float* x, int64_t stride_b,
+                         int64_t stride_c, void* workspace, size_t workspace_bytes);
 /* loss = mean_b -[pos_weight y log sigmoid(l) + (1 - y) log sigmoid(-l)] (BCEWithLogitsLoss(pos_weight), mean reduction);
  * dlogits = (sigmoid(l) (1 + (pos_weight - 1) y) - pos_weight y) / B.  loss: device float[1] or NULL; dlogits: device float[B] or NULL */
 int dfa_bce_pos_weight_fwd_bwd(dfa_ctx* ctx, const float* logits, const float* labels, float pos_weight, int B, float* loss,
