@@ -329,12 +329,12 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
       // one apply pass writes dz patch-major (what the two gradient GEMMs read) and leaves the records of its channel sums = the
       // ConvTranspose2d bias gradient (over ALL output pixels, the output_padding column included): dzd itself is never stored
       dfa::BnBwdFold fold{ws + pl.zp, Win, partial, 0};
-      DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], bn, nullptr, ws + pl.dd[l], partial, sm, nullptr, B, pl.Hd[l], pl.Wd[l],
+      DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], bn, ws + pl.dd[l], partial, sm, nullptr, B, pl.Hd[l], pl.Wd[l],
                                        Cout, nodrop, s, scratch2, sync, &fold));
       DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, Cout, s));
       DFA_HIP_CHECK(ctx, launch_reduce_partials(partial, fold.nrec, Cout, 1.0f, g.db, s, scratch2));
     } else {
-    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], bn, nullptr, ws + pl.dd[l], partial, sm, ws + pl.dzd[l], B, pl.Hd[l],
+    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_DIRECT, ws + pl.zd[l], bn, ws + pl.dd[l], partial, sm, ws + pl.dzd[l], B, pl.Hd[l],
                                      pl.Wd[l], Cout, nodrop, s, scratch2, sync));
     DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, Cout, s));
     {  // ConvTranspose2d bias gradient = channel sums of dz over ALL output pixels (the output_padding column included)
@@ -378,7 +378,7 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
     BnStats st = stat_of(ws, pl, l, kEC[l]);
     float* sm = sums_of(ws, pl, l);
     const LayerGrads g = layer_grads(grads, l);
-    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL22, ws + pl.z[l], bn_apply(st, layer_params(m.p, l)), nullptr, ws + pl.de[l], partial, sm,
+    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL22, ws + pl.z[l], bn_apply(st, layer_params(m.p, l)), ws + pl.de[l], partial, sm,
                                      ws + pl.dz[l], B, pl.H[l], pl.W[l], kEC[l], nodrop, s, scratch2, sync));
     DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, kEC[l], s));
     if (l == 3) {

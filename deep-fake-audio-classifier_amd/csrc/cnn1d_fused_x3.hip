@@ -228,7 +228,7 @@ __global__ __launch_bounds__(512) void cnn1d_ragged_x3_kernel(Cnn1dX3Args a, Cnn
 struct Conv1dX3Args {
   const float* x;              // [B] x [Cin][T] contiguous per utterance, utterance stride sb floats, 16-byte aligned
   int64_t sb;
-  const uint4* w;              // pack_conv1d_terms_kernel image [Cout / 32][3][nks][TERMS][64]
+  const uint4* w;              // pack_conv1d_train_all_kernel image [Cout / 32][3][nks][TERMS][64]
   const float* bias;           // [Cout]
   float* z;                    // [B][Cout][T]
   int T, Cin, Cout, NT, nks, slab_floats, offW;
@@ -236,37 +236,8 @@ struct Conv1dX3Args {
   const int* lens;             // RAGGED instantiation (training layer 1 of a ragged batch): device [B], utterance b owns frames [0, lens[b]) of T
 };
 
-// A-fragment images with TERMS bf16 terms per weight: wx[m][tap][ks][term][lane]
-__global__ void pack_conv1d_terms_kernel(const float* __restrict__ wf, uint4* __restrict__ wx, int cin, int cout, int nks, int terms) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int total = (cout / 32) * 3 * nks * 64;
-  if (i >= total) return;
-  const int lane = i & 63;
-  int rest = i >> 6;
-  const int ks = rest % nks; rest /= nks;
-  const int tap = rest % 3, m = rest / 3;
-  const int co = 32 * m + (lane & 31), hh = lane >> 5;
-  bf16_t t0[8], t1[8], t2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int ci = 16 * ks + 8 * hh + j;
-    const float w = ci < cin ? wf[((size_t)co * cin + ci) * 3 + tap] : 0.f;
-    t0[j] = float_to_bf16(w);
-    const float r1 = w - bf16_to_float(t0[j]);
-    t1[j] = float_to_bf16(r1);
-    t2[j] = float_to_bf16(r1 - bf16_to_float(t1[j]));
-  }
-  uint4* dst = wx + ((size_t)((m * 3 + tap) * nks + ks) * terms) * 64 + lane;
-  dst[0] = *reinterpret_cast<const uint4*>(t0);
-  dst[64] = *reinterpret_cast<const uint4*>(t1);
-  if (terms == 3) dst[128] = *reinterpret_cast<const uint4*>(t2);
-}
+// A-fragment images with TERMS bf16 terms per weight: wx[m][tap][ks][term][lane] (pack_conv1d_train_all_kernel writes them)
 size_t conv1d_terms_pack_bytes(int cin, int cout, int terms) { return (size_t)(cout / 32) * 3 * cnn1d_x3_nks(cin) * terms * 64 * 16; }
-hipError_t launch_pack_conv1d_terms(const float* wf, void* wx, int cin, int cout, int terms, hipStream_t s) {
-  const int total = (cout / 32) * 3 * cnn1d_x3_nks(cin) * 64;
-  hipLaunchKernelGGL(pack_conv1d_terms_kernel, dim3((total + 255) / 256), dim3(256), 0, s, wf, (uint4*)wx, cin, cout, cnn1d_x3_nks(cin), terms);
-  return hipGetLastError();
-}
 
 // The five images of a training step (forward layers 1-3, data gradients 3 -> 2 and 2 -> 1) in ONE launch, the data-gradient ones read
 // straight from the layer's own weight: W'[c][o][k'] = W[o][c][2 - k'] (a Conv1d with Cin' = Cout, Cout' = Cin) -- seven launches

@@ -84,6 +84,10 @@ struct BnSync {
 // local sums -> the sums the apply / finalize stage uses (buf after the all-reduce, or `sums` itself when not synchronising) and
 // the factor that turns 1 / n_local into 1 / n_global
 hipError_t bn_sync_sums(const BnSync* sy, const float* sums, int count, hipStream_t s, const float** sums_apply, float* inv_scale);
+// second stage of a BatchNorm backward (after its reduce kernel's launch): block records partial[nrec][C][2] -> sums[C][2] in a fixed
+// order -> bn_sync_sums; *inv_n (in: 1 / n_local) leaves as 1 / n_global
+hipError_t bn_bwd_sums(const float* partial, int nrec, int C, float* sums, float* scratch, const BnSync* sync, hipStream_t s,
+                       const float** sums_apply, float* inv_n);
 
 struct Cnn1dState {
   const float* p[DFA_CNN1D_NPARAMS] = {nullptr};
@@ -173,10 +177,10 @@ struct dfa_ctx {
   int cae_enc1_mfma = 1;       // auto-encoder eval forward, bf16 mode: block 1 on the matrix cores (cae_enc1_mfma.hip); 0 = the vector-ALU kernel
   int cae_enc_dma = 1;         // auto-encoder eval forward, bf16 mode: encoder blocks 2-4 stage their input rows by LDS-DMA; 0 = through registers
   int cae_dgrad_mfma = 1;      // auto-encoder training, bf16 mode: ConvTranspose2d data gradients on the bf16 matrix cores writing bf16
+                               // (convt_dgrad_bf16.hip); 0 = the fp32-MFMA GEMM + cast pass of round 2
   int cae_conv_stats = 1;      // auto-encoder training: encoder blocks 2-3 and decoder blocks 1-3 take their BatchNorm statistics in the convolution's epilogue (0 = separate pass over z)
   int cae_bwd_fold = 1;        // auto-encoder training: the decoder's BatchNorm-backward apply pass writes dz patch-major and sums the ConvTranspose2d bias gradient (0 = three passes)
   int cae_enc4_wide = 1;       // auto-encoder training, bf16 mode: encoder block 4 forward in ONE 128-input-channel launch, its data gradient in two (0 = 64-channel launches chained through fp32 partial sums)
-                               // (convt_dgrad_bf16.hip); 0 = the fp32-MFMA GEMM + cast pass of round 2
   int cae_dec_fused = 1;       // auto-encoder eval forward, bf16 mode: decoder + squared error as ONE kernel (cae_dec_fused.hip); 0 = four launches
   int cnn1d_train_x3 = 1;      // CNN1D training convolutions (3 forward, 2 data gradients) on the matrix-core layer kernel (conv1d_x3_kernel) where
                                // its layout rules hold: 1 = three bf16 terms per operand (fp32-grade), 3 = two terms (bf16x3, ~1e-5: opt-in),
@@ -413,7 +417,6 @@ bool conv1d_x3_supports(const float* x, int64_t sb, int64_t sc, int64_t st, cons
 hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int Cout, int T,
                             int terms, hipStream_t s, int mode = 1, const AugCfg* aug = nullptr, const int* lens = nullptr);
 size_t conv1d_terms_pack_bytes(int cin, int cout, int terms);
-hipError_t launch_pack_conv1d_terms(const float* wf, void* wx, int cin, int cout, int terms, hipStream_t s);
 hipError_t launch_pack_conv1d_train_all(const float* w1, const float* w2, const float* w3, void* const* dst, int F, int terms, float* zero_bias,
                                         hipStream_t s);
 hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int64_t hsc, int64_t hst, float* partial,
@@ -431,14 +434,12 @@ hipError_t launch_cae_latent_export(const void* lat, int prec, float* out, int B
 // train_elem.hip / train_conv1.hip / wgrad_mfma.hip
 // the `mode` of launch_conv1_train and the `src` of launch_bn_bwd (described at their kernels)
 enum { C1M_STATS = 0, C1M_BWD_REDUCE = 1, C1M_WGRAD = 2, C1M_BWD_FUSED = 3, C1M_STATS_XX = 4 };
-enum { SRC_MEANT = 0, SRC_POOL = 1, SRC_DIRECT = 2, SRC_POOL22 = 3 };
+enum { SRC_POOL = 1, SRC_DIRECT = 2, SRC_POOL22 = 3 };
 hipError_t launch_bn_finalize(const float* partial, int nparts, int C, double n, float* mean, float* var, float* invstd,
                               float* running_mean, float* running_var, float momentum, hipStream_t s,
                               const float* shift = nullptr, int shift_stride = 0);   // sums of z - shift[c * shift_stride]
 hipError_t launch_reduce_partials(const float* partial, int nparts, int n, float scale, float* out, hipStream_t s,
                                   float* scratch = nullptr);
-hipError_t launch_reduce_partials_strided(const float* partial, int nparts, int stride, int off, int n, float* out,
-                                          hipStream_t s);
 hipError_t launch_bn_relu_pool_drop(int prec, const void* z, const BnApply& bn, void* out, int B, int H, int W, int C, const DropCfg& dc,
                                     hipStream_t s);
 int cl_stats_blocks(size_t npix, int* pix_per_block);
@@ -454,9 +455,9 @@ int bn_bwd_blocks(int B, int H, int W, int* pix_per_block);
 // SRC_DIRECT apply pass that writes dz patch-major (the pixel-unshuffled operand of a ConvTranspose2d(k2, s2) layer's gradient GEMMs,
 // Wh input columns) and leaves [nrec][C] records of its channel sums in bias_partial (train_elem.hip bn_bwd_apply_unshuffle_kernel)
 struct BnBwdFold { void* zp; int Wh; float* bias_partial; int nrec; };
-hipError_t launch_bn_bwd(int prec, int src, const void* z, const BnApply& bn, const float* demb, const void* da, float* partial, float* sums,
-                         void* dz, int B, int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch = nullptr,
-                         const BnSync* sync = nullptr, BnBwdFold* fold = nullptr);
+hipError_t launch_bn_bwd(int prec, int src, const void* z, const BnApply& bn, const void* da, float* partial, float* sums, void* dz, int B,
+                         int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch = nullptr, const BnSync* sync = nullptr,
+                         BnBwdFold* fold = nullptr);
 // sums[C][2] -> dbeta = S1, dgamma = S2 (C <= 256); the conv1 weight-gradient record [32][10] -> dW1[32][9], db1[32]
 hipError_t launch_split_sums(const float* sums, float* dgamma, float* dbeta, int C, hipStream_t s);
 hipError_t launch_split_c1(const float* rec, float* dw, float* db, hipStream_t s);
@@ -496,8 +497,6 @@ hipError_t launch_mse_fwd_bwd(const float* recon, const FeatView& v, float* part
 bool convt_dgrad_bf16_supports(int Cin, int Cout);
 hipError_t launch_convt_dgrad_bf16(const void* zp, const float* wq, void* wfrag, void* dx, long P, int Cin, int Cout, hipStream_t s);
 hipError_t launch_cast_from_f32(int prec, const float* src, void* dst, size_t n, hipStream_t s);
-hipError_t launch_reduce_wgrad_window(const float* partial, int nparts, int stride, int cin, int cout, int cin_total,
-                                      int ci_off, int co_off, float* dw, hipStream_t s);
 hipError_t launch_wgrad3x3_window(int prec, int cin, int cout, int cin_total, int cout_total, int ci_off, int co_off,
                                   const void* dz, const void* a, float* partial, float* dw, float* db, int B, int H,
                                   int W, int nwg, hipStream_t s);

@@ -235,7 +235,7 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
   {
     int ppb_;
     float* scratch2 = partial + (size_t)bn_bwd_blocks(B, pl.H1, F, &ppb_) * 64 * 2;
-    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL, ws + pl.z2, bn_apply(s2, l2), nullptr, ws + pl.da2, partial, sm2, ws + pl.dz2,
+    DFA_HIP_CHECK(ctx, launch_bn_bwd(prec, SRC_POOL, ws + pl.z2, bn_apply(s2, l2), ws + pl.da2, partial, sm2, ws + pl.dz2,
                                      B, pl.H1, F, 64, dc, s, scratch2, sync));
   }
   DFA_HIP_CHECK(ctx, launch_split_sums(sm2, g2.dgamma, g2.dbeta, 64, s));

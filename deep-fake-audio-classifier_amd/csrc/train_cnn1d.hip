@@ -4,16 +4,16 @@
 // (about 0.3 % of the 2-D CNN): these are LDS-tiled fp32 VALU kernels bound by reading the 231 KB input, not matrix-core
 // kernels.  Reductions are two-stage with a fixed order (deterministic).
 #include "dfa_internal.h"
+#include "bn_device.h"
 #include "rng.h"
 
 namespace dfa {
 
-// ---- RAGGED twins of the channel-major kernels below (dfa_cnn1d_forward_train_ragged / dfa_cnn1d_backward_ragged): the batch is
-// padded to T frames, utterance b owns frames [0, lens[b]) (lens = the device table the forward staged).  Sums and the time mean
-// run over an utterance's own frames in the uniform loops' order, the element-wise kernels write an exact zero at every padding
-// frame (the next convolution / weight gradient reads it as that utterance's zero padding).  Each of these kernels is one *_body function
-// instantiated twice: RAGGED = false behind the uniform kernel (name and arguments as before the twins existed), RAGGED = true behind
-// *_ragged_kernel, which takes the table.
+// ---- The channel-major kernels are templates on RAGGED (dfa_cnn1d_forward_train_ragged / dfa_cnn1d_backward_ragged run the
+// <true> instantiations): the batch is padded to T frames, utterance b owns frames [0, lens[b]) (lens = the device table the
+// forward staged; nullptr and unread in the uniform instantiation).  Sums and the time mean run over an utterance's own frames in
+// the uniform loops' order, the element-wise kernels write an exact zero at every padding frame (the next convolution / weight
+// gradient reads it as that utterance's zero padding).  The BatchNorm element math is bn_device.h's one-channel form.
 
 // ---- per-channel sum / sum of squares of z[B][C][T]: one block per (channel, batch chunk) -> partial[chunk][C][2]
 // shifted: the sums are those of z - k, k = the channel's first sample z[0][c][0] (the same for every chunk; bn_finalize_kernel adds
@@ -21,7 +21,7 @@ namespace dfa {
 // mean and small spread had mean^2 / var = 3000 and an invstd off by 1e-4; with the shift the ratio is that of one sample's
 // distance from the mean.  Off under synchronised BatchNorm: the ranks' first samples differ and the hook carries plain sums.
 template <bool RAGGED>
-__device__ __forceinline__ void cm_stats_body(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens, int shifted) {
+__global__ __launch_bounds__(256) void cm_stats_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens, int shifted) {
   __shared__ float r1[256], r2[256];
   const int c = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
   const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
@@ -40,12 +40,6 @@ __device__ __forceinline__ void cm_stats_body(const float* __restrict__ z, float
   }
   if (tid == 0) { partial[((size_t)ch * C + c) * 2] = r1[0]; partial[((size_t)ch * C + c) * 2 + 1] = r2[0]; }
 }
-__global__ __launch_bounds__(256) void cm_stats_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, int shifted) {
-  cm_stats_body<false>(z, partial, B, C, T, bchunk, nullptr, shifted);
-}
-__global__ __launch_bounds__(256) void cm_stats_ragged_kernel(const float* __restrict__ z, float* __restrict__ partial, int B, int C, int T, int bchunk, const int* __restrict__ lens, int shifted) {
-  cm_stats_body<true>(z, partial, B, C, T, bchunk, lens, shifted);
-}
 
 // (drop_scale1 of dlq_common.h is the same value picked by a select chain; this one reads an indexed array, the two compile differently)
 __device__ __forceinline__ float drop1(const DropCfg& dc, uint64_t idx) {
@@ -57,7 +51,7 @@ __device__ __forceinline__ float drop1(const DropCfg& dc, uint64_t idx) {
 
 // ---- forward: h = dropout(relu(bn(z)))  (elementwise, [B][C][T])
 template <bool RAGGED>
-__device__ __forceinline__ void cm_bn_relu_drop_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n, DropCfg dc, const int* __restrict__ lens) {
+__global__ void cm_bn_relu_drop_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n, DropCfg dc, const int* __restrict__ lens) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int c = (int)((i / T) % C);
@@ -65,41 +59,29 @@ __device__ __forceinline__ void cm_bn_relu_drop_body(const float* __restrict__ z
     const size_t bc = i / T;
     if ((int)(i - bc * T) >= lens[bc / C]) { h[i] = 0.f; return; }
   }
-  const float y = fmaf((z[i] - mean[c]) * invstd[c], gamma[c], beta[c]);
+  const float y = bn_y(bn_xhat(z[i], mean[c], invstd[c]), gamma[c], beta[c]);
   h[i] = fmaxf(y, 0.f) * drop1(dc, i);
-}
-__global__ void cm_bn_relu_drop_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n, DropCfg dc) {
-  cm_bn_relu_drop_body<false>(z, mean, invstd, gamma, beta, h, C, T, n, dc, nullptr);
-}
-__global__ void cm_bn_relu_drop_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ h, int C, int T, size_t n, DropCfg dc, const int* __restrict__ lens) {
-  cm_bn_relu_drop_body<true>(z, mean, invstd, gamma, beta, h, C, T, n, dc, lens);
 }
 
 // ---- forward: pooled[b][c] = mean_t relu(bn(z[b][c][t]))   (one wave per (b, c) row)
 template <bool RAGGED>
-__device__ __forceinline__ void cm_bn_relu_meant_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ pooled, int C, int T, int rows, const int* __restrict__ lens) {
+__global__ __launch_bounds__(256) void cm_bn_relu_meant_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ pooled, int C, int T, int rows, const int* __restrict__ lens) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int c = row % C;
-  const float sc = gamma[c] * invstd[c], sh = beta[c] - mean[c] * sc;
+  const BnFwd1 bn = bn_fwd1(mean[c], invstd[c], gamma[c], beta[c]);
   float s = 0.f;
   const int Tb = RAGGED ? lens[row / C] : T;
-  for (int t = lane; t < Tb; t += 64) s += fmaxf(fmaf(z[(size_t)row * T + t], sc, sh), 0.f);
+  for (int t = lane; t < Tb; t += 64) s += bn_relu(z[(size_t)row * T + t], bn.sc, bn.sh);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
   if (lane == 0) pooled[row] = s / (float)Tb;
 }
-__global__ __launch_bounds__(256) void cm_bn_relu_meant_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ pooled, int C, int T, int rows) {
-  cm_bn_relu_meant_body<false>(z, mean, invstd, gamma, beta, pooled, C, T, rows, nullptr);
-}
-__global__ __launch_bounds__(256) void cm_bn_relu_meant_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ pooled, int C, int T, int rows, const int* __restrict__ lens) {
-  cm_bn_relu_meant_body<true>(z, mean, invstd, gamma, beta, pooled, C, T, rows, lens);
-}
 
-// ---- BatchNorm1d backward, channel-major.  Upstream gradient of the BN output after the ReLU mask:
-//   SRC 0 (mean over T then Linear): dy = (y > 0) * dpooled[b][c] / T;   SRC 1 (dropout): dy = (y > 0) * dropscale * dh[b][c][t]
+// ---- BatchNorm1d backward, channel-major.  Upstream gradient g of the ReLU output:
+//   SRC 0 (mean over T then Linear): dpooled[b][c] / T_b;   SRC 1 (dropout): dropscale * dh[b][c][t]
 template <int SRC, bool RAGGED>
-__device__ __forceinline__ void cm_bn_bwd_reduce_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ up, float* __restrict__ partial, int B, int C, int T, int bchunk, DropCfg dc, const int* __restrict__ lens) {
+__global__ __launch_bounds__(256) void cm_bn_bwd_reduce_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ up, float* __restrict__ partial, int B, int C, int T, int bchunk, DropCfg dc, const int* __restrict__ lens) {
   __shared__ float r1[256], r2[256];
   const int c = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
   const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
@@ -109,11 +91,9 @@ __device__ __forceinline__ void cm_bn_bwd_reduce_body(const float* __restrict__ 
     const size_t base = ((size_t)b * C + c) * T;
     const int Tb = RAGGED ? lens[b] : T;
     for (int t = tid; t < Tb; t += 256) {
-      const float xh = (z[base + t] - mu) * is;
-      float g = (SRC == 0) ? up[(size_t)b * C + c] / (float)Tb : up[base + t] * drop1(dc, base + t);
-      const float dy = (fmaf(gm, xh, bt) > 0.f) ? g : 0.f;
-      s1 += dy;
-      s2 = fmaf(dy, xh, s2);
+      const float xh = bn_xhat(z[base + t], mu, is);
+      const float g = (SRC == 0) ? up[(size_t)b * C + c] / (float)Tb : up[base + t] * drop1(dc, base + t);
+      bn_accum(bn_gate(xh, gm, bt, g), xh, s1, s2);
     }
   }
   r1[tid] = s1; r2[tid] = s2;
@@ -124,17 +104,9 @@ __device__ __forceinline__ void cm_bn_bwd_reduce_body(const float* __restrict__ 
   }
   if (tid == 0) { partial[((size_t)ch * C + c) * 2] = r1[0]; partial[((size_t)ch * C + c) * 2 + 1] = r2[0]; }
 }
-template <int SRC>
-__global__ __launch_bounds__(256) void cm_bn_bwd_reduce_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ up, float* __restrict__ partial, int B, int C, int T, int bchunk, DropCfg dc) {
-  cm_bn_bwd_reduce_body<SRC, false>(z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc, nullptr);
-}
-template <int SRC>
-__global__ __launch_bounds__(256) void cm_bn_bwd_reduce_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ up, float* __restrict__ partial, int B, int C, int T, int bchunk, DropCfg dc, const int* __restrict__ lens) {
-  cm_bn_bwd_reduce_body<SRC, true>(z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc, lens);
-}
 
 template <int SRC, bool RAGGED>
-__device__ __forceinline__ void cm_bn_bwd_apply_body(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n, float inv_n, DropCfg dc, const int* __restrict__ lens) {
+__global__ void cm_bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n, float inv_n, DropCfg dc, const int* __restrict__ lens) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int c = (int)((i / T) % C);
@@ -144,78 +116,26 @@ __device__ __forceinline__ void cm_bn_bwd_apply_body(const float* __restrict__ z
     Tb = lens[bc / C];
     if ((int)(i - bc * T) >= Tb) { dz[i] = 0.f; return; }      // an exact zero: the padding frame is no frame of the batch
   }
-  const float xh = (z[i] - mean[c]) * invstd[c];
+  const float xh = bn_xhat(z[i], mean[c], invstd[c]);
   const float g = (SRC == 0) ? up[bc] / (float)Tb : up[i] * drop1(dc, i);
-  const float dy = (fmaf(gamma[c], xh, beta[c]) > 0.f) ? g : 0.f;
+  const float dy = bn_gate(xh, gamma[c], beta[c], g);
+  // bn_dz's terms, but the last one associated (xh * S2) * inv_n where bn_dz forms xh * (S2 * inv_n): one rounding apart, and this
+  // kernel's results are pinned bit for bit, so it keeps the order it has always had
   dz[i] = gamma[c] * invstd[c] * (dy - sums[2 * c] * inv_n - xh * sums[2 * c + 1] * inv_n);
 }
-template <int SRC>
-__global__ void cm_bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n, float inv_n, DropCfg dc) {
-  cm_bn_bwd_apply_body<SRC, false>(z, mean, invstd, gamma, beta, sums, up, dz, C, T, n, inv_n, dc, nullptr);
-}
-template <int SRC>
-__global__ void cm_bn_bwd_apply_ragged_kernel(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, const float* __restrict__ up, float* __restrict__ dz, int C, int T, size_t n, float inv_n, DropCfg dc, const int* __restrict__ lens) {
-  cm_bn_bwd_apply_body<SRC, true>(z, mean, invstd, gamma, beta, sums, up, dz, C, T, n, inv_n, dc, lens);
-}
 
-// ---- Conv1d weight gradient: dW[o][c][k] = sum_{b,t} dz[b][o][t] * h[b][c][t+k-1],  db[o] = sum dz.
-// Block = (16 output channels x 16 input channels) tile for one batch chunk; thread (o, c) keeps its 3 taps (+ bias
-// sum) in registers and walks time through LDS slabs of 64 frames.  partial[chunk][Cout][Cin][3] (+ [Cout] for db).
-// RAGGED (all three weight-gradient kernels, layer 1 of a ragged batch): h = x padded to T frames, utterance b owns [0, lens[b]); a
-// padding frame is never loaded (it may hold NaN / Inf, and dz = 0 there would not clear it) -- another bound in the load, in a
-// branch of its own so that the uniform and AUG instantiations keep their code.
+// ---- Conv1d weight gradient: dW[o][c][k] = sum_{b,t} dz[b][o][t] * h[b][c][t+k-1],  db[o] = sum dz, in slabs of W1D_TT frames;
+// partial[chunk][Cout][Cin][3] (+ [Cout] for db).  Both kernels take 32 output channels per block (dfa_cnn1d_set_params admits
+// base_channels = 32 only, so Cout is 32, 64 or 128).
+// RAGGED (layer 1 of a ragged batch): h = x padded to T frames, utterance b owns [0, lens[b]); a padding frame is never loaded
+// (it may hold NaN / Inf, and dz = 0 there would not clear it) -- another bound in the load, in a branch of its own so that the
+// uniform and AUG instantiations keep their code.
 constexpr int W1D_TT = 64;
-template <bool RAGGED = false>
-__global__ __launch_bounds__(256) void conv1d_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ h,
-                                                           int64_t hsb, int64_t hsc, int64_t hst,
-                                                           float* __restrict__ partial, int B, int Cin, int Cout, int T,
-                                                           int bchunk, const int* __restrict__ lens = nullptr) {
-  __shared__ float dzs[16][W1D_TT];
-  __shared__ float hs[16][W1D_TT + 2];
-  const int tid = threadIdx.x, ol = tid >> 4, cl = tid & 15;
-  const int o0 = blockIdx.x * 16, c0 = blockIdx.y * 16, ch = blockIdx.z;
-  const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, ab = 0.f;
-  for (int b = b0; b < b1; ++b) {
-    for (int t0 = 0; t0 < T; t0 += W1D_TT) {
-      __syncthreads();
-      for (int e = tid; e < 16 * W1D_TT; e += 256) {
-        const int oo = e / W1D_TT, tt = e - oo * W1D_TT;
-        dzs[oo][tt] = (t0 + tt < T) ? dz[((size_t)b * Cout + o0 + oo) * T + t0 + tt] : 0.f;
-      }
-      for (int e = tid; e < 16 * (W1D_TT + 2); e += 256) {
-        const int cc = e / (W1D_TT + 2), tt = e - cc * (W1D_TT + 2);
-        const int t = t0 - 1 + tt, ci = c0 + cc;
-        if constexpr (RAGGED)
-          hs[cc][tt] = (ci < Cin && t >= 0 && t < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
-        else
-        hs[cc][tt] = (ci < Cin && t >= 0 && t < T) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
-      }
-      __syncthreads();
-#pragma unroll 8
-      for (int tt = 0; tt < W1D_TT; ++tt) {
-        const float d = dzs[ol][tt];
-        a0 = fmaf(d, hs[cl][tt], a0);
-        a1 = fmaf(d, hs[cl][tt + 1], a1);
-        a2 = fmaf(d, hs[cl][tt + 2], a2);
-        ab += d;
-      }
-    }
-  }
-  const int o = o0 + ol, c = c0 + cl;
-  float* rec = partial + (size_t)ch * ((size_t)Cout * Cin * 3 + Cout);
-  if (c < Cin) {
-    rec[((size_t)o * Cin + c) * 3] = a0;
-    rec[((size_t)o * Cin + c) * 3 + 1] = a1;
-    rec[((size_t)o * Cin + c) * 3 + 2] = a2;
-  }
-  if (blockIdx.y == 0 && cl == 0) rec[(size_t)Cout * Cin * 3 + o] = ab;
-}
 
-// ---- the same weight gradient on the fp32 matrix cores: three GEMMs [32 o x t] . [t x 32 c] (one per tap) sharing the dz
+// ---- on the fp32 matrix cores: three GEMMs [32 o x t] . [t x 32 c] (one per tap) sharing the dz
 // operand; both operands are channel-major with t contiguous, i.e. K-contiguous rows, so v_mfma_f32_32x32x2_f32 takes
 // them straight from LDS tiles (lane = channel, k = frame parity).  One wave per (o tile, c tile, utterance chunk):
-// 96 MFMAs per 64-frame slab; the VALU kernel above spent 4 LDS reads on every 3 FMAs and ran at 128-512 blocks.
+// 96 MFMAs per 64-frame slab.
 // AUG (layer 1 only): h = x read through the armed train-time augmentation, as the forward read it (conv1d.hip)
 template <bool AUG, bool RAGGED = false>
 __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __restrict__ dz, const float* __restrict__ h,
@@ -433,51 +353,38 @@ int cm_chunks(int B) { return B < kCmChunks ? B : kCmChunks; }
 
 hipError_t launch_cm_stats(const float* z, float* partial, int B, int C, int T, hipStream_t s, const int* lens, bool shifted) {
   const int nch = cm_chunks(B), bchunk = (B + nch - 1) / nch;
-  if (lens) hipLaunchKernelGGL(cm_stats_ragged_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, lens, (int)shifted);
-  else hipLaunchKernelGGL(cm_stats_kernel, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, (int)shifted);
+  hipLaunchKernelGGL(lens ? cm_stats_kernel<true> : cm_stats_kernel<false>, dim3(C, nch), dim3(256), 0, s, z, partial, B, C, T, bchunk, lens, (int)shifted);
   return hipGetLastError();
 }
 hipError_t launch_cm_bn_relu_drop(const float* z, const BnApply& bn, float* h, int B, int C, int T, const DropCfg& dc, hipStream_t s,
                                   const int* lens) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t n = (size_t)B * C * T;
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (lens) hipLaunchKernelGGL(cm_bn_relu_drop_ragged_kernel, grid, dim3(256), 0, s, z, mean, invstd, gamma, beta, h, C, T, n, dc, lens);
-  else hipLaunchKernelGGL(cm_bn_relu_drop_kernel, grid, dim3(256), 0, s, z, mean, invstd, gamma, beta, h, C, T, n, dc);
+  hipLaunchKernelGGL(lens ? cm_bn_relu_drop_kernel<true> : cm_bn_relu_drop_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z,
+                     bn.mean, bn.invstd, bn.gamma, bn.beta, h, C, T, n, dc, lens);
   return hipGetLastError();
 }
 hipError_t launch_cm_bn_relu_meant(const float* z, const BnApply& bn, float* pooled, int B, int C, int T, hipStream_t s, const int* lens) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const int rows = B * C;
-  if (lens) hipLaunchKernelGGL(cm_bn_relu_meant_ragged_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, z, mean, invstd, gamma, beta, pooled, C, T, rows, lens);
-  else hipLaunchKernelGGL(cm_bn_relu_meant_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, z, mean, invstd, gamma, beta, pooled, C, T, rows);
+  hipLaunchKernelGGL(lens ? cm_bn_relu_meant_kernel<true> : cm_bn_relu_meant_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, s, z, bn.mean,
+                     bn.invstd, bn.gamma, bn.beta, pooled, C, T, rows, lens);
   return hipGetLastError();
 }
-// lens != null: the ragged twins, n_valid = the batch's frame count (sum of the lengths)
+// lens != null: the ragged instantiations, n_valid = the batch's frame count (sum of the lengths)
 hipError_t launch_cm_bn_bwd(int src, const float* z, const BnApply& bn, const float* up, float* partial, float* sums, float* dz, int B, int C,
                             int T, const DropCfg& dc, hipStream_t s, const BnSync* sync, const int* lens, double n_valid) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const int nch = cm_chunks(B), bchunk = (B + nch - 1) / nch;
   const size_t n = (size_t)B * C * T;
-  float inv_n = (float)(1.0 / (lens ? n_valid : (double)B * T));
-  const dim3 rgrid(C, nch), agrid((unsigned)((n + 255) / 256));
-  auto reduce = [&](auto kern) { hipLaunchKernelGGL(kern, rgrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc); };
-  auto reduce_r = [&](auto kern) { hipLaunchKernelGGL(kern, rgrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, up, partial, B, C, T, bchunk, dc, lens); };
-  if (src == 0) { if (lens) reduce_r(cm_bn_bwd_reduce_ragged_kernel<0>); else reduce(cm_bn_bwd_reduce_kernel<0>); }
-  else { if (lens) reduce_r(cm_bn_bwd_reduce_ragged_kernel<1>); else reduce(cm_bn_bwd_reduce_kernel<1>); }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = launch_reduce_partials(partial, nch, C * 2, 1.0f, sums, s, nullptr);
-  if (e != hipSuccess) return e;
+  const auto reduce = src == 0 ? (lens ? cm_bn_bwd_reduce_kernel<0, true> : cm_bn_bwd_reduce_kernel<0, false>)
+                               : (lens ? cm_bn_bwd_reduce_kernel<1, true> : cm_bn_bwd_reduce_kernel<1, false>);
+  const auto apply = src == 0 ? (lens ? cm_bn_bwd_apply_kernel<0, true> : cm_bn_bwd_apply_kernel<0, false>)
+                              : (lens ? cm_bn_bwd_apply_kernel<1, true> : cm_bn_bwd_apply_kernel<1, false>);
+  hipLaunchKernelGGL(reduce, dim3(C, nch), dim3(256), 0, s, z, bn.mean, bn.invstd, bn.gamma, bn.beta, up, partial, B, C, T, bchunk, dc, lens);
   const float* sums_a;
-  float isc;
-  e = bn_sync_sums(sync, sums, C * 2, s, &sums_a, &isc);          // synchronised BatchNorm: global sums, global count
+  float inv_n = (float)(1.0 / (lens ? n_valid : (double)B * T));
+  const hipError_t e = bn_bwd_sums(partial, nch, C, sums, nullptr, sync, s, &sums_a, &inv_n);
   if (e != hipSuccess) return e;
-  inv_n *= isc;
-  auto apply = [&](auto kern) { hipLaunchKernelGGL(kern, agrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, sums_a, up, dz, C, T, n, inv_n, dc); };
-  auto apply_r = [&](auto kern) { hipLaunchKernelGGL(kern, agrid, dim3(256), 0, s, z, mean, invstd, gamma, beta, sums_a, up, dz, C, T, n, inv_n, dc, lens); };
-  if (src == 0) { if (lens) apply_r(cm_bn_bwd_apply_ragged_kernel<0>); else apply(cm_bn_bwd_apply_kernel<0>); }
-  else { if (lens) apply_r(cm_bn_bwd_apply_ragged_kernel<1>); else apply(cm_bn_bwd_apply_kernel<1>); }
+  hipLaunchKernelGGL(apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, bn.mean, bn.invstd, bn.gamma, bn.beta, sums_a, up, dz, C, T, n,
+                     inv_n, dc, lens);
   return hipGetLastError();
 }
 // partial: conv1d_wgrad_chunks(B) * (Cout*Cin*3 + Cout) floats
@@ -485,28 +392,15 @@ int conv1d_wgrad_chunks(int B) { return B < 256 ? B : 256; }
 hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int64_t hsc, int64_t hst, float* partial,
                                float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug, int x3, const int* lens) {
   const int nch = conv1d_wgrad_chunks(B), bchunk = (B + nch - 1) / nch;
-  if (lens && aug && aug->on) return hipErrorInvalidValue;     // a time roll has no per-utterance meaning
-  if (lens) {                      // ragged layer 1: h = the padded x, bounded per utterance in the loads
-    if (x3 && Cout % 32 == 0)
-      hipLaunchKernelGGL((conv1d_wgrad_x3_kernel<false, true>), dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, lens);
-    else if (Cout % 32 == 0)
-      hipLaunchKernelGGL((conv1d_wgrad_mfma_kernel<false, true>), dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, lens);
-    else
-      hipLaunchKernelGGL(conv1d_wgrad_kernel<true>, dim3(Cout / 16, (Cin + 15) / 16, nch), dim3(256), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, lens);
-  } else
-  if (x3 && Cout % 32 == 0) {      // three-term bf16 matrix-core form (fp32-grade sums)
-    const dim3 grid(Cout / 32, (Cin + 31) / 32, nch);
-    if (aug && aug->on)
-      hipLaunchKernelGGL(conv1d_wgrad_x3_kernel<true>, grid, dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, *aug, nullptr);
-    else
-      hipLaunchKernelGGL(conv1d_wgrad_x3_kernel<false>, grid, dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, nullptr);
-  } else if (aug && aug->on) {
-    if (Cout % 32 != 0) return hipErrorInvalidValue;   // the folded form exists for the MFMA kernel only (layer 1: Cout = 32)
-    hipLaunchKernelGGL(conv1d_wgrad_mfma_kernel<true>, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, *aug, nullptr);
-  } else if (Cout % 32 == 0)
-    hipLaunchKernelGGL(conv1d_wgrad_mfma_kernel<false>, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, AugCfg{}, nullptr);
-  else
-    hipLaunchKernelGGL(conv1d_wgrad_kernel<false>, dim3(Cout / 16, (Cin + 15) / 16, nch), dim3(256), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk, nullptr);
+  const bool aug_on = aug && aug->on;
+  if (Cout % 32 != 0) return hipErrorInvalidValue;     // both kernels tile 32 output channels
+  if (lens && aug_on) return hipErrorInvalidValue;     // a time roll has no per-utterance meaning
+  // x3: the three-term bf16 matrix-core form (fp32-grade sums), else the fp32 matrix cores; lens: ragged layer 1, h = the padded x,
+  // bounded per utterance in the loads
+  const auto kern = x3 ? (lens ? conv1d_wgrad_x3_kernel<false, true> : aug_on ? conv1d_wgrad_x3_kernel<true> : conv1d_wgrad_x3_kernel<false>)
+                       : (lens ? conv1d_wgrad_mfma_kernel<false, true> : aug_on ? conv1d_wgrad_mfma_kernel<true> : conv1d_wgrad_mfma_kernel<false>);
+  hipLaunchKernelGGL(kern, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk,
+                     aug_on ? *aug : AugCfg{}, lens);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int n = Cout * Cin * 3;

@@ -1,9 +1,12 @@
-// train_elem.hip -- train-mode passes of the 2-D CNN that are not convolutions (src/train.py:71-76 through
+// train_elem.hip -- train-mode passes of the 2-D CNN and the auto-encoder that are not convolutions (src/train.py:71-76 through
 // src/model.py:16-19,22-25,28-29,37-39 and torch autograd): BatchNorm with batch statistics (forward + backward),
-// ReLU, AvgPool2d((2,1)), Dropout, mean over T, Linear backward, BCE-with-logits on smoothed labels, AdamW.
+// ReLU, AvgPool2d((2,1)) / AvgPool2d(2), Dropout, mean over T, Linear backward, BCE-with-logits on smoothed labels, AdamW.
 // All tensors are channels-last [B][H][W][C]; every pass is HBM-bound and moves 8 channels (16-32 bytes) per lane.
 // Reductions are two-stage with a fixed order (per-block partials in fp32, final sum in fp64): deterministic.
+// The BatchNorm element math, the per-lane channel terms, the thread map and the block epilogue of the blocked passes are
+// bn_device.h's; a kernel here is its loads, its upstream gradient and its loop shape (pixels in flight, unroll).
 #include "dfa_internal.h"
+#include "bn_device.h"
 #include "rng.h"
 
 namespace dfa {
@@ -66,27 +69,6 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
   }
 }
 
-// out[j] = sum_k partial[k*stride + off + j]
-__global__ void reduce_partials_strided_kernel(const float* __restrict__ partial, int nparts, int stride, int off, int n,
-                                               float* __restrict__ out) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  double s = 0.0;
-  for (int k = 0; k < nparts; ++k) s += (double)partial[(size_t)k * stride + off + j];
-  out[j] = (float)s;
-}
-
-// weight-gradient window: out[(co_off+co)][ci_off+ci][tap] = sum_k partial[k*stride + (co*cin + ci)*9 + tap]
-__global__ void reduce_wgrad_window_kernel(const float* __restrict__ partial, int nparts, int stride, int cin, int cout,
-                                           int cin_total, int ci_off, int co_off, float* __restrict__ dw) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= cout * cin * 9) return;
-  double s = 0.0;
-  for (int k = 0; k < nparts; ++k) s += (double)partial[(size_t)k * stride + j];
-  const int tap = j % 9, ci = (j / 9) % cin, co = j / (9 * cin);
-  dw[((size_t)(co_off + co) * cin_total + ci_off + ci) * 9 + tap] = (float)s;
-}
-
 // whole weight-gradient record in one launch: elements [0, cout*cin*9) -> the dw window, [cout*cin*9, +cout) -> db.
 // 64 elements x 4 groups of partial records per block; fp64 sums, combined in a fixed order.
 __global__ __launch_bounds__(256) void reduce_wgrad_record_kernel(const float* __restrict__ partial, int nparts, int stride,
@@ -144,12 +126,9 @@ __global__ __launch_bounds__(256) void bn_relu_poolh2_drop_kernel(const T* __res
   ld8<T>(z + ((((size_t)b * H + 2 * to) * W + f) * C + cg * 8), z0);
   ld8<T>(z + ((((size_t)b * H + 2 * to + 1) * W + f) * C + cg * 8), z1);
   drop_scale8(dc, pix * C + cg * 8, ds);
+  const BnFwd8 bn = bn_fwd8(bn_load8(mean, invstd, gamma, beta, cg * 8));
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    const float sc = gamma[c] * invstd[c], sh = beta[c] - mean[c] * sc;
-    o[j] = 0.5f * (fmaxf(fmaf(z0[j], sc, sh), 0.f) + fmaxf(fmaf(z1[j], sc, sh), 0.f)) * ds[j];
-  }
+  for (int j = 0; j < 8; ++j) o[j] = 0.5f * (bn.relu(j, z0[j]) + bn.relu(j, z1[j])) * ds[j];
   st8<T>(out + pix * C + cg * 8, o);
 }
 
@@ -158,17 +137,17 @@ template <typename T>
 __global__ __launch_bounds__(256) void cl_stats_kernel(const T* __restrict__ z, float* __restrict__ partial, size_t npix,
                                                        int C, int pix_per_block) {
   extern __shared__ float red[];  // [PL][C][2]
-  const int CG = C >> 3, PL = 256 / CG;
-  const int tid = threadIdx.x, cg = tid % CG, pl = tid / CG;
-  const size_t p0 = (size_t)blockIdx.x * pix_per_block;
-  const size_t p1 = (p0 + pix_per_block < npix) ? p0 + pix_per_block : npix;
+  const BnLane ln = bn_lane(C);
+  const BnRange rg = bn_range(npix, pix_per_block);
+  const int PL = ln.PL, cg = ln.cg, pl = ln.pl;
+  const size_t p1 = rg.p1;
   float s1[8], s2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
   if (pl < PL) {
     // four pixels per trip: four independent 16-byte loads in flight per lane (one at a time left this pass at 0.8 TB/s: a
     // 4096-pixel block per workgroup gave 55-900 workgroups of serial single loads)
-    size_t p = p0 + pl;
+    size_t p = rg.p0 + pl;
     for (; p + 3 * (size_t)PL < p1; p += 4 * (size_t)PL) {
       float v[4][8];
 #pragma unroll
@@ -185,16 +164,8 @@ __global__ __launch_bounds__(256) void cl_stats_kernel(const T* __restrict__ z, 
       for (int j = 0; j < 8; ++j) { s1[j] += v[j]; s2[j] = fmaf(v[j], v[j], s2[j]); }
     }
   }
-  if (pl < PL) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { red[(pl * C + cg * 8 + j) * 2] = s1[j]; red[(pl * C + cg * 8 + j) * 2 + 1] = s2[j]; }
-  }
-  __syncthreads();
-  for (int e = tid; e < C * 2; e += 256) {
-    float s = 0.f;
-    for (int q = 0; q < PL; ++q) s += red[q * C * 2 + e];
-    partial[(size_t)blockIdx.x * C * 2 + e] = s;
-  }
+  if (pl < PL) bn_lds_put2(red, ln, C, s1, s2);
+  bn_lds_to_record<2>(red, PL, C, partial);
 }
 
 // ---- forward: BN(batch stats) + ReLU [+ AvgPool2d(2)]     z[B][H][W][C] -> out[B][H/P][W/P][C], P = 1 or 2
@@ -225,8 +196,8 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const T* __restrict__
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int c = cg * 8 + j;
-        const float sc = gamma[c] * invstd[c], sh = beta[c] - mean[c] * sc;
-        o[j] += fmaxf(fmaf(v[j], sc, sh), 0.f);
+        const BnFwd1 bn = bn_fwd1(mean[c], invstd[c], gamma[c], beta[c]);       // (loop-invariant: loaded once, behind the first z)
+        o[j] += bn_relu(v[j], bn.sc, bn.sh);
       }
     }
   if (P == 2) {
@@ -254,27 +225,22 @@ __global__ __launch_bounds__(256) void bn_relu_meant_kernel(const T* __restrict_
   if (i >= total) return;
   const int cg = (int)(i % CG);
   const int f = (int)((i / CG) % W), b = (int)(i / ((size_t)CG * W));
-  float sc[8], sh[8], acc[8], mu[8], is[8], gm[8], bt[8], cn[8], sx[8];
+  const Bn8 bn = bn_load8(mean, invstd, gamma, beta, cg * 8);
+  const BnFwd8 fw = bn_fwd8(bn);
+  float acc[8], cn[8], sx[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; gm[j] = gamma[c]; bt[j] = beta[c];
-    sc[j] = gm[j] * is[j];
-    sh[j] = bt[j] - mu[j] * sc[j];
-    acc[j] = 0.f; cn[j] = 0.f; sx[j] = 0.f;
-  }
+  for (int j = 0; j < 8; ++j) { acc[j] = 0.f; cn[j] = 0.f; sx[j] = 0.f; }
 #pragma unroll 4      // four 16-byte loads in flight per thread (the sums stay in t order)
   for (int t = 0; t < H; ++t) {
     float v[8];
     ld8<T>(z + ((((size_t)b * H + t) * W + f) * C + cg * 8), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      acc[j] += fmaxf(fmaf(v[j], sc[j], sh[j]), 0.f);
-      if (MSUM) {
-        const float xh = (v[j] - mu[j]) * is[j];
-        const bool on = fmaf(gm[j], xh, bt[j]) > 0.f;          // bn_bwd_apply_kernel's mask, bit for bit
-        cn[j] += on ? 1.f : 0.f;
-        sx[j] += on ? xh : 0.f;
+      acc[j] += fw.relu(j, v[j]);
+      if (MSUM) {       // the backward's gate on g = 1 and g = xh: n and sx under the mask the apply pass uses
+        const float xh = bn.xhat(j, v[j]);
+        cn[j] += bn.gate(j, xh, 1.f);
+        sx[j] += bn.gate(j, xh, xh);
       }
     }
   }
@@ -295,15 +261,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_saved_kernel(const float* _
                                                                   float* __restrict__ partial, size_t npos, int C, float inv_h,
                                                                   int pos_per_block) {
   extern __shared__ float red[];  // [PL][C][2]
-  const int CG = C >> 3, PL = 256 / CG;
-  const int tid = threadIdx.x, cg = tid % CG, pl = tid / CG;
-  const size_t p0 = (size_t)blockIdx.x * pos_per_block;
-  const size_t p1 = (p0 + pos_per_block < npos) ? p0 + pos_per_block : npos;
+  const BnLane ln = bn_lane(C);
+  const BnRange rg = bn_range(npos, pos_per_block);
+  const int PL = ln.PL, cg = ln.cg, pl = ln.pl;
   float s1[8], s2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
   if (pl < PL)
-    for (size_t p = p0 + pl; p < p1; p += PL) {
+    for (size_t p = rg.p0 + pl; p < rg.p1; p += PL) {
       float d[8];
       ld8<float>(demb + p * C + cg * 8, d);
       const float* m = msum + (p * C + cg * 8) * 2;
@@ -315,16 +280,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_saved_kernel(const float* _
         s1[j + 1] = fmaf(g1, q.z, s1[j + 1]); s2[j + 1] = fmaf(g1, q.w, s2[j + 1]);
       }
     }
-  if (pl < PL) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { red[(pl * C + cg * 8 + j) * 2] = s1[j]; red[(pl * C + cg * 8 + j) * 2 + 1] = s2[j]; }
-  }
-  __syncthreads();
-  for (int e = tid; e < C * 2; e += 256) {
-    float s = 0.f;
-    for (int q = 0; q < PL; ++q) s += red[q * C * 2 + e];
-    partial[(size_t)blockIdx.x * C * 2 + e] = s;
-  }
+  if (pl < PL) bn_lds_put2(red, ln, C, s1, s2);
+  bn_lds_to_record<2>(red, PL, C, partial);
 }
 
 // ---- backward of Linear(K,1): demb[b][j] = dlogit[b]*w[j];  dw[j] = sum_b dlogit[b]*emb[b][j];  db = sum_b dlogit[b]
@@ -363,22 +320,14 @@ __global__ __launch_bounds__(256) void linear_bwd_kernel(const float* __restrict
     dw[j] = ((red[0][jl] + red[1][jl]) + (red[2][jl] + red[3][jl])) + ((red[4][jl] + red[5][jl]) + (red[6][jl] + red[7][jl]));
 }
 
-// ---- BatchNorm backward.  Upstream gradient dy of the BN *output* y = gamma*xhat+beta after the ReLU mask:
-//   SRC_MEANT: dy = (y > 0) * demb[b][c][f] / H                                   (block 3: mean over T then Linear)
-//   SRC_POOL : dy = (y > 0) * 0.5 * dropscale * da[b][t/2][f][c], rows t >= 2*(H/2) get 0   (blocks 1, 2)
-// reduce: S1[c] = sum dy, S2[c] = sum dy*xhat  (= dbeta, dgamma);  apply: dz = gamma*invstd*(dy - S1/N - xhat*S2/N).
-//   SRC_DIRECT: dy = (y > 0) * da[b][t][f][c]                                   (CAE decoder: ReLU feeds the next layer)
-//   SRC_POOL22: dy = (y > 0) * 0.25 * da[b][t/2][f/2][c], rows/cols beyond 2*(H/2), 2*(W/2) get 0   (CAE encoder)
-
+// ---- BatchNorm backward (element math: bn_device.h).  Upstream gradient g of the ReLU output, by source:
+//   SRC_POOL  : 0.5 * dropscale * da[b][t/2][f][c], rows t >= 2*(H/2) get 0                   (CNN2D blocks 1, 2)
+//   SRC_DIRECT: da[b][t][f][c]                                                    (CAE decoder: ReLU feeds the next layer)
+//   SRC_POOL22: 0.25 * da[b][t/2][f/2][c], rows/cols beyond 2*(H/2), 2*(W/2) get 0            (CAE encoder)
+// (Block 3 of the CNN2D, mean over T then Linear, has kernels of its own: bn_bwd_reduce_saved_kernel, bn_bwd_apply_meant_kernel.)
 template <typename T, int SRC>
-__device__ __forceinline__ void upstream8(const float* demb, const T* da, const DropCfg& dc, int b, int t, int f, int cg,
-                                          int H, int W, int C, float inv_h, float* g) {
-  if (SRC == SRC_MEANT) {
-    float d[8];
-    ld8<float>(demb + ((size_t)b * W + f) * C + cg * 8, d);   // demb is [B][W][C] (linear_bwd_kernel with tc > 0)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] = d[j] * inv_h;
-  } else if (SRC == SRC_DIRECT) {
+__device__ __forceinline__ void upstream8(const T* da, const DropCfg& dc, int b, int t, int f, int cg, int H, int W, int C, float* g) {
+  if (SRC == SRC_DIRECT) {
     ld8<T>(da + (((size_t)b * H + t) * W + f) * C + cg * 8, g);
   } else if (SRC == SRC_POOL22) {
     // a last odd row / column was not pooled: zero gradient.  The load is unconditional (clamped address) and the factor selects --
@@ -410,44 +359,30 @@ template <typename T, int SRC>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ z, const float* __restrict__ mean,
                                                             const float* __restrict__ invstd,
                                                             const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta,
-                                                            const float* __restrict__ demb, const T* __restrict__ da,
+                                                            const float* __restrict__ beta, const T* __restrict__ da,
                                                             float* __restrict__ partial, int B, int H, int W, int C,
                                                             DropCfg dc, int pix_per_block) {
   extern __shared__ float red[];  // [PL][C][2]
-  const int CG = C >> 3, PL = 256 / CG;
-  const int tid = threadIdx.x, cg = tid % CG, pl = tid / CG;
-  const size_t npix = (size_t)B * H * W;
-  const size_t p0 = (size_t)blockIdx.x * pix_per_block;
-  const size_t p1 = (p0 + pix_per_block < npix) ? p0 + pix_per_block : npix;
-  float mu[8], is[8], gm[8], bt[8], s1[8], s2[8];
+  const BnLane ln = bn_lane(C);
+  const BnRange rg = bn_range((size_t)B * H * W, pix_per_block);
+  const int PL = ln.PL, cg = ln.cg;
+  const Bn8 bn = bn_load8(mean, invstd, gamma, beta, cg * 8);
+  float s1[8], s2[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; gm[j] = gamma[c]; bt[j] = beta[c];
-    s1[j] = 0.f; s2[j] = 0.f;
-  }
-  const float inv_h = 1.0f / (float)H;
+  for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
   // Pixel index arithmetic in 32 bits (npix < 2^31, launcher-checked: the 64-bit divisions by W and H cost more than the rest of
   // the loop body) and four pixels per trip, all eight loads requested before the first is used (one dependent pair at a time
-  // held this pass at ~1 TB/s)
-  auto body = [&](const float (&v)[8], const float (&g)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = (v[j] - mu[j]) * is[j];
-      const float dy = (fmaf(gm[j], xh, bt[j]) > 0.f) ? g[j] : 0.f;
-      s1[j] += dy;
-      s2[j] = fmaf(dy, xh, s2[j]);
-    }
-  };
+  // held this pass at ~1 TB/s).  (`body` is a lambda over array references on purpose: called directly, bn_bwd_accum8 compiles
+  // this kernel to other code -- the single-pixel tail gets packed adds, 16-39 fewer VGPRs.  Not measured, so not taken here.)
+  auto body = [&](const float (&v)[8], const float (&g)[8]) { bn_bwd_accum8(bn, v, g, s1, s2); };
   auto fetch = [&](unsigned p, float (&v)[8], float (&g)[8]) {
     const unsigned f = p % (unsigned)W, bt_ = p / (unsigned)W;
     const unsigned t = bt_ % (unsigned)H, b = bt_ / (unsigned)H;
     ld8<T>(z + (size_t)p * C + cg * 8, v);
-    upstream8<T, SRC>(demb, da, dc, (int)b, (int)t, (int)f, cg, H, W, C, inv_h, g);
+    upstream8<T, SRC>(da, dc, (int)b, (int)t, (int)f, cg, H, W, C, g);
   };
-  unsigned p = (unsigned)p0 + pl;
-  const unsigned pe = (unsigned)p1;
+  unsigned p = (unsigned)rg.p0 + ln.pl;
+  const unsigned pe = (unsigned)rg.p1;
   for (; p + 3u * PL < pe; p += 4u * PL) {
     float v[4][8], g[4][8];
 #pragma unroll
@@ -460,14 +395,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
     fetch(p, v, g);
     body(v, g);
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { red[(pl * C + cg * 8 + j) * 2] = s1[j]; red[(pl * C + cg * 8 + j) * 2 + 1] = s2[j]; }
-  __syncthreads();
-  for (int e = tid; e < C * 2; e += 256) {
-    float s = 0.f;
-    for (int q = 0; q < PL; ++q) s += red[q * C * 2 + e];
-    partial[(size_t)blockIdx.x * C * 2 + e] = s;
-  }
+  bn_lds_put2(red, ln, C, s1, s2);
+  bn_lds_to_record<2>(red, PL, C, partial);
 }
 
 template <typename T, int SRC>
@@ -475,40 +404,25 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                                                            const float* __restrict__ invstd,
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ sums,
-                                                           const float* __restrict__ demb, const T* __restrict__ da,
-                                                           T* __restrict__ dz, int B, int H, int W, int C, DropCfg dc,
-                                                           float inv_n, int pix_per_block) {
+                                                           const T* __restrict__ da, T* __restrict__ dz, int B, int H, int W,
+                                                           int C, DropCfg dc, float inv_n, int pix_per_block) {
   // thread = (channel octet cg, pixel lane pl): the per-channel coefficients are loaded once and reused over the block's
   // pixels (one thread per 16-byte chunk spent 48 parameter loads on every data load)
-  const int CG = C >> 3, PL = 256 / CG;
-  const int tid = threadIdx.x, cg = tid % CG, pl = tid / CG;
-  const size_t npix = (size_t)B * H * W;
-  const size_t p0 = (size_t)blockIdx.x * pix_per_block;
-  const size_t p1 = (p0 + pix_per_block < npix) ? p0 + pix_per_block : npix;
-  float mu[8], is[8], gm[8], bt[8], k0[8], k1[8], k2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; gm[j] = gamma[c]; bt[j] = beta[c];
-    k0[j] = gm[j] * is[j];
-    k1[j] = sums[2 * c] * inv_n;
-    k2[j] = sums[2 * c + 1] * inv_n;
-  }
-  const float inv_h = 1.0f / (float)H;
+  const BnLane ln = bn_lane(C);
+  const BnRange rg = bn_range((size_t)B * H * W, pix_per_block);
+  const int PL = ln.PL, cg = ln.cg;
+  Bn8 bn;
+  BnCoef8 k;
+  bn_load8(mean, invstd, gamma, beta, sums, cg * 8, inv_n, bn, k);
 #pragma unroll 4
-  for (unsigned p = (unsigned)p0 + pl; p < (unsigned)p1; p += PL) {          // (32-bit pixel arithmetic, see the reduce kernel)
+  for (unsigned p = (unsigned)rg.p0 + ln.pl; p < (unsigned)rg.p1; p += PL) {          // (32-bit pixel arithmetic, see the reduce kernel)
     const int f = (int)(p % (unsigned)W);
     const unsigned bt_ = p / (unsigned)W;
     const int t = (int)(bt_ % (unsigned)H), b = (int)(bt_ / (unsigned)H);
     float v[8], g[8], o[8];
     ld8<T>(z + (size_t)p * C + cg * 8, v);
-    upstream8<T, SRC>(demb, da, dc, b, t, f, cg, H, W, C, inv_h, g);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = (v[j] - mu[j]) * is[j];
-      const float dy = (fmaf(gm[j], xh, bt[j]) > 0.f) ? g[j] : 0.f;
-      o[j] = k0[j] * (dy - k1[j] - xh * k2[j]);
-    }
+    upstream8<T, SRC>(da, dc, b, t, f, cg, H, W, C, g);
+    bn_bwd_dz8(bn, k, v, g, o);
     st8<T>(dz + (size_t)p * C + cg * 8, o);
   }
 }
@@ -517,7 +431,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 // consumers used to do in passes of their own: dz is written straight in the PATCH-MAJOR order the layer's gradient GEMMs read
 // (zp[(b, t/2, f/2)][q = 2 (t&1) + (f&1)][C], `pixel_unshuffle_kernel`; a trailing output_padding column has no input pixel and is
 // not stored) and its per-channel sums -- the convolution's bias gradient, every output pixel included -- leave as one [C] record
-// per workgroup (summed as stored: after the rounding to T).  Same per-element formulas as bn_bwd_apply_kernel<T, SRC_DIRECT>.
+// per workgroup (summed as stored: after the rounding to T).
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_unshuffle_kernel(const T* __restrict__ z, const float* __restrict__ mean,
                                                                      const float* __restrict__ invstd,
@@ -527,54 +441,38 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_unshuffle_kernel(const T* __
                                                                      float* __restrict__ bias_partial, int B, int H, int W, int C,
                                                                      int Wh, float inv_n, int pix_per_block) {
   extern __shared__ float red[];  // [PL][C]
-  const int CG = C >> 3, PL = 256 / CG;
-  const int tid = threadIdx.x, cg = tid % CG, pl = tid / CG;
-  const size_t npix = (size_t)B * H * W;
-  const size_t p0 = (size_t)blockIdx.x * pix_per_block;
-  const size_t p1 = (p0 + pix_per_block < npix) ? p0 + pix_per_block : npix;
-  float mu[8], is[8], gm[8], bt[8], k0[8], k1[8], k2[8], bs[8];
+  const BnLane ln = bn_lane(C);
+  const BnRange rg = bn_range((size_t)B * H * W, pix_per_block);
+  const int PL = ln.PL, cg = ln.cg;
+  Bn8 bn;
+  BnCoef8 k;
+  bn_load8(mean, invstd, gamma, beta, sums, cg * 8, inv_n, bn, k);
+  float bs[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; gm[j] = gamma[c]; bt[j] = beta[c];
-    k0[j] = gm[j] * is[j];
-    k1[j] = sums[2 * c] * inv_n;
-    k2[j] = sums[2 * c + 1] * inv_n;
-    bs[j] = 0.f;
-  }
+  for (int j = 0; j < 8; ++j) bs[j] = 0.f;
   const unsigned Hh = (unsigned)H >> 1;
 #pragma unroll 4
-  for (unsigned p = (unsigned)p0 + pl; p < (unsigned)p1; p += PL) {
+  for (unsigned p = (unsigned)rg.p0 + ln.pl; p < (unsigned)rg.p1; p += PL) {
     const unsigned f = p % (unsigned)W, bt_ = p / (unsigned)W;
     const unsigned t = bt_ % (unsigned)H, b = bt_ / (unsigned)H;
     float v[8], g[8], o[8];
     ld8<T>(z + (size_t)p * C + cg * 8, v);
     ld8<T>(da + (size_t)p * C + cg * 8, g);
+    bn_bwd_dz8(bn, k, v, g, o);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = (v[j] - mu[j]) * is[j];
-      const float dy = (fmaf(gm[j], xh, bt[j]) > 0.f) ? g[j] : 0.f;
-      o[j] = k0[j] * (dy - k1[j] - xh * k2[j]);
-      bs[j] += (sizeof(T) == 2) ? bf16_to_float(float_to_bf16(o[j])) : o[j];
-    }
+    for (int j = 0; j < 8; ++j) bs[j] += (sizeof(T) == 2) ? bf16_to_float(float_to_bf16(o[j])) : o[j];
     if ((f >> 1) < (unsigned)Wh) {
       const size_t dst = ((((size_t)b * Hh + (t >> 1)) * Wh + (f >> 1)) * 4 + ((t & 1u) << 1) + (f & 1u)) * C + cg * 8;
       st8<T>(zp + dst, o);
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[pl * C + cg * 8 + j] = bs[j];
-  __syncthreads();
-  for (int e = tid; e < C; e += 256) {
-    float s = 0.f;
-    for (int q = 0; q < PL; ++q) s += red[q * C + e];
-    bias_partial[(size_t)blockIdx.x * C + e] = s;
-  }
+  bn_lds_put1(red, ln, C, bs);
+  bn_lds_to_record<1>(red, PL, C, bias_partial);
 }
 
 // ---- SRC_POOL reduction and apply pass on ROW PAIRS (H even): a thread takes a pooled pixel (to, f) x 8 channels -- ONE upstream load and ONE dropout
-// draw serve the two rows 2*to, 2*to+1 of z that were averaged into it; several pooled pixels in flight per thread.  Same
-// per-element formulas as the generic kernel (which ran one dependent 16-byte load at a time: 3.0 TB/s).
+// draw serve the two rows 2*to, 2*to+1 of z that were averaged into it; several pooled pixels in flight per thread.
+// (The generic kernel ran one dependent 16-byte load at a time: 3.0 TB/s.)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_pool_kernel(const T* __restrict__ z, const float* __restrict__ mean,
                                                                  const float* __restrict__ invstd,
@@ -583,20 +481,16 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_pool_kernel(const T* __rest
                                                                  float* __restrict__ partial, int B, int H, int W, int C,
                                                                  DropCfg dc, int pp_per_block) {
   extern __shared__ float red[];  // [PL][C][2]
-  const int CG = C >> 3, PL = 256 / CG, Ho = H >> 1;
-  const int tid = threadIdx.x, cg = tid % CG, pl = tid / CG;
-  const size_t npp = (size_t)B * Ho * W;
-  const size_t p0 = (size_t)blockIdx.x * pp_per_block;
-  const size_t p1 = (p0 + pp_per_block < npp) ? p0 + pp_per_block : npp;
-  float mu[8], is[8], gm[8], bt[8], s1[8], s2[8];
+  const int Ho = H >> 1;
+  const BnLane ln = bn_lane(C);
+  const BnRange rg = bn_range((size_t)B * Ho * W, pp_per_block);
+  const int PL = ln.PL, cg = ln.cg;
+  const Bn8 bn = bn_load8(mean, invstd, gamma, beta, cg * 8);
+  float s1[8], s2[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; gm[j] = gamma[c]; bt[j] = beta[c];
-    s1[j] = 0.f; s2[j] = 0.f;
-  }
+  for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
 #pragma unroll 2
-  for (size_t pp = p0 + pl; pp < p1; pp += PL) {
+  for (size_t pp = rg.p0 + ln.pl; pp < rg.p1; pp += PL) {
     const int f = (int)(pp % W);
     const size_t bt_ = pp / W;
     const int to = (int)(bt_ % Ho), b = (int)(bt_ / Ho);
@@ -609,23 +503,13 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_pool_kernel(const T* __rest
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float g = 0.5f * ds[j] * d[j];
-      const float xh0 = (v0[j] - mu[j]) * is[j], xh1 = (v1[j] - mu[j]) * is[j];
-      const float dy0 = (fmaf(gm[j], xh0, bt[j]) > 0.f) ? g : 0.f;
-      const float dy1 = (fmaf(gm[j], xh1, bt[j]) > 0.f) ? g : 0.f;
-      s1[j] += dy0;
-      s2[j] = fmaf(dy0, xh0, s2[j]);
-      s1[j] += dy1;
-      s2[j] = fmaf(dy1, xh1, s2[j]);
+      const float xh0 = bn.xhat(j, v0[j]), xh1 = bn.xhat(j, v1[j]);
+      bn_accum(bn.gate(j, xh0, g), xh0, s1[j], s2[j]);
+      bn_accum(bn.gate(j, xh1, g), xh1, s1[j], s2[j]);
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { red[(pl * C + cg * 8 + j) * 2] = s1[j]; red[(pl * C + cg * 8 + j) * 2 + 1] = s2[j]; }
-  __syncthreads();
-  for (int e = tid; e < C * 2; e += 256) {
-    float s = 0.f;
-    for (int q = 0; q < PL; ++q) s += red[q * C * 2 + e];
-    partial[(size_t)blockIdx.x * C * 2 + e] = s;
-  }
+  bn_lds_put2(red, ln, C, s1, s2);
+  bn_lds_to_record<2>(red, PL, C, partial);
 }
 
 template <typename T>
@@ -635,22 +519,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const T* __restr
                                                                 const float* __restrict__ beta, const float* __restrict__ sums,
                                                                 const T* __restrict__ da, T* __restrict__ dz, int B, int H,
                                                                 int W, int C, DropCfg dc, float inv_n, int pp_per_block) {
-  const int CG = C >> 3, PL = 256 / CG, Ho = H >> 1;
-  const int tid = threadIdx.x, cg = tid % CG, pl = tid / CG;
-  const size_t npp = (size_t)B * Ho * W;
-  const size_t p0 = (size_t)blockIdx.x * pp_per_block;
-  const size_t p1 = (p0 + pp_per_block < npp) ? p0 + pp_per_block : npp;
-  float mu[8], is[8], gm[8], bt[8], k0[8], k1[8], k2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; gm[j] = gamma[c]; bt[j] = beta[c];
-    k0[j] = gm[j] * is[j];
-    k1[j] = sums[2 * c] * inv_n;
-    k2[j] = sums[2 * c + 1] * inv_n;
-  }
+  const int Ho = H >> 1;
+  const BnLane ln = bn_lane(C);
+  const BnRange rg = bn_range((size_t)B * Ho * W, pp_per_block);
+  const int PL = ln.PL, cg = ln.cg;
+  Bn8 bn;
+  BnCoef8 k;
+  bn_load8(mean, invstd, gamma, beta, sums, cg * 8, inv_n, bn, k);
 #pragma unroll 2
-  for (size_t pp = p0 + pl; pp < p1; pp += PL) {
+  for (size_t pp = rg.p0 + ln.pl; pp < rg.p1; pp += PL) {
     const int f = (int)(pp % W);
     const size_t bt_ = pp / W;
     const int to = (int)(bt_ % Ho), b = (int)(bt_ / Ho);
@@ -663,20 +540,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const T* __restr
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float g = 0.5f * ds[j] * d[j];
-      const float xh0 = (v0[j] - mu[j]) * is[j], xh1 = (v1[j] - mu[j]) * is[j];
-      const float dy0 = (fmaf(gm[j], xh0, bt[j]) > 0.f) ? g : 0.f;
-      const float dy1 = (fmaf(gm[j], xh1, bt[j]) > 0.f) ? g : 0.f;
-      o0[j] = k0[j] * (dy0 - k1[j] - xh0 * k2[j]);
-      o1[j] = k0[j] * (dy1 - k1[j] - xh1 * k2[j]);
+      const float xh0 = bn.xhat(j, v0[j]), xh1 = bn.xhat(j, v1[j]);
+      const float dy0 = bn.gate(j, xh0, g), dy1 = bn.gate(j, xh1, g);
+      o0[j] = k.dz(j, dy0, xh0);
+      o1[j] = k.dz(j, dy1, xh1);
     }
     st8<T>(dz + zp * C + cg * 8, o0);
     st8<T>(dz + (zp + W) * C + cg * 8, o1);
   }
 }
 
-// ---- SRC_MEANT apply walking down T: a thread owns (b, f, 8 channels); the upstream gradient g = demb / H does not depend on
-// t, so it is loaded once (the generic kernel re-read 32 bytes of demb beside every 16 bytes of z) and there is no index
-// arithmetic in the loop; eight row loads in flight per thread.  Same per-element formulas as bn_bwd_apply_kernel.
+// ---- block 3 apply pass walking down T: a thread owns (b, f, 8 channels); the upstream gradient g = demb / H does not depend on
+// t, so it is loaded once and there is no index arithmetic in the loop; eight row loads in flight per thread.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_meant_kernel(const T* __restrict__ z, const float* __restrict__ mean,
                                                                  const float* __restrict__ invstd,
@@ -690,29 +565,20 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_meant_kernel(const T* __rest
   if (i >= total) return;
   const int cg = (int)(i % CG);
   const int f = (int)((i / CG) % W), b = (int)(i / ((size_t)CG * W));
-  float mu[8], is[8], gm[8], bt[8], k0[8], k1[8], k2[8], g[8];
-  ld8<float>(demb + ((size_t)b * W + f) * C + cg * 8, g);
+  float g[8];
+  ld8<float>(demb + ((size_t)b * W + f) * C + cg * 8, g);      // demb is [B][W][C] (linear_bwd_kernel with tc > 0)
   const float inv_h = 1.0f / (float)H;
+  Bn8 bn;
+  BnCoef8 k;
+  bn_load8(mean, invstd, gamma, beta, sums, cg * 8, inv_n, bn, k);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c]; is[j] = invstd[c]; gm[j] = gamma[c]; bt[j] = beta[c];
-    k0[j] = gm[j] * is[j];
-    k1[j] = sums[2 * c] * inv_n;
-    k2[j] = sums[2 * c + 1] * inv_n;
-    g[j] = g[j] * inv_h;
-  }
+  for (int j = 0; j < 8; ++j) g[j] = g[j] * inv_h;
   const size_t base = (((size_t)b * H) * W + f) * C + cg * 8, stride = (size_t)W * C;
 #pragma unroll 8
   for (int t = 0; t < H; ++t) {
     float v[8], o[8];
     ld8<T>(z + base + t * stride, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = (v[j] - mu[j]) * is[j];
-      const float dy = (fmaf(gm[j], xh, bt[j]) > 0.f) ? g[j] : 0.f;
-      o[j] = k0[j] * (dy - k1[j] - xh * k2[j]);
-    }
+    bn_bwd_dz8(bn, k, v, g, o);
     st8<T>(dz + base + t * stride, o);
   }
 }
@@ -777,21 +643,6 @@ hipError_t launch_reduce_partials(const float* partial, int nparts, int n, float
   return hipGetLastError();
 }
 
-hipError_t launch_reduce_partials_strided(const float* partial, int nparts, int stride, int off, int n, float* out,
-                                          hipStream_t s) {
-  hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, s, partial, nparts, stride, off,
-                     n, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_reduce_wgrad_window(const float* partial, int nparts, int stride, int cin, int cout, int cin_total,
-                                      int ci_off, int co_off, float* dw, hipStream_t s) {
-  const int n = cout * cin * 9;
-  hipLaunchKernelGGL(reduce_wgrad_window_kernel, dim3((n + 255) / 256), dim3(256), 0, s, partial, nparts, stride, cin, cout,
-                     cin_total, ci_off, co_off, dw);
-  return hipGetLastError();
-}
-
 hipError_t launch_reduce_wgrad_record(const float* partial, int nparts, int stride, int cin, int cout, int cin_total,
                                       int ci_off, int co_off, float* dw, float* db, hipStream_t s, int perm) {
   const int total = cout * cin * 9 + cout;
@@ -800,15 +651,21 @@ hipError_t launch_reduce_wgrad_record(const float* partial, int nparts, int stri
   return hipGetLastError();
 }
 
+// the element type behind `prec`, handed to a generic lambda as the type of its argument
+template <typename F>
+static void by_prec(int prec, F f) {
+  if (prec == DFA_PREC_BF16) f(bf16_t{});
+  else f(float{});
+}
+
 hipError_t launch_bn_relu_pool_drop(int prec, const void* z, const BnApply& bn, void* out, int B, int H, int W, int C, const DropCfg& dc,
                                     hipStream_t s) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t total = (size_t)B * (H / 2) * W * (C / 8);
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (prec == DFA_PREC_BF16)
-    hipLaunchKernelGGL(bn_relu_poolh2_drop_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)z, mean, invstd, gamma, beta, (bf16_t*)out, B, H, W, C, dc);
-  else
-    hipLaunchKernelGGL(bn_relu_poolh2_drop_kernel<float>, grid, block, 0, s, (const float*)z, mean, invstd, gamma, beta, (float*)out, B, H, W, C, dc);
+  by_prec(prec, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(bn_relu_poolh2_drop_kernel<T>, grid, block, 0, s, (const T*)z, bn.mean, bn.invstd, bn.gamma, bn.beta, (T*)out, B, H, W, C, dc);
+  });
   return hipGetLastError();
 }
 
@@ -822,72 +679,33 @@ hipError_t launch_cl_stats(int prec, const void* z, float* partial, size_t npix,
   const int nblk = cl_stats_blocks(npix, &ppb);
   const int PL = 256 / (C / 8);
   const size_t lds = (size_t)PL * C * 2 * sizeof(float);
-  if (prec == DFA_PREC_BF16)
-    hipLaunchKernelGGL(cl_stats_kernel<bf16_t>, dim3(nblk), dim3(256), lds, s, (const bf16_t*)z, partial, npix, C, ppb);
-  else
-    hipLaunchKernelGGL(cl_stats_kernel<float>, dim3(nblk), dim3(256), lds, s, (const float*)z, partial, npix, C, ppb);
+  by_prec(prec, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(cl_stats_kernel<T>, dim3(nblk), dim3(256), lds, s, (const T*)z, partial, npix, C, ppb);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_bn_relu_pool(int prec, int pool, const void* z, const BnApply& bn, void* out, int B, int H, int W, int C, hipStream_t s) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t total = (size_t)B * (H / pool) * (W / pool) * (C / 8);
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (prec == DFA_PREC_BF16) {
-    if (pool == 2) hipLaunchKernelGGL((bn_relu_pool_kernel<bf16_t, 2>), grid, block, 0, s, (const bf16_t*)z, mean, invstd, gamma, beta, (bf16_t*)out, B, H, W, C);
-    else hipLaunchKernelGGL((bn_relu_pool_kernel<bf16_t, 1>), grid, block, 0, s, (const bf16_t*)z, mean, invstd, gamma, beta, (bf16_t*)out, B, H, W, C);
-  } else {
-    if (pool == 2) hipLaunchKernelGGL((bn_relu_pool_kernel<float, 2>), grid, block, 0, s, (const float*)z, mean, invstd, gamma, beta, (float*)out, B, H, W, C);
-    else hipLaunchKernelGGL((bn_relu_pool_kernel<float, 1>), grid, block, 0, s, (const float*)z, mean, invstd, gamma, beta, (float*)out, B, H, W, C);
-  }
+  by_prec(prec, [&](auto tag) {
+    using T = decltype(tag);
+    auto kern = pool == 2 ? bn_relu_pool_kernel<T, 2> : bn_relu_pool_kernel<T, 1>;
+    hipLaunchKernelGGL(kern, grid, block, 0, s, (const T*)z, bn.mean, bn.invstd, bn.gamma, bn.beta, (T*)out, B, H, W, C);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_bn_relu_meant(int prec, const void* z, const BnApply& bn, float* emb, int B, int H, int W, int C, hipStream_t s,
                                 float* msum) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
   const size_t total = (size_t)B * W * (C / 8);
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define DFA_BRM(TT, MS) hipLaunchKernelGGL((bn_relu_meant_kernel<TT, MS>), grid, block, 0, s, (const TT*)z, mean, invstd, gamma, beta, emb, msum, B, H, W, C)
-  if (prec == DFA_PREC_BF16) { if (msum) DFA_BRM(bf16_t, true); else DFA_BRM(bf16_t, false); }
-  else { if (msum) DFA_BRM(float, true); else DFA_BRM(float, false); }
-#undef DFA_BRM
-  return hipGetLastError();
-}
-
-// BatchNorm backward of the mean-over-T layer with the reduction taken from the forward's saved sums (msum[B][W][C][2]):
-// reduce (3 floats per position) -> fixed-order second stage -> the usual apply pass (z -> dz).
-hipError_t launch_bn_bwd_meant_saved(int prec, const void* z, const BnApply& bn, const float* demb, const float* msum, float* partial,
-                                     float* sums, void* dz, int B, int H, int W, int C, hipStream_t s, const BnSync* sync) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
-  const size_t npos = (size_t)B * W;
-  const int PL = 256 / (C / 8);
-  const int ppb = 8 * PL;
-  const int nblk = (int)((npos + ppb - 1) / ppb);
-  const size_t lds = (size_t)PL * C * 2 * sizeof(float);
-  hipLaunchKernelGGL(bn_bwd_reduce_saved_kernel, dim3(nblk), dim3(256), lds, s, demb, msum, partial, npos, C, 1.0f / (float)H, ppb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = launch_reduce_partials(partial, nblk, C * 2, 1.0f, sums, s, nullptr);
-  if (e != hipSuccess) return e;
-  const float* sums_a;
-  float isc;
-  e = bn_sync_sums(sync, sums, C * 2, s, &sums_a, &isc);          // synchronised BatchNorm: global sums, global count
-  if (e != hipSuccess) return e;
-  dim3 g2((unsigned)(((size_t)B * W * (C / 8) + 255) / 256));
-  const float inv_n = (float)(1.0 / ((double)B * H * W)) * isc;
-  if (prec == DFA_PREC_BF16)
-    hipLaunchKernelGGL(bn_bwd_apply_meant_kernel<bf16_t>, g2, dim3(256), 0, s, (const bf16_t*)z, mean, invstd, gamma, beta, sums_a,
-                       demb, (bf16_t*)dz, B, H, W, C, inv_n);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_meant_kernel<float>, g2, dim3(256), 0, s, (const float*)z, mean, invstd, gamma, beta, sums_a,
-                       demb, (float*)dz, B, H, W, C, inv_n);
-  return hipGetLastError();
-}
-
-hipError_t launch_linear_bwd(const float* dlogits, const float* w, const float* emb, float* demb, float* dw, float* db,
-                             int B, int K, hipStream_t s, int tc, int tw) {
-  hipLaunchKernelGGL(linear_bwd_kernel, dim3((K + 31) / 32), dim3(256), 0, s, dlogits, w, emb, demb, dw, db, B, K, tc, tw);
+  by_prec(prec, [&](auto tag) {
+    using T = decltype(tag);
+    auto kern = msum ? bn_relu_meant_kernel<T, true> : bn_relu_meant_kernel<T, false>;
+    hipLaunchKernelGGL(kern, grid, block, 0, s, (const T*)z, bn.mean, bn.invstd, bn.gamma, bn.beta, emb, msum, B, H, W, C);
+  });
   return hipGetLastError();
 }
 
@@ -903,6 +721,50 @@ hipError_t bn_sync_sums(const BnSync* sy, const float* sums, int count, hipStrea
   return hipSuccess;
 }
 
+// Second stage of every BatchNorm backward, after the reduce kernel wrote partial[nrec][C][2]: its launch status, the fixed-order
+// sum of the records into sums[C][2] (S1 = dbeta, S2 = dgamma; scratch: launch_reduce_partials'), the all-reduce under
+// synchronised BatchNorm.  Out: the sums the apply pass reads (the global ones then) and *inv_n scaled by 1 / world.
+hipError_t bn_bwd_sums(const float* partial, int nrec, int C, float* sums, float* scratch, const BnSync* sync, hipStream_t s,
+                       const float** sums_apply, float* inv_n) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_reduce_partials(partial, nrec, C * 2, 1.0f, sums, s, scratch);
+  if (e != hipSuccess) return e;
+  float isc;
+  e = bn_sync_sums(sync, sums, C * 2, s, sums_apply, &isc);
+  *inv_n *= isc;
+  return e;
+}
+
+// BatchNorm backward of the mean-over-T layer with the reduction taken from the forward's saved sums (msum[B][W][C][2]):
+// reduce (3 floats per position) -> fixed-order second stage -> the apply pass (z -> dz).
+hipError_t launch_bn_bwd_meant_saved(int prec, const void* z, const BnApply& bn, const float* demb, const float* msum, float* partial,
+                                     float* sums, void* dz, int B, int H, int W, int C, hipStream_t s, const BnSync* sync) {
+  const size_t npos = (size_t)B * W;
+  const int PL = 256 / (C / 8);
+  const int ppb = 8 * PL;
+  const int nblk = (int)((npos + ppb - 1) / ppb);
+  const size_t lds = (size_t)PL * C * 2 * sizeof(float);
+  hipLaunchKernelGGL(bn_bwd_reduce_saved_kernel, dim3(nblk), dim3(256), lds, s, demb, msum, partial, npos, C, 1.0f / (float)H, ppb);
+  const float* sums_a;
+  float inv_n = (float)(1.0 / ((double)B * H * W));
+  const hipError_t e = bn_bwd_sums(partial, nblk, C, sums, nullptr, sync, s, &sums_a, &inv_n);
+  if (e != hipSuccess) return e;
+  dim3 g2((unsigned)(((size_t)B * W * (C / 8) + 255) / 256));
+  by_prec(prec, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(bn_bwd_apply_meant_kernel<T>, g2, dim3(256), 0, s, (const T*)z, bn.mean, bn.invstd, bn.gamma, bn.beta, sums_a, demb,
+                       (T*)dz, B, H, W, C, inv_n);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_linear_bwd(const float* dlogits, const float* w, const float* emb, float* demb, float* dw, float* db,
+                             int B, int K, hipStream_t s, int tc, int tw) {
+  hipLaunchKernelGGL(linear_bwd_kernel, dim3((K + 31) / 32), dim3(256), 0, s, dlogits, w, emb, demb, dw, db, B, K, tc, tw);
+  return hipGetLastError();
+}
+
 int bn_bwd_blocks(int B, int H, int W, int* pix_per_block) {
   const size_t npix = (size_t)B * H * W;
   int ppb = 4096;
@@ -910,81 +772,94 @@ int bn_bwd_blocks(int B, int H, int W, int* pix_per_block) {
   return (int)((npix + ppb - 1) / ppb);
 }
 
-// sums: [C][2] (S1 = dbeta, S2 = dgamma) written by the reduce stage; dz may alias nothing.  scratch: 64 * C * 2 floats for the
-// two-level reduction of the block records (nullptr: one level)
-hipError_t launch_bn_bwd(int prec, int src, const void* z, const BnApply& bn, const float* demb, const void* da, float* partial, float* sums,
-                         void* dz, int B, int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch, const BnSync* sync,
-                         BnBwdFold* fold) {
-  const float *mean = bn.mean, *invstd = bn.invstd, *gamma = bn.gamma, *beta = bn.beta;
+// What launch_bn_bwd's two paths share (its arguments, typed)
+template <typename T>
+struct BnBwdArgs {
+  const T *z, *da;
+  T* dz;
+  const BnApply& bn;
+  float *partial, *sums, *scratch;
+  int B, H, W, C;
+  const DropCfg& dc;
+  const BnSync* sync;
+  BnBwdFold* fold;
+  hipStream_t s;
+};
+
+// generic path: one pixel per (thread, trip)
+template <typename T, int SRC>
+static hipError_t bn_bwd_generic(const BnBwdArgs<T>& a) {
+  const int B = a.B, H = a.H, W = a.W, C = a.C;
+  const size_t npix = (size_t)B * H * W;
   int ppb;
   int nblk = bn_bwd_blocks(B, H, W, &ppb);
-  if (fold && (src != SRC_DIRECT || (H & 1) || 2 * fold->Wh > W || !fold->zp || !fold->bias_partial)) return hipErrorInvalidValue;
-  if ((size_t)B * H * W >= ((size_t)1 << 31)) return hipErrorInvalidValue;     // 32-bit pixel indices in the generic kernels
-  if (src == SRC_DIRECT || src == SRC_POOL22) {   // the auto-encoder's layers (55-900 blocks of 4096 pixels did not fill the chip)
+  if (SRC == SRC_DIRECT || SRC == SRC_POOL22) {   // the auto-encoder's layers (55-900 blocks of 4096 pixels did not fill the chip)
     ppb = 1024;
-    nblk = (int)(((size_t)B * H * W + ppb - 1) / ppb);
+    nblk = (int)((npix + ppb - 1) / ppb);
   }
   const int PL = 256 / (C / 8);
   const size_t lds = (size_t)PL * C * 2 * sizeof(float);
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, SRC>), dim3(nblk), dim3(256), lds, a.s, a.z, a.bn.mean, a.bn.invstd, a.bn.gamma, a.bn.beta, a.da,
+                     a.partial, B, H, W, C, a.dc, ppb);
+  const float* sums_a;
+  float inv_n = (float)(1.0 / ((double)B * H * W));
+  const hipError_t e = bn_bwd_sums(a.partial, nblk, C, a.sums, a.scratch, a.sync, a.s, &sums_a, &inv_n);
+  if (e != hipSuccess) return e;
   const int ppb2 = 16 * PL;                       // pixels per block of the apply pass: 16 chunks per thread
-  dim3 g2((unsigned)(((size_t)B * H * W + ppb2 - 1) / ppb2));
-  const float inv_n = (float)(1.0 / ((double)B * H * W));
-  const float* sums_a = sums;      // what the apply stage reads: the all-reduced copy under synchronised BatchNorm
-  float isc = 1.0f;
-#define DFA_BN_BWD_POOL(TT)                                                                                            \
-  do {                                                                                                                 \
-    const int ppp = ppb / 2;                                                                                           \
-    const int nb = (int)(((size_t)B * (H / 2) * W + ppp - 1) / ppp);   /* <= nblk: partial has room */                  \
-    hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<TT>, dim3(nb), dim3(256), lds, s, (const TT*)z, mean, invstd, gamma, beta, \
-                       (const TT*)da, partial, B, H, W, C, dc, ppp);                                                   \
-    hipError_t e = hipGetLastError();                                                                                  \
-    if (e != hipSuccess) return e;                                                                                     \
-    e = launch_reduce_partials(partial, nb, C * 2, 1.0f, sums, s, scratch);                                            \
-    if (e != hipSuccess) return e;                                                                                     \
-    e = bn_sync_sums(sync, sums, C * 2, s, &sums_a, &isc);                                                             \
-    if (e != hipSuccess) return e;                                                                                     \
-    if (dz) {   /* 0.435 vs 0.475 ms for the generic kernel at [256,160,180,64] */                                      \
-      const int ppp2 = 8 * PL;                                                                                         \
-      dim3 g3((unsigned)(((size_t)B * (H / 2) * W + ppp2 - 1) / ppp2));                                                \
-      hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<TT>, g3, dim3(256), 0, s, (const TT*)z, mean, invstd, gamma, beta, sums_a, \
-                         (const TT*)da, (TT*)dz, B, H, W, C, dc, inv_n * isc, ppp2);                                   \
-    }                                                                                                                  \
-  } while (0)
-#define DFA_BN_BWD(TT, SRC)                                                                                            \
-  do {                                                                                                                 \
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<TT, SRC>), dim3(nblk), dim3(256), lds, s, (const TT*)z, mean, invstd, gamma, \
-                       beta, demb, (const TT*)da, partial, B, H, W, C, dc, ppb);                                       \
-    hipError_t e = hipGetLastError();                                                                                  \
-    if (e != hipSuccess) return e;                                                                                     \
-    e = launch_reduce_partials(partial, nblk, C * 2, 1.0f, sums, s, scratch);                                                     \
-    if (e != hipSuccess) return e;                                                                                     \
-    e = bn_sync_sums(sync, sums, C * 2, s, &sums_a, &isc);                                                             \
-    if (e != hipSuccess) return e;                                                                                     \
-    if (fold) {                                                                                                        \
-      fold->nrec = (int)g2.x;                                                                                          \
-      hipLaunchKernelGGL((bn_bwd_apply_unshuffle_kernel<TT>), g2, dim3(256), lds / 2, s, (const TT*)z, mean, invstd, gamma, beta, \
-                         sums_a, (const TT*)da, (TT*)fold->zp, fold->bias_partial, B, H, W, C, fold->Wh, inv_n * isc, ppb2);  \
-    } else if (dz)                                                                                                     \
-      hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, SRC>), g2, dim3(256), 0, s, (const TT*)z, mean, invstd, gamma, beta, sums_a, \
-                         demb, (const TT*)da, (TT*)dz, B, H, W, C, dc, inv_n * isc, ppb2);                                  \
-  } while (0)
-  if (prec == DFA_PREC_BF16) {
-    if (src == SRC_MEANT) DFA_BN_BWD(bf16_t, SRC_MEANT);
-    else if (src == SRC_POOL && !(H & 1)) DFA_BN_BWD_POOL(bf16_t);
-    else if (src == SRC_POOL) DFA_BN_BWD(bf16_t, SRC_POOL);
-    else if (src == SRC_DIRECT) DFA_BN_BWD(bf16_t, SRC_DIRECT);
-    else DFA_BN_BWD(bf16_t, SRC_POOL22);
-  } else {
-    if (src == SRC_MEANT) DFA_BN_BWD(float, SRC_MEANT);
-    else if (src == SRC_POOL && !(H & 1)) DFA_BN_BWD_POOL(float);
-    else if (src == SRC_POOL) DFA_BN_BWD(float, SRC_POOL);
-    else if (src == SRC_DIRECT) DFA_BN_BWD(float, SRC_DIRECT);
-    else DFA_BN_BWD(float, SRC_POOL22);
-  }
-#undef DFA_BN_BWD
-#undef DFA_BN_BWD_POOL
+  dim3 g2((unsigned)((npix + ppb2 - 1) / ppb2));
+  if (a.fold) {
+    a.fold->nrec = (int)g2.x;
+    hipLaunchKernelGGL((bn_bwd_apply_unshuffle_kernel<T>), g2, dim3(256), lds / 2, a.s, a.z, a.bn.mean, a.bn.invstd, a.bn.gamma, a.bn.beta, sums_a,
+                       a.da, (T*)a.fold->zp, a.fold->bias_partial, B, H, W, C, a.fold->Wh, inv_n, ppb2);
+  } else if (a.dz)
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, SRC>), g2, dim3(256), 0, a.s, a.z, a.bn.mean, a.bn.invstd, a.bn.gamma, a.bn.beta, sums_a, a.da,
+                       a.dz, B, H, W, C, a.dc, inv_n, ppb2);
   return hipGetLastError();
 }
+
+// SRC_POOL with H even: row pairs
+template <typename T>
+static hipError_t bn_bwd_pool(const BnBwdArgs<T>& a) {
+  const int B = a.B, H = a.H, W = a.W, C = a.C;
+  const size_t npp = (size_t)B * (H / 2) * W;
+  const int PL = 256 / (C / 8);
+  const size_t lds = (size_t)PL * C * 2 * sizeof(float);
+  int ppb;
+  bn_bwd_blocks(B, H, W, &ppb);
+  const int ppp = ppb / 2;
+  const int nb = (int)((npp + ppp - 1) / ppp);   // <= bn_bwd_blocks: partial has room
+  hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<T>, dim3(nb), dim3(256), lds, a.s, a.z, a.bn.mean, a.bn.invstd, a.bn.gamma, a.bn.beta, a.da,
+                     a.partial, B, H, W, C, a.dc, ppp);
+  const float* sums_a;
+  float inv_n = (float)(1.0 / ((double)B * H * W));
+  const hipError_t e = bn_bwd_sums(a.partial, nb, C, a.sums, a.scratch, a.sync, a.s, &sums_a, &inv_n);
+  if (e != hipSuccess) return e;
+  if (a.dz) {   // 0.435 vs 0.475 ms for the generic kernel at [256,160,180,64]
+    const int ppp2 = 8 * PL;
+    dim3 g3((unsigned)((npp + ppp2 - 1) / ppp2));
+    hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<T>, g3, dim3(256), 0, a.s, a.z, a.bn.mean, a.bn.invstd, a.bn.gamma, a.bn.beta, sums_a, a.da, a.dz,
+                       B, H, W, C, a.dc, inv_n, ppp2);
+  }
+  return hipGetLastError();
+}
+
+// sums: [C][2] (S1 = dbeta, S2 = dgamma) written by the reduce stage; dz may alias nothing.  scratch: 64 * C * 2 floats for the
+// two-level reduction of the block records (nullptr: one level)
+hipError_t launch_bn_bwd(int prec, int src, const void* z, const BnApply& bn, const void* da, float* partial, float* sums, void* dz, int B,
+                         int H, int W, int C, const DropCfg& dc, hipStream_t s, float* scratch, const BnSync* sync, BnBwdFold* fold) {
+  if (fold && (src != SRC_DIRECT || (H & 1) || 2 * fold->Wh > W || !fold->zp || !fold->bias_partial)) return hipErrorInvalidValue;
+  if ((size_t)B * H * W >= ((size_t)1 << 31)) return hipErrorInvalidValue;     // 32-bit pixel indices in the generic kernels
+  hipError_t e = hipErrorInvalidValue;
+  by_prec(prec, [&](auto tag) {
+    using T = decltype(tag);
+    const BnBwdArgs<T> a{(const T*)z, (const T*)da, (T*)dz, bn, partial, sums, scratch, B, H, W, C, dc, sync, fold, s};
+    if (src == SRC_POOL) e = (H & 1) ? bn_bwd_generic<T, SRC_POOL>(a) : bn_bwd_pool<T>(a);
+    else if (src == SRC_DIRECT) e = bn_bwd_generic<T, SRC_DIRECT>(a);
+    else if (src == SRC_POOL22) e = bn_bwd_generic<T, SRC_POOL22>(a);
+  });
+  return e;
+}
+
 
 // dgamma = S2, dbeta = S1 from sums[C][2]
 __global__ void split_sums_kernel(const float* __restrict__ sums, float* __restrict__ dgamma, float* __restrict__ dbeta,

@@ -1,5 +1,5 @@
 """A/B two builds of the library (separate processes, alternating): DFA_LIB=<file name under lib/>; DFA_AB_MODE=train times the
-bf16 training step instead of the eval forward, DFA_AB_MODE=train1d the CNN1D's (fp32) uniform training step, DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
+bf16 training step instead of the eval forward, DFA_AB_MODE=train1d the CNN1D's (fp32) uniform training step, DFA_AB_MODE=caetrain the auto-encoder's bf16 training step at [256, 321, 180], DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
 z-score fused) at [256, 321, 180].  The eval forward runs at [DFA_AB_B, 321, 180] (default 256) and prints the median round's
 ms per call, its timing slots 0-3 and a checksum of the logits."""
 import os, sys, time, torch
@@ -47,6 +47,23 @@ if os.environ.get("DFA_AB_MODE") == "train1d":
         for _ in range(40): last = tr.step(x, y)
         torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 40 * 1e3)
     print(name, "cnn1d train step ms median %.4f min %.4f max %.4f" % (sorted(res)[3], min(res), max(res)),
+          "losses", ["%.6f" % v for v in losses], "last %.6f" % float(last), flush=True)
+    sys.exit(0)
+if os.environ.get("DFA_AB_MODE") == "caetrain":
+    from dfa_amd.model_cae import ConvAutoencoder
+    from dfa_amd.training.train_step import make_cae_trainer
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(256, 321, 180, generator=g).to(dev, torch.bfloat16)
+    torch.manual_seed(0)
+    tr = make_cae_trainer(ConvAutoencoder(precision="bf16").to(dev), lr=1e-6, weight_decay=1e-4)
+    losses = [float(tr.step(x)) for _ in range(5)]
+    res = []
+    for rnd in range(5):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(10): last = tr.step(x)
+        torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 10 * 1e3)
+    print(name, "cae train step ms median %.3f min %.3f" % (sorted(res)[2], min(res)),
           "losses", ["%.6f" % v for v in losses], "last %.6f" % float(last), flush=True)
     sys.exit(0)
 if os.environ.get("DFA_AB_MODE") == "cae":
