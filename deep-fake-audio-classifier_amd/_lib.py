@@ -33,6 +33,7 @@ SYMBOLS = [
     ("dfa_ctx_destroy", C.c_int, [C.c_void_p]),
     ("dfa_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("dfa_ctx_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    ("dfa_ctx_get_option", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     ("dfa_last_error", C.c_char_p, [C.c_void_p]),
     ("dfa_error_name", C.c_char_p, [C.c_int]),
     ("dfa_cnn2d_set_params", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
@@ -320,6 +321,11 @@ class Context:
 
     def set_option(self, name: str, value: int):
         check(self.handle, self.lib.dfa_ctx_set_option(self.handle, name.encode(), int(value)))
+
+    def get_option(self, name: str) -> int:
+        value = C.c_int(0)
+        check(self.handle, self.lib.dfa_ctx_get_option(self.handle, name.encode(), C.byref(value)))
+        return value.value
 
     # ---- timing -----------------------------------------------------------------------------------------------
     def timing(self, enable):

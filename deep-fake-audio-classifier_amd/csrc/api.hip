@@ -145,17 +145,16 @@ __global__ __launch_bounds__(256) void poison_lds_kernel(unsigned pattern, unsig
   if (lds_words[(threadIdx.x * 97 + blockIdx.x) % N] != pattern) sink[0] = 1;   // keeps the stores; never true
 }
 hipError_t launch_poison_lds(dfa_ctx* ctx, unsigned half) {
-  hipError_t e = hipSetDevice(ctx->device);   // the attribute is per device: set it on every call (a test hook, cheap)
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)poison_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return e;
   half &= 0xffffu;
-  hipLaunchKernelGGL(poison_lds_kernel, dim3(2048), dim3(256), 160 * 1024, ctx->stream, half | (half << 16), (unsigned*)ctx->zero_page);
-  return hipGetLastError();
+  return launch_lds(poison_lds_kernel, dim3(2048), dim3(256), 160 * 1024, ctx->stream, half | (half << 16), (unsigned*)ctx->zero_page);
 }
 }  // namespace
 
 namespace {
-// the options that are one int of the context: a 0/1 switch (any non-zero value = 1) or the value as given
+// the options that are one int of the context: a 0/1 switch (any non-zero value = 1) or the value as given.  dfa_ctx_get_option
+// reads every row; dfa_ctx_set_option stores the last four itself (a range, an allocation) before it comes to the table
 enum OptionKind { OPT_FLAG, OPT_INT };
 struct Option { const char* name; int dfa_ctx::*field; OptionKind kind; };
 const Option kOptions[] = {
@@ -169,6 +168,9 @@ const Option kOptions[] = {
     {"fuse_blocks123", &dfa_ctx::fuse_blocks123, OPT_FLAG}, {"persist123", &dfa_ctx::persist123, OPT_FLAG},
     {"lds_pipe", &dfa_ctx::lds_pipe, OPT_FLAG}, {"carry_a1", &dfa_ctx::carry_a1, OPT_FLAG},
     {"phase123", &dfa_ctx::phase123, OPT_FLAG}, {"cls123", &dfa_ctx::cls123, OPT_FLAG},
+    {"wgrad_variant", &dfa_ctx::wgrad_variant, OPT_INT}, {"train_conv_variant", &dfa_ctx::train_conv_variant, OPT_INT},
+    {"cnn1d_train_x3", &dfa_ctx::cnn1d_train_x3, OPT_INT}, {"cnn1d_fused", &dfa_ctx::cnn1d_fused, OPT_INT},
+    {"conv_dma", &dfa_ctx::conv_dma, OPT_INT}, {"clock_probe", &dfa_ctx::clock_probe, OPT_INT},
 };
 }  // namespace
 
@@ -178,8 +180,6 @@ int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value) {
     hipError_t e = launch_poison_lds(ctx, (unsigned)value);
     return e == hipSuccess ? DFA_OK : fail(ctx, DFA_E_HIP, "poison_lds: %s", hipGetErrorString(e));
   }
-  if (strcmp(name, "train_conv_variant") == 0) { set_train_conv_variant(value); return DFA_OK; }
-  if (strcmp(name, "wgrad_variant") == 0) { set_wgrad_variant(value); return DFA_OK; }
   if (strcmp(name, "clock_probe") == 0) {
     if (value && !ctx->clock_buf) {
       DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -195,6 +195,13 @@ int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value) {
   for (const Option& o : kOptions)
     if (strcmp(name, o.name) == 0) { ctx->*o.field = (o.kind == OPT_FLAG) ? (value ? 1 : 0) : value; return DFA_OK; }
   return fail(ctx, DFA_E_UNSUPPORTED, "unknown option '%s'", name);
+}
+
+int dfa_ctx_get_option(const dfa_ctx* ctx, const char* name, int* value) {
+  if (!ctx || !name || !value) return DFA_E_NULL_PTR;
+  for (const Option& o : kOptions)
+    if (strcmp(name, o.name) == 0) { *value = ctx->*o.field; return DFA_OK; }
+  return DFA_E_UNSUPPORTED;   // unknown, or the action "poison_lds"
 }
 
 int dfa_ctx_timing_enable(dfa_ctx* ctx, int enable) {

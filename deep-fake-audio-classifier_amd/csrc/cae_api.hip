@@ -167,7 +167,7 @@ int dfa_cae_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int 
     const ConvArgs a = cae_enc_args(ctx, pl, bf, l, B);
     const int dma = ctx->cae_enc_dma;
     hipError_t err = (l == 0) ? launch_cae_enc2(prec, a, s, ctx->lds_pipe, dma) : (l == 1) ? launch_cae_enc3(prec, a, s, ctx->lds_pipe, dma)
-                                                                             : launch_cae_enc4(prec, a, (float*)(ws + pl.raw_off), s, dma);
+                                                                             : launch_cae_enc4(prec, a, (float*)(ws + pl.raw_off), s, dma, ctx->train_conv_variant);
     DFA_HIP_CHECK(ctx, err);
   }
   if (latent) DFA_HIP_CHECK(ctx, launch_cae_latent_export(e[3], prec, latent, B, pl.H[4] * pl.W[4], 256, s));

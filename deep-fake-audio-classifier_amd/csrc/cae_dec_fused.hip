@@ -174,12 +174,7 @@ hipError_t launch_cae_dec_fused(const void* lat, const PackedConv* dec, const He
   CaeDecFusedArgs a = cae_dec_fused_args(lat, dec, head, w4pack, cst, v, mu, sigma, partial, H4, W4);
   a.stamps = stamps;
   a.recon = recon;
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, cdf::LDS_BYTES);
-    if (e != hipSuccess) return e;     // (per device: set on every launch, it is cheap)
-    hipLaunchKernelGGL(kern, dim3(a.ntile, B), dim3(512), cdf::LDS_BYTES, s, a);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(a.ntile, B), dim3(512), cdf::LDS_BYTES, s, a); };
   if (a.x_bf16) return mu ? go(cae_dec_fused_kernel<true, true>) : go(cae_dec_fused_kernel<true, false>);
   return mu ? go(cae_dec_fused_kernel<false, true>) : go(cae_dec_fused_kernel<false, false>);
 }
@@ -191,12 +186,7 @@ hipError_t launch_cae_dec_fused_ragged(const void* lat, const PackedConv* dec, c
   const int B = v.B;
   const CaeDecFusedArgs a = cae_dec_fused_args(lat, dec, head, w4pack, cst, v, mu, sigma, partial, H4, W4);
   const RaggedTab rt{tab, B};
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, cdf::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.ntile, B), dim3(512), cdf::LDS_BYTES, s, a, rt);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(a.ntile, B), dim3(512), cdf::LDS_BYTES, s, a, rt); };
   if (a.x_bf16) return mu ? go(cae_dec_fused_ragged_kernel<true, true>) : go(cae_dec_fused_ragged_kernel<true, false>);
   return mu ? go(cae_dec_fused_ragged_kernel<false, true>) : go(cae_dec_fused_ragged_kernel<false, false>);
 }

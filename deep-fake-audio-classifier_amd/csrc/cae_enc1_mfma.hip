@@ -86,19 +86,16 @@ hipError_t launch_cae_enc1_mfma(const FeatView& v, const float* mu, const float*
   const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
   const int64_t sb = v.sb, st = v.st, sf = v.sf;
   const int Ho = T / 2, Wo = F / 2, pitch = cae_enc1_mfma_pitch(F);
-  static const int dbg = getenv("DFA_E1_DBG") ? atoi(getenv("DFA_E1_DBG")) : 0;   // diagnostic phase skipping (timing only)
+#ifdef DFA_STAMPS
+  static const int dbg = getenv("DFA_E1_DBG") ? atoi(getenv("DFA_E1_DBG")) : 0;   // diagnostic build only: phase skipping (timing only)
+#else
+  constexpr int dbg = 0;
+#endif
   const size_t lds = cae_enc1_mfma_lds(F);
   dim3 grid((Ho + e1m::QG - 1) / e1m::QG, B), block(256);
-  if (x_dtype == DFA_DTYPE_BF16) {
-    hipError_t e = hipFuncSetAttribute((const void*)cae_enc1_mfma_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(cae_enc1_mfma_kernel<bf16_t>, grid, block, lds, s, (const bf16_t*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, dbg);
-  } else {
-    hipError_t e = hipFuncSetAttribute((const void*)cae_enc1_mfma_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(cae_enc1_mfma_kernel<float>, grid, block, lds, s, (const float*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, dbg);
-  }
-  return hipGetLastError();
+  if (x_dtype == DFA_DTYPE_BF16)
+    return launch_lds(cae_enc1_mfma_kernel<bf16_t>, grid, block, lds, s, (const bf16_t*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, dbg);
+  return launch_lds(cae_enc1_mfma_kernel<float>, grid, block, lds, s, (const float*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, dbg);
 }
 
 // ragged batch: T = the padded length (grid extent, output row pitch); tab = the device table, [0, B) the lengths
@@ -111,16 +108,9 @@ hipError_t launch_cae_enc1_mfma_ragged(const FeatView& v, const float* mu, const
   const size_t lds = cae_enc1_mfma_lds(F);
   const RaggedTab rt{tab, B};
   dim3 grid((Ho + e1m::QG - 1) / e1m::QG, B), block(256);
-  if (x_dtype == DFA_DTYPE_BF16) {
-    hipError_t e = hipFuncSetAttribute((const void*)cae_enc1_mfma_ragged_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(cae_enc1_mfma_ragged_kernel<bf16_t>, grid, block, lds, s, (const bf16_t*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, 0, rt);
-  } else {
-    hipError_t e = hipFuncSetAttribute((const void*)cae_enc1_mfma_ragged_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(cae_enc1_mfma_ragged_kernel<float>, grid, block, lds, s, (const float*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, 0, rt);
-  }
-  return hipGetLastError();
+  if (x_dtype == DFA_DTYPE_BF16)
+    return launch_lds(cae_enc1_mfma_ragged_kernel<bf16_t>, grid, block, lds, s, (const bf16_t*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, 0, rt);
+  return launch_lds(cae_enc1_mfma_ragged_kernel<float>, grid, block, lds, s, (const float*)x, sb, st, sf, mu, sigma, c1pack, c1bias, (bf16_t*)out, T, F, Ho, Wo, pitch, 0, rt);
 }
 
 }  // namespace dfa

@@ -246,7 +246,7 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
     ConvArgs a = conv_args(ws + pl.e[l - 1], m.tenc[l - 1], ws + pl.z[l], B, pl.H[l], pl.W[l], kEC[l], ctx);
     const bool epi_stats = ctx->cae_conv_stats && l < 3;         // (block 4: conv3x3_inst_cae_train.hip)
     a.stats_partial = epi_stats ? partial : nullptr;             // one [COUT][2] record per (sample, 32-column strip)
-    DFA_HIP_CHECK(ctx, launch_cae_train_fwd(prec, kEC[l - 1], a, (float*)(ws + pl.raw), s, m.train_enc4_wide));
+    DFA_HIP_CHECK(ctx, launch_cae_train_fwd(prec, kEC[l - 1], a, (float*)(ws + pl.raw), s, m.train_enc4_wide, ctx->train_conv_variant));
     BnStats st = stat_of(ws, pl, l, kEC[l]);
     const size_t npix = (size_t)B * pl.H[l] * pl.W[l];
     const RunningStats run = running_stats(q, upd);
@@ -385,15 +385,15 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
       for (int co = 0; co < 2; ++co)
         for (int ci = 0; ci < 2; ++ci)
           DFA_HIP_CHECK(ctx, launch_wgrad3x3_window(prec, 64, 128, 128, 256, 64 * ci, 128 * co, ws + pl.dz[3], ws + pl.e[2], partial, g.dw,
-                                                    ci == 0 ? g.db : nullptr, B, pl.H[3], pl.W[3], kWgradWGs, s));
+                                                    ci == 0 ? g.db : nullptr, B, pl.H[3], pl.W[3], kWgradWGs, s, ctx->wgrad_variant));
     } else {
       DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, kEC[l - 1], kEC[l], ws + pl.dz[l], ws + pl.e[l - 1], partial, g.dw, g.db, B,
-                                         pl.H[l], pl.W[l], kWgradWGs, s));
+                                         pl.H[l], pl.W[l], kWgradWGs, s, ctx->wgrad_variant));
     }
     const ConvArgs a = conv_args(ws + pl.dz[l], m.tdg[l - 1], ws + pl.de[l - 1], B, pl.H[l], pl.W[l], kEC[l - 1], ctx);
     DFA_HIP_CHECK(ctx, (l == 3)   ? launch_cae_dgrad4(prec, a, (float*)(ws + pl.raw), s, m.train_enc4_wide)
-                       : (l == 2) ? launch_dgrad3(m.train_dgrad_m16, prec, a, (float*)(ws + pl.raw), s)
-                                  : launch_dgrad2(m.train_dgrad_m16, prec, a, s));
+                       : (l == 2) ? launch_dgrad3(m.train_dgrad_m16, prec, a, (float*)(ws + pl.raw), s, ctx->train_conv_variant)
+                                  : launch_dgrad2(m.train_dgrad_m16, prec, a, s, ctx->train_conv_variant));
   }
   // ---- encoder block 1 (z1 recomputed from x; upstream through the 2x2 average pool): matrix-core pass + algebra, or two vector passes
   const bool c1_mfma = m.train_c1_mfma && ctx->conv1_mfma;

@@ -398,10 +398,7 @@ hipError_t launch_cnn1d_fused(const FeatView& v, const float* wp1, const float* 
   a.T = T; a.F = F; a.NT = (T + c1f::TW - 1) / c1f::TW; a.pitch = 32 * a.NT + 8; a.ncp1 = cnn1d_fused_ncp_pad(F, 0);
   const size_t lds = cnn1d_fused_lds_bytes(T);
   auto kern = (v.st == 1) ? cnn1d_fused_kernel<true> : cnn1d_fused_kernel<false>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, s, a);
-  return hipGetLastError();
+  return launch_lds(kern, dim3(B), dim3(256), lds, s, a);
 }
 
 }  // namespace dfa

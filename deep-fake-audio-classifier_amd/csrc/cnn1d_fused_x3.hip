@@ -501,12 +501,7 @@ hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const fl
   const int mt = conv1d_x3_mt(T, Cin, Cout, terms, mode);
   int total;
   conv1d_x3_layout(T, Cin, mt, terms, &a.offW, &total, &a.slab_floats);
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(B, Cout / (32 * mt)), dim3(c1x::NTH), total, s, a);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(B, Cout / (32 * mt)), dim3(c1x::NTH), total, s, a); };
   if (lens) {                     // ragged layer 1 (one channel tile), never with an augmentation
     if (mt != 1 || a.aug.on) return hipErrorInvalidValue;
     return terms == 3 ? go(conv1d_x3_kernel<1, 3, false, true>) : go(conv1d_x3_kernel<1, 2, false, true>);
@@ -537,10 +532,7 @@ hipError_t launch_cnn1d_fused_x3(const float* x, const void* w1, const float* b1
   a.logits = logits; a.T = T; a.F = F; a.NT = (T + 31) / 32; a.nks1 = cnn1d_x3_nks(F); a.stamps = stamps;
   int total;
   cnn1d_x3_layout(T, F, 0, &a.offB, &total, &a.slab_floats, &a.offS, &a.offH2);
-  hipError_t e = hipFuncSetAttribute((const void*)cnn1d_fused_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cnn1d_fused_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a);
-  return hipGetLastError();
+  return launch_lds(cnn1d_fused_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a);
 }
 
 // ---- ragged launch: x = the padded batch (element (b, f, t) at b stride_b + f stride_f + t), tab = the device table
@@ -576,10 +568,7 @@ hipError_t launch_cnn1d_ragged_x3(const float* x, int64_t stride_b, int64_t stri
   rg.wcap = cnn1d_ragged_wcap(F); rg.seg_step = cnn1d_ragged_seg_step(F);
   if (rg.wcap < 11 || rg.seg_step < 4) return hipErrorInvalidValue;
   const size_t total = cnn1d_ragged_lds_bytes(T_max, F);
-  hipError_t e = hipFuncSetAttribute((const void*)cnn1d_ragged_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cnn1d_ragged_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a, rg);
-  return hipGetLastError();
+  return launch_lds(cnn1d_ragged_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a, rg);
 }
 
 }  // namespace dfa

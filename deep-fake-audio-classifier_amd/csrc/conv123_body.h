@@ -1072,16 +1072,14 @@ typedef void (*C123Kernel)(Conv123Args);
 static hipError_t c123_launch(C123Kernel kern, int form, const char* tag, const Conv123Args& a, int num_cus, hipStream_t s) {
   const Conv123Plan p = conv123_plan(a.B, a.T, a.F, num_cus, form != DFA_CONV123_PER_UNIT, form == DFA_CONV123_CARRY, 0);
   if (p.form != form || p.grid < 1) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-  if (e != hipSuccess) return e;       // (per device: set on every launch, it is cheap)
-  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), p.lds, s, a);
+  const hipError_t e = launch_lds(kern, dim3(p.grid), dim3(512), p.lds, s, a);
 #ifdef DFA_STAMPS
   {
     static int calls = 0;      // seconds of back-to-back launches: the clock has settled (tools/gpu_stamps.py)
     if (++calls == 4000) c123_print_stamps(tag, p.grid);
   }
 #endif
-  return hipGetLastError();
+  return e;
 }
 
 }  // namespace dfa

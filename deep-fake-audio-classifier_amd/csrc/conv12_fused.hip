@@ -104,25 +104,23 @@ hipError_t launch_pack_conv1_mfma(const float* w1, const float* b1, uint4* c1pac
 template <typename TX, bool PIPE>
 static hipError_t launch_conv12_t(const Conv12Args& a, int B, hipStream_t s) {
   auto kern = conv12_fused_kernel<TX, PIPE>;
-  // diagnostic: DFA_C12_LDS_PAD=<bytes> pads the dynamic LDS request (e.g. 60000 -> one workgroup per CU, one wave per SIMD)
+#ifdef DFA_STAMPS
+  // diagnostic build only: DFA_C12_LDS_PAD=<bytes> pads the dynamic LDS request (e.g. 60000 -> one workgroup per CU, one wave per SIMD)
   static const int lds_bytes = c12::LDS_BYTES + (getenv("DFA_C12_LDS_PAD") ? atoi(getenv("DFA_C12_LDS_PAD")) : 0);
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) return e;       // (the attribute is per device: set on every launch, it is cheap)
+#else
+  constexpr int lds_bytes = c12::LDS_BYTES;
+#endif
   const int niter = (a.H1 + c12::BR - 1) / c12::BR;
   const int nseg = a.seg_iters ? (niter + a.seg_iters - 1) / a.seg_iters : 1;
-  hipLaunchKernelGGL(kern, dim3(B * a.nstrips, nseg), dim3(256), lds_bytes, s, a);
-  return hipGetLastError();
+  return launch_lds(kern, dim3(B * a.nstrips, nseg), dim3(256), lds_bytes, s, a);
 }
 
 template <typename TX, bool PIPE>
 static hipError_t launch_conv12_ragged_t(const Conv12Args& a, const RaggedTab& rt, int B, hipStream_t s) {
   auto kern = conv12_ragged_kernel<TX, PIPE>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, c12::LDS_BYTES);
-  if (e != hipSuccess) return e;       // (per device: set on every launch)
   const int niter = (a.H1 + c12::BR - 1) / c12::BR;      // of the longest utterance; shorter ones leave their late segments at once
   const int nseg = a.seg_iters ? (niter + a.seg_iters - 1) / a.seg_iters : 1;
-  hipLaunchKernelGGL(kern, dim3(B * a.nstrips, nseg), dim3(256), c12::LDS_BYTES, s, a, rt);
-  return hipGetLastError();
+  return launch_lds(kern, dim3(B * a.nstrips, nseg), dim3(256), c12::LDS_BYTES, s, a, rt);
 }
 
 // ragged batch: x is [B, T_max, F] (strided), a2 is [B][T_max/4][F][64] with utterance b's rows 0 .. T_b/4 - 1 written

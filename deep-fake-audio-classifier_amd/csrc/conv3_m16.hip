@@ -95,10 +95,8 @@ hipError_t launch_fold_pack_conv3x3_m16(const LayerParams& lp, int cin, int cout
 template <bool PIPE, bool TRAIN>
 static hipError_t launch_m16_t(const ConvArgs& a, hipStream_t stream) {
   auto kern = conv3_m16_meant_kernel<PIPE, TRAIN>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, m16::LDS_BYTES);
-  if (e != hipSuccess) return e;       // (the attribute is per device: set on every launch, it is cheap)
   const int nseg = a.seg_iters ? ((a.H + m16::BR - 1) / m16::BR + a.seg_iters - 1) / a.seg_iters : 1;
-  hipLaunchKernelGGL(kern, dim3(a.B * a.nstrips, a.COUT / 128, nseg), dim3(256), m16::LDS_BYTES, stream, a);
+  const hipError_t e = launch_lds(kern, dim3(a.B * a.nstrips, a.COUT / 128, nseg), dim3(256), m16::LDS_BYTES, stream, a);
 #ifdef DFA_STAMPS
   {
     static int calls = 0;
@@ -118,7 +116,7 @@ static hipError_t launch_m16_t(const ConvArgs& a, hipStream_t stream) {
     }
   }
 #endif
-  return hipGetLastError();
+  return e;
 }
 
 hipError_t launch_cnn2d_block3_m16(const ConvArgs& a0, hipStream_t stream, int pipe) {
@@ -133,10 +131,7 @@ hipError_t launch_cnn2d_block3_m16_ragged(const ConvArgs& a0, const RaggedTab& r
   ConvArgs a = a0;
   a.nstrips = (a.W + m16::SW - 1) / m16::SW;
   auto kern = pipe ? conv3_m16_ragged_kernel<true> : conv3_m16_ragged_kernel<false>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, m16::LDS_BYTES);
-  if (e != hipSuccess) return e;       // (per device: set on every launch)
-  hipLaunchKernelGGL(kern, dim3(a.B * a.nstrips, a.COUT / 128, a.seg_iters ? nseg : 1), dim3(256), m16::LDS_BYTES, stream, a, rt);
-  return hipGetLastError();
+  return launch_lds(kern, dim3(a.B * a.nstrips, a.COUT / 128, a.seg_iters ? nseg : 1), dim3(256), m16::LDS_BYTES, stream, a, rt);
 }
 
 // train-mode forward of block 3: a.out = z [B][H][W][128] bf16, a.stats_partial = [B*nstrips][128][2]

@@ -25,8 +25,9 @@ hipError_t launch_cae_enc3(int prec, const ConvArgs& a, hipStream_t s, int pipe,
   return launch_conv3x3<float, 64, 4, 1, 1, 1, EPI_POOL_2X2, 1>(a, s);
 }
 
-// a.wpack: bf16 -> one [256/32][9][8][64] image; fp32 -> two consecutive [256/32][9][8][64] images (Cin halves)
-hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int dma) {
+// a.wpack: bf16 -> one [256/32][9][8][64] image; fp32 -> two consecutive [256/32][9][8][64] images (Cin halves).
+// variant = the context's train_conv_variant
+hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int dma, int variant) {
   if (prec == DFA_PREC_BF16 && dma) return launch_conv3x3<bf16_t, 128, 4, 1, 1, 1, EPI_POOL_2X2, 1, false, true>(a, s);
   if (prec == DFA_PREC_BF16) return launch_conv3x3<bf16_t, 128, 4, 1, 1, 1, EPI_POOL_2X2, 1>(a, s);
   ConvArgs p1 = a;
@@ -42,8 +43,8 @@ hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStrea
   p2.wpack = a.wpack + (size_t)(256 / 32) * 9 * 8 * 64;
   // train_conv_variant 7 / 8 (diagnostic, tools/gpu_accin_probe.py): the asm-pipelined forms (3 / 4 reads in flight) of this
   // one-wave-per-SIMD fp32 ACCIN kernel with 288 weight registers; never the default
-  if (train_conv_variant() == 7) return launch_conv3x3<float, 64, 4, 1, 1, 1, EPI_POOL_2X2, 1, true, false, false, 3>(p2, s);
-  if (train_conv_variant() == 8) return launch_conv3x3<float, 64, 4, 1, 1, 1, EPI_POOL_2X2, 1, true, false, false, 4>(p2, s);
+  if (variant == 7) return launch_conv3x3<float, 64, 4, 1, 1, 1, EPI_POOL_2X2, 1, true, false, false, 3>(p2, s);
+  if (variant == 8) return launch_conv3x3<float, 64, 4, 1, 1, 1, EPI_POOL_2X2, 1, true, false, false, 4>(p2, s);
   return launch_conv3x3<float, 64, 4, 1, 1, 1, EPI_POOL_2X2, 1, true>(p2, s);
 }
 

@@ -9,10 +9,10 @@ namespace dfa {
 // the CNN2D's blocks 2 / 3 (records [B * strips][COUT][2], conv3x3_mfma.h; block 2 IS the CNN2D's block-2 kernel) -- no separate
 // pass over z.  Block 4 (one 22-column strip per sample at F = 180: little work per workgroup) keeps the separate pass: the
 // epilogue's fixed cost (+49 us) was twice the pass over its 118 MB output.
-hipError_t launch_cae_train_fwd(int prec, int cin, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide) {
+hipError_t launch_cae_train_fwd(int prec, int cin, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide, int variant) {
   const size_t es = (prec == DFA_PREC_BF16) ? 2 : 4;
   if (cin == 32) {
-    if (a.stats_partial) return launch_train_fwd2(prec, a, s);
+    if (a.stats_partial) return launch_train_fwd2(prec, a, s, variant);
     if (prec == DFA_PREC_BF16) return launch_conv3x3<bf16_t, 32, 2, 2, 2, 1, EPI_PLAIN, 1>(a, s);
     return launch_conv3x3<float, 32, 2, 2, 2, 1, EPI_PLAIN, 1>(a, s);
   }

@@ -6,16 +6,13 @@
 
 namespace dfa {
 
-// The bf16 kernels that fit two waves per SIMD without scratch run with asm-pipelined LDS reads (conv3x3_mfma.h); variant
-// 0 selects their compiler-scheduled twins (bit-identical; GPU test), 1 the earlier one-wave-per-SIMD instantiations.
-static int g_train_conv_variant = 2;
-void set_train_conv_variant(int v) { g_train_conv_variant = v; }
-int train_conv_variant() { return g_train_conv_variant; }
-
-hipError_t launch_train_fwd2(int prec, const ConvArgs& a, hipStream_t s) {
+// variant = the context's train_conv_variant.  The bf16 kernels that fit two waves per SIMD without scratch run with asm-pipelined
+// LDS reads (conv3x3_mfma.h: 2, the default); 0 selects their compiler-scheduled twins (bit-identical; GPU test), 1 the earlier
+// one-wave-per-SIMD instantiations.
+hipError_t launch_train_fwd2(int prec, const ConvArgs& a, hipStream_t s, int variant) {
   if (prec == DFA_PREC_BF16) {
-    if (g_train_conv_variant == 2) return launch_conv3x3<bf16_t, 32, 2, 2, 2, 1, EPI_PLAIN, 2, false, true, true, 4>(a, s);
-    if (g_train_conv_variant == 0) return launch_conv3x3<bf16_t, 32, 2, 2, 2, 1, EPI_PLAIN, 2, false, true, true, 0>(a, s);
+    if (variant == 2) return launch_conv3x3<bf16_t, 32, 2, 2, 2, 1, EPI_PLAIN, 2, false, true, true, 4>(a, s);
+    if (variant == 0) return launch_conv3x3<bf16_t, 32, 2, 2, 2, 1, EPI_PLAIN, 2, false, true, true, 0>(a, s);
     return launch_conv3x3<bf16_t, 32, 2, 2, 2, 1, EPI_PLAIN, 1, false, false, true>(a, s);
   }
   return launch_conv3x3<float, 32, 2, 2, 2, 1, EPI_PLAIN, 1, false, false, true>(a, s);
@@ -29,14 +26,14 @@ hipError_t launch_train_fwd3(int prec, const ConvArgs& a, hipStream_t s) {
 // a.wpack: two consecutive [64/32][9][64/KG][64] images (Cin halves 0-63, 64-127).  Cin = 128 in ONE launch needs
 // 288 weight VGPRs + the two-row epilogue and spills (1.44 ms measured for the bf16 form); two 64-channel launches
 // (raw fp32 partial sums, then accumulate + store) run spill-free.
-hipError_t launch_train_dgrad3(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s) {
+hipError_t launch_train_dgrad3(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int variant) {
   if (prec == DFA_PREC_BF16) {
     ConvArgs p1 = a;
     p1.in_pix_bytes = 128 * 2;
     p1.in_ch_off_bytes = 0;
     p1.raw_out = raw_tmp;
-    hipError_t e = g_train_conv_variant == 2   ? launch_conv3x3<bf16_t, 64, 2, 2, 2, 1, EPI_RAW, 2, false, true, false, 3>(p1, s)
-                   : g_train_conv_variant == 0 ? launch_conv3x3<bf16_t, 64, 2, 2, 2, 1, EPI_RAW, 2, false, true, false, 0>(p1, s)
+    hipError_t e = variant == 2   ? launch_conv3x3<bf16_t, 64, 2, 2, 2, 1, EPI_RAW, 2, false, true, false, 3>(p1, s)
+                   : variant == 0 ? launch_conv3x3<bf16_t, 64, 2, 2, 2, 1, EPI_RAW, 2, false, true, false, 0>(p1, s)
                                                : launch_conv3x3<bf16_t, 64, 2, 2, 2, 1, EPI_RAW, 1, false, true>(p1, s);
     if (e != hipSuccess) return e;
     ConvArgs p2 = a;
@@ -59,7 +56,7 @@ hipError_t launch_train_dgrad3(int prec, const ConvArgs& a, float* raw_tmp, hipS
   p2.wpack = a.wpack + (size_t)(64 / 32) * 9 * 8 * 64;
   // variant 7 (diagnostic, tools/gpu_accin_probe.py): the asm-pipelined form of this one-wave-per-SIMD fp32 ACCIN kernel --
   // the configuration whose wrong sums round 1 recorded; never the default
-  if (g_train_conv_variant == 7) return launch_conv3x3<float, 64, 2, 2, 2, 1, EPI_PLAIN, 1, true, true, false, 3>(p2, s);
+  if (variant == 7) return launch_conv3x3<float, 64, 2, 2, 2, 1, EPI_PLAIN, 1, true, true, false, 3>(p2, s);
   return launch_conv3x3<float, 64, 2, 2, 2, 1, EPI_PLAIN, 1, true, true>(p2, s);
 }
 

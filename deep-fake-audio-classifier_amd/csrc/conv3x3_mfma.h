@@ -50,6 +50,7 @@
 #include <utility>
 
 #include "dfa_device.h"
+#include "launch_views.h"
 #include "rng.h"
 
 namespace dfa {
@@ -217,14 +218,8 @@ hipError_t launch_conv3x3(const ConvArgs& a0, hipStream_t stream) {
   a.nstrips = (a.W + 31) / 32;
   if (STATS && a.relu) return hipErrorInvalidValue;     // the statistics forms store pre-BatchNorm outputs
   auto kern = conv3x3_mfma_kernel<T, CIN, NSL, MG, RP, MT, EPI, MINW, ACCIN, DMA, STATS, PFD>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
   dim3 grid(a.B * a.nstrips, a.COUT / (NSL * 32), 1), block(C::NT, 1, 1);
-  hipLaunchKernelGGL(kern, grid, block, C::LDS_BYTES, stream, a);
+  const hipError_t e = launch_lds(kern, grid, block, C::LDS_BYTES, stream, a);
 #ifdef DFA_STAMPS
   if ((EPI == EPI_MEAN_T || STATS) && sizeof(T) == 2) {
     static int calls = 0;
@@ -241,7 +236,7 @@ hipError_t launch_conv3x3(const ConvArgs& a0, hipStream_t stream) {
     }
   }
 #endif
-  return hipGetLastError();
+  return e;
 }
 
 // ragged batch: a.H = the height of the longest utterance at this layer (row pitch of a.in and a.out), hshift = log2 of
@@ -253,15 +248,8 @@ hipError_t launch_conv3x3_ragged(const ConvArgs& a0, const RaggedTab& rt, int hs
   ConvArgs a = a0;
   a.nstrips = (a.W + 31) / 32;
   auto kern = conv3x3_mfma_ragged_kernel<T, CIN, NSL, MG, RP, MT, EPI, MINW, ACCIN, DMA, STATS, PFD>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
   dim3 grid(a.B * a.nstrips, a.COUT / (NSL * 32), 1), block(C::NT, 1, 1);
-  hipLaunchKernelGGL(kern, grid, block, C::LDS_BYTES, stream, a, rt, hshift);
-  return hipGetLastError();
+  return launch_lds(kern, grid, block, C::LDS_BYTES, stream, a, rt, hshift);
 }
 
 }  // namespace dfa

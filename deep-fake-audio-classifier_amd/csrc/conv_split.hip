@@ -427,10 +427,8 @@ template <int CIN, int NW, int EPI, bool PIPE, bool SPLIT = true>
 static hipError_t launch_split_t(const ConvArgs& a, hipStream_t stream) {
   auto kern = conv_split_kernel<CIN, NW, EPI, PIPE, SPLIT>;
   constexpr int LDS = SplitCfg<CIN, SPLIT>::RING_BYTES + NW * 16 * 4 + (EPI == SPLIT_EPI_MEAN_T ? 64 * NW * 32 : 0);
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (e != hipSuccess) return e;       // (the attribute is per device: set on every launch, it is cheap)
   const int nseg = a.seg_iters ? ((a.H + 1) / 2 + a.seg_iters - 1) / a.seg_iters : 1;
-  hipLaunchKernelGGL(kern, dim3(a.B * a.nstrips, 1, nseg), dim3(64 * NW), LDS, stream, a);
+  const hipError_t e = launch_lds(kern, dim3(a.B * a.nstrips, 1, nseg), dim3(64 * NW), LDS, stream, a);
 #ifdef DFA_STAMPS
   {
     static int calls = 0;
@@ -447,7 +445,7 @@ static hipError_t launch_split_t(const ConvArgs& a, hipStream_t stream) {
     }
   }
 #endif
-  return hipGetLastError();
+  return e;
 }
 
 // block 2: a.in = a1 split [B][H][W][2*32], a.out = a2 split [B][H/2][W][2*64]

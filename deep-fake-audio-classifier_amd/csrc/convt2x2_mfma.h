@@ -167,16 +167,9 @@ hipError_t launch_convt2x2(const ConvTArgs& a, hipStream_t stream) {
   constexpr int LDS = MTILE * PB + MTILE * 4;
   if (STATS && (!a.stats_partial || !a.no_relu || a.COUT > 128 || (a.COUT != 32 && a.COUT != 64 && a.COUT != 128))) return hipErrorInvalidValue;
   auto kern = convt2x2_mfma_kernel<T, CIN, MSUB, STATS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
   const long P = (long)a.B * a.H * a.W;
   dim3 grid((unsigned)((P + MTILE - 1) / MTILE)), block(256);
-  hipLaunchKernelGGL(kern, grid, block, LDS, stream, a);
-  return hipGetLastError();
+  return launch_lds(kern, grid, block, LDS, stream, a);
 }
 
 }  // namespace dfa

@@ -125,11 +125,8 @@ hipError_t launch_convt_dgrad_bf16(const void* zp, const float* wq, void* wfrag,
   const int gx = ntiles_p < 1024 ? ntiles_p : 1024;
   dim3 grid(gx, ntiles_n / tiles_per_wg), block(256);
   const size_t lds = 2 * 32 * 1024;
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, block, lds, s, (const bf16_t*)zp, (const uint4*)wfrag, (bf16_t*)dx, P, Cin, waves_n, ntiles_p);
-    return hipGetLastError();
+  auto go = [&](auto kern) {
+    return launch_lds(kern, grid, block, lds, s, (const bf16_t*)zp, (const uint4*)wfrag, (bf16_t*)dx, P, Cin, waves_n, ntiles_p);
   };
   if (K == 512) return go(convt_dgrad_bf16_kernel<512, 1>);
   if (K == 256) return go(convt_dgrad_bf16_kernel<256, 2>);

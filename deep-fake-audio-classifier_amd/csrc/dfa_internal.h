@@ -187,6 +187,9 @@ struct dfa_ctx {
                                // 0 = the fp32 VALU kernel (conv1d.hip); 2 = diagnostic: as 1 with one channel tile per workgroup
   int cnn1d_fused = 1;         // CNN1D eval forward as ONE kernel when T <= 384: 1 = split-bf16 kernel (cnn1d_fused_x3.hip) for the reference's
                                // storage layout, the exact-fp32 one (cnn1d_fused.hip) otherwise; 2 = always the exact-fp32 one; 0 = the three-launch path
+  int wgrad_variant = 3;       // bf16 3x3 weight gradients (wgrad_mfma.hip): 3 = the asm-pipelined v3 kernels, 30 = their compiler-scheduled twins, 2 = the v2 kernels (test hook)
+  int train_conv_variant = 2;  // bf16 training convolutions (conv3x3_inst_train.hip): 2 = asm-pipelined LDS reads, 0 = their compiler-scheduled twins, 1 = the one-wave-per-SIMD
+                               // instantiations; 7 / 8 = diagnostic fp32 ACCIN forms (test hook)
   int clock_probe = 0;         // 1 = the bf16 block-3 kernel stamps its main loop (s_memtime / s_memrealtime) into clock_buf: dfa_ctx_clock_read
   long long* clock_buf = nullptr;   // device, 1024 x {cycles, 100 MHz ticks}
   float* aug_keep = nullptr;        // device copy of the armed augmentation's keep mask (dfa_cnn2d_set_train_augment copies keep_f)
@@ -497,18 +500,19 @@ hipError_t launch_mse_fwd_bwd(const float* recon, const FeatView& v, float* part
 bool convt_dgrad_bf16_supports(int Cin, int Cout);
 hipError_t launch_convt_dgrad_bf16(const void* zp, const float* wq, void* wfrag, void* dx, long P, int Cin, int Cout, hipStream_t s);
 hipError_t launch_cast_from_f32(int prec, const float* src, void* dst, size_t n, hipStream_t s);
+// wgrad_mfma.hip; variant = the context's wgrad_variant
 hipError_t launch_wgrad3x3_window(int prec, int cin, int cout, int cin_total, int cout_total, int ci_off, int co_off,
                                   const void* dz, const void* a, float* partial, float* dw, float* db, int B, int H,
-                                  int W, int nwg, hipStream_t s);
+                                  int W, int nwg, hipStream_t s, int variant);
 hipError_t launch_wgrad3x3(int prec, int cin, int cout, const void* dz, const void* a, float* partial, float* dw,
-                           float* db, int B, int H, int W, int nwg, hipStream_t s);
-// conv3x3_inst_*.hip
+                           float* db, int B, int H, int W, int nwg, hipStream_t s, int variant);
+// conv3x3_inst_*.hip; variant = the context's train_conv_variant
 hipError_t launch_fold_pack_conv3x3_m16(const LayerParams& lp, int cin, int cout, uint4* wpack, hipStream_t s);
-hipError_t launch_train_fwd2(int prec, const ConvArgs& a, hipStream_t s);
+hipError_t launch_train_fwd2(int prec, const ConvArgs& a, hipStream_t s, int variant);
 hipError_t launch_train_fwd3(int prec, const ConvArgs& a, hipStream_t s);
-hipError_t launch_train_dgrad3(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s);
+hipError_t launch_train_dgrad3(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int variant);
 hipError_t launch_train_dgrad2(int prec, const ConvArgs& a, hipStream_t s);
-hipError_t launch_cae_train_fwd(int prec, int cin, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide);
+hipError_t launch_cae_train_fwd(int prec, int cin, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide, int variant);
 hipError_t launch_cae_dgrad4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int wide);
 hipError_t launch_train_fwd3_m16(const ConvArgs& a, hipStream_t s, int pipe = 1);
 // conv_split.hip (DFA_PREC_BF16X3)
@@ -522,9 +526,6 @@ hipError_t launch_cnn2d_block3_m16(const ConvArgs& a, hipStream_t s, int pipe = 
 hipError_t launch_cnn2d_block3_m16_ragged(const ConvArgs& a, const RaggedTab& rt, int nseg, hipStream_t s, int pipe = 1);
 hipError_t launch_reduce_wgrad_record(const float* partial, int nparts, int stride, int cin, int cout, int cin_total,
                                       int ci_off, int co_off, float* dw, float* db, hipStream_t s, int perm = 0);
-void set_train_conv_variant(int v);
-int train_conv_variant();   // conv3x3_inst_train.hip (process-wide test hook)
-void set_wgrad_variant(int v);   // wgrad_mfma.hip: bf16 weight-gradient kernel selection (process-wide test hook)
 hipError_t launch_pack_conv1_mfma(const float* w1, const float* b1, uint4* c1pack, float* c1bias, hipStream_t s);
 hipError_t launch_conv12_fused(const FeatView& v, const uint4* c1pack, const float* c1bias, const uint4* wpack2, const float* bias2, void* a2,
                                hipStream_t s, int pipe = 1, int seg_iters = 0);
@@ -536,7 +537,7 @@ hipError_t launch_cnn2d_block3(int prec, const ConvArgs& a, hipStream_t s, int d
 struct ConvTArgs;
 hipError_t launch_cae_enc2(int prec, const ConvArgs& a, hipStream_t s, int pipe = 1, int dma = 0);
 hipError_t launch_cae_enc3(int prec, const ConvArgs& a, hipStream_t s, int pipe = 1, int dma = 0);
-hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int dma = 0);
+hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int dma, int variant);
 hipError_t launch_cae_enc_ragged(int layer, const ConvArgs& a, const RaggedTab& rt, hipStream_t s);
 hipError_t launch_cae_dec(int prec, int cin, const ConvTArgs& a, hipStream_t s);
 int cae_dec_stats_records(int prec, int cin, long P);

@@ -317,26 +317,14 @@ __global__ __launch_bounds__(dlq::NTH) void dlq_layer_kernel(const DlqLayerArgs 
 }
 
 hipError_t launch_dlq_layer(int layer, const DlqLayerArgs& a, int ntiles, hipStream_t s) {
-  const void* fn = layer == 1 ? (const void*)dlq_layer_kernel<1, 0> : layer == 2 ? (const void*)dlq_layer_kernel<2, 0> : (const void*)dlq_layer_kernel<3, 0>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, dlq::LDS_BYTES);   // per device: set on every launch
-  if (e != hipSuccess) return e;
-  if (layer == 1) hipLaunchKernelGGL((dlq_layer_kernel<1, 0>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  else if (layer == 2) hipLaunchKernelGGL((dlq_layer_kernel<2, 0>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  else hipLaunchKernelGGL((dlq_layer_kernel<3, 0>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  return hipGetLastError();
+  void (*const kerns[])(DlqLayerArgs) = {dlq_layer_kernel<1, 0>, dlq_layer_kernel<2, 0>, dlq_layer_kernel<3, 0>};
+  return launch_lds(kerns[layer == 1 ? 0 : layer == 2 ? 1 : 2], dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
 }
 
 // mode 1: the train forward of `layer`; mode 2: the data gradient (layer 2's shape).  ntiles = B * a.tpu
 hipError_t launch_dlq_layer_train(int layer, int mode, const DlqLayerArgs& a, int ntiles, hipStream_t s) {
-  const void* fn = mode == 2 ? (const void*)dlq_layer_kernel<2, 2>
-                             : layer == 1 ? (const void*)dlq_layer_kernel<1, 1> : layer == 2 ? (const void*)dlq_layer_kernel<2, 1> : (const void*)dlq_layer_kernel<3, 1>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, dlq::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  if (mode == 2) hipLaunchKernelGGL((dlq_layer_kernel<2, 2>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  else if (layer == 1) hipLaunchKernelGGL((dlq_layer_kernel<1, 1>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  else if (layer == 2) hipLaunchKernelGGL((dlq_layer_kernel<2, 1>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  else hipLaunchKernelGGL((dlq_layer_kernel<3, 1>), dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
-  return hipGetLastError();
+  void (*const kerns[])(DlqLayerArgs) = {dlq_layer_kernel<2, 2>, dlq_layer_kernel<1, 1>, dlq_layer_kernel<2, 1>, dlq_layer_kernel<3, 1>};
+  return launch_lds(kerns[mode == 2 ? 0 : layer == 1 ? 1 : layer == 2 ? 2 : 3], dim3(ntiles), dim3(dlq::NTH), dlq::LDS_BYTES, s, a);
 }
 
 // ---- pool + head: workgroup = dispatch position, thread = channel ------------------------------------------------------------------

@@ -483,12 +483,9 @@ hipError_t launch_dlq_wgrad(const DlqWgradArgs& a0, float* dw, hipStream_t s) {
   DlqWgradArgs a = a0;
   int nch;
   dlq_wgrad_chunks(a.N, &a.CH, &nch);
-  const void* fn = a.x ? (const void*)dlq_wgrad_kernel<1> : (const void*)dlq_wgrad_kernel<0>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS);
+  auto kern = a.x ? dlq_wgrad_kernel<1> : dlq_wgrad_kernel<0>;
+  hipError_t e = launch_lds(kern, dim3(nch, HID / 64, a.taps), dim3(256), WG_LDS, s, a);
   if (e != hipSuccess) return e;
-  const dim3 grid(nch, HID / 64, a.taps);
-  if (a.x) hipLaunchKernelGGL(dlq_wgrad_kernel<1>, grid, dim3(256), WG_LDS, s, a);
-  else hipLaunchKernelGGL(dlq_wgrad_kernel<0>, grid, dim3(256), WG_LDS, s, a);
   const int per = a.taps * HID * a.C;
   hipLaunchKernelGGL(dlq_wgrad_reduce_kernel, dim3((per + 255) / 256), dim3(256), 0, s, a.partial, nch, a.C, a.taps, dw);
   return hipGetLastError();

@@ -1,10 +1,24 @@
 // launch_views.h -- the typed views the host launch layer passes between the C ABI's entry points and the launchers: the feature
-// tensor, one layer's parameters / gradients, one BatchNorm layer's apply terms.  Host only: no view appears in a kernel signature
-// or in a struct passed to a kernel; a launcher unpacks it into the kernel's own arguments.
+// tensor, one layer's parameters / gradients, one BatchNorm layer's apply terms; and launch_lds, the launch of a kernel with dynamic
+// LDS.  Host only: no view appears in a kernel signature or in a struct passed to a kernel; a launcher unpacks it into the kernel's
+// own arguments.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace dfa {
+
+// THE launch of a kernel with dynamic LDS: every such launch of the library goes through here, and nothing else touches a kernel's
+// attributes.  The limit on a kernel's dynamic LDS is an attribute per device (and several kernels are launched with more than one
+// byte count), so it is set on the current device with every launch: nothing is remembered per process, and two contexts on two
+// GPUs, or two host threads, need no agreement.  Returns the attribute's error, or the launch's.
+template <typename... Params, typename... Args>
+inline hipError_t launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+  return hipGetLastError();
+}
 
 // the caller's feature tensor [B, T, F] (T = T_max of a ragged batch): element (b, t, f) at x[b sb + t st + f sf], dtype = DFA_DTYPE_*.
 // An extern "C" entry point builds it once, behind its argument checks, from its own arguments in this order; no other function takes

@@ -142,7 +142,7 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(l3), 64, 0, 64, 128, prec, m.t3.wpack, m.t3.bias, s));
   // bf16: the 16x16x32 image of the same raw weights, in the unused second half of the (fp32-sized) t3 buffer
   uint4* t3_m16 = (uint4*)((char*)m.t3.wpack + (size_t)128 * 64 * 9 * 2);
-  const bool fwd3_m16 = prec == DFA_PREC_BF16 && train_conv_variant() != 1;   // 2: pipelined, 0: its compiler-scheduled twin
+  const bool fwd3_m16 = prec == DFA_PREC_BF16 && ctx->train_conv_variant != 1;   // 2: pipelined, 0: its compiler-scheduled twin
   if (fwd3_m16)
     DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_m16(raw_conv(l3), 64, 128, t3_m16, s));
   m.train_dgrad_m16 = (prec == DFA_PREC_BF16 && ctx->dgrad_m16) ? 1 : 0;
@@ -173,7 +173,7 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   {
     ConvArgs a = conv_args(ws + pl.a1, m.t2, ws + pl.z2, B, pl.H1, F, 64, ctx);
     a.stats_partial = partial;
-    DFA_HIP_CHECK(ctx, launch_train_fwd2(prec, a, s));
+    DFA_HIP_CHECK(ctx, launch_train_fwd2(prec, a, s, ctx->train_conv_variant));
   }
   BnStats s2 = stat_ptrs(ws, pl, 1);
   DFA_TRY(finalize_bn_stats(ctx, partial, B * nstrips, 64, (double)B * pl.H1 * F, s2, running_stats(l2, update_running_stats), momentum, partial + (size_t)B * nstrips * 128));
@@ -185,7 +185,7 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
     a.stats_partial = partial;
     if (fwd3_m16) {
       a.wpack = t3_m16;
-      DFA_HIP_CHECK(ctx, launch_train_fwd3_m16(a, s, train_conv_variant() == 2));
+      DFA_HIP_CHECK(ctx, launch_train_fwd3_m16(a, s, ctx->train_conv_variant == 2));
     } else {
       DFA_HIP_CHECK(ctx, launch_train_fwd3(prec, a, s));
     }
@@ -228,8 +228,8 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
   DFA_HIP_CHECK(ctx, launch_bn_bwd_meant_saved(prec, ws + pl.z3, bn_apply(s3, l3), demb, (const float*)(ws + pl.msum), partial,
                                                sm3, ws + pl.dz3, B, pl.H2, F, 128, s, sync));
   DFA_HIP_CHECK(ctx, launch_split_sums(sm3, g3.dgamma, g3.dbeta, 128, s));
-  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 64, 128, ws + pl.dz3, ws + pl.a2, partial, g3.dw, g3.db, B, pl.H2, F, kWgradWGs, s));
-  DFA_HIP_CHECK(ctx, launch_dgrad3(m.train_dgrad_m16, prec, conv_args(ws + pl.dz3, m.d3, ws + pl.da2, B, pl.H2, F, 64, ctx), (float*)(ws + pl.raw), s));
+  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 64, 128, ws + pl.dz3, ws + pl.a2, partial, g3.dw, g3.db, B, pl.H2, F, kWgradWGs, s, ctx->wgrad_variant));
+  DFA_HIP_CHECK(ctx, launch_dgrad3(m.train_dgrad_m16, prec, conv_args(ws + pl.dz3, m.d3, ws + pl.da2, B, pl.H2, F, 64, ctx), (float*)(ws + pl.raw), s, ctx->train_conv_variant));
   // block 2
   dc.layer = 2;
   {
@@ -239,11 +239,11 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
                                      B, pl.H1, F, 64, dc, s, scratch2, sync));
   }
   DFA_HIP_CHECK(ctx, launch_split_sums(sm2, g2.dgamma, g2.dbeta, 64, s));
-  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 32, 64, ws + pl.dz2, ws + pl.a1, partial, g2.dw, g2.db, B, pl.H1, F, kWgradWGs, s));
+  DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 32, 64, ws + pl.dz2, ws + pl.a1, partial, g2.dw, g2.db, B, pl.H1, F, kWgradWGs, s, ctx->wgrad_variant));
   {
     ConvArgs a = conv_args(ws + pl.dz2, m.d2, ws + pl.da1, B, pl.H1, F, 32, ctx);
     if (m.train_c1_mfma) { a.drop = dc; a.drop.layer = 1; }   // keep mask of a1's dropout where da1 is produced (idempotent for the vector kernel)
-    DFA_HIP_CHECK(ctx, launch_dgrad2(m.train_dgrad_m16, prec, a, s));
+    DFA_HIP_CHECK(ctx, launch_dgrad2(m.train_dgrad_m16, prec, a, s, ctx->train_conv_variant));
   }
   // block 1 (z1 recomputed from x; conv1_mfma may be cleared between forward and backward: the vector kernel reads the same state)
   dc.layer = 1;

@@ -367,7 +367,9 @@ hipError_t launch_conv1_mfma(int mode, const FeatView& v, const float* w, const 
   a.T = T; a.F = F; a.Ho = T / 2; a.FP = (F + 31) / 32 * 32;
   a.rows_per_wg = conv1_mfma_rows_per_wg(B, T, F);
   a.dc = dc;
-  { static const char* e = getenv("DFA_C1X_DBG"); a.dbg = e ? atoi(e) : 0; }
+#ifdef DFA_STAMPS
+  { static const char* e = getenv("DFA_C1X_DBG"); a.dbg = e ? atoi(e) : 0; }   // diagnostic build only: phase skipping (timing only)
+#endif
   a.out_scale = (poolw == 2 ? 0.25f : 0.5f) * (dc.thresh != 0 ? dc.scale : 1.0f);
   const int np = (T + 1) / 2;
   dim3 grid((np + a.rows_per_wg - 1) / a.rows_per_wg, B), block(256);

@@ -73,11 +73,12 @@ inline int pack_dgrad_images(dfa_ctx* ctx, const float* w2, const float* w3, int
     DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(w3, 64, 128, 64 * hlf, 64, prec, d3.wpack + (size_t)hlf * (64 / 32) * 9 * nkg * 64, d3.bias, s));
   return DFA_OK;
 }
-inline hipError_t launch_dgrad2(int m16, int prec, const ConvArgs& a, hipStream_t s) {
-  return m16 ? launch_train_dgrad2_m16(a, s, train_conv_variant() != 0) : launch_train_dgrad2(prec, a, s);
+// variant = the context's train_conv_variant (0: the compiler-scheduled twins)
+inline hipError_t launch_dgrad2(int m16, int prec, const ConvArgs& a, hipStream_t s, int variant) {
+  return m16 ? launch_train_dgrad2_m16(a, s, variant != 0) : launch_train_dgrad2(prec, a, s);
 }
-inline hipError_t launch_dgrad3(int m16, int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s) {
-  return m16 ? launch_train_dgrad3_m16(a, s, train_conv_variant() != 0) : launch_train_dgrad3(prec, a, raw_tmp, s);
+inline hipError_t launch_dgrad3(int m16, int prec, const ConvArgs& a, float* raw_tmp, hipStream_t s, int variant) {
+  return m16 ? launch_train_dgrad3_m16(a, s, variant != 0) : launch_train_dgrad3(prec, a, raw_tmp, s, variant);
 }
 
 // ---- block 1 of the CNN2D and the auto-encoder: conv 1 -> 32 whose pre-BN output is recomputed from x in every pass -------------

@@ -583,13 +583,7 @@ static hipError_t launch_wgrad_bf16_v3(const void* dz, const void* a, float* par
   constexpr int LDS = 2 * (ROWS * SEG * wg_stride(COUT) + (ROWS + 2) * (SEG + 2) * wg_stride(CIN)) + 1024;   // + spare write slots
   static_assert(LDS <= 160 * 1024, "LDS of a CU");
   auto kern = wgrad3x3_bf16_v3_kernel<CIN, COUT, SEG, ROWS, KS, PIPE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), LDS, s, (const bf16_t*)dz, (const bf16_t*)a, partial, B, H, W, dzs_c, as_c);
+  const hipError_t e = launch_lds(kern, dim3(nwg), dim3(512), LDS, s, (const bf16_t*)dz, (const bf16_t*)a, partial, B, H, W, dzs_c, as_c);
 #ifdef DFA_STAMPS
   {
     static int calls = 0;
@@ -606,7 +600,7 @@ static hipError_t launch_wgrad_bf16_v3(const void* dz, const void* a, float* par
     }
   }
 #endif
-  return hipGetLastError();
+  return e;
 }
 
 template <int CIN, int COUT, int SEG, bool KSPLIT>
@@ -614,14 +608,7 @@ static hipError_t launch_wgrad_bf16_v2(const void* dz, const void* a, float* par
                                        hipStream_t s, int dzs_c, int as_c) {
   constexpr int LDS = 2 * (2 * SEG * wg_stride(COUT) + 4 * (SEG + 2) * wg_stride(CIN));
   auto kern = wgrad3x3_bf16_v2_kernel<CIN, COUT, SEG, KSPLIT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), LDS, s, (const bf16_t*)dz, (const bf16_t*)a, partial, B, H, W, dzs_c, as_c);
-  return hipGetLastError();
+  return launch_lds(kern, dim3(nwg), dim3(256), LDS, s, (const bf16_t*)dz, (const bf16_t*)a, partial, B, H, W, dzs_c, as_c);
 }
 
 template <typename T, int CIN, int COUT>
@@ -629,25 +616,15 @@ static hipError_t launch_wgrad_t(const void* dz, const void* a, float* partial, 
                                  hipStream_t s, int dzs_c, int as_c) {
   constexpr int LDS = (WG_SEG * COUT + 3 * (WG_SEG + 2) * CIN) * 4;
   auto kern = wgrad3x3_mfma_kernel<T, CIN, COUT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), LDS, s, (const T*)dz, (const T*)a, partial, B, H, W, dzs_c, as_c);
-  return hipGetLastError();
+  return launch_lds(kern, dim3(nwg), dim3(256), LDS, s, (const T*)dz, (const T*)a, partial, B, H, W, dzs_c, as_c);
 }
 
-static int g_wgrad_variant = 3;   // 3 = asm-pipelined v3 (product), 30 = its compiler-scheduled twin, 2 = v2 (test hooks)
-void set_wgrad_variant(int v) { g_wgrad_variant = v; }
-static int wgrad_variant() { return g_wgrad_variant; }
-
 // dW [COUT][CIN][3][3] and db [COUT] <- dz [B][H][W][COUT], a [B][H][W][CIN]; partial: nwg * (128*64*9 + 256) floats
-// (the bf16 32 -> 64 kernel writes 4 records of 64*32*9 + 64 floats per workgroup)
+// (the bf16 32 -> 64 kernel writes 4 records of 64*32*9 + 64 floats per workgroup).  variant: the context's wgrad_variant (bf16
+// kernel selection: 3 = asm-pipelined v3 (product), 30 = its compiler-scheduled twin, 2 = v2)
 hipError_t launch_wgrad3x3(int prec, int cin, int cout, const void* dz, const void* a, float* partial, float* dw,
-                           float* db, int B, int H, int W, int nwg, hipStream_t s) {
-  return launch_wgrad3x3_window(prec, cin, cout, cin, cout, 0, 0, dz, a, partial, dw, db, B, H, W, nwg, s);
+                           float* db, int B, int H, int W, int nwg, hipStream_t s, int variant) {
+  return launch_wgrad3x3_window(prec, cin, cout, cin, cout, 0, 0, dz, a, partial, dw, db, B, H, W, nwg, s, variant);
 }
 
 // channel-window form: the kernel shapes are (cin, cout) in {(32,64), (64,128)}; a layer with more channels is covered by
@@ -655,14 +632,13 @@ hipError_t launch_wgrad3x3(int prec, int cin, int cout, const void* dz, const vo
 // channels per pixel.  dw is the FULL [cout_total][cin_total][9] gradient; db (may be null) the full [cout_total] one.
 hipError_t launch_wgrad3x3_window(int prec, int cin, int cout, int cin_total, int cout_total, int ci_off, int co_off,
                                   const void* dz, const void* a, float* partial, float* dw, float* db, int B, int H,
-                                  int W, int nwg, hipStream_t s) {
+                                  int W, int nwg, hipStream_t s, int variant) {
   const size_t es = (prec == DFA_PREC_BF16) ? 2 : 4;
   const void* dzw = (const char*)dz + (size_t)co_off * es;
   const void* aw = (const char*)a + (size_t)ci_off * es;
   hipError_t e;
   int nparts = nwg;     // partial records written
   if (prec == DFA_PREC_BF16) {
-    const int variant = wgrad_variant();
     if (cin == 64 && cout == 128) {
       if (variant == 2) e = launch_wgrad_bf16_v2<64, 128, 32, false>(dzw, aw, partial, B, H, W, nwg, s, cout_total, cin_total);
       else if (variant == 30) e = launch_wgrad_bf16_v3<64, 128, 32, 4, 1, false>(dzw, aw, partial, B, H, W, nwg, s, cout_total, cin_total);
@@ -682,7 +658,7 @@ hipError_t launch_wgrad3x3_window(int prec, int cin, int cout, int cin_total, in
   if (e != hipSuccess) return e;
   const int n = cout * cin * 9;
   // weight block: partial record [cout][cin][9] -> dw rows co_off.., columns ci_off.. of [cout_total][cin_total][9]
-  const int perm = (prec == DFA_PREC_BF16 && wgrad_variant() != 2) ? 1 : 0;   // the v3 kernels write accumulator-order records
+  const int perm = (prec == DFA_PREC_BF16 && variant != 2) ? 1 : 0;   // the v3 kernels write accumulator-order records
   return launch_reduce_wgrad_record(partial, nparts, n + cout, cin, cout, cin_total, ci_off, co_off, dw, db, s, perm);
 }
 

@@ -105,9 +105,9 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *   "dgrad_m16"     1 (default) = bf16 training: each data-gradient convolution is ONE launch of the 16x16x32 kernel
  *                   (conv_split.hip), 0 = the 32x32x16 kernels (block 3 as two Cin-half launches through fp32 partial sums)
  *   "wgrad_variant" 3 (default) = pipelined bf16 weight-gradient kernel, 30 = its compiler-scheduled twin, 2 = the
- *                   earlier 4-wave kernel (process-wide)
+ *                   earlier 4-wave kernel.  Held by the context, like every option: it selects kernels for this context's calls only
  *   "train_conv_variant" 2 (default) = pipelined two-wave bf16 training convolutions where they fit, 0 = their
- *                   compiler-scheduled twins, 1 = the one-wave-per-SIMD instantiations (process-wide)
+ *                   compiler-scheduled twins, 1 = the one-wave-per-SIMD instantiations.  Per context as well
  *   "cae_enc1_mfma" 1 (default) = auto-encoder eval forward in bf16 mode: block 1 (conv 1 -> 32 + ReLU + 2 x 2 pool) on the matrix
  *                   cores with hi + lo bf16 operands; 0 = the vector-ALU kernel
  *   "cae_enc_dma"   1 (default) = auto-encoder eval forward in bf16 mode: encoder blocks 2-4 stage their input rows by LDS-DMA;
@@ -144,6 +144,9 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *                   (tests/test_lds_poison_gpu.py) run every path after this and require bit-identical results
  * unknown names return DFA_E_UNSUPPORTED */
 int dfa_ctx_set_option(dfa_ctx* ctx, const char* name, int value);
+/* the value this context holds for an option: *value = what dfa_ctx_set_option stored (a switch set to any non-zero value reads 1),
+ * or the default above.  "poison_lds" is an action and holds no value: DFA_E_UNSUPPORTED, as for unknown names */
+int dfa_ctx_get_option(const dfa_ctx* ctx, const char* name, int* value);
 const char* dfa_last_error(const dfa_ctx* ctx);
 const char* dfa_error_name(int code);
 

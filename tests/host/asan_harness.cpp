@@ -98,6 +98,7 @@ int main() {
     for (int prec = -1; prec < 4; ++prec) EXPECT(dfa_dominant_kernel(model, prec) != nullptr);
   EXPECT(dfa_last_error(nullptr) != nullptr);
   EXPECT(dfa_ctx_set_option(nullptr, "time_split", 1) == DFA_E_NULL_PTR);
+  { int v = 0; EXPECT(dfa_ctx_get_option(nullptr, "time_split", &v) == DFA_E_NULL_PTR); }
   EXPECT(dfa_ctx_destroy(nullptr) == DFA_E_NULL_PTR);
   EXPECT(dfa_ctx_create(0, nullptr, nullptr) == DFA_E_NULL_PTR);
   float out[4] = {0, 0, 0, 0};

@@ -1,5 +1,5 @@
 """A/B two builds of the library (separate processes, alternating): DFA_LIB=<file name under lib/>; DFA_AB_MODE=train times the
-bf16 training step instead of the eval forward, DFA_AB_MODE=train1d the CNN1D's (fp32) uniform training step, DFA_AB_MODE=caetrain the auto-encoder's bf16 training step at [256, 321, 180], DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
+bf16 training step instead of the eval forward, DFA_AB_MODE=train1d the CNN1D's (fp32) uniform training step, DFA_AB_MODE=caetrain the auto-encoder's bf16 training step at [256, 321, 180], DFA_AB_MODE=dlqtrain the DeepfakeDetector's training step at [256, 180, 321] with lengths in [161, 321], DFA_AB_MODE=cae the auto-encoder's bf16 anomaly score (ConvAutoencoder.score,
 z-score fused) at [256, 321, 180].  The eval forward runs at [DFA_AB_B, 321, 180] (default 256) and prints the median round's
 ms per call, its timing slots 0-3 and a checksum of the logits."""
 import os, sys, time, torch
@@ -64,6 +64,28 @@ if os.environ.get("DFA_AB_MODE") == "caetrain":
         for _ in range(10): last = tr.step(x)
         torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 10 * 1e3)
     print(name, "cae train step ms median %.3f min %.3f" % (sorted(res)[2], min(res)),
+          "losses", ["%.6f" % v for v in losses], "last %.6f" % float(last), flush=True)
+    sys.exit(0)
+if os.environ.get("DFA_AB_MODE") == "dlqtrain":
+    from dfa_amd.dlqueen_model import DeepfakeDetector
+    from dfa_amd.training import DlqTrainer
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(1)
+    x = (torch.randn((256, 180, 324), generator=g) * 3.2 - 0.07)[:, :, :321]
+    lengths = torch.randint(161, 322, (256,), generator=g)
+    lengths[0] = 321
+    for b in range(256): x[b, :, int(lengths[b]):] = 0.0
+    y = (torch.rand(256, generator=g) > 0.5).float().to(dev)
+    x, lens = x.to(dev), lengths.numpy()
+    torch.manual_seed(0)
+    tr = DlqTrainer(DeepfakeDetector(180, dropout=0.3).to(dev), lr=1e-6, weight_decay=1e-4, pos_weight=2.5, grad_clip=5.0, ema_decay=0.999)
+    losses = [float(tr.step(x, lens, y)) for _ in range(5)]
+    res = []
+    for rnd in range(5):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(10): last = tr.step(x, lens, y)
+        torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 10 * 1e3)
+    print(name, "dlq train step ms median %.3f min %.3f" % (sorted(res)[2], min(res)),
           "losses", ["%.6f" % v for v in losses], "last %.6f" % float(last), flush=True)
     sys.exit(0)
 if os.environ.get("DFA_AB_MODE") == "cae":
