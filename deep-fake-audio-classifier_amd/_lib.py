@@ -364,7 +364,8 @@ class BnSync:
     """Synchronised BatchNorm for data-parallel training (dfa_ctx_set_bn_sync): while armed on the device's context, every
     BatchNorm layer's per-channel sums are added over the ranks of `process_group` between their reduction and their use, so
     N ranks x B utterances behave like one rank x N*B.  Built once per trainer (sync buffer and callback); the hook is global
-    to the context and must stay the same across a forward / backward pair, so its owner arms it around exactly that pair."""
+    to the context and must stay the same across a forward / backward pair (the library refuses a backward whose forward found
+    it otherwise), so its owner arms it around exactly that pair."""
     FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
 
     def __init__(self, device, process_group=None):

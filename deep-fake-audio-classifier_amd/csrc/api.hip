@@ -104,10 +104,9 @@ int dfa_ctx_create(int device_id, void* hip_stream, dfa_ctx** out) {
 int dfa_ctx_destroy(dfa_ctx* ctx) {
   if (!ctx) return DFA_E_NULL_PTR;
   (void)hipSetDevice(ctx->device);
-  void* const packed[] = {ctx->cnn2d.packed, ctx->cnn2d.train_packed, ctx->cnn1d.packed, ctx->cnn1d.train_packed,
-                          ctx->cae.packed,   ctx->cae.train_packed,   ctx->dlq.packed,   ctx->dlq.train_packed};
-  for (void* p : packed)
+  for (void* p : {ctx->cnn2d.packed, ctx->cnn1d.packed, ctx->cae.packed, ctx->dlq.packed})
     if (p) (void)hipFree(p);
+  ctx->cnn2d.train.release(); ctx->cnn1d.train.release(); ctx->cae.train.release(); ctx->dlq.train.release();
   if (ctx->clip_partial) (void)hipFree(ctx->clip_partial);
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   if (ctx->clock_buf) (void)hipFree(ctx->clock_buf);

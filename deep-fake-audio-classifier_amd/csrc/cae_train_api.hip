@@ -97,11 +97,11 @@ int finalize_stats(dfa_ctx* ctx, int prec, const void* z, size_t npix, int C, co
 
 // encoder block 1 of a step: what conv1_train_stats (forward) and conv1_train_backward (backward, da = de[0]) take.  The matrix-core
 // passes keep XX | Xs and their [32][11] record behind the decoder-block-4 record in pl.rec; the two-pass record is pl.rec itself
-Conv1Train conv1_block(CaeState& m, const FeatView& v, char* ws, const CaeTrainPlan& pl, bool mfma) {
+Conv1Train conv1_block(const CaeState& m, const TrainStep& step, const FeatView& v, char* ws, const CaeTrainPlan& pl, bool mfma) {
   float* rec = (float*)(ws + pl.rec);
   Conv1Train c{};             // (no dropout, no augmentation, single-level synchronised statistics)
-  c.v = v; c.prec = m.train_prec; c.poolw = 2;
-  c.p = layer_params(m.p, 0); c.fw = m.tw1; c.fb = m.tb1; c.partial = (float*)(ws + pl.partial); c.xxs = rec + 512; c.c1rec = mfma ? rec + 640 : rec;
+  c.v = v; c.prec = step.prec; c.poolw = 2;
+  c.p = layer_params(m.p, 0); c.fw = m.train.tw1; c.fb = m.train.tb1; c.partial = (float*)(ws + pl.partial); c.xxs = rec + 512; c.c1rec = mfma ? rec + 640 : rec;
   c.sums = sums_of(ws, pl, 0); c.stats = stat_of(ws, pl, 0, 32); c.da = ws + pl.de[0];
   return c;
 }
@@ -163,6 +163,8 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
   TraceRange trace_("dfa_cae_forward_train");
   if (!ctx) return DFA_E_NULL_PTR;
   CaeState& m = ctx->cae;
+  CaeTrain& tr = m.train;
+  tr.step.live = false;     // whatever this call returns, the batch that was in flight is over
   if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cae_set_params has not been called");
   if (!x || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x and workspace must be non-null");
   if (!recon && !mse) return fail(ctx, DFA_E_NULL_PTR, "give recon, mse or both (the decoder's last kernel needs an output)");
@@ -172,7 +174,7 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
   DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total, false, "train "));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int prec = precision;
-  if (!m.train_packed) {  // raw conv images enc2-4 (+ their dgrad images), raw convT images, conv1 fold target, biases
+  if (!tr.train_packed) {  // raw conv images enc2-4 (+ their dgrad images), raw convT images, conv1 fold target, biases
     Bump take;
     size_t eb[3], db[3], ew[3], dgw[3], dw[3];
     const size_t c1 = take((288 + 32) * 4);
@@ -182,13 +184,13 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
     for (int l = 0; l < 3; ++l) ew[l] = take((size_t)kEC[l + 1] * kEC[l] * 9 * 4);
     for (int l = 0; l < 3; ++l) dgw[l] = take((size_t)kEC[l + 1] * kEC[l] * 9 * 4);
     for (int l = 0; l < 3; ++l) dw[l] = take((size_t)kDC[l] * kDCin[l] * 4 * 4);
-    DFA_HIP_CHECK(ctx, hipMalloc(&m.train_packed, take.off));
-    char* b = (char*)m.train_packed;
-    m.tw1 = (float*)(b + c1); m.tb1 = m.tw1 + 288;
+    DFA_HIP_CHECK(ctx, hipMalloc(&tr.train_packed, take.off));
+    char* b = (char*)tr.train_packed;
+    tr.tw1 = (float*)(b + c1); tr.tb1 = tr.tw1 + 288;
     for (int l = 0; l < 3; ++l) {
-      m.tenc[l].bias = (float*)(b + eb[l]); m.tenc[l].wpack = (uint4*)(b + ew[l]);
-      m.tdg[l].bias = (float*)(b + dgb); m.tdg[l].wpack = (uint4*)(b + dgw[l]);
-      m.tdec[l].bias = (float*)(b + db[l]); m.tdec[l].wpack = (uint4*)(b + dw[l]);
+      tr.tenc[l].bias = (float*)(b + eb[l]); tr.tenc[l].wpack = (uint4*)(b + ew[l]);
+      tr.tdg[l].bias = (float*)(b + dgb); tr.tdg[l].wpack = (uint4*)(b + dgw[l]);
+      tr.tdec[l].bias = (float*)(b + db[l]); tr.tdec[l].wpack = (uint4*)(b + dw[l]);
     }
   }
   const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
@@ -198,55 +200,56 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
   float* partial = (float*)(ws + pl.partial);
   const int nkg = (prec == DFA_PREC_BF16) ? 4 : 8;
   // ---- weight images (weights move every step)
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e2), 32, 0, 32, 64, prec, m.tenc[0].wpack, m.tenc[0].bias, s));
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e3), 64, 0, 64, 128, prec, m.tenc[1].wpack, m.tenc[1].bias, s));
-  m.train_enc4_wide = (prec == DFA_PREC_BF16 && ctx->cae_enc4_wide) ? 1 : 0;
-  if (m.train_enc4_wide) {   // one 128-input-channel image (the eval forward's layout)
-    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e4), 128, 0, 128, 256, prec, m.tenc[2].wpack, m.tenc[2].bias, s));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e2), 32, 0, 32, 64, prec, tr.tenc[0].wpack, tr.tenc[0].bias, s));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e3), 64, 0, 64, 128, prec, tr.tenc[1].wpack, tr.tenc[1].bias, s));
+  TrainStep step;             // this call's record: committed to tr.step by the last statement
+  step.B = B; step.T = T; step.F = F; step.prec = prec; step.x_dtype = x_dtype; step.synced = ctx->bn_sync.fn != nullptr;
+  step.enc4_wide = (prec == DFA_PREC_BF16 && ctx->cae_enc4_wide) ? 1 : 0;
+  if (step.enc4_wide) {   // one 128-input-channel image (the eval forward's layout)
+    DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e4), 128, 0, 128, 256, prec, tr.tenc[2].wpack, tr.tenc[2].bias, s));
   } else {
   for (int hlf = 0; hlf < 2; ++hlf)
     DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(e4), 128, 64 * hlf, 64, 256, prec,
-                                                m.tenc[2].wpack + (size_t)hlf * (256 / 32) * 9 * nkg * 64, m.tenc[2].bias, s));
+                                                tr.tenc[2].wpack + (size_t)hlf * (256 / 32) * 9 * nkg * 64, tr.tenc[2].bias, s));
   }
   // bf16 mode: the 64 -> 32 and 128 -> 64 data gradients on the 16x16x32 kernels of conv_split.hip, one launch each (as the CNN2D's;
   // the 32x32x16 forms ran the first with one channel slice per workgroup -- 0.31 ms -- and the second as two launches chained
   // through fp32 partial sums)
-  m.train_dgrad_m16 = (prec == DFA_PREC_BF16 && ctx->dgrad_m16) ? 1 : 0;
-  DFA_TRY(pack_dgrad_images(ctx, e2.w, e3.w, prec, m.train_dgrad_m16, m.tdg[0], m.tdg[1]));
-  if (m.train_enc4_wide) {
+  step.dgrad_m16 = (prec == DFA_PREC_BF16 && ctx->dgrad_m16) ? 1 : 0;
+  DFA_TRY(pack_dgrad_images(ctx, e2.w, e3.w, prec, step.dgrad_m16, tr.tdg[0], tr.tdg[1]));
+  if (step.enc4_wide) {
     for (int c = 0; c < 2; ++c)
-      DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(e4.w, 128, 256, 128 * c, 128, prec, m.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * 8 * 64, m.tdg[2].bias, s));
+      DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(e4.w, 128, 256, 128 * c, 128, prec, tr.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * 8 * 64, tr.tdg[2].bias, s));
   } else {
   for (int c = 0; c < 4; ++c)
-    DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(e4.w, 128, 256, 64 * c, 64, prec, m.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * nkg * 64, m.tdg[2].bias, s));
+    DFA_HIP_CHECK(ctx, launch_pack_conv3x3_dgrad(e4.w, 128, 256, 64 * c, 64, prec, tr.tdg[2].wpack + (size_t)c * (128 / 32) * 9 * nkg * 64, tr.tdg[2].bias, s));
   }
   for (int l = 0; l < 3; ++l)
-    DFA_HIP_CHECK(ctx, launch_fold_pack_convt2x2(raw_conv(layer_params(m.p, kCaeDec0 + l)), kDCin[l], kDC[l], prec, m.tdec[l].wpack, m.tdec[l].bias, s));
-  m.train_prec = prec; m.train_B = B; m.train_T = T;
+    DFA_HIP_CHECK(ctx, launch_fold_pack_convt2x2(raw_conv(layer_params(m.p, kCaeDec0 + l)), kDCin[l], kDC[l], prec, tr.tdec[l].wpack, tr.tdec[l].bias, s));
   const bool upd = update_running_stats != 0;
   // ---- encoder block 1 (pre-BN output recomputed from x: statistics pass, fold, fused eval kernel)
   {
     // bf16 mode on bf16 features (F even): the statistics pass (with the 9 x 9 tap moments the fused backward algebra needs) and
     // the backward pass on the matrix cores (train_conv1_mfma.hip, as the CNN2D's block 1), the forward on cae_enc1_mfma.hip
     // (synchronised BatchNorm: the backward needs the layer's sums before the weight gradient is formed -> the two-pass vector path)
-    m.train_c1_mfma = (ctx->conv1_mfma && !ctx->bn_sync.fn && prec == DFA_PREC_BF16 && x_dtype == DFA_DTYPE_BF16 && F <= 224 && !(F & 1) && T >= 4) ? 1 : 0;
-    DFA_TRY(conv1_train_stats(ctx, conv1_block(m, v, ws, pl, m.train_c1_mfma), m.train_c1_mfma, m.train_c1_mfma, upd, momentum));
-    if (m.train_c1_mfma && ctx->cae_enc1_mfma) {
+    step.c1_mfma = (ctx->conv1_mfma && !step.synced && prec == DFA_PREC_BF16 && x_dtype == DFA_DTYPE_BF16 && F <= 224 && !(F & 1) && T >= 4) ? 1 : 0;
+    DFA_TRY(conv1_train_stats(ctx, conv1_block(m, step, v, ws, pl, step.c1_mfma), step.c1_mfma, step.c1_mfma, upd, momentum));
+    if (step.c1_mfma && ctx->cae_enc1_mfma) {
       uint4* tpack = (uint4*)(ws + pl.wq);                // this step's three-term A operands (pl.wq is free until the decoder's backward)
       float* tbias = (float*)(ws + pl.wq) + 6 * 64 * 4;
-      DFA_HIP_CHECK(ctx, launch_pack_cae_enc1_mfma(m.tw1, m.tb1, tpack, tbias, s));
+      DFA_HIP_CHECK(ctx, launch_pack_cae_enc1_mfma(tr.tw1, tr.tb1, tpack, tbias, s));
       DFA_HIP_CHECK(ctx, launch_cae_enc1_mfma(v, nullptr, nullptr, tpack, tbias, ws + pl.e[0], s));
     } else {
-      DFA_HIP_CHECK(ctx, launch_cae_enc1(v, nullptr, nullptr, m.tw1, m.tb1, ws + pl.e[0], prec, s));
+      DFA_HIP_CHECK(ctx, launch_cae_enc1(v, nullptr, nullptr, tr.tw1, tr.tb1, ws + pl.e[0], prec, s));
     }
   }
   // ---- encoder blocks 2-4
   for (int l = 1; l < 4; ++l) {
     const LayerParams q = layer_params(m.p, l);
-    ConvArgs a = conv_args(ws + pl.e[l - 1], m.tenc[l - 1], ws + pl.z[l], B, pl.H[l], pl.W[l], kEC[l], ctx);
+    ConvArgs a = conv_args(ws + pl.e[l - 1], tr.tenc[l - 1], ws + pl.z[l], B, pl.H[l], pl.W[l], kEC[l], ctx);
     const bool epi_stats = ctx->cae_conv_stats && l < 3;         // (block 4: conv3x3_inst_cae_train.hip)
     a.stats_partial = epi_stats ? partial : nullptr;             // one [COUT][2] record per (sample, 32-column strip)
-    DFA_HIP_CHECK(ctx, launch_cae_train_fwd(prec, kEC[l - 1], a, (float*)(ws + pl.raw), s, m.train_enc4_wide, ctx->train_conv_variant));
+    DFA_HIP_CHECK(ctx, launch_cae_train_fwd(prec, kEC[l - 1], a, (float*)(ws + pl.raw), s, step.enc4_wide, ctx->train_conv_variant));
     BnStats st = stat_of(ws, pl, l, kEC[l]);
     const size_t npix = (size_t)B * pl.H[l] * pl.W[l];
     const RunningStats run = running_stats(q, upd);
@@ -261,12 +264,12 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
     const LayerParams q = layer_params(m.p, kCaeDec0 + l);
     ConvTArgs a{};
     a.in = (l == 0) ? ws + pl.e[3] : ws + pl.d[l - 1];
-    a.wpack = m.tdec[l].wpack; a.bias = m.tdec[l].bias; a.out = ws + pl.zd[l];
+    a.wpack = tr.tdec[l].wpack; a.bias = tr.tdec[l].bias; a.out = ws + pl.zd[l];
     a.B = B; a.H = pl.Hd[l] / 2; a.W = (l == 1) ? (pl.Wd[l] - 1) / 2 : pl.Wd[l] / 2;
     a.COUT = kDC[l]; a.opad_w = (l == 1) ? 1 : 0; a.no_relu = 1;
     a.stats_partial = ctx->cae_conv_stats ? partial : nullptr;   // one [COUT][2] record per workgroup (the padding column's share in record 0)
     DFA_HIP_CHECK(ctx, launch_cae_dec(prec, kDCin[l], a, s));
-    if (l == 1) DFA_HIP_CHECK(ctx, launch_cae_opad_col(ws + pl.zd[1], m.tdec[1].bias, prec, B * pl.Hd[1], pl.Wd[1], 64, s, 1));
+    if (l == 1) DFA_HIP_CHECK(ctx, launch_cae_opad_col(ws + pl.zd[1], tr.tdec[1].bias, prec, B * pl.Hd[1], pl.Wd[1], 64, s, 1));
     BnStats st = stat_of(ws, pl, kCaeDec0 + l, kDC[l]);
     const size_t npix = (size_t)B * pl.Hd[l] * pl.Wd[l];
     const RunningStats run = running_stats(q, upd);
@@ -279,6 +282,8 @@ int dfa_cae_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T
   // ---- decoder block 4 + zero time padding (+ per-sample MSE)
   DFA_HIP_CHECK(ctx, launch_cae_dec4_mse(ws + pl.d[2], prec, head_params(m.p, kCaeLayers, 0), v, nullptr, nullptr, recon, partial, mse, pl.Hd[2],
                                          pl.Wd[2], s));
+  step.live = true;
+  tr.step = step;
   return DFA_OK;
 }
 
@@ -287,12 +292,13 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
                      size_t workspace_bytes) {
   TraceRange trace_("dfa_cae_backward");
   if (!ctx) return DFA_E_NULL_PTR;
-  CaeState& m = ctx->cae;
-  const int prec = m.train_prec;
+  const CaeState& m = ctx->cae;
+  const CaeTrain& tr = m.train;
+  const TrainStep& step = tr.step;
+  const int prec = step.prec;
   CaeTrainPlan pl;
-  DFA_TRY(check_backward(ctx, {"dfa_cae_backward", "dfa_cae_forward_train", "the auto-encoder", kCaeGrads, nullptr, false},
-                         m.train_packed && m.train_B == B && m.train_T == T, x, x_dtype, drecon, grads, ngrads, workspace, workspace_bytes,
-                         [&] { return (pl = plan_cae_train(B, T, F, prec)).total; }));
+  DFA_TRY(check_backward(ctx, {"dfa_cae_backward", "dfa_cae_forward_train", "the auto-encoder", kCaeGrads, nullptr, false}, step, B, T, F, 0, x, x_dtype,
+                         drecon, grads, ngrads, workspace, workspace_bytes, [&] { return (pl = plan_cae_train(B, T, F, prec)).total; }, no_late_checks));
   const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
   const HeadParams head = head_params(m.p, kCaeLayers, 0);
   const HeadGrads gh = head_grads(grads, kCaeLayers, 0);
@@ -304,7 +310,7 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
   // second-level scratch of the block-record reductions (64 x C x 2 floats): the upper half of the partial buffer -- the records
   // of the BatchNorm / statistics passes (<= 3600 x 512 floats) use a fraction of the lower half (sized for the weight gradients)
   float* scratch2 = partial + pl.partial_bytes / 8;
-  const dfa::BnSync* sync = ctx->bn_sync.fn ? &ctx->bn_sync : nullptr;     // synchronised BatchNorm (dfa_ctx_set_bn_sync)
+  const dfa::BnSync* sync = step.synced ? &ctx->bn_sync : nullptr;           // synchronised BatchNorm (dfa_ctx_set_bn_sync)
   const int bf = (prec == DFA_PREC_BF16) ? 1 : 0;
   DropCfg nodrop{};
   // ---- decoder block 4
@@ -390,14 +396,14 @@ int dfa_cae_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int
       DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, kEC[l - 1], kEC[l], ws + pl.dz[l], ws + pl.e[l - 1], partial, g.dw, g.db, B,
                                          pl.H[l], pl.W[l], kWgradWGs, s, ctx->wgrad_variant));
     }
-    const ConvArgs a = conv_args(ws + pl.dz[l], m.tdg[l - 1], ws + pl.de[l - 1], B, pl.H[l], pl.W[l], kEC[l - 1], ctx);
-    DFA_HIP_CHECK(ctx, (l == 3)   ? launch_cae_dgrad4(prec, a, (float*)(ws + pl.raw), s, m.train_enc4_wide)
-                       : (l == 2) ? launch_dgrad3(m.train_dgrad_m16, prec, a, (float*)(ws + pl.raw), s, ctx->train_conv_variant)
-                                  : launch_dgrad2(m.train_dgrad_m16, prec, a, s, ctx->train_conv_variant));
+    const ConvArgs a = conv_args(ws + pl.dz[l], tr.tdg[l - 1], ws + pl.de[l - 1], B, pl.H[l], pl.W[l], kEC[l - 1], ctx);
+    DFA_HIP_CHECK(ctx, (l == 3)   ? launch_cae_dgrad4(prec, a, (float*)(ws + pl.raw), s, step.enc4_wide)
+                       : (l == 2) ? launch_dgrad3(step.dgrad_m16, prec, a, (float*)(ws + pl.raw), s, ctx->train_conv_variant)
+                                  : launch_dgrad2(step.dgrad_m16, prec, a, s, ctx->train_conv_variant));
   }
   // ---- encoder block 1 (z1 recomputed from x; upstream through the 2x2 average pool): matrix-core pass + algebra, or two vector passes
-  const bool c1_mfma = m.train_c1_mfma && ctx->conv1_mfma;
-  return conv1_train_backward(ctx, conv1_block(m, v, ws, pl, c1_mfma), c1_mfma, false, sync, layer_grads(grads, 0));
+  const bool c1_mfma = step.c1_mfma && ctx->conv1_mfma;
+  return conv1_train_backward(ctx, conv1_block(m, step, v, ws, pl, c1_mfma), c1_mfma, false, sync, layer_grads(grads, 0));
 }
 
 int dfa_mse_fwd_bwd(dfa_ctx* ctx, const float* recon, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,

@@ -61,9 +61,10 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
   Cnn1dState& m = ctx->cnn1d;
   const float* x = (const float*)v.x;       // (float32: refused below otherwise)
   const int x_dtype = v.dtype, B = v.B, T = v.T, F = v.F;
-  const AugCfg armed = m.aug_armed;     // one-shot: consumed here, also by a call that fails its checks below
-  m.aug_armed = AugCfg{};
-  m.train_aug = AugCfg{};
+  Cnn1dTrain& tr = m.train;
+  const AugCfg armed = tr.aug_armed;    // one-shot: consumed here, also by a call that fails its checks below
+  tr.aug_armed = AugCfg{};
+  tr.step.live = false;                 // and the batch that was in flight is over, whatever this call returns
   if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_set_params has not been called");
   if (!x || !logits || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, logits and workspace must be non-null");
   if (x_dtype != DFA_DTYPE_F32) return fail(ctx, DFA_E_BAD_DTYPE, "cnn1d takes float32 input (got dtype %d)", x_dtype);
@@ -93,26 +94,28 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
     DFA_TRY(stage_ragged_lengths(ctx, lengths, B, (char*)workspace + pl.total));
     lens = (const int*)((char*)workspace + pl.total);
   }
-  m.train_aug = armed;
-  const AugCfg* aug = m.train_aug.on ? &m.train_aug : nullptr;
-  if (!m.train_packed) {
+  TrainStep step;                              // this call's record: committed to tr.step by the last statement
+  step.B = B; step.T = T; step.F = F; step.x_dtype = x_dtype; step.ragged = lengths ? 1 : 0; step.frames = frames;
+  step.synced = ctx->bn_sync.fn != nullptr; step.aug = armed;
+  const AugCfg* aug = step.aug.on ? &step.aug : nullptr;
+  if (!tr.train_packed) {
     Bump take;
     const size_t wt0 = take((size_t)64 * 32 * 3 * 4), wt1 = take((size_t)128 * 64 * 3 * 4), zb = take(256 * 4);
-    DFA_HIP_CHECK(ctx, hipMalloc(&m.train_packed, take.off));
-    char* base = (char*)m.train_packed;
-    m.wt[0] = (float*)(base + wt0); m.wt[1] = (float*)(base + wt1); m.zero_bias = (float*)(base + zb);
+    DFA_HIP_CHECK(ctx, hipMalloc(&tr.train_packed, take.off));
+    char* base = (char*)tr.train_packed;
+    tr.wt[0] = (float*)(base + wt0); tr.wt[1] = (float*)(base + wt1); tr.zero_bias = (float*)(base + zb);
   }
   // bf16x3 A-fragment images of this step's weights (they change every step): forward layers 1-3, data gradients 3->2, 2->1
   const int xcin[5] = {F, 32, 64, 128, 64}, xcout[5] = {32, 64, 128, 64, 32};
-  if (!m.wx3[0] || m.wx3_F != F) {
-    if (m.wx3[0]) { DFA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); DFA_HIP_CHECK(ctx, hipFree(m.wx3[0])); m.wx3[0] = nullptr; }
+  if (!tr.wx3[0] || tr.wx3_F != F) {
+    if (tr.wx3[0]) { DFA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); DFA_HIP_CHECK(ctx, hipFree(tr.wx3[0])); tr.wx3[0] = nullptr; }
     Bump take;
     size_t off[5];
     for (int i = 0; i < 5; ++i) off[i] = take(conv1d_terms_pack_bytes(xcin[i], xcout[i], 3));
     char* base = nullptr;
     DFA_HIP_CHECK(ctx, hipMalloc((void**)&base, take.off));
-    for (int i = 0; i < 5; ++i) m.wx3[i] = base + off[i];
-    m.wx3_F = F;
+    for (int i = 0; i < 5; ++i) tr.wx3[i] = base + off[i];
+    tr.wx3_F = F;
   }
   const LayerParams layer[3] = {layer_params(m.p, 0), layer_params(m.p, 1), layer_params(m.p, 2)};
   const HeadParams head = head_params(m.p, kCnn1dLayers, 0);
@@ -122,14 +125,13 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
   const bool dgrad_x3 = x3 && conv1d_x3_supports((const float*)workspace, (int64_t)128 * T, T, 1, (const float*)workspace, T, 128, 64, terms) &&
                         conv1d_x3_supports((const float*)workspace, (int64_t)64 * T, T, 1, (const float*)workspace, T, 64, 32, terms);
   if (!dgrad_x3) {
-    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[1].w, m.wt[0], m.zero_bias, 32, 64, s));
-    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[2].w, m.wt[1], m.zero_bias, 64, 128, s));
+    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[1].w, tr.wt[0], tr.zero_bias, 32, 64, s));
+    DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[2].w, tr.wt[1], tr.zero_bias, 64, 128, s));
   }
-  if (x3) DFA_HIP_CHECK(ctx, launch_pack_conv1d_train_all(layer[0].w, layer[1].w, layer[2].w, m.wx3, F, terms, m.zero_bias, s));   // all five images, one launch
-  m.train_x3 = x3;
+  if (x3) DFA_HIP_CHECK(ctx, launch_pack_conv1d_train_all(layer[0].w, layer[1].w, layer[2].w, tr.wx3, F, terms, tr.zero_bias, s));   // all five images, one launch
+  step.x3 = x3;
   DropCfg dc = drop_cfg(p_drop, seed, offset);
-  m.train_drop = dc; m.train_B = B; m.train_T = T;
-  m.train_ragged = lengths ? 1 : 0; m.train_frames = frames;
+  step.drop = dc;
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
   const int C[3] = {32, 64, 128}, Cin[3] = {F, 32, 64};
@@ -139,18 +141,18 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
     const LayerParams& q = layer[l];
     if (l == 0) {
       if (x3 && conv1d_x3_supports(x, v.sb, v.sf, v.st, z, T, F, 32, terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3(x, v.sb, m.wx3[0], q.b, z, B, F, 32, T, terms, s, x3, aug, lens));
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(x, v.sb, tr.wx3[0], q.b, z, B, F, 32, T, terms, s, x3, aug, lens));
       else
         DFA_HIP_CHECK(ctx, launch_conv1d(x, v.sb, v.sf, v.st, q.w, q.b, z, B, F, 32, T, false, s, false, aug, lens));
     } else {
       const float* hin = (const float*)(ws + pl.h[l - 1]);
       if (x3 && conv1d_x3_supports(hin, (int64_t)Cin[l] * T, T, 1, z, T, Cin[l], C[l], terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3(hin, (int64_t)Cin[l] * T, m.wx3[l], q.b, z, B, Cin[l], C[l], T, terms, s, x3));
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(hin, (int64_t)Cin[l] * T, tr.wx3[l], q.b, z, B, Cin[l], C[l], T, terms, s, x3));
       else
         DFA_HIP_CHECK(ctx, launch_conv1d(hin, (int64_t)Cin[l] * T, T, 1, q.w, q.b, z, B, Cin[l], C[l], T, false, s, false));
     }
     BnStats st = st1d(ws, pl, l);
-    const bool shifted = !ctx->bn_sync.fn;       // sums of z - z[0][c][0]: see cm_stats_body
+    const bool shifted = !step.synced;             // sums of z - z[0][c][0]: see cm_stats_body
     DFA_HIP_CHECK(ctx, launch_cm_stats(z, partial, B, C[l], T, s, lens, shifted));
     DFA_TRY(finalize_bn_stats(ctx, partial, nch, C[l], frames, st, running_stats(q, update_running_stats), momentum, nullptr, shifted ? z : nullptr, T));
     if (l < 2) {
@@ -161,27 +163,34 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
     }
   }
   DFA_HIP_CHECK(ctx, launch_linear((const float*)(ws + pl.pooled), head.w, head.b, logits, B, 128, s));
+  step.live = true;
+  tr.step = step;
   return DFA_OK;
 }
 
 // ragged = which of the two entry points this is: it must be the one whose forward is in flight
 int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const FeatView& v, const float* dlogits, float* const* grads, int ngrads, void* workspace,
                         size_t workspace_bytes) {
-  Cnn1dState& m = ctx->cnn1d;
+  const Cnn1dState& m = ctx->cnn1d;
+  const Cnn1dTrain& tr = m.train;
+  const TrainStep& step = tr.step;
   const int B = v.B, T = v.T, F = v.F;
   Train1dPlan pl;
-  DFA_TRY(check_backward(ctx, {ragged ? "dfa_cnn1d_backward_ragged" : "dfa_cnn1d_backward",
-                               ragged ? "dfa_cnn1d_forward_train_ragged" : "dfa_cnn1d_forward_train", "cnn1d", kCnn1dGrads, "dlogits", true},
-                         m.train_packed && m.train_B == B && m.train_T == T && m.train_ragged == ragged, v.x, v.dtype, dlogits, grads, ngrads,
-                         workspace, workspace_bytes, [&] { return (pl = plan_train1d(B, T, F)).total + (ragged ? ragged1d_tab_bytes(B) : 0); }));
-  if (ragged && ctx->bn_sync.fn)
-    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed)");
+  DFA_TRY(check_backward(
+      ctx, {ragged ? "dfa_cnn1d_backward_ragged" : "dfa_cnn1d_backward", ragged ? "dfa_cnn1d_forward_train_ragged" : "dfa_cnn1d_forward_train",
+            "cnn1d", kCnn1dGrads, "dlogits", true},
+      step, B, T, F, ragged, v.x, v.dtype, dlogits, grads, ngrads, workspace, workspace_bytes,
+      [&] { return (pl = plan_train1d(B, T, F)).total + (ragged ? ragged1d_tab_bytes(B) : 0); },
+      [&] {
+        return !(ragged && ctx->bn_sync.fn) ? DFA_OK : fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised "
+                                                                                     "BatchNorm (dfa_ctx_set_bn_sync is armed)");
+      }));
   char* ws = (char*)workspace;
   const int* lens = ragged ? (const int*)(ws + pl.total) : nullptr;     // the table the forward left behind the plan
   float* partial = (float*)(ws + pl.partial);
   const HeadGrads gh = head_grads(grads, kCnn1dLayers, 0);
   hipStream_t s = ctx->stream;
-  DropCfg dc = m.train_drop;
+  DropCfg dc = step.drop;
   const int C[3] = {32, 64, 128}, Cin[3] = {F, 32, 64};
   float* dpooled = (float*)(ws + pl.dpooled);
   DFA_HIP_CHECK(ctx, launch_linear_bwd(dlogits, head_params(m.p, kCnn1dLayers, 0).w, (const float*)(ws + pl.pooled), dpooled, gh.dw, gh.db, B, 128, s));
@@ -193,21 +202,21 @@ int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const FeatView& v, const float
     const float* up = (l == 2) ? dpooled : (const float*)(ws + pl.dh[l]);
     dc.layer = 1 + l;
     DFA_HIP_CHECK(ctx, launch_cm_bn_bwd(l == 2 ? 0 : 1, (const float*)(ws + pl.z[l]), bn_apply(st, layer_params(m.p, l)), up, partial, sm, dz,
-                                        B, C[l], T, dc, s, ctx->bn_sync.fn ? &ctx->bn_sync : nullptr, lens, m.train_frames));
+                                        B, C[l], T, dc, s, step.synced ? &ctx->bn_sync : nullptr, lens, step.frames));
     DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, C[l], s));
     if (l == 0) {
       DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)v.x, v.sb, v.sf, v.st, partial, g.dw, g.db, B, F, 32, T, s,
-                                             m.train_aug.on ? &m.train_aug : nullptr, m.train_x3, lens));
+                                             step.aug.on ? &step.aug : nullptr, step.x3, lens));
     } else {
       DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)(ws + pl.h[l - 1]), (int64_t)Cin[l] * T, T, 1, partial, g.dw,
-                                             g.db, B, Cin[l], C[l], T, s, nullptr, m.train_x3));
+                                             g.db, B, Cin[l], C[l], T, s, nullptr, step.x3));
       // data gradient: dh[l-1] = conv1d(dz; W'[Cin][Cout][3]) -- a Conv1d with Cout input channels, Cin output channels
       float* dh = (float*)(ws + pl.dh[l - 1]);
-      const int terms = (m.train_x3 == 3) ? 2 : 3;
-      if (m.train_x3 && conv1d_x3_supports(dz, (int64_t)C[l] * T, T, 1, dh, T, C[l], Cin[l], terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3(dz, (int64_t)C[l] * T, m.wx3[l == 2 ? 3 : 4], m.zero_bias, dh, B, C[l], Cin[l], T, terms, s, m.train_x3));
+      const int terms = (step.x3 == 3) ? 2 : 3;
+      if (step.x3 && conv1d_x3_supports(dz, (int64_t)C[l] * T, T, 1, dh, T, C[l], Cin[l], terms))
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(dz, (int64_t)C[l] * T, tr.wx3[l == 2 ? 3 : 4], tr.zero_bias, dh, B, C[l], Cin[l], T, terms, s, step.x3));
       else
-        DFA_HIP_CHECK(ctx, launch_conv1d(dz, (int64_t)C[l] * T, T, 1, m.wt[l - 1], m.zero_bias, dh, B, C[l], Cin[l], T, false, s, false));
+        DFA_HIP_CHECK(ctx, launch_conv1d(dz, (int64_t)C[l] * T, T, 1, tr.wt[l - 1], tr.zero_bias, dh, B, C[l], Cin[l], T, false, s, false));
     }
   }
   return DFA_OK;
@@ -268,7 +277,8 @@ int dfa_cnn1d_forward_train_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int
   TraceRange trace_("dfa_cnn1d_forward_train_ragged");
   if (!ctx) return DFA_E_NULL_PTR;
   if (!lengths) {
-    ctx->cnn1d.aug_armed = AugCfg{};      // one-shot, as in every forward_train
+    ctx->cnn1d.train.aug_armed = AugCfg{};      // one-shot, as in every forward_train; and the batch in flight is over
+    ctx->cnn1d.train.step.live = false;
     return fail(ctx, DFA_E_NULL_PTR, "lengths must be non-null");
   }
   return cnn1d_forward_train_impl(ctx, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T_max, F}, lengths, p_drop, seed, offset, momentum,

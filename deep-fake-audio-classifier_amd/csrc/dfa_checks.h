@@ -52,8 +52,9 @@ inline int check_channel_major(dfa_ctx* ctx, const char* who, const char* cname,
   return DFA_OK;
 }
 
-// dfa_<model>_backward: the forward_train of the same batch in flight, no null pointer, [float32 x], the gradient count, no null
-// gradient, the workspace's size (`need`, a callable that forms the plan: only once B and T are known to be the forward's)
+// dfa_<model>_backward: the model's step record matches the call (train_step.h: match_step), no null pointer, [float32 x], the
+// gradient count, no null gradient, the workspace's size (`need`, a callable that forms the plan: only once the shape is known to
+// be the forward's), the model's own later checks (`late`, a callable returning a code), the SyncBN hook as the forward found it
 struct BackwardNames {
   const char* bwd;        // "dfa_cnn2d_backward"
   const char* fwd;        // "dfa_cnn2d_forward_train"
@@ -62,10 +63,11 @@ struct BackwardNames {
   const char* upstream;   // "dlogits"; nullptr where the upstream gradient may be null
   bool f32_only;          // x must be float32 (x_dtype is not looked at otherwise)
 };
-template <typename Need>
-int check_backward(dfa_ctx* ctx, const BackwardNames& w, bool in_flight, const void* x, int x_dtype, const void* upstream,
-                   float* const* grads, int ngrads, const void* workspace, size_t have, Need need) {
-  if (!in_flight) return fail(ctx, DFA_E_NOT_PREPARED, "%s must follow %s on the same batch", w.bwd, w.fwd);
+template <typename Need, typename Late>
+int check_backward(dfa_ctx* ctx, const BackwardNames& w, const TrainStep& step, int B, int T, int F, int ragged, const void* x, int x_dtype,
+                   const void* upstream, float* const* grads, int ngrads, const void* workspace, size_t have, Need need, Late late) {
+  const StepVerdict verdict = match_step(step, {B, T, F, x_dtype, ragged, ctx->bn_sync.fn != nullptr}, w.f32_only);
+  if (verdict == STEP_OTHER_BATCH) return fail(ctx, DFA_E_NOT_PREPARED, "%s must follow %s on the same batch", w.bwd, w.fwd);
   if (w.upstream) {
     if (!x || !upstream || !grads || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, %s, grads and workspace must be non-null", w.upstream);
   } else if (!x || !grads || !workspace) {
@@ -76,8 +78,13 @@ int check_backward(dfa_ctx* ctx, const BackwardNames& w, bool in_flight, const v
   for (int i = 0; i < w.nparams; ++i)
     if (!grads[i]) return fail(ctx, DFA_E_NULL_PTR, "gradient pointer %d is null", i);
   if (have < need()) return fail(ctx, DFA_E_WORKSPACE, "train workspace too small");
+  DFA_TRY(late());
+  if (verdict == STEP_HOOK_CHANGED)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the SyncBN hook changed between %s and %s: dfa_ctx_set_bn_sync was %s since the forward", w.fwd, w.bwd,
+                step.synced ? "cleared" : "armed");
   return DFA_OK;
 }
+inline int no_late_checks() { return DFA_OK; }
 
 // dfa_<model>_set_params: null context / array, the pointer count, the model's own dimension rules (`dims`, a callable returning
 // a code, run at their place between the two), no null pointer; then the pointers are bound to the model's slot `state`
@@ -92,6 +99,7 @@ int set_params_core(dfa_ctx* ctx, State dfa_ctx::*state, const char* name, const
     if (!device_params[i]) return fail(ctx, DFA_E_NULL_PTR, "%s parameter %d is null", name, i);
   for (int i = 0; i < n; ++i) m.p[i] = device_params[i];
   m.have_params = true;
+  m.train.step.live = false;      // a backward never runs with other weights than its forward's
   return DFA_OK;
 }
 

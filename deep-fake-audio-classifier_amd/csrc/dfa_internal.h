@@ -14,6 +14,7 @@
 #include "conv123_host.h"
 #include "launch_views.h"
 #include "rng.h"
+#include "train_step.h"
 
 namespace dfa {
 
@@ -45,10 +46,9 @@ static_assert(DFA_CNN2D_NPARAMS == n_params(kCnn2dLayers, 1) && DFA_CNN1D_NPARAM
               DFA_CAE_NPARAMS == n_params(kCaeLayers, 1) && DFA_DLQ_NPARAMS == n_params(kDlqLayers, 2), "parameter arrays: 6 per layer + the head");
 static_assert(kCnn2dGrads == 14 && kCnn1dGrads == 14 && kCaeGrads == 30 && kDlqGrads == 16, "gradient arrays (dfa_hip.h): 4 per layer + the head");
 
-struct Cnn2dState {
-  const float* p[DFA_CNN2D_NPARAMS] = {nullptr};
-  bool have_params = false;
-  int in_features = 0;
+// A model's slot in the context: the bound parameters, the eval part (folded images, dfa_<model>_prepare) and the train part (the
+// per-step weight images of forward_train / backward and the step record, train_step.h).  release() frees the train part's allocations.
+struct Cnn2dEval {
   int prepared_prec = -1;
   void* packed = nullptr;  // one device allocation holding everything below
   size_t packed_bytes = 0;
@@ -58,17 +58,20 @@ struct Cnn2dState {
   float* c1bias = nullptr; // [32]
   uint4* c3_m16 = nullptr; // block 3 weights in the 16x16x32 operand order (conv3_m16.hip), bf16 mode only
   PackedConv c2, c3;
-  // train mode (train_api.hip)
+};
+struct Cnn2dTrain {          // train_api.hip
   void* train_packed = nullptr;
   float *tw1 = nullptr, *tb1 = nullptr;   // conv1 folded with the current batch statistics
   PackedConv t2, t3, d2, d3;              // raw forward images and data-gradient images
-  DropCfg train_drop{};
   AugCfg aug_armed{};                     // dfa_cnn2d_set_train_augment: consumed by the next forward_train
-  AugCfg train_aug{};                     // the augmentation of the forward_train in flight (its backward re-reads x through it)
-  int train_prec = -1, train_B = 0, train_T = 0;
-  int train_c1_fused = 0;                 // the forward left XX / Xs behind for the one-pass conv1 backward
-  int train_c1_mfma = 0;                  // this step's block-1 passes ran on train_conv1_mfma.hip
-  int train_dgrad_m16 = 0;                // the d2/d3 images are in the 16x16x32 order of conv_split.hip (bf16 mode)
+  TrainStep step;
+  void release() { if (train_packed) (void)hipFree(train_packed); train_packed = nullptr; }
+};
+struct Cnn2dState : Cnn2dEval {
+  const float* p[DFA_CNN2D_NPARAMS] = {nullptr};
+  bool have_params = false;
+  int in_features = 0;
+  Cnn2dTrain train;
 };
 
 // Synchronised BatchNorm for data-parallel training ("SyncBN via two small all-reduces per layer -- makes
@@ -89,31 +92,34 @@ hipError_t bn_sync_sums(const BnSync* sy, const float* sums, int count, hipStrea
 hipError_t bn_bwd_sums(const float* partial, int nrec, int C, float* sums, float* scratch, const BnSync* sync, hipStream_t s,
                        const float** sums_apply, float* inv_n);
 
-struct Cnn1dState {
-  const float* p[DFA_CNN1D_NPARAMS] = {nullptr};
-  bool have_params = false;
+struct Cnn1dEval {
   bool prepared = false;
-  int in_features = 0;
   void* packed = nullptr;
   float *w[3] = {nullptr, nullptr, nullptr}, *b[3] = {nullptr, nullptr, nullptr};
   float* wp[3] = {nullptr, nullptr, nullptr};   // MFMA A-fragment images of the folded weights (cnn1d_fused.hip)
   void* wx[3] = {nullptr, nullptr, nullptr};    // hi / lo bf16 A-fragment images (cnn1d_fused_x3.hip)
-  // train mode: data-gradient weight images of conv layers 2 and 3 (+ a zero bias), dropout state
-  void* train_packed = nullptr;
+};
+struct Cnn1dTrain {          // cnn1d_train_api.hip
+  void* train_packed = nullptr;   // data-gradient weight images of conv layers 2 and 3 (+ a zero bias)
   float *wt[2] = {nullptr, nullptr}, *zero_bias = nullptr;
-  int wx3_F = 0, train_x3 = 0;
-  void* wx3[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // per-step bf16x3 A-fragment images: forward layers 1-3, data gradients 3->2, 2->1 (conv1d_x3_kernel)
-  DropCfg train_drop{};
-  int train_B = 0, train_T = 0;
-  int train_ragged = 0;       // the forward_train in flight was dfa_cnn1d_forward_train_ragged (its table sits behind the plan in the workspace)
-  double train_frames = 0.0;  // ... and its frame count, the sum of the lengths
-  AugCfg aug_armed{};   // dfa_cnn1d_set_train_augment: consumed by the next forward_train
-  AugCfg train_aug{};   // the augmentation of the forward_train in flight (the layer-1 weight gradient re-reads x through it)
+  int wx3_F = 0;
+  void* wx3[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // per-step bf16x3 A-fragment images: forward layers 1-3, data gradients 3->2, 2->1 (conv1d_x3_kernel); wx3[0] = their one allocation
+  AugCfg aug_armed{};             // dfa_cnn1d_set_train_augment: consumed by the next forward_train
+  TrainStep step;
+  void release() {
+    if (train_packed) (void)hipFree(train_packed);
+    if (wx3[0]) (void)hipFree(wx3[0]);
+    train_packed = wx3[0] = nullptr;
+  }
+};
+struct Cnn1dState : Cnn1dEval {
+  const float* p[DFA_CNN1D_NPARAMS] = {nullptr};
+  bool have_params = false;
+  int in_features = 0;
+  Cnn1dTrain train;
 };
 
-struct CaeState {
-  const float* p[DFA_CAE_NPARAMS] = {nullptr};
-  bool have_params = false;
+struct CaeEval {
   int prepared_prec = -1;
   void* packed = nullptr;
   float *w1 = nullptr, *b1 = nullptr;
@@ -123,31 +129,39 @@ struct CaeState {
   float* c1bias = nullptr;     // [32] 0.5 * folded bias
   uint4* dec4pack = nullptr;   // decoder block 4 as MFMA A operands [4][64] (cae_dec_fused.hip)
   float* opad_cst = nullptr;   // [16] reconstruction constants of the output_padding columns (cae_dec_fused.hip)
-  // train mode (cae_train_api.hip): raw forward images, data-gradient images, raw ConvTranspose2d images
+};
+struct CaeTrain {            // cae_train_api.hip: raw forward images, data-gradient images, raw ConvTranspose2d images
   void* train_packed = nullptr;
   float *tw1 = nullptr, *tb1 = nullptr;
-  int train_c1_mfma = 0;       // this step's block-1 passes run on the matrix cores (train_conv1_mfma.hip, 2x2-pool backward)
-  int train_dgrad_m16 = 0;     // this step's 64 -> 32 and 128 -> 64 data-gradient images are in the 16x16x32 order of conv_split.hip (bf16 mode)
-  int train_enc4_wide = 0;     // this step's block-4 forward / data-gradient images are 128-input-channel ones (bf16 mode, option cae_enc4_wide)
   PackedConv tenc[3], tdg[3], tdec[3];
-  int train_prec = -1, train_B = 0, train_T = 0;
+  TrainStep step;
+  void release() { if (train_packed) (void)hipFree(train_packed); train_packed = nullptr; }
+};
+struct CaeState : CaeEval {
+  const float* p[DFA_CAE_NPARAMS] = {nullptr};
+  bool have_params = false;
+  CaeTrain train;
 };
 
-// DeepfakeDetector eval forward (dlq.hip, dlq_api.hip)
-struct DlqState {
-  const float* p[DFA_DLQ_NPARAMS] = {nullptr};
-  bool have_params = false;
+// DeepfakeDetector (dlq.hip, dlq_api.hip)
+struct DlqEval {
   bool prepared = false;
-  int in_ch = 0;
   void* packed = nullptr;                       // one device allocation: the three A-fragment images, then the folded biases
   void* w[3] = {nullptr, nullptr, nullptr};     // three-term bf16 A-fragment images, BatchNorm folded
   float* b[3] = {nullptr, nullptr, nullptr};    // folded biases [256]
-  // train mode (dlq_train_api.hip): this step's raw weight images -- forward layers 1-3, data gradients 3 -> 2 and 2 -> 1
+};
+struct DlqTrain {            // dlq_train_api.hip: this step's raw weight images -- forward layers 1-3, data gradients 3 -> 2 and 2 -> 1
   void* train_packed = nullptr;
   void* tw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int tw_in_ch = 0;
-  int train_B = 0, train_T = 0;                 // the forward_train in flight (0: none); its dropout key
-  DropCfg train_drop{};
+  TrainStep step;
+  void release() { if (train_packed) (void)hipFree(train_packed); train_packed = nullptr; }
+};
+struct DlqState : DlqEval {
+  const float* p[DFA_DLQ_NPARAMS] = {nullptr};
+  bool have_params = false;
+  int in_ch = 0;
+  DlqTrain train;
 };
 
 }  // namespace dfa

@@ -85,7 +85,8 @@ int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_
   TraceRange trace_("dfa_dlq_forward_train");
   if (!ctx) return DFA_E_NULL_PTR;
   DlqState& m = ctx->dlq;
-  m.train_B = 0;                                 // a refused forward leaves none in flight
+  DlqTrain& tr = m.train;
+  tr.step.live = false;                          // a refused forward leaves none in flight
   if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_dlq_set_params has not been called");
   if (!x || !logits || !workspace || !lengths) return fail(ctx, DFA_E_NULL_PTR, "x, lengths, logits and workspace must be non-null");
   DFA_TRY(check_dlq_shape(ctx, B, T_max, in_ch));
@@ -100,22 +101,22 @@ int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_
   DFA_TRY(refuse_capture(ctx, "training step"));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  if (!m.train_packed || m.tw_in_ch != in_ch) {
-    if (m.train_packed) { DFA_HIP_CHECK(ctx, hipStreamSynchronize(s)); DFA_HIP_CHECK(ctx, hipFree(m.train_packed)); m.train_packed = nullptr; }
+  if (!tr.train_packed || tr.tw_in_ch != in_ch) {
+    if (tr.train_packed) { DFA_HIP_CHECK(ctx, hipStreamSynchronize(s)); DFA_HIP_CHECK(ctx, hipFree(tr.train_packed)); tr.train_packed = nullptr; }
     Bump take;
     size_t off[5];
     off[0] = take(dlq_pack_bytes(in_ch, 5));
     for (int q = 1; q < 5; ++q) off[q] = take(dlq_pack_bytes(HID, 3));
-    DFA_HIP_CHECK(ctx, hipMalloc(&m.train_packed, take.off));
-    for (int q = 0; q < 5; ++q) m.tw[q] = (char*)m.train_packed + off[q];
-    m.tw_in_ch = in_ch;
+    DFA_HIP_CHECK(ctx, hipMalloc(&tr.train_packed, take.off));
+    for (int q = 0; q < 5; ++q) tr.tw[q] = (char*)tr.train_packed + off[q];
+    tr.tw_in_ch = in_ch;
   }
   DFA_TRY(stage_ragged_lengths(ctx, lengths, B, workspace));
   char* ws = (char*)workspace;
   const long long N = (long long)B * T_max;
   {
     ScopedSlot ts(ctx, 8);
-    DFA_HIP_CHECK(ctx, launch_dlq_train_pack(layer_params(m.p, 0).w, layer_params(m.p, 1).w, layer_params(m.p, 2).w, m.tw, in_ch, s));
+    DFA_HIP_CHECK(ctx, launch_dlq_train_pack(layer_params(m.p, 0).w, layer_params(m.p, 1).w, layer_params(m.p, 2).w, tr.tw, in_ch, s));
   }
   DropCfg dc = drop_cfg(p_drop, seed, offset);
   DlqLayerArgs a{};
@@ -130,7 +131,7 @@ int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_
     {
       ScopedSlot ts(ctx, 9);
       a.hin = l ? (const uint4*)(ws + pl.h[l - 1]) : nullptr;
-      a.w = (const uint4*)m.tw[l]; a.bias = q.b;
+      a.w = (const uint4*)tr.tw[l]; a.bias = q.b;
       a.C = l ? HID : in_ch; a.nks = dlq_nks(a.C);
       a.zout = (float*)(ws + pl.z[l]);
       DFA_HIP_CHECK(ctx, launch_dlq_layer_train(l + 1, 1, a, pl.ntiles, s));
@@ -153,8 +154,10 @@ int dfa_dlq_forward_train(dfa_ctx* ctx, const void* x, int B, int T_max, int in_
     h.drop = dc;
     DFA_HIP_CHECK(ctx, launch_dlq_pool_head(h, B, s));
   }
-  m.train_drop = dc;
-  m.train_B = B; m.train_T = T_max;
+  TrainStep step;                                  // committed last: live only once every launch above went out
+  step.B = B; step.T = T_max; step.F = in_ch; step.x_dtype = DFA_DTYPE_F32; step.drop = dc;
+  step.live = true;
+  tr.step = step;
   return DFA_OK;
 }
 
@@ -162,15 +165,17 @@ int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, i
                      float* const* grads, int ngrads, void* workspace, size_t workspace_bytes) {
   TraceRange trace_("dfa_dlq_backward");
   if (!ctx) return DFA_E_NULL_PTR;
-  DlqState& m = ctx->dlq;
+  const DlqState& m = ctx->dlq;
+  const DlqTrain& tr = m.train;
   DlqTrainPlan pl;
-  DFA_TRY(check_backward(ctx, {"dfa_dlq_backward", "dfa_dlq_forward_train", "the DeepfakeDetector", kDlqGrads, "dlogits", false},
-                         m.train_packed && m.train_B > 0 && m.train_B == B && m.train_T == T_max && m.in_ch == in_ch, x, DFA_DTYPE_F32, dlogits,
-                         grads, ngrads, workspace, workspace_bytes, [&] { return (pl = plan_dlq_train(B, T_max, in_ch)).total; }));
-  DFA_TRY(check_channel_major(ctx, "DeepfakeDetector training step", "stride_c", x, stride_b, stride_c, T_max));
-  if (ctx->bn_sync.fn)
-    return fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector training step is single-rank in this version: it cannot run under synchronised "
-                                        "BatchNorm (dfa_ctx_set_bn_sync is armed)");
+  DFA_TRY(check_backward(
+      ctx, {"dfa_dlq_backward", "dfa_dlq_forward_train", "the DeepfakeDetector", kDlqGrads, "dlogits", false}, tr.step, B, T_max, in_ch, 0, x,
+      DFA_DTYPE_F32, dlogits, grads, ngrads, workspace, workspace_bytes, [&] { return (pl = plan_dlq_train(B, T_max, in_ch)).total; },
+      [&] {
+        DFA_TRY(check_channel_major(ctx, "DeepfakeDetector training step", "stride_c", x, stride_b, stride_c, T_max));
+        return !ctx->bn_sync.fn ? DFA_OK : fail(ctx, DFA_E_UNSUPPORTED, "the DeepfakeDetector training step is single-rank in this version: it cannot "
+                                                                        "run under synchronised BatchNorm (dfa_ctx_set_bn_sync is armed)");
+      }));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   char* ws = (char*)workspace;
@@ -181,7 +186,7 @@ int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, i
   float* scratch = (float*)(ws + pl.scratch);
   float* dy = (float*)(ws + pl.dy);
   float* dbrec = (float*)(ws + pl.dbrec);
-  DropCfg dc = m.train_drop;
+  DropCfg dc = tr.step.drop;
   {
     ScopedSlot ts(ctx, 11);
     const HeadGrads g0 = head_grads(grads, kDlqLayers, 0), g3 = head_grads(grads, kDlqLayers, 1);
@@ -218,7 +223,7 @@ int dfa_dlq_backward(dfa_ctx* ctx, const void* x, int B, int T_max, int in_ch, i
       const BnApply below = bn_apply(st_dlq(ws, pl, l - 1), layer_params(m.p, l - 1));
       DlqLayerArgs a{};
       a.tab = lens; a.B = B; a.T_max = T_max; a.tpu = pl.tpu; a.C = HID; a.nks = 16;
-      a.hin = (const uint4*)(ws + pl.dz); a.w = (const uint4*)m.tw[l == 2 ? 3 : 4];
+      a.hin = (const uint4*)(ws + pl.dz); a.w = (const uint4*)tr.tw[l == 2 ? 3 : 4];
       a.zout = dy; a.rec = rec;
       a.zprev = (const float*)(ws + pl.z[l - 1]); a.st_mean = below.mean; a.st_invstd = below.invstd; a.gamma = below.gamma; a.beta = below.beta;
       dc.layer = l;

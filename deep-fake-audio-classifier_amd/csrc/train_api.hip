@@ -55,11 +55,11 @@ BnStats stat_ptrs(char* ws, const TrainPlan& pl, int layer) { return bn_stats(ws
 float* sums_ptr(char* ws, const TrainPlan& pl, int layer) { return bn_sums(ws + pl.sums, kBnOff[layer]); }
 
 // block 1 of a step: what conv1_train_stats (forward) and conv1_train_backward (backward, da = da1) take
-Conv1Train conv1_block(Cnn2dState& m, const FeatView& v, char* ws, const TrainPlan& pl, const DropCfg& dc) {
+Conv1Train conv1_block(const Cnn2dState& m, const TrainStep& step, const FeatView& v, char* ws, const TrainPlan& pl, const DropCfg& dc) {
   float* c1rec = (float*)(ws + pl.sums) + 2 * (32 + 64 + 128);      // [32][11] record, then XX[9][9] | Xs[9]
   Conv1Train c{};
-  c.v = v; c.prec = m.train_prec; c.poolw = 1;
-  c.drop = dc; c.aug = m.train_aug.on ? &m.train_aug : nullptr; c.p = layer_params(m.p, 0); c.fw = m.tw1; c.fb = m.tb1;
+  c.v = v; c.prec = step.prec; c.poolw = 1;
+  c.drop = dc; c.aug = step.aug.on ? &step.aug : nullptr; c.p = layer_params(m.p, 0); c.fw = m.train.tw1; c.fb = m.train.tb1;
   c.partial = (float*)(ws + pl.partial); c.stats_scratch = true; c.xxs = c1rec + 352; c.c1rec = c1rec;
   c.sums = sums_ptr(ws, pl, 0); c.stats = stat_ptrs(ws, pl, 0); c.da = ws + pl.da1;
   return c;
@@ -106,11 +106,13 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   TraceRange trace_("dfa_cnn2d_forward_train");
   if (!ctx) return DFA_E_NULL_PTR;
   Cnn2dState& m = ctx->cnn2d;
+  Cnn2dTrain& tr = m.train;
   // The augmentation armed by dfa_cnn2d_set_train_augment is one-shot and belongs to THIS call: it is taken (and the arm cleared)
-  // before any check can return, so a failed forward never leaves it armed for an unrelated later batch.
-  const AugCfg armed = m.aug_armed;
-  m.aug_armed = AugCfg{};
-  m.train_aug = AugCfg{};
+  // before any check can return, so a failed forward never leaves it armed for an unrelated later batch.  The step record
+  // likewise: whatever this call returns, the batch that was in flight is over.
+  const AugCfg armed = tr.aug_armed;
+  tr.aug_armed = AugCfg{};
+  tr.step.live = false;
   if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn2d_set_params has not been called");
   if (!x || !logits || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, logits and workspace must be non-null");
   if (x_dtype != DFA_DTYPE_F32 && x_dtype != DFA_DTYPE_BF16) return fail(ctx, DFA_E_BAD_DTYPE, "x dtype %d not supported", x_dtype);
@@ -121,57 +123,59 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total, true, "train "));
   DFA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // train-mode weight images: raw convs (BN is its own pass) + data-gradient images; rebuilt every step (weights move)
-  if (!m.train_packed) {
+  if (!tr.train_packed) {
     const size_t w2 = (size_t)64 * 32 * 9 * 4, w3 = (size_t)128 * 64 * 9 * 4;
     Bump take;
     const size_t small = take((288 + 32 + 64 + 128 + 32 + 64) * 4), t2 = take(w2), t3 = take(w3), d2 = take(w2), d3 = take(w3);
-    DFA_HIP_CHECK(ctx, hipMalloc(&m.train_packed, take.off));
-    char* base = (char*)m.train_packed;
-    m.tw1 = (float*)(base + small); m.tb1 = m.tw1 + 288;
-    m.t2.bias = m.tb1 + 32; m.t3.bias = m.t2.bias + 64;
-    m.d2.bias = m.t3.bias + 128; m.d3.bias = m.d2.bias + 32;
-    m.t2.wpack = (uint4*)(base + t2); m.t3.wpack = (uint4*)(base + t3);
-    m.d2.wpack = (uint4*)(base + d2); m.d3.wpack = (uint4*)(base + d3);
+    DFA_HIP_CHECK(ctx, hipMalloc(&tr.train_packed, take.off));
+    char* base = (char*)tr.train_packed;
+    tr.tw1 = (float*)(base + small); tr.tb1 = tr.tw1 + 288;
+    tr.t2.bias = tr.tb1 + 32; tr.t3.bias = tr.t2.bias + 64;
+    tr.d2.bias = tr.t3.bias + 128; tr.d3.bias = tr.d2.bias + 32;
+    tr.t2.wpack = (uint4*)(base + t2); tr.t3.wpack = (uint4*)(base + t3);
+    tr.d2.wpack = (uint4*)(base + d2); tr.d3.wpack = (uint4*)(base + d3);
   }
   const FeatView v{x, x_dtype, stride_b, stride_t, stride_f, B, T, F};
   const LayerParams l2 = layer_params(m.p, 1), l3 = layer_params(m.p, 2);
   const HeadParams head = head_params(m.p, kCnn2dLayers, 0);
   hipStream_t s = ctx->stream;
   const int prec = precision;
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(l2), 32, 0, 32, 64, prec, m.t2.wpack, m.t2.bias, s));
-  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(l3), 64, 0, 64, 128, prec, m.t3.wpack, m.t3.bias, s));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(l2), 32, 0, 32, 64, prec, tr.t2.wpack, tr.t2.bias, s));
+  DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3(raw_conv(l3), 64, 0, 64, 128, prec, tr.t3.wpack, tr.t3.bias, s));
   // bf16: the 16x16x32 image of the same raw weights, in the unused second half of the (fp32-sized) t3 buffer
-  uint4* t3_m16 = (uint4*)((char*)m.t3.wpack + (size_t)128 * 64 * 9 * 2);
+  uint4* t3_m16 = (uint4*)((char*)tr.t3.wpack + (size_t)128 * 64 * 9 * 2);
   const bool fwd3_m16 = prec == DFA_PREC_BF16 && ctx->train_conv_variant != 1;   // 2: pipelined, 0: its compiler-scheduled twin
   if (fwd3_m16)
     DFA_HIP_CHECK(ctx, launch_fold_pack_conv3x3_m16(raw_conv(l3), 64, 128, t3_m16, s));
-  m.train_dgrad_m16 = (prec == DFA_PREC_BF16 && ctx->dgrad_m16) ? 1 : 0;
-  DFA_TRY(pack_dgrad_images(ctx, l2.w, l3.w, prec, m.train_dgrad_m16, m.d2, m.d3));
+  TrainStep step;              // this call's record: committed to tr.step by the last statement
+  step.B = B; step.T = T; step.F = F; step.prec = prec; step.x_dtype = x_dtype; step.synced = ctx->bn_sync.fn != nullptr;
+  step.dgrad_m16 = (prec == DFA_PREC_BF16 && ctx->dgrad_m16) ? 1 : 0;
+  DFA_TRY(pack_dgrad_images(ctx, l2.w, l3.w, prec, step.dgrad_m16, tr.d2, tr.d3));
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
   DropCfg dc = drop_cfg(p_drop, seed, offset);
-  m.train_drop = dc; m.train_prec = prec; m.train_B = B; m.train_T = T;
+  step.drop = dc;
   // ---- block 1
   // augmentation armed by dfa_cnn2d_set_train_augment: one-shot, folded into the three kernels that read x
-  m.train_aug = armed;
-  const AugCfg* aug = m.train_aug.on ? &m.train_aug : nullptr;
+  step.aug = armed;
+  const AugCfg* aug = step.aug.on ? &step.aug : nullptr;
   // synchronised BatchNorm needs the layer's (sum dy, sum dy*xhat) BEFORE the weight gradient is formed: block 1 then takes the
   // two-pass vector path (reduce -> hook -> weight gradient), not the one-pass moment algebra
-  m.train_c1_fused = (ctx->conv1_bwd_fused && !ctx->bn_sync.fn) ? 1 : 0;
+  step.c1_fused = (ctx->conv1_bwd_fused && !step.synced) ? 1 : 0;
   // matrix-core passes: bf16 mode on bf16 features without a folded augmentation (its noise makes x non-bf16), fused backward
   // (the backward reads da1 with the dropout keep mask already applied by the 16x16x32 data-gradient kernel)
-  m.train_c1_mfma = (ctx->conv1_mfma && m.train_c1_fused && prec == DFA_PREC_BF16 && x_dtype == DFA_DTYPE_BF16 && !aug && F <= 224 &&
-                     (dc.thresh == 0 || m.train_dgrad_m16)) ? 1 : 0;
-  DFA_TRY(conv1_train_stats(ctx, conv1_block(m, v, ws, pl, dc), m.train_c1_mfma, m.train_c1_fused, update_running_stats != 0, momentum));
+  step.c1_mfma = (ctx->conv1_mfma && step.c1_fused && prec == DFA_PREC_BF16 && x_dtype == DFA_DTYPE_BF16 && !aug && F <= 224 &&
+                (dc.thresh == 0 || step.dgrad_m16)) ? 1 : 0;
+  DFA_TRY(conv1_train_stats(ctx, conv1_block(m, step, v, ws, pl, dc), step.c1_mfma, step.c1_fused, update_running_stats != 0, momentum));
   dc.layer = 1;
-  if (m.train_c1_mfma)
-    DFA_HIP_CHECK(ctx, launch_conv1_mfma(C1X_FWD, v, m.tw1, m.tb1, ws + pl.a1, nullptr, nullptr, dc, 1, s));
+  if (step.c1_mfma)
+    DFA_HIP_CHECK(ctx, launch_conv1_mfma(C1X_FWD, v, tr.tw1, tr.tb1, ws + pl.a1, nullptr, nullptr, dc, 1, s));
   else
-    DFA_HIP_CHECK(ctx, launch_conv1(v, m.tw1, m.tb1, ws + pl.a1, prec, s, &dc, aug));
+    DFA_HIP_CHECK(ctx, launch_conv1(v, tr.tw1, tr.tb1, ws + pl.a1, prec, s, &dc, aug));
   // ---- block 2
   const int nstrips = (F + 31) / 32;
   {
-    ConvArgs a = conv_args(ws + pl.a1, m.t2, ws + pl.z2, B, pl.H1, F, 64, ctx);
+    ConvArgs a = conv_args(ws + pl.a1, tr.t2, ws + pl.z2, B, pl.H1, F, 64, ctx);
     a.stats_partial = partial;
     DFA_HIP_CHECK(ctx, launch_train_fwd2(prec, a, s, ctx->train_conv_variant));
   }
@@ -181,7 +185,7 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   DFA_HIP_CHECK(ctx, launch_bn_relu_pool_drop(prec, ws + pl.z2, bn_apply(s2, l2), ws + pl.a2, B, pl.H1, F, 64, dc, s));
   // ---- block 3
   {
-    ConvArgs a = conv_args(ws + pl.a2, m.t3, ws + pl.z3, B, pl.H2, F, 128, ctx);
+    ConvArgs a = conv_args(ws + pl.a2, tr.t3, ws + pl.z3, B, pl.H2, F, 128, ctx);
     a.stats_partial = partial;
     if (fwd3_m16) {
       a.wpack = t3_m16;
@@ -197,6 +201,8 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
   DFA_HIP_CHECK(ctx, launch_bn_relu_meant(prec, ws + pl.z3, bn_apply(s3, l3), emb, B, pl.H2, F, 128, s, (float*)(ws + pl.msum)));
   if (embedding) DFA_HIP_CHECK(ctx, hipMemcpyAsync(embedding, emb, (size_t)B * 128 * F * 4, hipMemcpyDeviceToDevice, s));
   DFA_HIP_CHECK(ctx, launch_linear(emb, head.w, head.b, logits, B, 128 * F, s));
+  step.live = true;
+  tr.step = step;
   return DFA_OK;
 }
 
@@ -205,23 +211,24 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
                        size_t workspace_bytes) {
   TraceRange trace_("dfa_cnn2d_backward");
   if (!ctx) return DFA_E_NULL_PTR;
-  Cnn2dState& m = ctx->cnn2d;
-  const int prec = m.train_prec;
+  const Cnn2dState& m = ctx->cnn2d;
+  const Cnn2dTrain& tr = m.train;
+  const TrainStep& step = tr.step;
+  const int prec = step.prec;
   TrainPlan pl;
-  DFA_TRY(check_backward(ctx, {"dfa_cnn2d_backward", "dfa_cnn2d_forward_train", "cnn2d", kCnn2dGrads, "dlogits", false},
-                         m.train_packed && m.train_B == B && m.train_T == T, x, x_dtype, dlogits, grads, ngrads, workspace, workspace_bytes,
-                         [&] { return (pl = plan_train(B, T, F, prec)).total; }));
+  DFA_TRY(check_backward(ctx, {"dfa_cnn2d_backward", "dfa_cnn2d_forward_train", "cnn2d", kCnn2dGrads, "dlogits", false}, step, B, T, F, 0, x, x_dtype,
+                         dlogits, grads, ngrads, workspace, workspace_bytes, [&] { return (pl = plan_train(B, T, F, prec)).total; }, no_late_checks));
   char* ws = (char*)workspace;
   float* partial = (float*)(ws + pl.partial);
   const LayerParams l2 = layer_params(m.p, 1), l3 = layer_params(m.p, 2);
   const LayerGrads g2 = layer_grads(grads, 1), g3 = layer_grads(grads, 2);
   const HeadGrads gh = head_grads(grads, kCnn2dLayers, 0);
   hipStream_t s = ctx->stream;
-  DropCfg dc = m.train_drop;
+  DropCfg dc = step.drop;
   BnStats s2 = stat_ptrs(ws, pl, 1), s3 = stat_ptrs(ws, pl, 2);
   float *sm2 = sums_ptr(ws, pl, 1), *sm3 = sums_ptr(ws, pl, 2);
   float* demb = (float*)(ws + pl.demb);
-  const dfa::BnSync* sync = ctx->bn_sync.fn ? &ctx->bn_sync : nullptr;     // synchronised BatchNorm (dfa_ctx_set_bn_sync)
+  const dfa::BnSync* sync = step.synced ? &ctx->bn_sync : nullptr;           // synchronised BatchNorm (dfa_ctx_set_bn_sync)
   // classifier
   DFA_HIP_CHECK(ctx, launch_linear_bwd(dlogits, head_params(m.p, kCnn2dLayers, 0).w, (const float*)(ws + pl.emb), demb, gh.dw, gh.db, B, 128 * F, s, 128, F));
   // block 3: BN backward (upstream = mean_T then Linear), weight gradient, data gradient
@@ -229,7 +236,7 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
                                                sm3, ws + pl.dz3, B, pl.H2, F, 128, s, sync));
   DFA_HIP_CHECK(ctx, launch_split_sums(sm3, g3.dgamma, g3.dbeta, 128, s));
   DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 64, 128, ws + pl.dz3, ws + pl.a2, partial, g3.dw, g3.db, B, pl.H2, F, kWgradWGs, s, ctx->wgrad_variant));
-  DFA_HIP_CHECK(ctx, launch_dgrad3(m.train_dgrad_m16, prec, conv_args(ws + pl.dz3, m.d3, ws + pl.da2, B, pl.H2, F, 64, ctx), (float*)(ws + pl.raw), s, ctx->train_conv_variant));
+  DFA_HIP_CHECK(ctx, launch_dgrad3(step.dgrad_m16, prec, conv_args(ws + pl.dz3, tr.d3, ws + pl.da2, B, pl.H2, F, 64, ctx), (float*)(ws + pl.raw), s, ctx->train_conv_variant));
   // block 2
   dc.layer = 2;
   {
@@ -241,14 +248,14 @@ int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
   DFA_HIP_CHECK(ctx, launch_split_sums(sm2, g2.dgamma, g2.dbeta, 64, s));
   DFA_HIP_CHECK(ctx, launch_wgrad3x3(prec, 32, 64, ws + pl.dz2, ws + pl.a1, partial, g2.dw, g2.db, B, pl.H1, F, kWgradWGs, s, ctx->wgrad_variant));
   {
-    ConvArgs a = conv_args(ws + pl.dz2, m.d2, ws + pl.da1, B, pl.H1, F, 32, ctx);
-    if (m.train_c1_mfma) { a.drop = dc; a.drop.layer = 1; }   // keep mask of a1's dropout where da1 is produced (idempotent for the vector kernel)
-    DFA_HIP_CHECK(ctx, launch_dgrad2(m.train_dgrad_m16, prec, a, s, ctx->train_conv_variant));
+    ConvArgs a = conv_args(ws + pl.dz2, tr.d2, ws + pl.da1, B, pl.H1, F, 32, ctx);
+    if (step.c1_mfma) { a.drop = dc; a.drop.layer = 1; }   // keep mask of a1's dropout where da1 is produced (idempotent for the vector kernel)
+    DFA_HIP_CHECK(ctx, launch_dgrad2(step.dgrad_m16, prec, a, s, ctx->train_conv_variant));
   }
   // block 1 (z1 recomputed from x; conv1_mfma may be cleared between forward and backward: the vector kernel reads the same state)
   dc.layer = 1;
-  return conv1_train_backward(ctx, conv1_block(m, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T, F}, ws, pl, dc),
-                              m.train_c1_mfma && ctx->conv1_mfma, m.train_c1_fused, sync, layer_grads(grads, 0));
+  return conv1_train_backward(ctx, conv1_block(m, step, FeatView{x, x_dtype, stride_b, stride_t, stride_f, B, T, F}, ws, pl, dc),
+                              step.c1_mfma && ctx->conv1_mfma, step.c1_fused, sync, layer_grads(grads, 0));
 }
 
 // shared by the CNN2D and CNN1D entry points: validate, copy the keep mask into the context's double buffer, fill `armed`
@@ -290,7 +297,7 @@ int dfa_cnn2d_set_train_augment(dfa_ctx* ctx, int enable, int T, int F, int shif
                                 int tmask_len, int fmask_start, int fmask_len, float jitter_std, uint64_t seed,
                                 uint64_t offset) {
   if (!ctx) return DFA_E_NULL_PTR;
-  return arm_train_augment(ctx, ctx->cnn2d.aug_armed, enable, T, F, shift, keep_f, tmask_start, tmask_len, fmask_start, fmask_len,
+  return arm_train_augment(ctx, ctx->cnn2d.train.aug_armed, enable, T, F, shift, keep_f, tmask_start, tmask_len, fmask_start, fmask_len,
                            jitter_std, seed, offset);
 }
 
@@ -298,7 +305,7 @@ int dfa_cnn1d_set_train_augment(dfa_ctx* ctx, int enable, int T, int F, int shif
                                 int tmask_len, int fmask_start, int fmask_len, float jitter_std, uint64_t seed,
                                 uint64_t offset) {
   if (!ctx) return DFA_E_NULL_PTR;
-  return arm_train_augment(ctx, ctx->cnn1d.aug_armed, enable, T, F, shift, keep_f, tmask_start, tmask_len, fmask_start, fmask_len,
+  return arm_train_augment(ctx, ctx->cnn1d.train.aug_armed, enable, T, F, shift, keep_f, tmask_start, tmask_len, fmask_start, fmask_len,
                            jitter_std, seed, offset);
 }
 

@@ -1,8 +1,9 @@
 // train_host.h -- what the training steps of the C ABI share on the host (train_api.hip, cnn1d_train_api.hip, cae_train_api.hip,
 // dlq_train_api.hip): the bump that carves plans and allocations, the BatchNorm accessors and finalize, the ConvArgs / DropCfg fills,
 // the data-gradient images and launches, the block-1 passes of the CNN2D and the auto-encoder.  Features, a layer's parameters and
-// gradients, running statistics and BatchNorm terms travel as the views of launch_views.h.  Host only; int-returning helpers go in
-// DFA_TRY.
+// gradients, running statistics and BatchNorm terms travel as the views of launch_views.h; what a backward must know about its
+// forward is the model's TrainStep (train_step.h), matched by check_backward (dfa_checks.h).  Host only; int-returning helpers go
+// in DFA_TRY.
 #pragma once
 #include "dfa_checks.h"
 

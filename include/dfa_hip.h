@@ -254,7 +254,13 @@ int dfa_cnn2d_forward_train(dfa_ctx* ctx, const void* x, int x_dtype, int B, int
 /* gradients of the 14 parameters w.r.t. sum_b dlogits[b]*logit[b], written (not accumulated) to grads[0..13] in
  * parameters() order: conv.0.{weight,bias}, conv.1.{weight,bias}, conv.5.*, conv.6.*, conv.10.*, conv.11.*,
  * classifier.{weight,bias}.  Pointing grads[] into ONE flat buffer gives the single all-reduce payload of data-parallel
- * training (464,644 bytes). */
+ * training (464,644 bytes).
+ * The rule of all four pairs (CNN2D, CNN1D uniform and ragged, auto-encoder, DeepfakeDetector): dfa_<model>_backward must follow
+ * its own forward on the same workspace and shape (else DFA_E_NOT_PREPARED) -- B, T, F (T_max, in_ch), x_dtype and the ragged or
+ * uniform form are the forward's.  The forward it follows is the model's LATEST dfa_<model>_forward_train call, and only if that
+ * call returned DFA_OK: a forward refused by an argument check, or one that failed, ends the batch that was in flight, and so
+ * does dfa_<model>_set_params.  A backward, refused or completed, ends nothing: it may be called again.  The SyncBN hook must be
+ * what the forward found: a dfa_ctx_set_bn_sync that armed or cleared it between the two calls is DFA_E_UNSUPPORTED. */
 int dfa_cnn2d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
                        int64_t stride_t, int64_t stride_f, const float* dlogits, float* const* grads, int ngrads,
                        void* workspace, size_t workspace_bytes);
@@ -299,7 +305,8 @@ int dfa_cnn1d_set_train_augment(dfa_ctx* ctx, int enable, int T, int F, int shif
  * tensor that owns buf does) and returns 0.  dgamma / dbeta stay the rank's own sums: the flat-gradient all-reduce adds them.
  * Block 1 of the CNN2D / auto-encoder then runs the two-pass vector backward (the one-pass moment algebra needs the sums too late).
  * fn = NULL: local statistics (torch DistributedDataParallel's default; what dfa_amd.train / train_cae use unless --sync-bn is given).
- * Set it before a forward_train; it stays in force until changed. */
+ * Set it before a forward_train; it stays in force until changed, and a backward whose forward ran under another setting is
+ * refused (DFA_E_UNSUPPORTED). */
 typedef int (*dfa_bn_sync_fn)(void* user, float* buf, int count);
 int dfa_ctx_set_bn_sync(dfa_ctx* ctx, dfa_bn_sync_fn fn, void* user, int world, float* buf, int capacity);
 /* one torch.optim.AdamW step over a flat fp32 buffer: p *= 1-lr*wd; m,v update; p -= lr/bc1 * m/(sqrt(v)/sqrt(bc2)+eps).

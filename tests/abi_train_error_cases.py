@@ -6,10 +6,11 @@ replays them and compares).
 The rules are those of tests/abi_error_cases.py, whose Rig this one extends: every case is refused by an argument check BEFORE
 any launch, in the order the entry point makes its checks; every pointer is live and large enough for the call to run in full
 (neither recon nor mse, which dfa_cae_forward_train names in its own text, and neither loss nor drecon of dfa_mse_fwd_bwd are
-the null-pointer cases the list needs); every case leaves the context as it found it -- the SyncBN hook cleared with fn = NULL,
-no augmentation left armed.  A backward can only be refused for its own arguments after a forward_train of its model has run,
-so the list makes four successful forward_train calls (CNN2D, CNN1D uniform, CNN1D ragged, auto-encoder) at the shapes below,
-each when the first case that needs it comes up; they are its only launches.
+the null-pointer cases the list needs); every case leaves the SyncBN hook cleared with fn = NULL and no augmentation armed.
+A backward can only be refused for its own arguments after a forward_train of its model has run, so the rig makes a successful
+forward_train (CNN2D, CNN1D uniform, CNN1D ragged, auto-encoder) at the shapes below whenever a case needs one in flight and
+none is; and after every refused backward, record() runs the valid backward of the batch in flight, which must return 0: a
+refusal leaves the step record as it was.  Those forwards and backwards are the list's only launches.
 
 Shapes: B = 2; F = 20 and T = 8 for the classifiers; F = 20, T = 32 for the auto-encoder.  The training plans carry a
 weight-gradient partial of about 76 MB whatever the batch: the workspace is twice the largest dfa_*_train_workspace_bytes."""
@@ -19,6 +20,7 @@ import torch
 
 from abi_error_cases import B, F, F_WIDE, PREC_BF16, T, T_CAE, Rig, _p
 
+F_CAE_OTHER = 36              # the auto-encoder's other legal feature dimension (16 k + 4)
 NGRADS = {"cnn2d": 14, "cnn1d": 14, "cae": 30}
 G_FLOATS = 1 << 19            # floats behind every gradient pointer: more than the largest parameter (256 x 128 x 9)
 HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
@@ -40,13 +42,15 @@ class TrainRig(Rig):
         self.grads = (C.c_void_p * max(NGRADS.values()))(*[self.gbuf.data_ptr() + 4 * G_FLOATS * i for i in range(max(NGRADS.values()))])
         self.dout = torch.zeros(1 << 16, dtype=torch.float32, device=dev)      # dlogits / drecon / loss
         self.hook_buf = torch.zeros(512, dtype=torch.float32, device=dev)
-        self._hook = HOOK(lambda user, buf, count: 0)                           # never reached by a refused call
-        self.inflight = dict.fromkeys(NGRADS)                                   # model -> kind of its latest successful forward_train
+        self._hook = HOOK(lambda user, buf, count: 0)                           # world 1: the local sums are the global ones
+        self.hook_armed = False
+        self.inflight = dict.fromkeys(NGRADS)                                   # model -> kind of the forward_train its step record holds live
         torch.cuda.synchronize()
 
-    # ---- state: the parent's, plus "fwd" / "fwd_ragged" = bound and that forward_train is the model's latest successful one.
-    # `inflight` only changes here: a refused forward_train returns before it touches the batch it has in flight, and the list
-    # keeps every forward_train case of a model before its first backward case (asserted below CASES) ---------------------------
+    # ---- state: the parent's, plus "fwd" / "fwd_ragged" = bound and that forward_train is in flight: the model's latest
+    # forward_train call, successful, with no set_params and no change of the SyncBN hook since.  Whatever ends a batch in flight
+    # resets `inflight` (every forward_train call, refused ones included; set_params; arming or clearing the hook) and need()
+    # makes the next one.  The list keeps every forward_train case of a model before its first backward case (asserted below CASES)
     def need(self, model, state):
         if state not in ("fwd", "fwd_ragged"):
             return super().need(model, state)
@@ -55,6 +59,11 @@ class TrainRig(Rig):
             rc = self.cnn1d_fwd(ragged=True) if state == "fwd_ragged" else getattr(self, model + "_fwd")()
             assert rc == 0, self.last_error()
             self.inflight[model] = state
+
+    def set_params(self, model, n=None, **dims):
+        if model in self.inflight:
+            self.inflight[model] = None
+        return super().set_params(model, n, **dims)
 
     def restore(self):
         """what a case may leave behind: an armed hook or augmentation"""
@@ -77,11 +86,13 @@ class TrainRig(Rig):
         return a
 
     def cnn2d_fwd(self, **kw):
+        self.inflight["cnn2d"] = None
         a = self._args(kw, prec=PREC_BF16)
         return self.lib.dfa_cnn2d_forward_train(*self._head(a), a["prec"], a["p_drop"], 1, 0, 0.1, 0, _p(self.out.data_ptr()), None,
                                                 *self._ws(a))
 
     def cnn1d_fwd(self, ragged=False, **kw):
+        self.inflight["cnn1d"] = None
         a = self._args(kw)
         tail = (a["p_drop"], 1, 0, 0.1, 0, _p(self.out.data_ptr()), *self._ws(a))
         if ragged:
@@ -89,6 +100,7 @@ class TrainRig(Rig):
         return self.lib.dfa_cnn1d_forward_train(*self._head(a), *tail)
 
     def cae_fwd(self, **kw):
+        self.inflight["cae"] = None
         a = self._args(kw, T=T_CAE, prec=PREC_BF16, recon=self.aux.data_ptr(), mse=self.out.data_ptr())
         return self.lib.dfa_cae_forward_train(*self._head(a), a["prec"], 0.1, 0, _p(a["recon"]), None, _p(a["mse"]), *self._ws(a))
 
@@ -104,8 +116,14 @@ class TrainRig(Rig):
 
     def arm_hook(self, fn="hook", world=1, capacity=512):
         if fn is None:
-            return self.lib.dfa_ctx_set_bn_sync(self.ctx, None, None, 1, None, 0)
-        return self.lib.dfa_ctx_set_bn_sync(self.ctx, C.cast(self._hook, C.c_void_p), None, world, _p(self.hook_buf.data_ptr()), capacity)
+            rc = self.lib.dfa_ctx_set_bn_sync(self.ctx, None, None, 1, None, 0)
+        else:
+            rc = self.lib.dfa_ctx_set_bn_sync(self.ctx, C.cast(self._hook, C.c_void_p), None, world, _p(self.hook_buf.data_ptr()), capacity)
+        armed = fn is not None and rc == 0          # (a refused call leaves the hook cleared)
+        if armed != self.hook_armed:
+            self.inflight = dict.fromkeys(NGRADS)
+        self.hook_armed = armed
+        return rc
 
     def bce(self, smoothing=0.1, B=B):
         d = self.dout.data_ptr()
@@ -129,6 +147,23 @@ def _armed(r, model, call, **aug):
 def _hooked(r, call):
     assert r.arm_hook() == 0
     return call(r)
+
+
+def _after(r, model, what):
+    """the backward of a forward_train that `what` came after: a set_params, or a forward_train refused by an argument check"""
+    if what == "set_params":
+        assert r.set_params(model) == 0
+    else:
+        assert getattr(r, model + "_fwd")(B=0) != 0
+    return r.bwd(model)
+
+
+def _hook_cleared(r):
+    """a CNN2D forward_train under the rig's do-nothing hook (world 1), its backward with the hook cleared"""
+    assert r.arm_hook() == 0
+    assert r.cnn2d_fwd() == 0, r.last_error()
+    assert r.arm_hook(fn=None) == 0
+    return r.bwd("cnn2d")
 
 
 def _cases():
@@ -198,7 +233,15 @@ def _cases():
             add(f"{pre}/x_dtype", model, "fwd", lambda r: r.bwd("cnn1d", dtype=1))
         add(f"{pre}/gradient_count", model, "fwd", lambda r, m=model: r.bwd(m, ngrads=NGRADS[m] - 1))
         ws_small(pre, model, "fwd", lambda r, m=model, **kw: r.bwd(m, **kw))
+        add(f"{pre}/other_F", model, "fwd", lambda r, m=model: r.bwd(m, F=F_CAE_OTHER if m == "cae" else F_WIDE))
+        if model != "cnn1d":
+            add(f"{pre}/other_x_dtype", model, "fwd", lambda r, m=model: r.bwd(m, dtype=1))
+        add(f"{pre}/after_set_params", model, "fwd", lambda r, m=model: _after(r, m, "set_params"))
+        add(f"{pre}/after_refused_forward", model, "fwd", lambda r, m=model: _after(r, m, "refused_forward"))
+        add(f"{pre}/hook_armed_since_forward", model, "fwd", lambda r, m=model: _hooked(r, lambda r: r.bwd(m)))
+    add("cnn2d_backward/hook_cleared_since_forward", "cnn2d", "fwd", _hook_cleared)
     add("cnn1d_backward/after_ragged_forward", "cnn1d", "fwd_ragged", lambda r: r.bwd("cnn1d"))
+    add("cnn1d_backward_ragged/other_F", "cnn1d", "fwd_ragged", lambda r: r.bwd("cnn1d", ragged=True, F=F_WIDE))
     add("cnn1d_backward_ragged/bn_sync_armed", "cnn1d", "fwd_ragged", lambda r: _hooked(r, lambda r: r.bwd("cnn1d", ragged=True)))
     # ---- augmentation arming, SyncBN hook, losses, optimiser --------------------------------------------------------------------------------
     for model in ("cnn2d", "cnn1d"):
@@ -241,6 +284,9 @@ def record():
             rc = fn(rig)
             rows.append([cid, int(rc), rig.last_error()])
             rig.restore()
+            if state in ("fwd", "fwd_ragged"):      # the refused backward left the record alone: the valid one still runs
+                rig.need(model, state)
+                assert rig.bwd(model, ragged=state == "fwd_ragged") == 0, (cid, rig.last_error())
     finally:
         rig.close()
     return rows

@@ -266,8 +266,8 @@ def test_abi_refusals_name_the_argument_and_leave_the_gradients():
         return lib.dfa_dlq_forward_train(h, _lib.ptr(x), B_, T_, C_, sb_, sc_, C.c_void_p(ln.ctypes.data), 0.0, 1, 0, 0.1, 1, _lib.ptr(logits),
                                          None, _lib.ptr(ws), nb)
 
-    def bwd(B_=B, n=16):
-        return lib.dfa_dlq_backward(h, _lib.ptr(x), B_, T, C_in, sb, sc, _lib.ptr(dl), _lib.ptr_array(grads), n, _lib.ptr(ws), nbytes)
+    def bwd(B_=B, n=16, C_=C_in):
+        return lib.dfa_dlq_backward(h, _lib.ptr(x), B_, T, C_, sb, sc, _lib.ptr(dl), _lib.ptr_array(grads), n, _lib.ptr(ws), nbytes)
 
     def refused(code, want, *words):
         msg = lib.dfa_last_error(h).decode()
@@ -300,11 +300,16 @@ def test_abi_refusals_name_the_argument_and_leave_the_gradients():
     assert fwd() == 0, lib.dfa_last_error(h).decode()
     refused(bwd(n=15), _lib.E_BAD_SHAPE, "16", "15")
     refused(bwd(B_=B + 1), _lib.E_NOT_PREPARED, "dfa_dlq_forward_train")
+    refused(bwd(C_=C_in - 4), _lib.E_NOT_PREPARED, "dfa_dlq_forward_train")  # another in_ch than the forward's (a smaller plan)
     torch.cuda.synchronize()
     assert all(bool((g == 3.0).all()) for g in grads)                      # no refused call wrote a gradient
     assert bwd() == 0, lib.dfa_last_error(h).decode()                      # and the next valid one succeeds
     torch.cuda.synchronize()
     assert all(bool(torch.isfinite(g).all()) and not bool((g == 3.0).all()) for g in grads)
+    _lib.check(h, lib.dfa_dlq_set_params(h, _lib.ptr_array(ts), len(ts), C_in, 256))
+    refused(bwd(), _lib.E_NOT_PREPARED, "dfa_dlq_forward_train")           # set_params ends the batch in flight
+    assert fwd() == 0 and bwd() == 0, lib.dfa_last_error(h).decode()       # and the next pair runs
+    torch.cuda.synchronize()
     hh = C.c_void_p()
     assert lib.dfa_ctx_create(ctx.index, None, C.byref(hh)) == 0             # parameters not set: a context of its own
     try:
