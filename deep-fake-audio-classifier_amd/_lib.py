@@ -20,6 +20,7 @@ E_BAD_SHAPE, E_BAD_DTYPE, E_NULL_PTR, E_NOT_PREPARED, E_HIP, E_WORKSPACE, E_UNSU
 DTYPE_F32, DTYPE_BF16 = 0, 1
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 MODEL_CNN2D, MODEL_CNN1D, MODEL_CAE = 0, 1, 2
+EMB_OCSVM, EMB_GMM, EMB_MAX_P, EMB_MAX_K = 0, 1, 256, 64
 PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "float32": PREC_F32, "bf16": PREC_BF16, "bfloat16": PREC_BF16,
               "bf16x3": PREC_BF16X3}
 
@@ -116,6 +117,12 @@ SYMBOLS = [
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t]),
     ("dfa_bce_pos_weight_fwd_bwd", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     ("dfa_clip_grad_norm", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]),
+    ("dfa_emb_ocsvm_bind", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),
+    ("dfa_emb_gmm_bind", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    ("dfa_emb_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dfa_emb_ocsvm_score", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("dfa_emb_gmm_score", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]),
     ("dfa_cnn1d_ragged_segments", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.c_int]),
     ("dfa_cnn1d_ragged_lds_bytes", C.c_size_t, [C.c_int, C.c_int]),

@@ -104,7 +104,7 @@ int dfa_ctx_create(int device_id, void* hip_stream, dfa_ctx** out) {
 int dfa_ctx_destroy(dfa_ctx* ctx) {
   if (!ctx) return DFA_E_NULL_PTR;
   (void)hipSetDevice(ctx->device);
-  for (void* p : {ctx->cnn2d.packed, ctx->cnn1d.packed, ctx->cae.packed, ctx->dlq.packed})
+  for (void* p : {ctx->cnn2d.packed, ctx->cnn1d.packed, ctx->cae.packed, ctx->dlq.packed, (void*)ctx->emb_ocsvm.svn, ctx->emb_gmm.image})
     if (p) (void)hipFree(p);
   ctx->cnn2d.train.release(); ctx->cnn1d.train.release(); ctx->cae.train.release(); ctx->dlq.train.release();
   if (ctx->clip_partial) (void)hipFree(ctx->clip_partial);

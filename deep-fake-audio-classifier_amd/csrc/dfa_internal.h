@@ -164,6 +164,23 @@ struct DlqState : DlqEval {
   DlqTrain train;
 };
 
+// Embedding anomaly detectors (emb_score.hip, emb_api.hip): the caller's arrays as bound (remembered, not copied) and the image the
+// context owns beside them -- |sv_i|^2; prec_chol transposed and the mixture means, both zero-padded to P_pad
+struct EmbOcsvm {
+  bool bound = false;
+  int D = 0, n_sv = 0;
+  const float *mean = nullptr, *inv_scale = nullptr, *sv = nullptr, *coef = nullptr;
+  float gamma = 0.f, intercept = 0.f;
+  float* svn = nullptr;      // [n_sv], the image
+};
+struct EmbGmm {
+  bool bound = false;
+  int D = 0, P = 0, K = 0;
+  const float *mean = nullptr, *inv_scale = nullptr, *pca_mean = nullptr, *comp = nullptr, *log_const = nullptr;
+  void* image = nullptr;     // one allocation: LT, then mpad
+  float *LT = nullptr, *mpad = nullptr;   // [K][P_pad][P_pad], [K][P_pad]
+};
+
 }  // namespace dfa
 
 struct dfa_ctx {
@@ -222,6 +239,8 @@ struct dfa_ctx {
   dfa::Cnn1dState cnn1d;
   dfa::CaeState cae;
   dfa::DlqState dlq;
+  dfa::EmbOcsvm emb_ocsvm;
+  dfa::EmbGmm emb_gmm;
   unsigned timing = 0;         // bit s set: record HIP events around the launches of timing slot s
   dfa::SlotTimer slots[dfa::kMaxSlots];
 };
@@ -555,5 +574,16 @@ hipError_t launch_cae_enc4(int prec, const ConvArgs& a, float* raw_tmp, hipStrea
 hipError_t launch_cae_enc_ragged(int layer, const ConvArgs& a, const RaggedTab& rt, hipStream_t s);
 hipError_t launch_cae_dec(int prec, int cin, const ConvTArgs& a, hipStream_t s);
 int cae_dec_stats_records(int prec, int cin, long P);
+// emb_score.hip: the split of the reduction over D (a function of D and the column count M alone: a row's score does not depend on
+// the batch it is scored in), P rounded up to the GEMM frame's stage, and the launches of the two detectors
+struct EmbSplit { int klen, nsplit; };
+EmbSplit emb_split(int D, int M);
+inline int emb_ppad(int P) { return (P + 31) / 32 * 32; }
+hipError_t launch_emb_rownorm(const float* x, int64_t ld, int rows, int D, float* out, hipStream_t s);
+hipError_t launch_emb_pack_gmm(const float* prec_chol, const float* means, int P, int K, float* LT, float* mpad, hipStream_t s);
+// part: [nsplit][N][n_sv] floats
+hipError_t launch_emb_ocsvm(const EmbOcsvm& d, const float* emb, int N, int64_t ld, float* part, float* out, hipStream_t s);
+// zpart: [nsplit][N][P], z: [N][P_pad], y: [K][N][P] floats
+hipError_t launch_emb_gmm(const EmbGmm& d, const float* emb, int N, int64_t ld, float* zpart, float* z, float* y, float* out, hipStream_t s);
 
 }  // namespace dfa

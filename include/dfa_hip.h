@@ -563,6 +563,49 @@ int dfa_bce_pos_weight_fwd_bwd(dfa_ctx* ctx, const float* logits, const float* l
  * then grad *= min(1, max_norm / (norm + 1e-6)).  norm_out: device float[1] (the norm before clipping) or NULL. */
 int dfa_clip_grad_norm(dfa_ctx* ctx, float* grad, size_t n, float max_norm, float* norm_out);
 
+/* ---- embedding anomaly detectors (replace the scoring half of src/embedding_anomaly.py:129-163) ---------
+ * The reference fits a StandardScaler, a OneClassSVM and a PCA + GaussianMixture on the bonafide CNN2D embeddings with sklearn
+ * (a one-off on the host: dfa_amd/embedding_anomaly.py does the same) and scores with decision_function / score_samples.
+ * Here a fitted detector is plain fp32 device arrays, and the scores are computed from the embedding rows where
+ * dfa_cnn2d_forward[_ragged] left them: emb[n] = emb + n stride_n, D = 128 * F floats each.  The scaler is applied as the rows are
+ * staged (x~ = (x - mean) inv_scale, inv_scale = 1 / scale_ with sklearn's scale_ = 1 on a zero-variance column); every product
+ * runs on the exact-fp32 matrix cores (v_mfma_f32_32x32x2_f32).  No atomics: the reduction over D is split by a rule of D and the
+ * column count alone and summed in that order, so out[n] is bit for bit a function of row n -- the same scored alone, in any
+ * batch, at any position, in any run.
+ *
+ * dfa_emb_ocsvm_bind (OneClassSVM(kernel="rbf").decision_function, :136-140): sv[n_sv][D] = support_vectors_ (already scaled),
+ *   dual_coef[n_sv] = dual_coef_[0], gamma = _gamma, intercept = intercept_[0];
+ *   out[n] = sum_i dual_coef[i] exp(-gamma |x~_n - sv_i|^2) + intercept, the distance as |x~|^2 + |sv|^2 - 2 x~ . sv.
+ * dfa_emb_gmm_bind (PCA.transform + GaussianMixture("full").score_samples, :147-161): pca_mean[D] = mean_, components[P][D] =
+ *   components_, means[K][P] = means_, prec_chol[K][P][P] = precisions_cholesky_, log_const[K] = sum log diag(prec_chol[k]) +
+ *   log weights_[k] - P log(2 pi) / 2;
+ *   z = (x~ - pca_mean) components^T, y_k = (z - means[k]) prec_chol[k], out[n] = logsumexp_k(-|y_k|^2 / 2 + log_const[k]).
+ * Both remember the pointers (not copied) and build an image the context owns (|sv_i|^2; prec_chol transposed and the means,
+ * zero-padded) on the context's stream: bind again when an array moves or changes; dfa_ctx_destroy frees the images.  One
+ * detector of each kind per context.  DFA_E_BAD_SHAPE: D not 128 * F with F >= 1, n_sv < 1, P outside [1, DFA_EMB_MAX_P], K
+ * outside [1, DFA_EMB_MAX_K]; DFA_E_NULL_PTR names the array; DFA_E_UNSUPPORTED: gamma <= 0, mean / inv_scale / sv / dual_coef /
+ * pca_mean / components not 16-byte aligned, a capturing stream (the image is allocated).  A refused bind leaves that detector
+ * unbound.
+ *
+ * dfa_emb_ocsvm_score / dfa_emb_gmm_score: emb device fp32, 16-byte aligned, stride_n >= D and a multiple of 4; out device
+ * float[N]; workspace device, 256-byte aligned, >= dfa_emb_workspace_bytes(detector, N, D, M, K) with M = n_sv (K ignored) or
+ * M = P (the planner returns 0 for a shape the calls refuse).  Nothing is copied per call: both may be captured.  Two launches
+ * (OC-SVM), four (GMM: one product for all K components).  DFA_E_NOT_PREPARED: no successful bind; DFA_E_BAD_SHAPE: N < 1, D not
+ * the bound D, stride_n < D; DFA_E_WORKSPACE: a short or misaligned workspace; DFA_E_NULL_PTR names emb, out or workspace. */
+#define DFA_EMB_OCSVM 0
+#define DFA_EMB_GMM 1
+#define DFA_EMB_MAX_P 256
+#define DFA_EMB_MAX_K 64
+int dfa_emb_ocsvm_bind(dfa_ctx* ctx, int D, int n_sv, const float* mean, const float* inv_scale, const float* sv, const float* dual_coef,
+                       float gamma, float intercept);
+int dfa_emb_gmm_bind(dfa_ctx* ctx, int D, int P, int K, const float* mean, const float* inv_scale, const float* pca_mean,
+                     const float* components, const float* means, const float* prec_chol, const float* log_const);
+size_t dfa_emb_workspace_bytes(int detector, int N, int D, int M, int K);
+int dfa_emb_ocsvm_score(dfa_ctx* ctx, const float* emb, int N, int D, int64_t stride_n, float* out, void* workspace,
+                        size_t workspace_bytes);
+int dfa_emb_gmm_score(dfa_ctx* ctx, const float* emb, int N, int D, int64_t stride_n, float* out, void* workspace,
+                      size_t workspace_bytes);
+
 /* ---- shared ------------------------------------------------------------------------------------ */
 size_t dfa_workspace_bytes(const dfa_ctx* ctx, int model, int B, int T, int F, int precision);
 /* workspace of dfa_cnn2d_forward_ragged / dfa_cnn1d_forward_ragged for B utterances padded to T_max frames (0 for a model
