@@ -21,6 +21,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 MODEL_CNN2D, MODEL_CNN1D, MODEL_CAE = 0, 1, 2
 EMB_OCSVM, EMB_GMM, EMB_MAX_P, EMB_MAX_K = 0, 1, 256, 64
+NORM_CMN, NORM_CVMN, UTT_NORM_HELD_FRAMES, UTT_NORM_MAX_PACKED = 1, 2, 1024, 65536
 PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "float32": PREC_F32, "bf16": PREC_BF16, "bfloat16": PREC_BF16,
               "bf16x3": PREC_BF16X3}
 
@@ -115,6 +116,11 @@ SYMBOLS = [
     ("dfa_dlq_gather_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("dfa_dlq_gather_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t]),
+    ("dfa_utt_norm_workspace_bytes", C.c_size_t, [C.c_int]),
+    ("dfa_utt_norm", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                               C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("dfa_utt_norm_packed", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_size_t]),
     ("dfa_bce_pos_weight_fwd_bwd", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     ("dfa_clip_grad_norm", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]),
     ("dfa_emb_ocsvm_bind", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),

@@ -1,5 +1,5 @@
 // dfa_checks.h -- the argument checks the C ABI's entry points share (api.hip, cnn2d_api.hip, cnn1d_api.hip, cae_api.hip, dlq_api.hip,
-// emb_api.hip, train_api.hip, cnn1d_train_api.hip, cae_train_api.hip, dlq_train_api.hip).
+// emb_api.hip, utt_norm_api.hip, train_api.hip, cnn1d_train_api.hip, cae_train_api.hip, dlq_train_api.hip).
 // Host code only.  Every helper returns DFA_OK or the code it left, with its text, in the context (dfa::fail); an entry point
 // wraps it in DFA_TRY.  The wording belongs to the entry points: where it differs between them it comes in as an argument.
 #pragma once

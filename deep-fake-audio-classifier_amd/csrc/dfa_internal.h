@@ -370,6 +370,12 @@ hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, con
 int stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void* dst);
 // the same with `extra` words the caller supplies behind them: [2B, 2B + extra) (words = 2 B + extra)
 int stage_ragged_lengths_extra(dfa_ctx* ctx, const int32_t* lengths, int B, const int32_t* extra, size_t n_extra, void* dst);
+// utt_norm.hip: per-utterance CMN / CVMN (dfa_utt_norm).  tab: device table ([0, B) lengths; packed: [2B, 4B) float offsets, low
+// word then high word) or null (every row spans T_max)
+hipError_t launch_utt_norm_time(const float* x, float* y, const int* tab, int mode, int B, int C, int T_max, int64_t stride_b,
+                                int64_t stride_c, bool packed, hipStream_t s);
+hipError_t launch_utt_norm_feat(const float* x, float* y, const int* tab, int mode, int B, int C, int T_max, int64_t stride_b,
+                                int64_t stride_t, hipStream_t s);
 // cnn2d_api.hip, cnn1d_api.hip, cae_api.hip: the models' planners behind dfa_workspace_bytes and dfa_ragged_workspace_bytes
 // (api.hip), for B, T, F >= 1.  ctx may be null (CNN2D: the plan of the default options); ragged: T = T_max, the table included
 size_t cnn2d_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, int prec, bool ragged);

@@ -249,17 +249,23 @@ class ResidentBatcher:
     are 23 GB in fp32, so for the reference's data sets the host never takes part in an epoch again -- the loop runs at the speed
     of the training step (the host-fed IndexedFlatBatcher delivers ~100 k utterances/s per rank; the CNN1D step consumes 430 k).
     Same interface and batch contents as IndexedFlatBatcher(features, labels, indices, batch_size): `epoch(indices)` returns the
-    iterable for one epoch's index order (dataloaders.train_shard_indices)."""
+    iterable for one epoch's index order (dataloaders.train_shard_indices).
+    norm: "cmn" / "cvmn" normalise every stored utterance [180, 321] over its frames (normalization.normalize_batch) as its
+    chunk arrives, in float32 and before any rounding to bf16: once per set, nothing per epoch."""
 
     def __init__(self, features: torch.Tensor, labels: torch.Tensor | None, batch_size: int, device="cuda",
-                 dtype: torch.dtype | None = None, chunk_rows: int = 2048):
-        self.device, self.batch_size = torch.device(device), int(batch_size)
+                 dtype: torch.dtype | None = None, chunk_rows: int = 2048, norm: str = "raw"):
+        from .normalization import check_mode, normalize_batch
+        self.device, self.batch_size, self.norm = torch.device(device), int(batch_size), check_mode(norm)
         n = features.shape[0]
         store = dtype or features.dtype
         self.features = torch.empty((n, *features.shape[1:]), dtype=store, device=self.device)
         for lo in range(0, n, chunk_rows):                   # bounded host staging: the source is a memory map
             hi = min(n, lo + chunk_rows)
-            self.features[lo:hi].copy_(features[lo:hi].to(self.device, non_blocking=False))
+            chunk = features[lo:hi].to(self.device, non_blocking=False)
+            if norm != "raw":                                # the stored [n, F, T] chunk as the [n, T, F] batch the call takes
+                chunk = normalize_batch(chunk.float().transpose(1, 2), norm).transpose(1, 2)
+            self.features[lo:hi].copy_(chunk)
         self.labels = None if labels is None else labels.to(self.device)
         self.bytes_resident = self.features.numel() * self.features.element_size()
 
@@ -310,10 +316,14 @@ class DlqResidentSet:
     What ResidentBatcher is to the equal-length models; utterances of unequal lengths and per-sample masks need a kernel.
 
     offsets / lengths: host numpy arrays (int64 / int32); labels: float32 device tensor, labels_host its numpy copy (or None);
-    set: the packed float32 device buffer (the floats T_i .. pitch_i of a row are unspecified); bytes_resident."""
+    set: the packed float32 device buffer (the floats T_i .. pitch_i of a row are unspecified); bytes_resident.
+    norm: "cmn" / "cvmn" normalise every utterance of the set in place, once, after the upload (dfa_utt_norm_packed): the gather's
+    SpecAugment spans then mask normalised data, the reference's order (its dataset normalises, its training loop masks)."""
 
-    def __init__(self, feature_list, labels=None, device="cuda", chunk_utts: int = 1024):
+    def __init__(self, feature_list, labels=None, device="cuda", chunk_utts: int = 1024, norm: str = "raw"):
         from . import _lib
+        from .normalization import check_mode, normalize_packed_
+        self.norm = check_mode(norm)
         self.device = torch.device(device)
         self.ctx = _lib.Context.get(self.device)               # (raises off the GPU: there is no CPU path)
         if len(feature_list) == 0:
@@ -339,6 +349,8 @@ class DlqResidentSet:
                 rows = host[int(self.offsets[i]) - base:int(ends[i]) - base].view(self.C, -1)
                 rows[:, :T] = torch.as_tensor(feature_list[i]).float()
             self.set[base:int(ends[hi - 1])].copy_(host)
+        with torch.cuda.device(self.ctx.index):
+            normalize_packed_(self.set, self.offsets, self.lengths, self.C, norm)
         self.labels_host = None if labels is None else np.asarray(labels, dtype=np.float32).reshape(-1)
         if self.labels_host is not None and self.labels_host.shape[0] != n:
             raise ValueError(f"got {self.labels_host.shape[0]} labels for {n} utterances")

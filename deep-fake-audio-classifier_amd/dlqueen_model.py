@@ -117,31 +117,39 @@ def _file_order_batches(feature_list, batch_size, device):
 
 
 @torch.no_grad()
-def run_inference(model, feature_list, batch_size: int = 32, device="cuda", use_prob: bool = False, file_order: bool = False):
+def run_inference(model, feature_list, batch_size: int = 32, device="cuda", use_prob: bool = False, file_order: bool = False,
+                  norm: str = "raw"):
     """Scores of a list of per-utterance [C, T_i] tensors, in input order, as one tensor on `device`.  Default: batches from
     dataloaders.RaggedBatcher (longest first, order restored) -- an utterance's padding class min(T - len, 2) can then differ
-    from the reference's file-order batches; file_order=True batches consecutive files as the reference does."""
+    from the reference's file-order batches; file_order=True batches consecutive files as the reference does.
+    norm: "cmn" / "cvmn" normalise every utterance over its own frames, in place in the batch's device copy."""
     from .dataloaders import RaggedBatcher
+    from .normalization import normalize_batch
     model.eval()
     outs = []
     if file_order:
         for x, lengths in _file_order_batches(feature_list, batch_size, device):
+            if norm != "raw":
+                xt = x.transpose(1, 2)
+                normalize_batch(xt, norm, lengths, out=xt)
             outs.append(model(x, lengths))
         scores = torch.cat(outs) if outs else torch.empty(0, device=device)
     else:
         batcher = RaggedBatcher(feature_list, None, batch_size, device=device, dtype=torch.float32)
         for xt, _, lengths in batcher:           # xt: [b, T_pad, C], the transposed view of the staged [b, C, T_pad] batch
             T = int(lengths.max())               # T_pad rounds the rows up to 16 bytes: the batch ends at its longest utterance
+            if norm != "raw":
+                normalize_batch(xt, norm, lengths, out=xt)
             outs.append(model(xt.transpose(1, 2)[:, :, :T], lengths))
         scores = batcher.restore(outs) if outs else torch.empty(0, device=device)
     return torch.sigmoid(scores) if use_prob else scores
 
 
 @torch.no_grad()
-def evaluate_eer(model, feature_list, labels, batch_size: int = 32, device="cuda", file_order: bool = False) -> float:
+def evaluate_eer(model, feature_list, labels, batch_size: int = 32, device="cuda", file_order: bool = False, norm: str = "raw") -> float:
     """EER of the logits against 0 / 1 labels (src/dlqueen_model.py:236-252)"""
     from .evaluation import calculate_eer
-    scores = run_inference(model, feature_list, batch_size, device=device, file_order=file_order).cpu().numpy()
+    scores = run_inference(model, feature_list, batch_size, device=device, file_order=file_order, norm=norm).cpu().numpy()
     eer, _thr = calculate_eer(np.asarray(scores, dtype=np.float64), np.asarray(labels))
     return float(eer)
 
@@ -149,7 +157,8 @@ def evaluate_eer(model, feature_list, labels, batch_size: int = 32, device="cuda
 @torch.no_grad()
 def run_inference_resident(model, rset, batch_size: int = 32, use_prob: bool = False):
     """run_inference(..., file_order=True) on a dataloaders.DlqResidentSet: the same file-order batches, assembled on the device
-    by the set's gather and read in place by the forward; the same scores, bit for bit."""
+    by the set's gather and read in place by the forward; the same scores, bit for bit.  (A set built with norm= holds
+    normalised utterances: nothing is normalised here.)"""
     model.eval()
     outs = []
     for lo in range(0, len(rset), batch_size):
@@ -182,6 +191,8 @@ def parse_args(argv=None):
     ap.add_argument("--use_prob", action="store_true", help="save sigmoid(prob) instead of logits")
     ap.add_argument("--file-order", dest="file_order", action="store_true",
                     help="batch consecutive files as the reference does (same padding classes) instead of sorting by length")
+    from .normalization import add_norm_argument
+    add_norm_argument(ap)         # not given: the checkpoint's "norm_mode", else raw (normalization.resolve_norm)
     args = ap.parse_args(argv)
     if args.epochs > 0:
         ap.exit(2, f"--epochs {args.epochs}: {_EVAL_ONLY}; train with `python -m dfa_amd.train_dlqueen` (or the reference) and pass its --ckpt_path\n")
@@ -202,9 +213,12 @@ def main(argv=None):
     if not os.path.exists(args.ckpt_path):
         raise FileNotFoundError(f"Checkpoint not found: {args.ckpt_path}")
     model = DeepfakeDetector(in_ch=int(feats[0].shape[0]), hidden=args.hidden, dropout=args.dropout)
-    model.load_state_dict(torch.load(args.ckpt_path, map_location="cpu"))
+    from .normalization import explicit_norm, resolve_norm
+    blob = torch.load(args.ckpt_path, map_location="cpu")
+    model.load_state_dict(blob["model_state"] if isinstance(blob, dict) and "model_state" in blob else blob)
+    norm = resolve_norm(explicit_norm(args), blob)
     model = model.to(args.device).eval()
-    logits = run_inference(model, feats, args.batch_size, device=args.device, file_order=args.file_order)
+    logits = run_inference(model, feats, args.batch_size, device=args.device, file_order=args.file_order, norm=norm)
     scores = torch.sigmoid(logits) if args.use_prob else logits
     pred = pd.DataFrame({"uttid": uttids, "predictions": [float(s) for s in scores.cpu().numpy()]})
     pred.to_pickle(args.prediction_pkl)

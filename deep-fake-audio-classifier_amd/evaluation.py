@@ -61,8 +61,9 @@ def confusion_at_threshold(scores, labels, threshold):
     return tp, fp, tn, fn, float(far), float(frr)
 
 
-def evaluate(model, dataloader, criterion=None, device="cuda", apply_sigmoid=False, swap_tf: bool = False):
+def evaluate(model, dataloader, criterion=None, device="cuda", apply_sigmoid=False, swap_tf: bool = False, norm: str = "raw"):
     """Run `model` over a labelled loader; returns (metrics{avg_loss, eer, threshold}, scores, labels).
+    norm: "cmn" / "cvmn" normalise each stored [b, F, T] batch on the device first (normalization.normalize_stored).
 
     Counterpart of src/evaluation.py:51-104.  Differences that do not change results: logits stay on the GPU until
     the end of the loop (one device->host copy instead of one `.item()`/`.tolist()` sync per batch).
@@ -75,6 +76,9 @@ def evaluate(model, dataloader, criterion=None, device="cuda", apply_sigmoid=Fal
         for features, batch_labels in dataloader:
             features = features.to(device, non_blocking=True)
             batch_labels = batch_labels.to(device, non_blocking=True)
+            if norm != "raw":
+                from .normalization import normalize_stored
+                features = normalize_stored(features, norm)
             if swap_tf:
                 features = features.transpose(1, 2)
             logits = model(features).squeeze(-1)
@@ -99,17 +103,21 @@ def evaluate(model, dataloader, criterion=None, device="cuda", apply_sigmoid=Fal
 
 def evaluate_sharded(model, features: torch.Tensor, labels: torch.Tensor, criterion=None, device="cuda",
                      apply_sigmoid: bool = False, swap_tf: bool = True, batch_size: int = 32, rank: int = 0,
-                     world: int = 1, input_dtype=None):
+                     world: int = 1, input_dtype=None, norm: str = "raw"):
     """`evaluate` for data-parallel runs ("dev evaluation inside training = sharded inference +
     gather"): rank r scores the contiguous utterance range [r*ceil(N/world), ...) of the stacked set, the per-rank
     logit vectors are gathered in rank order, and every rank computes the SAME loss / EER from the same gathered
-    vector -- so best-checkpoint and early-stop decisions cannot diverge between ranks.  No data-path collective."""
+    vector -- so best-checkpoint and early-stop decisions cannot diverge between ranks.  No data-path collective.
+    norm: "cmn" / "cvmn" normalise each stored batch on the device first (float32 input only)."""
     from . import distributed as dfa_dist
     from .dataloaders import FlatBatcher
     model.eval()
     chunks = []
     with torch.no_grad():
         for feats, _ in FlatBatcher(features, None, batch_size, device=device, rank=rank, world=world, dtype=input_dtype):
+            if norm != "raw":
+                from .normalization import normalize_stored
+                feats = normalize_stored(feats, norm)
             x = feats.transpose(1, 2) if swap_tf else feats
             chunks.append(model(x).squeeze(-1).detach())
     local = torch.cat(chunks).double().cpu().numpy() if chunks else np.zeros(0)
@@ -125,17 +133,22 @@ def evaluate_sharded(model, features: torch.Tensor, labels: torch.Tensor, criter
     return {"avg_loss": avg_loss, "eer": eer, "threshold": threshold}, scores.tolist(), y.tolist()
 
 
-def evaluate_ragged(model, features, labels, criterion=None, device="cuda", apply_sigmoid: bool = False, batch_size: int = 32):
+def evaluate_ragged(model, features, labels, criterion=None, device="cuda", apply_sigmoid: bool = False, batch_size: int = 32,
+                    norm: str = "raw"):
     """`evaluate` for a list of per-utterance [F, T_i] tensors (of unequal lengths, or not) with their 0/1 labels: batches
     padded to their longest utterance (dataloaders.RaggedBatcher, longest first) through `model(x, lengths=...)`, logits put
     back in input order (`restore`).  Same returns as `evaluate`: (metrics{avg_loss, eer, threshold}, scores, labels); the
-    loss is the criterion's mean over all utterances, which is what evaluate's sample-weighted mean of batch means is."""
+    loss is the criterion's mean over all utterances, which is what evaluate's sample-weighted mean of batch means is.
+    norm: "cmn" / "cvmn" normalise each utterance over its own frames, in place in the batch's device copy."""
     from .dataloaders import RaggedBatcher
     model.eval()
     batcher = RaggedBatcher(features, None, batch_size, device=device)
     outs = []
     with torch.no_grad():
         for x, _, lengths in batcher:
+            if norm != "raw":
+                from .normalization import normalize_batch
+                x = normalize_batch(x, norm, lengths, out=x)
             outs.append(model(x, lengths=lengths).squeeze(-1).detach())
     if not outs:
         return {"avg_loss": None, "eer": None, "threshold": None}, [], []

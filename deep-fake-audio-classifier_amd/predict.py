@@ -22,27 +22,41 @@ def build_model(name: str, in_features: int = 180, dropout: float = 0.3, precisi
     raise ValueError(f"unknown model {name!r} (choices: cnn2d, cnn1d)")
 
 
-def load_weights(model, checkpoint_path: str, device="cuda"):
-    """Accept the reference's checkpoint dict {"model_state": ...} or a bare state_dict (src/predict.py:78-85)."""
+def read_checkpoint(checkpoint_path: str, device="cuda"):
+    """What torch.load finds in the file: the reference's checkpoint dict or a bare state_dict."""
     try:
-        ckpt = torch.load(checkpoint_path, map_location=device, weights_only=True)
+        return torch.load(checkpoint_path, map_location=device, weights_only=True)
     except TypeError:
-        ckpt = torch.load(checkpoint_path, map_location=device)
+        return torch.load(checkpoint_path, map_location=device)
+
+
+def load_weights(model, checkpoint_path: str, device="cuda", blob=None):
+    """Accept the reference's checkpoint dict {"model_state": ...} or a bare state_dict (src/predict.py:78-85).
+    blob: the file's content when the caller has read it already (read_checkpoint)."""
+    ckpt = read_checkpoint(checkpoint_path, device) if blob is None else blob
     state = ckpt["model_state"] if isinstance(ckpt, dict) and "model_state" in ckpt else ckpt
     model.load_state_dict(state)
     return model
 
 
-def _forward_batches(model, source, batch_size, device, rank, world, input_dtype, swap_tf=True, return_embedding=False):
+def _forward_batches(model, source, batch_size, device, rank, world, input_dtype, swap_tf=True, return_embedding=False,
+                     norm: str = "raw"):
     """The one scoring loop: `source` (a stacked tensor or a list of [F, T_i] tensors: dataloaders.EvalBatches) through
     `model(x)` / `model(x, lengths=...)` -> (logits [n] on the device, embeddings [n, 128*F] on the host or None), in input
-    order; (None, None) when this rank's shard is empty."""
+    order; (None, None) when this rank's shard is empty.  norm: "cmn" / "cvmn" normalise each batch where it reaches the
+    device, every utterance over the stored time axis and its own frames (float32 input)."""
     from .dataloaders import EvalBatches
+    from .normalization import normalize_batch, normalize_stored
     model.eval()
     batches = EvalBatches(source, batch_size, device=device, rank=rank, world=world, dtype=input_dtype, swap_tf=swap_tf)
     outs, embs = [], []
     for x, lengths in batches:
         kw = {} if lengths is None else {"lengths": lengths}
+        if norm != "raw":
+            if lengths is not None:
+                x = normalize_batch(x, norm, lengths, out=x)           # the padded batch's own device copy: in place
+            else:
+                x = normalize_batch(x, norm) if swap_tf else normalize_stored(x, norm)
         if return_embedding:
             logits, e = model(x, return_embedding=True, **kw)
             embs.append(e.cpu())
@@ -56,9 +70,9 @@ def _forward_batches(model, source, batch_size, device, rank, world, input_dtype
 
 @torch.no_grad()
 def predict_scores(model, features: torch.Tensor, batch_size: int = 32, device="cuda", apply_sigmoid: bool = True,
-                   swap_tf: bool = True, rank: int = 0, world: int = 1, input_dtype=None) -> torch.Tensor:
+                   swap_tf: bool = True, rank: int = 0, world: int = 1, input_dtype=None, norm: str = "raw") -> torch.Tensor:
     """Scores for a stacked [N,180,321] feature tensor (this rank's shard when world > 1), as one GPU tensor."""
-    logits, _ = _forward_batches(model, features, batch_size, device, rank, world, input_dtype, swap_tf)
+    logits, _ = _forward_batches(model, features, batch_size, device, rank, world, input_dtype, swap_tf, norm=norm)
     if logits is None:
         return torch.empty(0, device=device)
     return torch.sigmoid(logits) if apply_sigmoid else logits
@@ -80,12 +94,12 @@ def check_ragged_args(model: str, precision: str, swap_tf: bool = True) -> None:
 
 @torch.no_grad()
 def predict_scores_ragged(model, feature_list, batch_size: int = 32, device="cuda", apply_sigmoid: bool = True,
-                          input_dtype=None, rank: int = 0, world: int = 1, return_embedding: bool = False):
+                          input_dtype=None, rank: int = 0, world: int = 1, return_embedding: bool = False, norm: str = "raw"):
     """Scores for a list of per-utterance [F, T_i] tensors of unequal lengths, in input order, as one GPU tensor: batches
     padded to their longest utterance (dataloaders.RaggedBatcher, longest first) through `model(x, lengths=...)`.
-    return_embedding (cnn2d): also the [N, 128*F] embeddings, as a host tensor."""
+    return_embedding (cnn2d): also the [N, 128*F] embeddings, as a host tensor.  norm: see _forward_batches."""
     logits, emb = _forward_batches(model, feature_list, batch_size, device, rank, world, input_dtype,
-                                   return_embedding=return_embedding)
+                                   return_embedding=return_embedding, norm=norm)
     if logits is None:
         scores = torch.empty(0, device=device)
     else:
@@ -97,14 +111,15 @@ def predict_scores_ragged(model, feature_list, batch_size: int = 32, device="cud
 
 @torch.no_grad()
 def extract_embeddings(model, features: torch.Tensor, batch_size: int = 256, device="cuda", swap_tf: bool = True,
-                       rank: int = 0, world: int = 1, input_dtype=None):
+                       rank: int = 0, world: int = 1, input_dtype=None, norm: str = "raw"):
     """Bulk export of the block-3 time-mean embedding [N, 128*F] (what src/embedding_anomaly.py:49-73 collects with
     forward hooks for its OC-SVM / GMM stage) together with the logits [N]: the HIP forward writes the embedding rows
     straight from the block-3 epilogue (`return_embedding=True`), so the export costs one extra 92 KB store per utterance.
     Returns (embeddings, logits) as host tensors (this rank's shard when world > 1)."""
     if not isinstance(model, CNN2D):
         raise ValueError("extract_embeddings needs the CNN2D model (the 1D CNN has no [128*F] embedding)")
-    logits, emb = _forward_batches(model, features, batch_size, device, rank, world, input_dtype, swap_tf, return_embedding=True)
+    logits, emb = _forward_batches(model, features, batch_size, device, rank, world, input_dtype, swap_tf, return_embedding=True,
+                                   norm=norm)
     if logits is None:
         return torch.empty(0, 0), torch.empty(0)
     return emb, logits.cpu()
@@ -169,6 +184,8 @@ def parse_args(argv=None):
     p.add_argument("--apply-sigmoid", action="store_true", default=True)
     p.add_argument("--no-apply-sigmoid", action="store_true", default=False)
     p.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
+    from .normalization import add_norm_argument
+    add_norm_argument(p)          # not given: the checkpoint's "norm_mode", else raw (normalization.resolve_norm)
     sw = p.add_mutually_exclusive_group()
     sw.add_argument("--swap-tf", dest="swap_tf", action="store_true", help="swap time and feature dims (default)")
     sw.add_argument("--no-swap-tf", dest="swap_tf", action="store_false")
@@ -194,27 +211,31 @@ def main(argv=None):
     if ragged:
         check_ragged_args(args.model, args.precision, args.swap_tf)
     model = build_model(args.model, args.in_features, args.dropout, args.precision).to(device)
-    load_weights(model, args.checkpoint, device)
+    from .normalization import explicit_norm, resolve_norm
+    blob = read_checkpoint(args.checkpoint, device)
+    load_weights(model, args.checkpoint, device, blob=blob)
+    norm = resolve_norm(explicit_norm(args), blob)
     model.eval()
     if ragged:
         feature_list = [f.float() for f in features_df["features"]]
         scores = predict_scores_ragged(model, feature_list, batch_size=args.batch_size, device=device,
-                                       apply_sigmoid=apply_sigmoid)
+                                       apply_sigmoid=apply_sigmoid, norm=norm)
         write_predictions(features_df["uttid"].values, scores.cpu().tolist(), args.out)
         if args.embeddings_out:
             if args.model != "cnn2d":
                 raise ValueError("extract_embeddings needs the CNN2D model (the 1D CNN has no [128*F] embedding)")
             logits, emb = predict_scores_ragged(model, feature_list, batch_size=max(args.batch_size, 256), device=device,
-                                                apply_sigmoid=False, return_embedding=True)
+                                                apply_sigmoid=False, return_embedding=True, norm=norm)
             torch.save({"uttid": list(features_df["uttid"].values), "embeddings": emb, "logits": logits.cpu()},
                        args.embeddings_out)
         return
     feats = torch.stack([f.float() for f in features_df["features"]]) if len(features_df) else torch.empty(0, 180, 321)
     scores = predict_scores(model, feats, batch_size=args.batch_size, device=device, apply_sigmoid=apply_sigmoid,
-                            swap_tf=args.swap_tf)
+                            swap_tf=args.swap_tf, norm=norm)
     write_predictions(features_df["uttid"].values, scores.cpu().tolist(), args.out)
     if args.embeddings_out:
-        emb, logits = extract_embeddings(model, feats, batch_size=max(args.batch_size, 256), device=device, swap_tf=args.swap_tf)
+        emb, logits = extract_embeddings(model, feats, batch_size=max(args.batch_size, 256), device=device, swap_tf=args.swap_tf,
+                                         norm=norm)
         torch.save({"uttid": list(features_df["uttid"].values), "embeddings": emb, "logits": logits}, args.embeddings_out)
 
 

@@ -25,20 +25,25 @@ from .dataloaders import FlatBatcher, IndexedFlatBatcher, ResidentBatcher, make_
 from .dataset import AudioDeepfakeDataset
 from .evaluation import evaluate, evaluate_ragged, evaluate_sharded
 from .model import CNN2D
+from .normalization import add_norm_argument, normalize_batch, normalize_stored
 from .training import save_checkpoint
 
 
 def train_one_epoch(model, dataloader, criterion, optimizer, device: str = "cuda", batch_context=None,
-                    augment_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, swap_tf: bool = False):
+                    augment_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, swap_tf: bool = False,
+                    norm: str = "raw"):
     """One pass over `dataloader` (src/train.py:31-91); returns the sample-weighted mean training loss.
     The running loss is accumulated on the device; it is synchronised to the host only when a `batch_context`
-    (progress display) asks for it, not once per batch."""
+    (progress display) asks for it, not once per batch.  norm: "cmn" / "cvmn" normalise each stored [b, F, T] batch on the
+    device (normalization.normalize_stored) before the axis swap, the augmentation and the model."""
     model.train()
     loss_sum = None
     count = 0
     for batch_idx, (features, labels) in enumerate(dataloader):
         features = features.to(device, non_blocking=True)
         labels = labels.to(device, non_blocking=True)
+        if norm != "raw":
+            features = normalize_stored(features, norm)
         if swap_tf:
             features = features.transpose(1, 2)
         if augment_fn is not None:
@@ -61,8 +66,9 @@ class _BatchMetrics:
         self.batch_idx, self.running_loss, self.batch_size = batch_idx, running_loss, batch_size
 
 
-def train_one_epoch_native(trainer, batcher, augment_fn=None, swap_tf: bool = True):
-    """One pass with the all-native step; `batcher` yields (stored-layout features [b,180,321], labels [b]) on the GPU."""
+def train_one_epoch_native(trainer, batcher, augment_fn=None, swap_tf: bool = True, norm: str = "raw"):
+    """One pass with the all-native step; `batcher` yields (stored-layout features [b,180,321], labels [b]) on the GPU.
+    norm: "cmn" / "cvmn" normalise each batch as it arrives (a ResidentBatcher(norm=...) has done so at upload: pass "raw")."""
     total, count = None, 0
     # bf16 storage mode of the CNN2D without augmentation: the fp32 batch is rounded to bf16 on the compute stream (the same
     # round-to-nearest-even the first kernel applies on load), so block 1 takes its matrix-core passes, which read bf16 features:
@@ -70,6 +76,8 @@ def train_one_epoch_native(trainer, batcher, augment_fn=None, swap_tf: bool = Tr
     # behind the H2D, measured 32 k)
     to_bf16 = (augment_fn is None and getattr(trainer, "kind", "") == "cnn2d" and getattr(trainer.model, "precision", "") == "bf16")
     for feats, labels in batcher:
+        if norm != "raw":
+            feats = normalize_stored(feats, norm)
         if to_bf16 and feats.dtype == torch.float32:
             feats = feats.to(torch.bfloat16)
         x = feats.transpose(1, 2) if swap_tf else feats
@@ -158,6 +166,7 @@ def parse_args(argv=None):
     p.add_argument("--resident", default="auto", choices=["auto", "on", "off"],
                    help="flat-buffer trainers: keep the whole training set in GPU memory (uploaded once; batches are device-side row "
                         "gathers) -- auto: when it needs at most half of the free memory")
+    add_norm_argument(p)
     p.add_argument("--sync-bn", action="store_true",
                    help="data-parallel training: BatchNorm statistics over the global batch (N ranks x B train like one rank x N*B); "
                         "default: each rank's own statistics, as torch DistributedDataParallel")
@@ -205,10 +214,13 @@ def _ragged_train_set(args):
     return (utts, labels) if len({tuple(u.shape) for u in utts}) > 1 else None
 
 
-def train_one_epoch_ragged(trainer, batcher):
-    """One pass with the all-native variable-length step; `batcher` is a dataloaders.RaggedBatcher with labels."""
+def train_one_epoch_ragged(trainer, batcher, norm: str = "raw"):
+    """One pass with the all-native variable-length step; `batcher` is a dataloaders.RaggedBatcher with labels.
+    norm: "cmn" / "cvmn" normalise each utterance over its own frames, in place in the batch's device copy."""
     total, count = None, 0
     for x, labels, lengths in batcher:
+        if norm != "raw":
+            x = normalize_batch(x, norm, lengths, out=x)
         loss = trainer.step(x, labels, lengths=lengths)
         term = loss.detach().double().squeeze() * labels.size(0)
         total = term if total is None else total + term
@@ -297,10 +309,10 @@ def main(argv=None):
     resident = None
     for epoch in range(1, args.epochs + 1):
         if ragged_batcher is not None:
-            train_loss = train_one_epoch_ragged(trainer, ragged_batcher)
+            train_loss = train_one_epoch_ragged(trainer, ragged_batcher, norm=args.norm)
             model._prepared = None
             metrics, _, _ = evaluate_ragged(model, dev_utts, dev_utt_labels, criterion=criterion, device=device,
-                                            batch_size=args.batch_size)
+                                            batch_size=args.batch_size, norm=args.norm)
         elif flat_mode:
             # every rank draws the SAME permutation and takes its rows of every global batch: equal step counts and equal
             # local batch sizes on all ranks (dataloaders.train_shard_indices)
@@ -311,22 +323,22 @@ def main(argv=None):
                 # row gathers; "auto" takes it when the set needs at most half of the free memory
                 store = torch.bfloat16 if (args.precision == "bf16" and args.model == "cnn2d" and augment_fn is None) else None
                 if args.resident == "on" or ResidentBatcher.fits(feats, device, store):
-                    resident = ResidentBatcher(feats, labels, args.batch_size, device=device, dtype=store)
+                    resident = ResidentBatcher(feats, labels, args.batch_size, device=device, dtype=store, norm=args.norm)
                 else:
                     resident = False
             batcher = resident.epoch(idx) if resident else IndexedFlatBatcher(feats, labels, idx, args.batch_size, device=device)
-            train_loss = train_one_epoch_native(trainer, batcher, augment_fn, args.swap_tf)
+            train_loss = train_one_epoch_native(trainer, batcher, augment_fn, args.swap_tf, norm="raw" if resident else args.norm)
             train_loss = dfa_dist.mean_scalar(train_loss, device)
             # BatchNorm running statistics come from rank-local batches: average them so that every rank evaluates (and
             # rank 0 checkpoints) the same model
             dfa_dist.average_tensors_(dfa_dist.bn_running_stats(model))
             model._prepared = None
             metrics, _, _ = evaluate_sharded(model, dev_feats, dev_labels, criterion=criterion, device=device,
-                                             swap_tf=args.swap_tf, batch_size=args.batch_size, rank=rank, world=world)
+                                             swap_tf=args.swap_tf, batch_size=args.batch_size, rank=rank, world=world, norm=args.norm)
         else:
             train_loss = train_one_epoch(model, train_loader, criterion, optimizer, device=device,
-                                         augment_fn=augment_fn, swap_tf=args.swap_tf)
-            metrics, _, _ = evaluate(model, dev_loader, criterion=criterion, device=device, swap_tf=args.swap_tf)
+                                         augment_fn=augment_fn, swap_tf=args.swap_tf, norm=args.norm)
+            metrics, _, _ = evaluate(model, dev_loader, criterion=criterion, device=device, swap_tf=args.swap_tf, norm=args.norm)
         eer, dev_loss = metrics["eer"], metrics["avg_loss"]
         is_best = False
         if eer is not None:
@@ -345,12 +357,12 @@ def main(argv=None):
             print(f"epoch {epoch}: train_loss={train_loss:.6f} dev_loss={dev_loss:.6f} dev_eer={eer:.6f}"
                   + ("  *best*" if is_best else ""))
             if is_best:
-                save_checkpoint(model, optimizer, epoch, args, best_path, scheduler=scheduler)
+                save_checkpoint(model, optimizer, epoch, args, best_path, scheduler=scheduler, norm_mode=args.norm)
         last_epoch = epoch
         if args.early_stop and no_improve >= args.early_stop:
             break                                  # same decision on every rank: it depends on gathered metrics only
     if rank == 0:
-        save_checkpoint(model, optimizer, last_epoch, args, last_path, scheduler=scheduler)
+        save_checkpoint(model, optimizer, last_epoch, args, last_path, scheduler=scheduler, norm_mode=args.norm)
 
 
 if __name__ == "__main__":

@@ -47,6 +47,8 @@ def parse_args(argv=None):
     ap.add_argument("--patience", type=int, default=6)
     ap.add_argument("--resident", action="store_true",
                     help="keep the train and dev sets in GPU memory and assemble every batch there (dataloaders.DlqResidentSet)")
+    from .normalization import add_norm_argument
+    add_norm_argument(ap)
     args = ap.parse_args(argv)
     if args.hidden != 256:
         ap.exit(2, f"--hidden {args.hidden}: the DeepfakeDetector HIP path is built for hidden=256\n")
@@ -95,16 +97,37 @@ def spec_augment(x, rng, time_mask_max, time_mask_n, freq_mask_max, freq_mask_n)
     return x
 
 
-def epoch_batches(feats, labels, order, batch_size, specaug=None, rng=None):
+def epoch_batches(feats, labels, order, batch_size, specaug=None, rng=None, norm: str = "raw", device=None):
     """Batches of one epoch in the order given (no sorting): (x [b, C, T] host float32 in the stored layout, zero behind every
     utterance, rows padded to 16 bytes; lengths int32 [b]; y float32 [b]).  specaug: (time_mask_max, time_mask_n, freq_mask_max,
-    freq_mask_n) applied per sample to a copy, or None."""
+    freq_mask_n) applied per sample to a copy, or None.
+    norm "cmn" / "cvmn" (needs `device`): x is then a DEVICE tensor -- the unmasked batch is uploaded, every utterance normalised
+    there over its own frames, and the masks, drawn as spans by the same rng in the same order (draw_spans), zero the normalised
+    data: the reference's order (its dataset normalises, its loop masks), and what a DlqResidentSet(norm=...) batch holds."""
+    if norm != "raw" and device is None:
+        raise ValueError("epoch_batches(norm=...) normalises on the GPU: pass device=")
     for lo in range(0, len(order), batch_size):
         idx = order[lo:lo + batch_size]
         utts = [torch.as_tensor(feats[i]).float() for i in idx]
         lengths = np.array([u.shape[-1] for u in utts], dtype=np.int32)
         T = int(lengths.max())
         host = torch.zeros((len(utts), utts[0].shape[0], -(-T // 4) * 4), dtype=torch.float32)
+        if norm != "raw":
+            from .normalization import normalize_batch
+            n_t = span_counts(*specaug)[0] if specaug is not None else 0
+            spans = [draw_spans(rng, u.shape[0], u.shape[-1], *specaug) for u in utts] if specaug is not None else None
+            for j, u in enumerate(utts):
+                host[j, :, :u.shape[-1]] = u
+            xt = host.to(device).transpose(1, 2)                   # [b, T_pad, C]: the stored batch, read and written in place
+            x = normalize_batch(xt, norm, lengths, out=xt).transpose(1, 2)
+            for j, sp in enumerate(spans or ()):
+                for k, (s0, w) in enumerate(sp.tolist()):
+                    if w and k < n_t:
+                        x[j, :, s0:s0 + w] = 0.0
+                    elif w:
+                        x[j, s0:s0 + w, :] = 0.0
+            yield x[:, :, :T], lengths, torch.tensor([float(labels[i]) for i in idx], dtype=torch.float32)
+            continue
         for j, u in enumerate(utts):
             if specaug is not None:
                 u = spec_augment(u.clone(), rng, *specaug)
@@ -165,6 +188,13 @@ def _load_split(data_dir, split):
     return feats, np.array([int(label_map[u]) for u in df["uttid"].tolist()], dtype=int)
 
 
+def dlq_checkpoint(model, norm: str = "raw"):
+    """What train_dlqueen saves: the bare state_dict the reference's script saves and loads; with "cmn" / "cvmn" (which the
+    reference's script cannot reproduce) {"model_state": state_dict, "norm_mode": mode}, which dfa_amd.dlqueen_model resolves."""
+    state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    return state if norm == "raw" else {"model_state": state, "norm_mode": norm}
+
+
 def main(argv=None):
     from .dataloaders import DlqResidentSet
     from .dlqueen_model import DeepfakeDetector, evaluate_eer, evaluate_eer_resident
@@ -189,23 +219,24 @@ def main(argv=None):
     specaug = (args.time_mask_max, args.time_mask_n, args.freq_mask_max, args.freq_mask_n) if args.specaug else None
     best_eer, bad = 1.0, 0
     if args.resident:           # both splits uploaded once; from here on the host sends indices and mask spans only
-        train_set = DlqResidentSet(train_feats, y_train, device=args.device)
-        dev_set = DlqResidentSet(dev_feats, None, device=args.device)
+        train_set = DlqResidentSet(train_feats, y_train, device=args.device, norm=args.norm)
+        dev_set = DlqResidentSet(dev_feats, None, device=args.device, norm=args.norm)
     for epoch in range(1, args.epochs + 1):
         order = sample_order(y_train, gen)
         if args.resident:
             loss = train_epoch(trainer, resident_epoch_batches(train_set, order, args.batch_size, specaug, rng), args.device)
         else:
-            loss = train_epoch(trainer, epoch_batches(train_feats, y_train, order, args.batch_size, specaug, rng), args.device)
+            loss = train_epoch(trainer, epoch_batches(train_feats, y_train, order, args.batch_size, specaug, rng, norm=args.norm,
+                                                      device=args.device), args.device)
         with trainer.ema_applied():
             if args.resident:
                 dev_eer = evaluate_eer_resident(model, dev_set, y_dev, args.batch_size)
             else:
-                dev_eer = evaluate_eer(model, dev_feats, y_dev, args.batch_size, device=args.device, file_order=True)
+                dev_eer = evaluate_eer(model, dev_feats, y_dev, args.batch_size, device=args.device, file_order=True, norm=args.norm)
         print(f"Epoch {epoch}: train_loss={loss:.6f} dev EER={dev_eer:.6f}  (lower is better)")
         if dev_eer < best_eer:
             best_eer, bad = dev_eer, 0
-            torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, args.ckpt_path)
+            torch.save(dlq_checkpoint(model, args.norm), args.ckpt_path)
             print(f"  Saved best ckpt -> {args.ckpt_path}")
         else:
             bad += 1

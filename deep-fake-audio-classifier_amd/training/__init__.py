@@ -1,6 +1,6 @@
 """Training-side pieces: checkpoint format (counterpart of src/training/checkpoint.py) and, in train_step.py, the
 train-mode forward/backward path."""
-from .checkpoint import build_config_dict, load_checkpoint, save_checkpoint  # noqa: F401
+from .checkpoint import build_config_dict, checkpoint_blob, load_checkpoint, save_checkpoint  # noqa: F401
 
 
 def cnn2d_train_forward(model, x, return_embedding=False):

@@ -22,11 +22,21 @@ def build_config_dict(args) -> Dict[str, Any]:
     return cfg
 
 
-def save_checkpoint(model, optimizer, epoch: int, args, path: str, scheduler: Optional[Any] = None) -> None:
+def checkpoint_blob(model, optimizer, epoch: int, args, scheduler: Optional[Any] = None, norm_mode: str = "raw") -> Dict[str, Any]:
+    """The dict save_checkpoint writes.  norm_mode: the per-utterance normalisation the model was trained with; "cmn" / "cvmn" are
+    recorded as blob["norm_mode"] (the key src/compare_kernels.py:178-184 writes; the reference's loader ignores it), "raw" adds
+    no key: a raw checkpoint is byte for byte what it was."""
     blob = {"model_state": model.state_dict(), "optimizer_state": optimizer.state_dict(), "epoch": epoch,
             "config": build_config_dict(args)}
     if scheduler is not None:
         blob["scheduler_state"] = scheduler.state_dict()
+    if norm_mode != "raw":
+        blob["norm_mode"] = norm_mode
+    return blob
+
+
+def save_checkpoint(model, optimizer, epoch: int, args, path: str, scheduler: Optional[Any] = None, norm_mode: str = "raw") -> None:
+    blob = checkpoint_blob(model, optimizer, epoch, args, scheduler=scheduler, norm_mode=norm_mode)
     Path(path).parent.mkdir(parents=True, exist_ok=True)
     torch.save(blob, path)
 

@@ -563,6 +563,44 @@ int dfa_bce_pos_weight_fwd_bwd(dfa_ctx* ctx, const float* logits, const float* l
  * then grad *= min(1, max_norm / (norm + 1e-6)).  norm_out: device float[1] (the norm before clipping) or NULL. */
 int dfa_clip_grad_norm(dfa_ctx* ctx, float* grad, size_t n, float max_norm, float* norm_out);
 
+/* ---- per-utterance feature normalisation (src/compare_normalization.py:53-62, src/compare_kernels.py:83-90; DESIGN.md section
+ * 3.17).  For utterance b, feature row c and its own n = lengths[b] frames (n = T_max for every b when lengths is NULL):
+ *   mean = (1/n) sum_{t<n} x[b][c][t]
+ *   DFA_NORM_CMN :  y = x - mean
+ *   DFA_NORM_CVMN:  y = (x - mean) / max(sqrt(sum_{t<n} (x - mean)^2 / (n - 1)), 1e-8)        (torch.std: unbiased)
+ *   y[b][c][t] = +0.0f for n <= t < T_max: a select, x there (NaN included) is never used.
+ * x, y: device float32 with the SAME strides, element (b, t, c) at b stride_b + t stride_t + c stride_c; y == x is allowed, any
+ * other overlap is the caller's error.  Two layout forms:
+ *   time fastest (stride_t == 1): the stored [B][C][T_pad] batch.  x and y 16-byte aligned, stride_c % 4 == 0, stride_c >= T_max,
+ *     stride_b % 4 == 0, stride_b >= 0.  The whole 16-byte pieces of a row are read and written: floats [0, ceil(T_max / 4) * 4) of
+ *     every row of y are written (those behind n as +0.0f).  A row of at most DFA_UTT_NORM_HELD_FRAMES frames is read once.
+ *   feature fastest (stride_c == 1, stride_t != 1): a [B, T, F] tensor.  stride_t >= C, stride_b >= 0; frames [0, T_max) of the C
+ *     features are written, nothing else.
+ * The statistics are two-pass float64 sums in a fixed order that depends on n alone (no atomics): within one layout form a row's
+ * output is bit for bit a function of its n values, n and the mode -- not of B, b, T_max, the strides, its companions, what lies
+ * behind n, or whether the call is in place.
+ * lengths: HOST int32[B] or NULL.  With lengths the table goes through the context's pinned staging slots, so a capturing stream
+ *   returns DFA_E_UNSUPPORTED; with NULL nothing is copied and the call may be captured.
+ * workspace: device, 256-byte aligned, >= dfa_utt_norm_workspace_bytes(B) (0 for B < 1), else DFA_E_WORKSPACE.
+ * Refusals, in this order, each with a message and before anything is launched: unknown mode DFA_E_UNSUPPORTED; B, C or T_max < 1
+ *   DFA_E_BAD_SHAPE; a length outside [1, T_max], or < 2 with DFA_NORM_CVMN (T_max < 2 without lengths), DFA_E_BAD_SHAPE; neither
+ *   stride_t == 1 nor stride_c == 1, or a misaligned base or pitch, DFA_E_UNSUPPORTED; the workspace.  Timing slot: 15.
+ *
+ * dfa_utt_norm_packed: the same, in place, on a packed resident set (dfa_dlq_gather_batch above: utterance i = C rows of pitch_i =
+ *   ceil(T_i / 4) * 4 floats from float offset offsets[i]); the floats T_i .. pitch_i of a row become +0.0f.  offsets: HOST
+ *   int64[N], lengths: HOST int32[N] (both required), checked as dfa_dlq_gather_batch checks src_off.  At most
+ *   DFA_UTT_NORM_MAX_PACKED utterances per call (else DFA_E_UNSUPPORTED): callers walk a larger set in chunks.  Bit for bit the
+ *   time-fastest form of dfa_utt_norm on the same utterance.  workspace: >= dfa_utt_norm_workspace_bytes(N). */
+#define DFA_NORM_CMN 1
+#define DFA_NORM_CVMN 2
+#define DFA_UTT_NORM_HELD_FRAMES 1024
+#define DFA_UTT_NORM_MAX_PACKED 65536
+size_t dfa_utt_norm_workspace_bytes(int B);
+int dfa_utt_norm(dfa_ctx* ctx, int mode, const float* x, float* y, int B, int T_max, int C, int64_t stride_b, int64_t stride_t,
+                 int64_t stride_c, const int32_t* lengths, void* workspace, size_t workspace_bytes);
+int dfa_utt_norm_packed(dfa_ctx* ctx, int mode, float* set, int64_t set_floats, const int64_t* offsets, const int32_t* lengths, int N,
+                        int C, void* workspace, size_t workspace_bytes);
+
 /* ---- embedding anomaly detectors (replace the scoring half of src/embedding_anomaly.py:129-163) ---------
  * The reference fits a StandardScaler, a OneClassSVM and a PCA + GaussianMixture on the bonafide CNN2D embeddings with sklearn
  * (a one-off on the host: dfa_amd/embedding_anomaly.py does the same) and scores with decision_function / score_samples.
