@@ -63,6 +63,7 @@ SYMBOLS = [
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float]),
     ("dfa_cnn1d_set_params", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     ("dfa_cnn1d_prepare", C.c_int, [C.c_void_p]),
+    ("dfa_cnn1d_set_kernels", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ("dfa_cnn1d_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]),
     ("dfa_cnn1d_train_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -132,6 +133,10 @@ SYMBOLS = [
     ("dfa_cnn1d_ragged_segments", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.c_int]),
     ("dfa_cnn1d_ragged_lds_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("dfa_cnn1d_ragged_segments_k", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), C.c_int]),
+    ("dfa_cnn1d_ragged_lds_bytes_k", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("dfa_cnn1d_fused_max_t", C.c_int, [C.c_int, C.c_int]),
     ("dfa_dominant_kernel", C.c_char_p, [C.c_int, C.c_int]),
     ("dfa_ctx_timing_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("dfa_ctx_timing_reset", C.c_int, [C.c_void_p]),
@@ -423,10 +428,11 @@ def ptr(t):
 
 
 # ---- the eval bridge: what every model's eval-mode forward does around its one ABI call --------------------------------------------
-def ensure_prepared(model, ctx: Context, slot: str, set_params: str, dims, prepare: str, precision=None):
+def ensure_prepared(model, ctx: Context, slot: str, set_params: str, dims, prepare: str, precision=None, before=None):
     """Bind model._abi_tensors() to the context's `slot` (`set_params`(ctx, pointers, n, *dims)) and fold them for the eval
     forward (`prepare`(ctx[, precision code])), unless that is what the slot already holds: model._prepared remembers the
-    signature (device, precision where the model has one, tensor addresses and versions) of the last preparation."""
+    signature (device, precision where the model has one, tensor addresses and versions) of the last preparation.
+    before: (name, args) of a sticky setter of the slot that goes in front of every `set_params` (the CNN1D's kernel sizes)."""
     ts = model._abi_tensors()
     for t in ts:
         if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
@@ -437,6 +443,8 @@ def ensure_prepared(model, ctx: Context, slot: str, set_params: str, dims, prepa
     if sig == model._prepared and not stale:
         return
     arr = ptr_array([t.detach() for t in ts])
+    if before is not None:
+        check(ctx.handle, getattr(ctx.lib, before[0])(ctx.handle, *before[1]))
     check(ctx.handle, getattr(ctx.lib, set_params)(ctx.handle, arr, len(ts), *dims))
     check(ctx.handle, getattr(ctx.lib, prepare)(ctx.handle, *(() if precision is None else (PRECISIONS[precision],))))
     model._prepared = sig

@@ -30,35 +30,38 @@ constexpr int TW = 32, NW = 8, NTH = 64 * NW, MAXT1 = 2;   // 8 waves = two per 
 }
 
 // A-fragment images: wx[m][tap][ks][part][lane] (uint4), part 0 = hi, 1 = lo; lane: co = 32 m + (lane & 31), element j <-> input
-// channel 16 ks + 8 (lane >> 5) + j (zero beyond cin).  wf = BN-folded fp32 weights [cout][cin][3].
-__global__ void pack_cnn1d_x3_kernel(const float* __restrict__ wf, uint4* __restrict__ wx, int cin, int cout, int nks) {
+// channel 16 ks + 8 (lane >> 5) + j (zero beyond cin).  wf = BN-folded fp32 weights [cout][cin][taps].  ksmajor (the five-tap
+// layer 1, whose image is streamed one k-step per trip): wx[m][ks][tap][part][lane], a k-step's taps contiguous.
+__global__ void pack_cnn1d_x3_kernel(const float* __restrict__ wf, uint4* __restrict__ wx, int cin, int cout, int nks, int taps, int ksmajor) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int total = (cout / 32) * 3 * nks * 64;
+  const int total = (cout / 32) * taps * nks * 64;
   if (i >= total) return;
   const int lane = i & 63;
   int rest = i >> 6;
   const int ks = rest % nks; rest /= nks;
-  const int tap = rest % 3, m = rest / 3;
+  const int tap = rest % taps, m = rest / taps;
   const int co = 32 * m + (lane & 31), hh = lane >> 5;
   bf16_t hi[8], lo[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int ci = 16 * ks + 8 * hh + j;
-    const float w = ci < cin ? wf[((size_t)co * cin + ci) * 3 + tap] : 0.f;
+    const float w = ci < cin ? wf[((size_t)co * cin + ci) * taps + tap] : 0.f;
     hi[j] = float_to_bf16(w);
     lo[j] = float_to_bf16(w - bf16_to_float(hi[j]));
   }
-  uint4* dst = wx + ((size_t)((m * 3 + tap) * nks + ks) * 2) * 64 + lane;
+  uint4* dst = wx + ((size_t)(ksmajor ? (m * nks + ks) * taps + tap : (m * taps + tap) * nks + ks) * 2) * 64 + lane;
   dst[0] = *reinterpret_cast<const uint4*>(hi);
   dst[64] = *reinterpret_cast<const uint4*>(lo);
 }
 
 // k-steps of 16 input channels; layer 1 (the only layer with cin != 32, 64) runs its slabs two per loop trip: padded to an even count
 int cnn1d_x3_nks(int cin) { const int n = (cin + 15) / 16; return (cin == 32 || cin == 64) ? n : (n + 1) & ~1; }
-size_t cnn1d_x3_pack_bytes(int cin, int cout) { return (size_t)(cout / 32) * 3 * cnn1d_x3_nks(cin) * 2 * 64 * 16; }
-hipError_t launch_pack_cnn1d_x3(const float* wf, void* wx, int cin, int cout, hipStream_t s) {
-  const int total = (cout / 32) * 3 * cnn1d_x3_nks(cin) * 64;
-  hipLaunchKernelGGL(pack_cnn1d_x3_kernel, dim3((total + 255) / 256), dim3(256), 0, s, wf, (uint4*)wx, cin, cout, cnn1d_x3_nks(cin));
+size_t cnn1d_x3_pack_bytes(int cin, int cout, int taps) { return (size_t)(cout / 32) * taps * cnn1d_x3_nks(cin) * 2 * 64 * 16; }
+// taps = 5 (layer 1 of the k = (5, 3, 3) variant) packs the k-step-major image the five-tap kernels stream
+hipError_t launch_pack_cnn1d_x3(const float* wf, void* wx, int cin, int cout, hipStream_t s, int taps) {
+  const int total = (cout / 32) * taps * cnn1d_x3_nks(cin) * 64;
+  hipLaunchKernelGGL(pack_cnn1d_x3_kernel, dim3((total + 255) / 256), dim3(256), 0, s, wf, (uint4*)wx, cin, cout, cnn1d_x3_nks(cin), taps,
+                     taps == 5 ? 1 : 0);
   return hipGetLastError();
 }
 
@@ -144,14 +147,17 @@ __device__ __forceinline__ void store_split(const f32x16_t& acc, const float* bi
 // pitch of T rounded up to 4 floats (rows of the padded batch are loaded 16 bytes at a time), otherwise at T (contiguous slab).
 // Host and device: the ragged kernel asks it per segment, its launch for the largest window.
 __host__ __device__ inline int cnn1d_x3_nks_hd(int cin) { const int n = (cin + 15) / 16; return (cin == 32 || cin == 64) ? n : (n + 1) & ~1; }
+// k1 = taps of layer 1.  3: its whole A-fragment image sits behind the split images.  5 (the k = (5, 3, 3) variant): the image
+// (120 KB at F = 180) does not fit beside the slabs, so only TWO k-steps of it (5 taps x 2 parts x 1 KB each) are resident and the
+// kernel streams the rest with the slabs; the split images carry a two-frame halo.
 __host__ __device__ inline void cnn1d_x3_layout(int T, int F, int ragged, int* offB, int* total, int* slab_floats, int* offS = nullptr,
-                                                int* offH2 = nullptr) {
+                                                int* offH2 = nullptr, int k1 = 3) {
   const int NT = (T + 31) / 32, nslots = 32 * NT + 2, nks1 = cnn1d_x3_nks_hd(F);
   const int SL = 16 * (ragged ? (T + 3) & ~3 : T) + 8;
   const int oS = (2 * SL * 4 + 255) / 256 * 256;                       // two fp32 slabs
-  const int oB = (oS + 2 * nslots * 64 + 255) / 256 * 256;             // two split images
+  const int oB = (oS + 2 * (nslots + (k1 == 5 ? 2 : 0)) * 64 + 255) / 256 * 256;             // two split images
   const int oH2 = (nslots * 128 + 255) / 256 * 256;                    // h1, then h2
-  const int l1 = oB + 3 * nks1 * 2 * 64 * 16, l23 = oH2 + nslots * 256 + 64;
+  const int l1 = oB + (k1 == 5 ? 2 * 5 : 3 * nks1) * 2 * 64 * 16, l23 = oH2 + nslots * 256 + 64;
   *offB = oB;
   *total = l1 > l23 ? l1 : l23;
   *slab_floats = SL;
@@ -168,22 +174,23 @@ __host__ __device__ inline void cnn1d_x3_layout(int T, int F, int ragged, int* o
 // aligned; layer 3 needs 3) to 3 frames behind the owned range, both clipped to [0, T).
 __host__ __device__ inline int cnn1d_ragged_nseg(int T, int seg_step, int wcap) { return T <= wcap ? 1 : (T + seg_step - 1) / seg_step; }
 // -> window start w0 and length W in the utterance, owned frames [olo, ohi) in WINDOW coordinates
-__host__ __device__ inline void cnn1d_ragged_segment(int T, int seg_step, int wcap, int seg, int* w0, int* W, int* olo, int* ohi) {
+// back = the frames a window runs on behind its owned range: 3 (three-tap layers: 1 + 1 + 1), 4 with a five-tap layer 1 (2 + 1 + 1)
+__host__ __device__ inline void cnn1d_ragged_segment(int T, int seg_step, int wcap, int seg, int* w0, int* W, int* olo, int* ohi, int back = 3) {
   if (T <= wcap) { *w0 = 0; *W = T; *olo = 0; *ohi = T; return; }
   const int lo = seg * seg_step, hi = lo + seg_step < T ? lo + seg_step : T;
-  const int ws = lo >= 4 ? lo - 4 : 0, we = hi + 3 < T ? hi + 3 : T;
+  const int ws = lo >= 4 ? lo - 4 : 0, we = hi + back < T ? hi + back : T;
   *w0 = ws; *W = we - ws; *olo = lo - ws; *ohi = hi - ws;
 }
-int cnn1d_ragged_wcap(int F) {
+int cnn1d_ragged_wcap(int F, int k1) {
   int w = 0;
   for (int T = 3; T <= 384 && (T + 31) / 32 <= c1x::NW * c1x::MAXT1; ++T) {   // (a slab's 16 rows of ceil(T / 4) float4 fit the 3 x 512 loads of a trip)
     int offB, total, sl;
-    cnn1d_x3_layout(T, F, 1, &offB, &total, &sl);
+    cnn1d_x3_layout(T, F, 1, &offB, &total, &sl, nullptr, nullptr, k1);
     if (total <= 160 * 1024) w = T;      // (the layout grows with T)
   }
   return w;
 }
-int cnn1d_ragged_seg_step(int F) { return (cnn1d_ragged_wcap(F) - 7) & ~3; }
+int cnn1d_ragged_seg_step(int F, int k1) { return (cnn1d_ragged_wcap(F, k1) - (k1 == 5 ? 8 : 7)) & ~3; }
 
 // what the ragged form takes beside Cnn1dX3Args (whose x is then the padded batch and whose T / NT / LDS offsets are unused)
 struct Cnn1dRaggedArgs {
@@ -194,6 +201,11 @@ struct Cnn1dRaggedArgs {
 };
 
 #define DFA_KERNEL_BODY_SCOPE   // the kernel bodies below include cnn1d_x3_body.h
+// C1X_K1 = taps of layer 1.  With 3 the body must stay, token for token, what it was before the five-tap form existed -- the two
+// kernels below are held to the same instructions -- so everything five taps add sits under `#if C1X_K1 == 5`,
+// and the one name both forms share, `nslots1` (slots of a split image), is a #define of `nslots` in the three-tap body rather
+// than a second variable: an `int nslots1 = nslots` changed the order of hipcc's scalar address arithmetic.  Keep it a macro.
+#define C1X_K1 3
 __global__ __launch_bounds__(512) void cnn1d_fused_x3_kernel(Cnn1dX3Args a) {
 #define C1X_RAGGED 0
 #include "cnn1d_x3_body.h"
@@ -208,6 +220,25 @@ __global__ __launch_bounds__(512) void cnn1d_ragged_x3_kernel(Cnn1dX3Args a, Cnn
 #include "cnn1d_x3_body.h"
 #undef C1X_RAGGED
 }
+#undef C1X_K1
+
+// The k = (5, 3, 3) variant (the reference's src/compare_kernels.py:38-67): layer 1 has five taps and padding 2, layers 2 and 3
+// are the three-tap ones.  Same body; what C1X_K1 = 5 changes is layer 1 alone -- a two-frame halo in the split images, five
+// fragment pairs per frame tile, and the A fragments STREAMED: the k-step-major image (pack_cnn1d_x3_kernel, ksmajor) passes
+// through two 10 KB LDS buffers, k-step s + 1 parked while k-step s is computed, k-step s + 2 in flight in registers -- the
+// slabs' own pipeline, one barrier per trip as before.  a.w1 = that image, a.nks1 k-steps of 640 uint4.
+#define C1X_K1 5
+__global__ __launch_bounds__(512) void cnn1d_fused_x3_k5_kernel(Cnn1dX3Args a) {
+#define C1X_RAGGED 0
+#include "cnn1d_x3_body.h"
+#undef C1X_RAGGED
+}
+__global__ __launch_bounds__(512) void cnn1d_ragged_x3_k5_kernel(Cnn1dX3Args a, Cnn1dRaggedArgs rg) {
+#define C1X_RAGGED 1
+#include "cnn1d_x3_body.h"
+#undef C1X_RAGGED
+}
+#undef C1X_K1
 #undef DFA_KERNEL_BODY_SCOPE
 
 
@@ -237,7 +268,7 @@ struct Conv1dX3Args {
 };
 
 // A-fragment images with TERMS bf16 terms per weight: wx[m][tap][ks][term][lane] (pack_conv1d_train_all_kernel writes them)
-size_t conv1d_terms_pack_bytes(int cin, int cout, int terms) { return (size_t)(cout / 32) * 3 * cnn1d_x3_nks(cin) * terms * 64 * 16; }
+size_t conv1d_terms_pack_bytes(int cin, int cout, int terms, int taps) { return (size_t)(cout / 32) * taps * cnn1d_x3_nks(cin) * terms * 64 * 16; }
 
 // The five images of a training step (forward layers 1-3, data gradients 3 -> 2 and 2 -> 1) in ONE launch, the data-gradient ones read
 // straight from the layer's own weight: W'[c][o][k'] = W[o][c][2 - k'] (a Conv1d with Cin' = Cout, Cout' = Cin) -- seven launches
@@ -246,6 +277,7 @@ struct Conv1dPackAll {
   const float* w[5];     // the layer's weight [Cout][Cin][3] (for a flipped entry: the FORWARD layer's weight)
   uint4* dst[5];
   int cin[5], cout[5], nks[5], flip[5], begin[6];   // cin / cout of the convolution the image serves; fragment range [begin[i], begin[i+1])
+  int taps[5];           // 3; 5 for entry 0 of the k = (5, 3, 3) variant, whose image is k-step-major: [ks][tap][term][lane] (conv1d_x3_k5_kernel)
   int terms;
   float* zero_bias;      // [256] zeroed here (the data gradients' bias)
 };
@@ -260,7 +292,8 @@ __global__ void pack_conv1d_train_all_kernel(Conv1dPackAll a) {
   const int lane = li & 63;
   int rest = li >> 6;
   const int ks = rest % nks; rest /= nks;
-  const int tap = rest % 3, m = rest / 3;
+  const int taps = a.taps[e];
+  const int tap = rest % taps, m = rest / taps;
   const int co = 32 * m + (lane & 31), hh = lane >> 5;
   const float* w = a.w[e];
   bf16_t t0[8], t1[8], t2[8];
@@ -269,20 +302,20 @@ __global__ void pack_conv1d_train_all_kernel(Conv1dPackAll a) {
     const int ci = 16 * ks + 8 * hh + j;
     float v = 0.f;
     if (ci < cin) v = a.flip[e] ? w[((size_t)ci * cout + co) * 3 + (2 - tap)]      // forward weight [o = ci'][c = co'][2 - k'], its Cin = cout'
-                                : w[((size_t)co * cin + ci) * 3 + tap];
+                                : w[((size_t)co * cin + ci) * taps + tap];
     t0[j] = float_to_bf16(v);
     const float r1 = v - bf16_to_float(t0[j]);
     t1[j] = float_to_bf16(r1);
     t2[j] = float_to_bf16(r1 - bf16_to_float(t1[j]));
   }
-  uint4* dst = a.dst[e] + ((size_t)((m * 3 + tap) * nks + ks) * a.terms) * 64 + lane;
+  uint4* dst = a.dst[e] + ((size_t)(taps == 5 ? (m * nks + ks) * taps + tap : (m * 3 + tap) * nks + ks) * a.terms) * 64 + lane;
   dst[0] = *reinterpret_cast<const uint4*>(t0);
   dst[64] = *reinterpret_cast<const uint4*>(t1);
   if (a.terms == 3) dst[128] = *reinterpret_cast<const uint4*>(t2);
 }
 // w1, w2, w3: the three Conv1d weights [32][F][3], [64][32][3], [128][64][3]; dst[0..4]: forward 1-3, data gradients 3 -> 2, 2 -> 1
 hipError_t launch_pack_conv1d_train_all(const float* w1, const float* w2, const float* w3, void* const* dst, int F, int terms, float* zero_bias,
-                                        hipStream_t s) {
+                                        hipStream_t s, int k1) {
   Conv1dPackAll a{};
   const float* w[5] = {w1, w2, w3, w3, w2};
   const int cin[5] = {F, 32, 64, 128, 64}, cout[5] = {32, 64, 128, 64, 32}, flip[5] = {0, 0, 0, 1, 1};
@@ -290,7 +323,8 @@ hipError_t launch_pack_conv1d_train_all(const float* w1, const float* w2, const 
   for (int i = 0; i < 5; ++i) {
     a.w[i] = w[i]; a.dst[i] = (uint4*)dst[i]; a.cin[i] = cin[i]; a.cout[i] = cout[i]; a.flip[i] = flip[i];
     a.nks[i] = cnn1d_x3_nks(cin[i]);
-    a.begin[i + 1] = a.begin[i] + (cout[i] / 32) * 3 * a.nks[i] * 64;
+    a.taps[i] = i == 0 ? k1 : 3;
+    a.begin[i + 1] = a.begin[i] + (cout[i] / 32) * a.taps[i] * a.nks[i] * 64;
   }
   a.terms = terms; a.zero_bias = zero_bias;
   const int total = a.begin[5] > 256 ? a.begin[5] : 256;
@@ -514,41 +548,234 @@ hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const fl
   return mt == 2 ? go(conv1d_x3_kernel<2, 2>) : go(conv1d_x3_kernel<1, 2>);
 }
 
-bool cnn1d_fused_x3_supports(const FeatView& v) {
+
+// ---- layer 1 of the k = (5, 3, 3) variant's training step: Conv1d(k = 5, pad 2), F -> 32, the kernel above with five taps and
+// one channel tile.  Its image -- 5 taps x nks x TERMS KB, 180 KB at F = 180 with three terms -- has no resident form, so it is
+// STREAMED as in the eval kernel (cnn1d_x3_body.h, C1X_K1 = 5): packed k-step-major (pack_conv1d_train_all_kernel, ksmajor), one
+// k-step's [5 taps][TERMS][64 lanes] fragments (15 KB / 10 KB) pass through two LDS buffers -- k-step s + 1 is parked while k-step s
+// is computed, k-step s + 2 is in flight in two registers -- on the slabs' own barrier.  A function of its own, so that the
+// three-tap instantiations above keep their text.  The lane splits x[c][t - 2 .. t + 2] per tap inside the tap loop (16 values live
+// instead of 80).
+template <int TERMS, bool AUG>
+__global__ __launch_bounds__(512) void conv1d_x3_k5_kernel(Conv1dX3Args a) {
+  using namespace c1x;
+  constexpr int K = 5, WKS = K * TERMS * 64;               // uint4 of one k-step's fragments: 960 (three terms) or 640
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 31, h = lane >> 5;
+  const int b = blockIdx.x;
+  const int T = a.T, NT = a.NT, nks = a.nks;
+  float* const slab0 = (float*)smem;                      // two slabs of slab_floats floats: [4 pad][16 x T][4 pad]
+  char* const wS = smem + a.offW;                         // W[0], W[1]: one k-step each, [5][TERMS][64] x 16 B
+  f32x16_t acc[MAXT1];
+  const float4* xg = (const float4*)(a.x + (size_t)b * a.sb);
+  const int SL = a.slab_floats;
+  constexpr int NLD = 3;
+  float4 xrA[NLD], xrB[NLD];
+  const int nreal = (a.Cin + 15) / 16;
+  auto slab_n4 = [&](int s) { return max(0, min(16, a.Cin - 16 * s)) * T / 4; };
+  auto slab_load = [&](int s, float4 (&xr)[NLD]) {         // unconditional, clamped (as conv1d_x3_kernel)
+    const int sc = min(s, nreal - 1), n4 = slab_n4(sc);
+    if constexpr (AUG) {
+      const float* xf = a.x + (size_t)b * a.sb;
+#pragma unroll
+      for (int k = 0; k < NLD; ++k) {
+        const int i = min(k * NTH + tid, n4 - 1);
+        float e[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int flat = 4 * i + u, c = flat / T, t = flat - c * T, f = 16 * sc + c;
+          e[u] = aug_apply(a.aug, xf[(size_t)f * T + aug_src_t(a.aug, t)], b, t, f);
+        }
+        xr[k] = make_float4(e[0], e[1], e[2], e[3]);
+      }
+    } else {
+      const float4* src = xg + (size_t)4 * sc * T;
+#pragma unroll
+      for (int k = 0; k < NLD; ++k) xr[k] = src[min(k * NTH + tid, n4 - 1)];
+    }
+  };
+  auto slab_store = [&](int s, const float4 (&xr)[NLD]) {
+    float* dst = slab0 + (s & 1) * SL + 4;
+    const int n4 = slab_n4(s);
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) {
+      const int i = k * NTH + tid;
+      const unsigned m = i < n4 ? 0xffffffffu : 0u;
+      const float4 v = xr[k];
+      if (i < 4 * T)
+        *(uint4*)(dst + 4 * i) = make_uint4(__float_as_uint(v.x) & m, __float_as_uint(v.y) & m, __float_as_uint(v.z) & m, __float_as_uint(v.w) & m);
+    }
+  };
+  uint4 wr0, wr1;                                          // k-step in flight (two scalars: an array of two was kept in scratch)
+  auto w_load = [&](int s) {                               // unconditional, clamped: past the last k-step the last one again
+    const uint4* src = a.w + (size_t)min(s, nks - 1) * WKS;
+    wr0 = src[tid];
+    wr1 = src[min(NTH + tid, WKS - 1)];
+  };
+  auto w_park = [&](int s) {                               // registers -> W[s & 1]
+    char* dst = wS + (s & 1) * (WKS * 16);
+    *(uint4*)(dst + (size_t)tid * 16) = wr0;
+    if (tid < WKS - NTH) *(uint4*)(dst + (size_t)(NTH + tid) * 16) = wr1;
+  };
+  w_load(0);
+  slab_load(0, xrA);
+  slab_load(1, xrB);
+  w_park(0);
+  w_load(1);
+  if (tid < 16) {
+    const int sbuf = tid >> 3, e = tid & 7;
+    slab0[sbuf * SL + (e < 4 ? e : 16 * T + e)] = 0.f;
+  }
+  slab_store(0, xrA);
+  __syncthreads();
+
+  const int nmine = (NT - wave + NW - 1) / NW;
+  unsigned tin[MAXT1][K];                                  // all-ones where tap k of this lane's frame exists (t - 2 + k in [0, T)), else 0
+  int tl[MAXT1];
+#pragma unroll
+  for (int j = 0; j < MAXT1; ++j) {
+    const int t = TW * (wave + NW * j) + col;
+    tl[j] = t;
+#pragma unroll
+    for (int k = 0; k < K; ++k) tin[j][k] = ((j < nmine) && t < T && t - 2 + k >= 0 && t - 2 + k < T) ? 0xffffffffu : 0u;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  }
+  // trip s: compute k-step s from slab buffer s & 1 and W[s & 1]; request slab s + 2; park k-step s + 1 in W[(s + 1) & 1] (last read
+  // in trip s - 1, behind that trip's barrier) and request k-step s + 2; park slab s + 1; one barrier
+  auto trip = [&](int s, float4 (&xr_next)[NLD], float4 (&xr_far)[NLD], bool load) {
+    if (load) slab_load(s + 2, xr_far);
+    const float* sl = slab0 + (s & 1) * SL + 4 + 8 * h * T - 2;       // this lane half's 8 channels, frame index - 2
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      uint4 w[TERMS];
+#pragma unroll
+      for (int p = 0; p < TERMS; ++p) w[p] = *(const uint4*)(wS + ((size_t)((((s & 1) * K + k) * TERMS + p) * 64 + lane)) * 16);
+#pragma unroll
+      for (int j = 0; j < MAXT1; ++j) {
+        float v[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = sl[c * T + tl[j] + k];
+        uint4 xs[TERMS];
+        split8n<TERMS>(v, xs);
+#pragma unroll
+        for (int p = 0; p < TERMS; ++p) xs[p] = and4(tin[j][k], xs[p]);
+        if constexpr (TERMS == 3) {                        // smallest terms first
+          acc[j] = mma32(w[2], xs[0], acc[j]);
+          acc[j] = mma32(w[0], xs[2], acc[j]);
+          acc[j] = mma32(w[1], xs[1], acc[j]);
+        }
+        acc[j] = mma32(w[1], xs[0], acc[j]);
+        acc[j] = mma32(w[0], xs[1], acc[j]);
+        acc[j] = mma32(w[0], xs[0], acc[j]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    w_park(s + 1);
+    w_load(s + 2);
+    slab_store(s + 1, xr_next);
+    __syncthreads();
+  };
+  int s = 0;
+  for (; s + 2 < nks; s += 2) {                              // nks is even
+    trip(s, xrB, xrA, true);
+    trip(s + 1, xrA, xrB, true);
+  }
+  trip(s, xrB, xrA, false);
+  trip(s + 1, xrA, xrB, false);
+
+  // ---- + bias, channel-major store (as conv1d_x3_kernel, channel tile 0)
+  const int cb = 4 * h;
+  float bv[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) bv[r] = a.bias[cb + (r & 3) + 8 * (r >> 2)];
+#pragma unroll
+  for (int j = 0; j < MAXT1; ++j) {
+    const int t = tl[j];
+    if (j < nmine && t < T) {
+      float* zr = a.z + ((size_t)b * a.Cout + cb) * T + t;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) zr[(size_t)((r & 3) + 8 * (r >> 2)) * T] = acc[j][r] + bv[r];
+    }
+  }
+}
+
+static void conv1d_x3_k5_layout(int T, int terms, int* offW, int* total, int* slab_floats) {
+  const int sl = 16 * T + 8;
+  *slab_floats = sl;
+  *offW = (2 * sl * 4 + 255) & ~255;
+  *total = *offW + 2 * 5 * terms * 64 * 16;
+}
+bool conv1d_x3_k5_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms) {
+  if (T < 3 || T > 384 || (T + 31) / 32 > c1x::NW * c1x::MAXT1 || Cin < 1 || (Cin & 3) || Cout != 32) return false;
+  if (st != 1 || sc != T || (sb & 3) || ((uintptr_t)x & 15) || ((uintptr_t)z & 3)) return false;
+  if ((cnn1d_x3_nks(Cin) & 1) || (terms != 2 && terms != 3)) return false;
+  int offW, total, sl;
+  conv1d_x3_k5_layout(T, terms, &offW, &total, &sl);
+  return total <= 160 * 1024;
+}
+// wx: the k-step-major five-tap image of launch_pack_conv1d_train_all(..., k1 = 5)
+hipError_t launch_conv1d_x3_k5(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int T, int terms,
+                               hipStream_t s, const AugCfg* aug) {
+  Conv1dX3Args a{};
+  if (aug && aug->on) a.aug = *aug;
+  a.x = x; a.sb = sb; a.w = (const uint4*)wx; a.bias = bias; a.z = z; a.T = T; a.Cin = Cin; a.Cout = 32;
+  a.NT = (T + 31) / 32; a.nks = cnn1d_x3_nks(Cin);
+  int total;
+  conv1d_x3_k5_layout(T, terms, &a.offW, &total, &a.slab_floats);
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(B), dim3(c1x::NTH), total, s, a); };
+  if (a.aug.on) return terms == 3 ? go(conv1d_x3_k5_kernel<3, true>) : go(conv1d_x3_k5_kernel<2, true>);
+  return terms == 3 ? go(conv1d_x3_k5_kernel<3, false>) : go(conv1d_x3_k5_kernel<2, false>);
+}
+
+bool cnn1d_fused_x3_supports(const FeatView& v, int k1) {
   const int T = v.T, F = v.F;
   // (a slab of 16 channels = 4 T float4 must fit the 3 x 512 loads of a trip: T <= 384)
   if (T < 3 || T > 384 || (T + 31) / 32 > c1x::NW * c1x::MAXT1 || F < 1 || (F & 3)) return false;
   if (v.st != 1 || v.sf != T || v.sb != (int64_t)F * T || ((uintptr_t)v.x & 15)) return false;
   int offB, total, sl;
-  cnn1d_x3_layout(T, F, 0, &offB, &total, &sl);
+  cnn1d_x3_layout(T, F, 0, &offB, &total, &sl, nullptr, nullptr, k1);
   return total <= 160 * 1024;
+}
+// the longest utterance the one-kernel form takes at F features (0: none), the bound cnn1d_fused_x3_supports applies
+int cnn1d_fused_x3_max_t(int F, int k1) {
+  int best = 0;
+  for (int T = 3; T <= 384 && (T + 31) / 32 <= c1x::NW * c1x::MAXT1; ++T) {
+    int offB, total, sl;
+    cnn1d_x3_layout(T, F, 0, &offB, &total, &sl, nullptr, nullptr, k1);
+    if (total <= 160 * 1024) best = T;
+  }
+  return best;
 }
 
 hipError_t launch_cnn1d_fused_x3(const float* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
                                  const float* b3, const float* cw, const float* cb, float* logits, int B, int T, int F, hipStream_t s,
-                                 long long* stamps) {
+                                 long long* stamps, int k1) {
   Cnn1dX3Args a{};
   a.x = x; a.w1 = (const uint4*)w1; a.w2 = (const uint4*)w2; a.w3 = (const uint4*)w3; a.b1 = b1; a.b2 = b2; a.b3 = b3; a.cw = cw; a.cb = cb;
   a.logits = logits; a.T = T; a.F = F; a.NT = (T + 31) / 32; a.nks1 = cnn1d_x3_nks(F); a.stamps = stamps;
   int total;
-  cnn1d_x3_layout(T, F, 0, &a.offB, &total, &a.slab_floats, &a.offS, &a.offH2);
+  cnn1d_x3_layout(T, F, 0, &a.offB, &total, &a.slab_floats, &a.offS, &a.offH2, k1);
+  if (k1 == 5) return launch_lds(cnn1d_fused_x3_k5_kernel, dim3(B), dim3(c1x::NTH), total, s, a);
   return launch_lds(cnn1d_fused_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a);
 }
 
 // ---- ragged launch: x = the padded batch (element (b, f, t) at b stride_b + f stride_f + t), tab = the device table
-size_t cnn1d_ragged_lds_bytes(int T_max, int F) {
+size_t cnn1d_ragged_lds_bytes(int T_max, int F, int k1) {
   int offB, total, sl;
-  cnn1d_x3_layout(std::min(T_max, cnn1d_ragged_wcap(F)), F, 1, &offB, &total, &sl);
+  cnn1d_x3_layout(std::min(T_max, cnn1d_ragged_wcap(F, k1)), F, 1, &offB, &total, &sl, nullptr, nullptr, k1);
   return (size_t)total;
 }
 // the plan as the kernel walks it (tests, tools): fills up to cap entries, returns the number of segments
-int cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap) {
-  const int wcap = cnn1d_ragged_wcap(F), step = cnn1d_ragged_seg_step(F);
+int cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap, int k1) {
+  const int wcap = cnn1d_ragged_wcap(F, k1), step = cnn1d_ragged_seg_step(F, k1);
   if (T < 3 || wcap < 11 || step < 4) return 0;
   const int n = cnn1d_ragged_nseg(T, step, wcap);
   for (int i = 0; i < n && i < cap; ++i) {
     int w0, W, lo, hi;
-    cnn1d_ragged_segment(T, step, wcap, i, &w0, &W, &lo, &hi);
+    cnn1d_ragged_segment(T, step, wcap, i, &w0, &W, &lo, &hi, k1 == 5 ? 4 : 3);
     if (starts) starts[i] = w0;
     if (lens) lens[i] = W;
     if (owned_lo) owned_lo[i] = w0 + lo;
@@ -558,16 +785,17 @@ int cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, i
 }
 hipError_t launch_cnn1d_ragged_x3(const float* x, int64_t stride_b, int64_t stride_f, const int* tab, const void* w1, const float* b1,
                                   const void* w2, const float* b2, const void* w3, const float* b3, const float* cw, const float* cb,
-                                  float* logits, int B, int T_max, int F, hipStream_t s, long long* stamps) {
+                                  float* logits, int B, int T_max, int F, hipStream_t s, long long* stamps, int k1) {
   Cnn1dX3Args a{};
   a.x = x; a.w1 = (const uint4*)w1; a.w2 = (const uint4*)w2; a.w3 = (const uint4*)w3; a.b1 = b1; a.b2 = b2; a.b3 = b3; a.cw = cw; a.cb = cb;
   a.logits = logits; a.F = F; a.nks1 = cnn1d_x3_nks(F); a.stamps = stamps;
   Cnn1dRaggedArgs rg{};
   rg.rt = RaggedTab{tab, B};
   rg.stride_b = stride_b; rg.stride_f = (int)stride_f;
-  rg.wcap = cnn1d_ragged_wcap(F); rg.seg_step = cnn1d_ragged_seg_step(F);
+  rg.wcap = cnn1d_ragged_wcap(F, k1); rg.seg_step = cnn1d_ragged_seg_step(F, k1);
   if (rg.wcap < 11 || rg.seg_step < 4) return hipErrorInvalidValue;
-  const size_t total = cnn1d_ragged_lds_bytes(T_max, F);
+  const size_t total = cnn1d_ragged_lds_bytes(T_max, F, k1);
+  if (k1 == 5) return launch_lds(cnn1d_ragged_x3_k5_kernel, dim3(B), dim3(c1x::NTH), total, s, a, rg);
   return launch_lds(cnn1d_ragged_x3_kernel, dim3(B), dim3(c1x::NTH), total, s, a, rg);
 }
 

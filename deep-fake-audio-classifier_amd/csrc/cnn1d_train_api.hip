@@ -12,7 +12,8 @@ struct Train1dPlan {
   size_t z[3], h[2], pooled, dpooled, dz[3], dh[2], stats, sums, partial, partial_bytes, total;
 };
 
-Train1dPlan plan_train1d(int B, int T, int F) {
+// k1 = taps of layer 1 (Cnn1dState::k1): sizes the weight-gradient records [32][F][k1] + [32]
+Train1dPlan plan_train1d(int B, int T, int F, int k1) {
   Train1dPlan p;
   Bump take;
   const int C[3] = {32, 64, 128};
@@ -27,7 +28,7 @@ Train1dPlan plan_train1d(int B, int T, int F) {
   const size_t nch = (size_t)cm_chunks(B);
   size_t pb = nch * 128 * 2 * 4;
   const size_t wch = (size_t)conv1d_wgrad_chunks(B);
-  pb = std::max(pb, wch * ((size_t)32 * F * 3 + 32) * 4);
+  pb = std::max(pb, wch * ((size_t)32 * F * k1 + 32) * 4);
   pb = std::max(pb, wch * ((size_t)128 * 64 * 3 + 128) * 4);
   p.partial_bytes = pb;
   p.partial = take(pb);
@@ -66,6 +67,9 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
   tr.aug_armed = AugCfg{};
   tr.step.live = false;                 // and the batch that was in flight is over, whatever this call returns
   if (!m.have_params) return fail(ctx, DFA_E_NOT_PREPARED, "dfa_cnn1d_set_params has not been called");
+  if (m.k1 != 3 && lengths)    // the five-tap layer-1 kernels have no per-utterance bound in their loads
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step is built for kernels (3, 3, 3): dfa_cnn1d_set_kernels bound (%d, 3, 3), "
+                                        "which trains on uniform batches only", m.k1);
   if (!x || !logits || !workspace) return fail(ctx, DFA_E_NULL_PTR, "x, logits and workspace must be non-null");
   if (x_dtype != DFA_DTYPE_F32) return fail(ctx, DFA_E_BAD_DTYPE, "cnn1d takes float32 input (got dtype %d)", x_dtype);
   DFA_TRY(check_shape1d(ctx, B, T, lengths != nullptr));
@@ -77,7 +81,7 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
     frames = 0.0;
     for (int b = 0; b < B; ++b) frames += (double)lengths[b];
   }
-  const Train1dPlan pl = plan_train1d(B, T, F);
+  const Train1dPlan pl = plan_train1d(B, T, F, m.k1);
   DFA_TRY(check_workspace(ctx, workspace, workspace_bytes, pl.total + (lengths ? ragged1d_tab_bytes(B) : 0), false, "train "));
   if (armed.on && (armed.T != T || armed.F != F))
     return fail(ctx, DFA_E_BAD_SHAPE, "armed augmentation is for [T=%d, F=%d], the batch is [T=%d, F=%d]", armed.T, armed.F, T, F);
@@ -107,15 +111,15 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
   }
   // bf16x3 A-fragment images of this step's weights (they change every step): forward layers 1-3, data gradients 3->2, 2->1
   const int xcin[5] = {F, 32, 64, 128, 64}, xcout[5] = {32, 64, 128, 64, 32};
-  if (!tr.wx3[0] || tr.wx3_F != F) {
+  if (!tr.wx3[0] || tr.wx3_F != F || tr.wx3_k1 != m.k1) {
     if (tr.wx3[0]) { DFA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); DFA_HIP_CHECK(ctx, hipFree(tr.wx3[0])); tr.wx3[0] = nullptr; }
     Bump take;
     size_t off[5];
-    for (int i = 0; i < 5; ++i) off[i] = take(conv1d_terms_pack_bytes(xcin[i], xcout[i], 3));
+    for (int i = 0; i < 5; ++i) off[i] = take(conv1d_terms_pack_bytes(xcin[i], xcout[i], 3, i == 0 ? m.k1 : 3));
     char* base = nullptr;
     DFA_HIP_CHECK(ctx, hipMalloc((void**)&base, take.off));
     for (int i = 0; i < 5; ++i) tr.wx3[i] = base + off[i];
-    tr.wx3_F = F;
+    tr.wx3_F = F; tr.wx3_k1 = m.k1;
   }
   const LayerParams layer[3] = {layer_params(m.p, 0), layer_params(m.p, 1), layer_params(m.p, 2)};
   const HeadParams head = head_params(m.p, kCnn1dLayers, 0);
@@ -128,7 +132,7 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
     DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[1].w, tr.wt[0], tr.zero_bias, 32, 64, s));
     DFA_HIP_CHECK(ctx, launch_conv1d_dgrad_pack(layer[2].w, tr.wt[1], tr.zero_bias, 64, 128, s));
   }
-  if (x3) DFA_HIP_CHECK(ctx, launch_pack_conv1d_train_all(layer[0].w, layer[1].w, layer[2].w, tr.wx3, F, terms, tr.zero_bias, s));   // all five images, one launch
+  if (x3) DFA_HIP_CHECK(ctx, launch_pack_conv1d_train_all(layer[0].w, layer[1].w, layer[2].w, tr.wx3, F, terms, tr.zero_bias, s, m.k1));   // all five images, one launch
   step.x3 = x3;
   DropCfg dc = drop_cfg(p_drop, seed, offset);
   step.drop = dc;
@@ -139,7 +143,14 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
   for (int l = 0; l < 3; ++l) {
     float* z = (float*)(ws + pl.z[l]);
     const LayerParams& q = layer[l];
-    if (l == 0) {
+    if (l == 0 && m.k1 == 5) {
+      // five taps: the streamed matrix-core kernel where the three-tap one would run (its image is k-step-major), else the
+      // tap-templated fp32 kernel; the armed augmentation is folded into the loads of either
+      if (x3 && conv1d_x3_k5_supports(x, v.sb, v.sf, v.st, z, T, F, 32, terms))
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3_k5(x, v.sb, tr.wx3[0], q.b, z, B, F, T, terms, s, aug));
+      else
+        DFA_HIP_CHECK(ctx, launch_conv1d(x, v.sb, v.sf, v.st, q.w, q.b, z, B, F, 32, T, false, s, false, aug, nullptr, 5));
+    } else if (l == 0) {
       if (x3 && conv1d_x3_supports(x, v.sb, v.sf, v.st, z, T, F, 32, terms))
         DFA_HIP_CHECK(ctx, launch_conv1d_x3(x, v.sb, tr.wx3[0], q.b, z, B, F, 32, T, terms, s, x3, aug, lens));
       else
@@ -180,7 +191,7 @@ int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const FeatView& v, const float
       ctx, {ragged ? "dfa_cnn1d_backward_ragged" : "dfa_cnn1d_backward", ragged ? "dfa_cnn1d_forward_train_ragged" : "dfa_cnn1d_forward_train",
             "cnn1d", kCnn1dGrads, "dlogits", true},
       step, B, T, F, ragged, v.x, v.dtype, dlogits, grads, ngrads, workspace, workspace_bytes,
-      [&] { return (pl = plan_train1d(B, T, F)).total + (ragged ? ragged1d_tab_bytes(B) : 0); },
+      [&] { return (pl = plan_train1d(B, T, F, m.k1)).total + (ragged ? ragged1d_tab_bytes(B) : 0); },
       [&] {
         return !(ragged && ctx->bn_sync.fn) ? DFA_OK : fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step cannot run under synchronised "
                                                                                      "BatchNorm (dfa_ctx_set_bn_sync is armed)");
@@ -206,7 +217,7 @@ int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const FeatView& v, const float
     DFA_HIP_CHECK(ctx, launch_split_sums(sm, g.dgamma, g.dbeta, C[l], s));
     if (l == 0) {
       DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)v.x, v.sb, v.sf, v.st, partial, g.dw, g.db, B, F, 32, T, s,
-                                             step.aug.on ? &step.aug : nullptr, step.x3, lens));
+                                             step.aug.on ? &step.aug : nullptr, step.x3, lens, m.k1));
     } else {
       DFA_HIP_CHECK(ctx, launch_conv1d_wgrad(dz, (const float*)(ws + pl.h[l - 1]), (int64_t)Cin[l] * T, T, 1, partial, g.dw,
                                              g.db, B, Cin[l], C[l], T, s, nullptr, step.x3));
@@ -227,15 +238,17 @@ int cnn1d_backward_impl(dfa_ctx* ctx, int ragged, const FeatView& v, const float
 extern "C" {
 
 size_t dfa_cnn1d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F) {
-  (void)ctx;
   if (B < 1 || T < 1 || F < 1) return 0;
-  return plan_train1d(B, T, F).total;
+  return plan_train1d(B, T, F, ctx ? ctx->cnn1d.k1 : 3).total;
 }
 
 int dfa_cnn1d_train_plan(dfa_ctx* ctx, int B, int T, int F, int ragged, long long* fields, int cap) {
   DFA_TRY(check_shape1d(ctx, B, T, ragged != 0));
   if (F < 1) return fail(ctx, DFA_E_BAD_SHAPE, "feature dim %d: need F >= 1", F);
-  const Train1dPlan pl = plan_train1d(B, T, F);
+  if (ragged && ctx && ctx->cnn1d.k1 != 3)
+    return fail(ctx, DFA_E_UNSUPPORTED, "the ragged cnn1d training step is built for kernels (3, 3, 3): dfa_cnn1d_set_kernels bound (%d, 3, 3)",
+                ctx->cnn1d.k1);
+  const Train1dPlan pl = plan_train1d(B, T, F, ctx ? ctx->cnn1d.k1 : 3);
   const long long v[] = {(long long)pl.z[0], (long long)pl.z[1], (long long)pl.z[2], (long long)pl.h[0], (long long)pl.h[1],
                          (long long)pl.pooled, (long long)pl.dpooled, (long long)pl.dz[0], (long long)pl.dz[1], (long long)pl.dz[2],
                          (long long)pl.dh[0], (long long)pl.dh[1], (long long)pl.stats, (long long)pl.sums, (long long)pl.partial,
@@ -265,9 +278,8 @@ int dfa_cnn1d_backward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, i
 }
 
 size_t dfa_cnn1d_train_ragged_workspace_bytes(const dfa_ctx* ctx, int B, int T_max, int F) {
-  (void)ctx;
-  if (B < 1 || T_max < 3 || F < 1) return 0;
-  return plan_train1d(B, T_max, F).total + ragged1d_tab_bytes(B);
+  if (B < 1 || T_max < 3 || F < 1 || (ctx && ctx->cnn1d.k1 != 3)) return 0;     // (no ragged step with five taps)
+  return plan_train1d(B, T_max, F, 3).total + ragged1d_tab_bytes(B);
 }
 
 int dfa_cnn1d_forward_train_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T_max, int F, int64_t stride_b,

@@ -10,6 +10,10 @@
 // cnn1d_x3_layout(T) -- and only the layer-3 frames [olo, ohi) of the window (the frames the segment owns) enter the sums.
 // Frames outside [0, T_b) are the zero slots the body keeps anyway; at an interior window edge those zeros are wrong inputs,
 // which reach at most 3 frames into the window, and the owned range starts 4 frames / ends 3 frames inside such an edge.
+//
+// C1X_K1 = taps of layer 1: 3, or 5 for the k = (5, 3, 3) variant (cnn1d_fused_x3.hip has what that changes; here every such
+// place is an #if, so that the three-tap kernels keep their text).  With five taps the wrong inputs of an interior edge reach
+// 4 frames, and the owned range ends 4 frames inside one.
 #ifndef DFA_KERNEL_BODY_SCOPE
 #error "cnn1d_x3_body.h is a kernel body: include it only inside the __global__ functions of cnn1d_fused_x3.hip"
 #endif
@@ -29,10 +33,18 @@
   __builtin_assume(tid_ >= 0 && tid_ < NTH);
   const int tid = tid_, lane = tid & 63;
   int w0, T, olo, ohi;                                     // window start (a multiple of 4), window length, owned frames of the window
+#if C1X_K1 == 5
+  cnn1d_ragged_segment(TB, rg.seg_step, rg.wcap, seg, &w0, &T, &olo, &ohi, 4);
+#else
   cnn1d_ragged_segment(TB, rg.seg_step, rg.wcap, seg, &w0, &T, &olo, &ohi);
+#endif
   const int NT = (T + 31) / 32, P = (T + 3) & ~3, n4r = P >> 2;   // P: row pitch of a slab in LDS, n4r float4 per row
   int offB, offS, offH2, slab_fl, lds_total;
+#if C1X_K1 == 5
+  cnn1d_x3_layout(T, a.F, 1, &offB, &lds_total, &slab_fl, &offS, &offH2, 5);
+#else
   cnn1d_x3_layout(T, a.F, 1, &offB, &lds_total, &slab_fl, &offS, &offH2);
+#endif
   const bool first_seg = seg == 0, last_seg = seg == nseg - 1;
   // (loads through these pointers stay inside the segment: hoisted out of the loop, the 176 registers of weight fragments,
   //  biases and classifier weights were spilled to scratch at the top of the kernel)
@@ -65,6 +77,13 @@
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, h = lane >> 5;
   const int nslots = 32 * NT + 2;
+#if C1X_K1 == 5
+  constexpr int KT = 5, HL = 2;                             // layer 1: taps, halo slots per side of a split image
+  const int nslots1 = 32 * NT + 4;
+#else
+  constexpr int KT = 3, HL = 1;
+#define nslots1 nslots                                      // (a name, not a second variable: the three-tap kernels compile to what they were)
+#endif
   float* const slab0 = (float*)smem;                      // two slabs of slab_floats floats: [4 pad][16 x T][4 pad]
   char* const h1S = smem;                                 // region A again, after layer 1: [nslots][128 B]
   char* const w1S = smem + C1X_OFFB;                        // region B: layer-1 A fragments [3][nks1][2][64] x 16 B ...
@@ -94,7 +113,7 @@
 #endif
     const int SL = C1X_SLAB;
     char* const S0 = smem + C1X_OFFS;                          // two split images of nslots x 64 bytes
-    const int SB = nslots * 64;
+    const int SB = nslots1 * 64;
     constexpr int NLD = 3;                                   // 16 T / 4 float4 per slab <= 1536 = 3 x 512
     float4 xrA[NLD], xrB[NLD];                                // even / odd slabs in flight
     const int nreal = (a.F + 15) / 16;                        // slabs that exist (nks1 may be one more: a zero slab)
@@ -161,16 +180,43 @@
           for (int c = 0; c < 8; ++c) v[c] = fb[(8 * g + c) * P + t];
           uint4 hi, lo;
           split8(v, hi, lo);
-          const int slot = t + 1, sw = lds_swz<64>(slot);
+          const int slot = t + HL, sw = lds_swz<64>(slot);
           *(uint4*)(sb + slot * 64 + ((g ^ sw) << 4)) = hi;
           *(uint4*)(sb + slot * 64 + (((2 + g) ^ sw) << 4)) = lo;
         }
       }
     };
+#if C1X_K1 == 5
+    // one k-step of A fragments = [5 taps][hi | lo][64 lanes] uint4 = 640, contiguous in the k-step-major image: item tid and, for
+    // the first 128 threads, item 512 + tid.  Unconditional clamped loads like the slabs'; past the last k-step the last one again.
+    constexpr int WKS = KT * 2 * 64;
+    uint4 wr0, wr1;                                           // (two scalars: as an array the pair was kept in scratch)
+    auto w_load = [&](int s) {
+      const uint4* src = a.w1 + (size_t)min(s, nks1 - 1) * WKS;
+      wr0 = src[tid];
+      wr1 = src[min(NTH + tid, WKS - 1)];
+    };
+    auto w_park = [&](int s) {                                // registers -> W[s & 1]
+      char* dst = w1S + (s & 1) * (WKS * 16);
+      *(uint4*)(dst + (size_t)tid * 16) = wr0;
+      if (tid < WKS - NTH) *(uint4*)(dst + (size_t)(NTH + tid) * 16) = wr1;
+    };
+    w_load(0);
+#endif
     slab_load(0, xrA);
     slab_load(1, xrB);
     // layer-1 A fragments -> LDS (contiguous copy); the never-written slots of both split images (0 and T + 1 ...) -> zero
     {
+#if C1X_K1 == 5
+      w_park(0);                                              // (five taps: k-step 0 only; the halo is slots 0, 1 and T + 2 ...)
+      w_load(1);
+      const int nz = (nslots1 - T) * 4;
+      for (int i = tid; i < 2 * nz; i += NTH) {
+        const int img = i >= nz, q = i - img * nz, zs = q >> 2;
+        const int slot = zs < HL ? zs : T + zs;
+        *(uint4*)(S0 + img * SB + slot * 64 + (q & 3) * 16) = make_uint4(0u, 0u, 0u, 0u);
+      }
+#else
       const int n = 3 * nks1 * 2 * 64;
       for (int i = tid; i < n; i += NTH) *(uint4*)(w1S + (size_t)i * 16) = a.w1[i];
       const int nz = (nslots - T) * 4;                        // 16-byte chunks of the zero slots, per image
@@ -179,6 +225,7 @@
         const int slot = zs == 0 ? 0 : T + zs;
         *(uint4*)(S0 + img * SB + slot * 64 + (q & 3) * 16) = make_uint4(0u, 0u, 0u, 0u);
       }
+#endif
     }
     slab_park(0, xrA);
     slab_load(2, xrA);
@@ -195,18 +242,45 @@
       for (int r = 0; r < 16; ++r) acc1[j][r] = 0.f;
     auto trip = [&](int s, float4 (&xr)[NLD]) {               // xr: the register set of this trip's parity (holds slab s + 2)
       const char* sb = S0 + (s & 1) * SB;
-      uint4 wh[3], wl[3];
+      uint4 wh[KT], wl[KT];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
+      for (int k = 0; k < KT; ++k) {
+#if C1X_K1 == 5
+        wh[k] = *(const uint4*)(w1S + ((size_t)(((s & 1) * KT + k) * 2) * 64 + lane) * 16);
+        wl[k] = *(const uint4*)(w1S + ((size_t)(((s & 1) * KT + k) * 2 + 1) * 64 + lane) * 16);
+#else
         wh[k] = *(const uint4*)(w1S + ((size_t)((k * nks1 + s) * 2) * 64 + lane) * 16);
         wl[k] = *(const uint4*)(w1S + ((size_t)((k * nks1 + s) * 2 + 1) * 64 + lane) * 16);
+#endif
       }
-      uint4 xh[MAXT1][3], xl[MAXT1][3];
+#if C1X_K1 == 5
+      // (five taps: the fragments of BOTH frame tiles are 80 registers and spilled; one tile's are read while the other's MFMAs run)
+#pragma unroll
+      for (int j = 0; j < MAXT1; ++j) {
+        uint4 xh5[KT], xl5[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+          const int slot = min(TW * (wave + NW * j) + col + k, nslots1 - 1);      // (tiles this wave does not have: clamped, unused)
+          const int sw = lds_swz<64>(slot);
+          xh5[k] = *(const uint4*)(sb + slot * 64 + ((h ^ sw) << 4));
+          xl5[k] = *(const uint4*)(sb + slot * 64 + (((2 + h) ^ sw) << 4));
+        }
+        if (j < nmine) {
+#pragma unroll
+          for (int k = 0; k < KT; ++k) {
+            acc1[j] = mma32(wh[k], xh5[k], acc1[j]);
+            acc1[j] = mma32(wl[k], xh5[k], acc1[j]);
+            acc1[j] = mma32(wh[k], xl5[k], acc1[j]);
+          }
+        }
+      }
+#else
+      uint4 xh[MAXT1][KT], xl[MAXT1][KT];
 #pragma unroll
       for (int j = 0; j < MAXT1; ++j)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int slot = min(TW * (wave + NW * j) + col + k, nslots - 1);      // (tiles this wave does not have: clamped, unused)
+        for (int k = 0; k < KT; ++k) {
+          const int slot = min(TW * (wave + NW * j) + col + k, nslots1 - 1);      // (tiles this wave does not have: clamped, unused)
           const int sw = lds_swz<64>(slot);
           xh[j][k] = *(const uint4*)(sb + slot * 64 + ((h ^ sw) << 4));
           xl[j][k] = *(const uint4*)(sb + slot * 64 + (((2 + h) ^ sw) << 4));
@@ -216,15 +290,20 @@
       for (int j = 0; j < MAXT1; ++j)
         if (j < nmine) {
 #pragma unroll
-          for (int k = 0; k < 3; ++k) {
+          for (int k = 0; k < KT; ++k) {
             acc1[j] = mma32(wh[k], xh[j][k], acc1[j]);
             acc1[j] = mma32(wl[k], xh[j][k], acc1[j]);
             acc1[j] = mma32(wh[k], xl[j][k], acc1[j]);
           }
         }
+#endif
       __builtin_amdgcn_sched_barrier(0);
       slab_split(s + 1);                                      // (past the last slab: a stale buffer into an image nobody reads)
       slab_park(s + 2, xr);
+#if C1X_K1 == 5
+      w_park(s + 1);                                          // W[(s + 1) & 1] was last read in trip s - 1, behind that trip's barrier
+      w_load(s + 2);
+#endif
       slab_load(s + 4, xr);                                   // (clamped: past the end it re-reads the last slab, never parked as data)
       __syncthreads();
     };
@@ -350,6 +429,9 @@
   if (tid == 0 && last_seg) a.logits[b] = (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) + a.cb[0];
 #if C1X_RAGGED
   }   // segments
+#endif
+#if C1X_K1 != 5
+#undef nslots1
 #endif
 #undef C1X_OFFB
 #undef C1X_OFFS

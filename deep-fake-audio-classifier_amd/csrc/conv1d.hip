@@ -17,7 +17,8 @@ constexpr int C1D_OT = 32, C1D_TT = 64, C1D_CC = 16;
 // dfa_cnn1d_set_train_augment) -- the element the stand-alone dfa_augment_batch pass would have written, never materialised.
 // RAGGED (train-mode layer 1 of a ragged batch): x is padded to T frames, utterance b owns [0, lens[b]); a padding frame is
 // never loaded (it may hold NaN / Inf) and reads as the utterance's own zero padding.
-template <bool MEAN, bool RELU = true, bool AUG = false, bool RAGGED = false>
+// K = taps (padding K / 2): 3, or 5 for layer 1 of the k = (5, 3, 3) variant; the x slab holds 64 + K - 1 <= 68 frames.
+template <bool MEAN, bool RELU = true, bool AUG = false, bool RAGGED = false, int K = 3>
 __global__ __launch_bounds__(256) void conv1d_k3_bn_relu_kernel(const float* __restrict__ x, int64_t sb, int64_t sc,
                                                                  int64_t st, const float* __restrict__ w,
                                                                  const float* __restrict__ bias,
@@ -25,7 +26,7 @@ __global__ __launch_bounds__(256) void conv1d_k3_bn_relu_kernel(const float* __r
                                                                  float inv_t, AugCfg aug = AugCfg{},
                                                                  const int* __restrict__ lens = nullptr) {
   __shared__ float xs[C1D_CC][C1D_TT + 4];
-  __shared__ float ws[C1D_CC][3][C1D_OT];
+  __shared__ float ws[C1D_CC][K][C1D_OT];
   __shared__ float red[C1D_OT][17];
   const int tid = threadIdx.x;
   const int tq = tid & 15, oq = tid >> 4;       // 16 frame-quads x 16 channel-pairs
@@ -44,27 +45,27 @@ __global__ __launch_bounds__(256) void conv1d_k3_bn_relu_kernel(const float* __r
     for (int j = 0; j < 4; ++j) { acc[0][j] = b0; acc[1][j] = b1; }
     for (int c0 = 0; c0 < Cin; c0 += C1D_CC) {
       __syncthreads();
-      for (int e = tid; e < C1D_CC * (C1D_TT + 2); e += 256) {
-        const int c = e / (C1D_TT + 2), tt = e - c * (C1D_TT + 2);
-        const int t = t0 - 1 + tt, ci = c0 + c;
+      for (int e = tid; e < C1D_CC * (C1D_TT + K - 1); e += 256) {
+        const int c = e / (C1D_TT + K - 1), tt = e - c * (C1D_TT + K - 1);
+        const int t = t0 - K / 2 + tt, ci = c0 + c;
         if constexpr (AUG)
           xs[c][tt] = (ci < Cin && t >= 0 && t < T) ? aug_apply(aug, xb[(int64_t)ci * sc + (int64_t)aug_src_t(aug, t) * st], b, t, ci) : 0.f;
         else
           xs[c][tt] = (ci < Cin && t >= 0 && t < Tx) ? xb[(int64_t)ci * sc + (int64_t)t * st] : 0.f;
       }
-      for (int e = tid; e < C1D_CC * 3 * C1D_OT; e += 256) {
-        const int o = e & (C1D_OT - 1), k = (e / C1D_OT) % 3, c = e / (3 * C1D_OT);
+      for (int e = tid; e < C1D_CC * K * C1D_OT; e += 256) {
+        const int o = e & (C1D_OT - 1), k = (e / C1D_OT) % K, c = e / (K * C1D_OT);
         const int ci = c0 + c;
-        ws[c][k][o] = (ci < Cin) ? w[((size_t)(o0 + o) * Cin + ci) * 3 + k] : 0.f;
+        ws[c][k][o] = (ci < Cin) ? w[((size_t)(o0 + o) * Cin + ci) * K + k] : 0.f;
       }
       __syncthreads();
 #pragma unroll 4
       for (int c = 0; c < C1D_CC; ++c) {
-        float xv[6];
+        float xv[K + 3];
 #pragma unroll
-        for (int j = 0; j < 6; ++j) xv[j] = xs[c][4 * tq + j];
+        for (int j = 0; j < K + 3; ++j) xv[j] = xs[c][4 * tq + j];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < K; ++k) {
           const float w0 = ws[c][k][2 * oq], w1 = ws[c][k][2 * oq + 1];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -103,28 +104,44 @@ __global__ __launch_bounds__(256) void conv1d_k3_bn_relu_kernel(const float* __r
   }
 }
 
-// fold BN1d into conv weights (same [Cout][Cin][3] layout) and bias
+// fold BN1d into conv weights (same [Cout][Cin][taps] layout) and bias
 __global__ void fold_conv1d_kernel(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ g,
                                    const float* __restrict__ beta, const float* __restrict__ mean,
                                    const float* __restrict__ var, float* __restrict__ wf, float* __restrict__ bf,
-                                   int cin, int cout) {
+                                   int cin, int cout, int taps) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < cout * cin * 3) {
-    const int o = i / (cin * 3);
+  if (i < cout * cin * taps) {
+    const int o = i / (cin * taps);
     wf[i] = w[i] * (g[o] / sqrtf(var[o] + kBnEps));
   }
   if (i < cout) bf[i] = (b[i] - mean[i]) * (g[i] / sqrtf(var[i] + kBnEps)) + beta[i];
 }
 
-hipError_t launch_fold_conv1d(const LayerParams& lp, float* wf, float* bf, int cin, int cout, hipStream_t s) {
-  const int n = cout * cin * 3;
+hipError_t launch_fold_conv1d(const LayerParams& lp, float* wf, float* bf, int cin, int cout, hipStream_t s, int taps) {
+  const int n = cout * cin * taps;
   hipLaunchKernelGGL(fold_conv1d_kernel, dim3((n + 255) / 256), dim3(256), 0, s, lp.w, lp.b, lp.gamma, lp.beta, lp.rmean, lp.rvar, wf, bf, cin,
-                     cout);
+                     cout, taps);
   return hipGetLastError();
 }
 
 hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, const float* w, const float* bias,
-                         float* out, int B, int Cin, int Cout, int T, bool mean, hipStream_t s, bool relu, const AugCfg* aug, const int* lens) {
+                         float* out, int B, int Cin, int Cout, int T, bool mean, hipStream_t s, bool relu, const AugCfg* aug, const int* lens,
+                         int taps) {
+  if (taps == 5) {        // layer 1 of the k = (5, 3, 3) variant: eval (BatchNorm folded, ReLU) or train mode (raw, the augmentation folded)
+    if (lens || mean || (relu && aug && aug->on)) return hipErrorInvalidValue;
+    const dim3 grid((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B);
+    if (relu)
+      hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, true, false, false, 5>), grid, dim3(256), 0, s, x, sb, sc, st, w, bias, out, Cin, Cout,
+                         T, 0.f, AugCfg{}, nullptr);
+    else if (aug && aug->on)
+      hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, true, false, 5>), grid, dim3(256), 0, s, x, sb, sc, st, w, bias, out, Cin, Cout,
+                         T, 0.f, *aug, nullptr);
+    else
+      hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, false, false, 5>), grid, dim3(256), 0, s, x, sb, sc, st, w, bias, out, Cin, Cout,
+                         T, 0.f, AugCfg{}, nullptr);
+    return hipGetLastError();
+  }
+  if (taps != 3) return hipErrorInvalidValue;
   if (lens) {             // train-mode layer 1 of a ragged batch
     if (relu || mean || (aug && aug->on)) return hipErrorInvalidValue;
     hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, false, true>), dim3((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256),

@@ -102,7 +102,7 @@ struct Cnn1dEval {
 struct Cnn1dTrain {          // cnn1d_train_api.hip
   void* train_packed = nullptr;   // data-gradient weight images of conv layers 2 and 3 (+ a zero bias)
   float *wt[2] = {nullptr, nullptr}, *zero_bias = nullptr;
-  int wx3_F = 0;
+  int wx3_F = 0, wx3_k1 = 3;      // what the wx3 allocation was sized for
   void* wx3[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // per-step bf16x3 A-fragment images: forward layers 1-3, data gradients 3->2, 2->1 (conv1d_x3_kernel); wx3[0] = their one allocation
   AugCfg aug_armed{};             // dfa_cnn1d_set_train_augment: consumed by the next forward_train
   TrainStep step;
@@ -116,6 +116,7 @@ struct Cnn1dState : Cnn1dEval {
   const float* p[DFA_CNN1D_NPARAMS] = {nullptr};
   bool have_params = false;
   int in_features = 0;
+  int k1 = 3;                  // taps of layer 1: 3, or 5 for the k = (5, 3, 3) variant (dfa_cnn1d_set_kernels; sticky)
   Cnn1dTrain train;
 };
 
@@ -318,7 +319,7 @@ hipError_t launch_linear(const float* emb, const float* w, const float* bias, fl
 hipError_t launch_emb_reduce(const float* parts, int nparts, size_t stride, size_t n, float inv_h, float* out, hipStream_t s);
 hipError_t launch_emb_reduce_ragged(const float* parts, size_t stride, int per_b, const int* tab, int B, float* out, hipStream_t s);
 // conv1d.hip
-hipError_t launch_fold_conv1d(const LayerParams& lp, float* wf, float* bf, int cin, int cout, hipStream_t s);
+hipError_t launch_fold_conv1d(const LayerParams& lp, float* wf, float* bf, int cin, int cout, hipStream_t s, int taps = 3);
 // cae_enc1_mfma.hip: auto-encoder block 1 (conv 1 -> 32 + ReLU + 2 x 2 pool) on the matrix cores, bf16 mode
 hipError_t launch_cae_enc1_mfma(const FeatView& v, const float* mu, const float* sigma, const uint4* c1pack, const float* c1bias, void* out,
                                 hipStream_t s);
@@ -349,22 +350,24 @@ hipError_t launch_cnn1d_fused(const FeatView& v, const float* wp1, const float* 
                               const float* b3, const float* cw, const float* cb, float* logits, hipStream_t s, long long* stamps = nullptr);
 // cnn1d_fused_x3.hip: the same forward on the bf16 matrix cores with hi + lo bf16 operands (fp32-grade accuracy)
 int cnn1d_x3_nks(int cin);
-size_t cnn1d_x3_pack_bytes(int cin, int cout);
-hipError_t launch_pack_cnn1d_x3(const float* wf, void* wx, int cin, int cout, hipStream_t s);
-bool cnn1d_fused_x3_supports(const FeatView& v);
+// k1 / taps: the taps of layer 1, 3 or 5 (the k = (5, 3, 3) variant: five-tap kernels, a k-step-major layer-1 image)
+size_t cnn1d_x3_pack_bytes(int cin, int cout, int taps = 3);
+hipError_t launch_pack_cnn1d_x3(const float* wf, void* wx, int cin, int cout, hipStream_t s, int taps = 3);
+bool cnn1d_fused_x3_supports(const FeatView& v, int k1 = 3);
+int cnn1d_fused_x3_max_t(int F, int k1);
 // ragged form (cnn1d_ragged_x3_kernel): x = the batch padded to T_max, element (b, f, t) at b stride_b + f stride_f + t;
 // tab = device table, [0, B) lengths, [B, 2B) dispatch order
 hipError_t launch_cnn1d_ragged_x3(const float* x, int64_t stride_b, int64_t stride_f, const int* tab, const void* w1, const float* b1,
                                   const void* w2, const float* b2, const void* w3, const float* b3, const float* cw, const float* cb,
-                                  float* logits, int B, int T_max, int F, hipStream_t s, long long* stamps);
-size_t cnn1d_ragged_lds_bytes(int T_max, int F);
-int cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap);
+                                  float* logits, int B, int T_max, int F, hipStream_t s, long long* stamps, int k1 = 3);
+size_t cnn1d_ragged_lds_bytes(int T_max, int F, int k1 = 3);
+int cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap, int k1 = 3);
 hipError_t launch_cnn1d_fused_x3(const float* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
                                  const float* b3, const float* cw, const float* cb, float* logits, int B, int T, int F, hipStream_t s,
-                                 long long* stamps = nullptr);
+                                 long long* stamps = nullptr, int k1 = 3);
 hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, const float* w, const float* bias,
                          float* out, int B, int Cin, int Cout, int T, bool mean, hipStream_t s, bool relu = true,
-                         const AugCfg* aug = nullptr, const int* lens = nullptr);
+                         const AugCfg* aug = nullptr, const int* lens = nullptr, int taps = 3);
 // api.hip: the per-call table of a ragged batch ([0, B) lengths, [B, 2B) dispatch order: 2 B words) through the next pinned staging
 // slot to `dst` (device) on the context's stream
 int stage_ragged_lengths(dfa_ctx* ctx, const int32_t* lengths, int B, void* dst);
@@ -458,11 +461,17 @@ hipError_t launch_cm_bn_bwd(int src, const float* z, const BnApply& bn, const fl
 bool conv1d_x3_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms);
 hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int Cout, int T,
                             int terms, hipStream_t s, int mode = 1, const AugCfg* aug = nullptr, const int* lens = nullptr);
-size_t conv1d_terms_pack_bytes(int cin, int cout, int terms);
+size_t conv1d_terms_pack_bytes(int cin, int cout, int terms, int taps = 3);
+// layer 1 of the k = (5, 3, 3) variant's training step: five taps, weights streamed (image of launch_pack_conv1d_train_all, k1 = 5)
+bool conv1d_x3_k5_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms);
+hipError_t launch_conv1d_x3_k5(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int T, int terms,
+                               hipStream_t s, const AugCfg* aug);
 hipError_t launch_pack_conv1d_train_all(const float* w1, const float* w2, const float* w3, void* const* dst, int F, int terms, float* zero_bias,
-                                        hipStream_t s);
+                                        hipStream_t s, int k1 = 3);
+// taps = 5: layer 1 of the k = (5, 3, 3) variant (uniform batches; record [Cout][Cin][5] + [Cout])
 hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int64_t hsc, int64_t hst, float* partial,
-                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug = nullptr, int x3 = 0, const int* lens = nullptr);
+                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug = nullptr, int x3 = 0, const int* lens = nullptr,
+                               int taps = 3);
 hipError_t launch_conv1d_dgrad_pack(const float* w, float* wt, float* zero_bias, int cin, int cout, hipStream_t s);
 // cae.hip
 hipError_t launch_cae_enc1(const FeatView& v, const float* mu, const float* sigma, const float* w1, const float* b1, void* out, int prec,

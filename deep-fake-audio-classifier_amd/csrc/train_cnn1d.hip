@@ -137,19 +137,21 @@ constexpr int W1D_TT = 64;
 // them straight from LDS tiles (lane = channel, k = frame parity).  One wave per (o tile, c tile, utterance chunk):
 // 96 MFMAs per 64-frame slab.
 // AUG (layer 1 only): h = x read through the armed train-time augmentation, as the forward read it (conv1d.hip)
-template <bool AUG, bool RAGGED = false>
+// K = taps (padding K / 2): 3, or 5 for layer 1 of the k = (5, 3, 3) variant -- record [Cout][Cin][K] + [Cout], a window of 64 + K - 1
+// frames per slab (K = 5: two more extra frames per channel, rh3)
+template <bool AUG, bool RAGGED = false, int K = 3>
 __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __restrict__ dz, const float* __restrict__ h,
                                                                int64_t hsb, int64_t hsc, int64_t hst,
                                                                float* __restrict__ partial, int B, int Cin, int Cout, int T,
                                                                int bchunk, AugCfg aug, const int* __restrict__ lens = nullptr) {
   __shared__ float dzs[32][W1D_TT + 1];
-  __shared__ float hs[32][W1D_TT + 3];
+  __shared__ float hs[32][W1D_TT + K];
   const int lane = threadIdx.x, r = lane & 31, hh = lane >> 5;
   const int o0 = blockIdx.x * 32, c0 = blockIdx.y * 32, ch = blockIdx.z;
   const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
-  f32x16_t acc[3];
+  f32x16_t acc[K];
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < K; ++k)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[k][i] = 0.f;
   float ab = 0.f;
@@ -158,12 +160,13 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
   const int nslab_t = (T + W1D_TT - 1) / W1D_TT;
   const int nslab = (b1 - b0) * nslab_t;
   float rdz[32], rh[32], rh2 = 0.f;
+  [[maybe_unused]] float rh3 = 0.f;
   auto fetch = [&](int sl) {
     const int b = b0 + sl / nslab_t, t0 = (sl % nslab_t) * W1D_TT;
 #pragma unroll
     for (int oo = 0; oo < 32; ++oo)
       rdz[oo] = (t0 + lane < T) ? dz[((size_t)b * Cout + o0 + oo) * T + t0 + lane] : 0.f;
-    const int t = t0 - 1 + lane;
+    const int t = t0 - K / 2 + lane;
 #pragma unroll
     for (int cc = 0; cc < 32; ++cc) {
       const int ci = c0 + cc;
@@ -175,13 +178,20 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
         rh[cc] = (ci < Cin && t >= 0 && t < T) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
     }
     // the two extra frames of the 66-frame window: lane = (channel, which frame)
-    const int ci2 = c0 + (lane & 31), t2 = t0 + 63 + (lane >> 5);
+    const int ci2 = c0 + (lane & 31), t2 = t0 + 64 - K / 2 + (lane >> 5);
     if constexpr (AUG)
       rh2 = (ci2 < Cin && t2 < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)aug_src_t(aug, t2) * hst], b, t2, ci2) : 0.f;
     else if constexpr (RAGGED)
       rh2 = (ci2 < Cin && t2 < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
     else
       rh2 = (ci2 < Cin && t2 < T) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
+    if constexpr (K == 5) {      // frames 66, 67 of the window (uniform batches only: never RAGGED)
+      const int t3 = t2 + 2;
+      if constexpr (AUG)
+        rh3 = (ci2 < Cin && t3 < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)aug_src_t(aug, t3) * hst], b, t3, ci2) : 0.f;
+      else
+        rh3 = (ci2 < Cin && t3 < T) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t3 * hst] : 0.f;
+    }
   };
   if (nslab > 0) fetch(0);
   for (int sl = 0; sl < nslab; ++sl) {
@@ -191,6 +201,7 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
 #pragma unroll
     for (int cc = 0; cc < 32; ++cc) hs[cc][lane] = rh[cc];
     hs[lane & 31][64 + (lane >> 5)] = rh2;
+    if constexpr (K == 5) hs[lane & 31][66 + (lane >> 5)] = rh3;
     __syncthreads();
     if (sl + 1 < nslab) fetch(sl + 1);
 #pragma unroll 8
@@ -198,20 +209,20 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
       const float a = dzs[r][tt + hh];
       ab += a;
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
+      for (int k = 0; k < K; ++k)
         acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, hs[r][tt + hh + k], acc[k], 0, 0, 0);
     }
   }
-  float* rec = partial + (size_t)ch * ((size_t)Cout * Cin * 3 + Cout);
+  float* rec = partial + (size_t)ch * ((size_t)Cout * Cin * K + Cout);
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < K; ++k)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int o = o0 + (i & 3) + 8 * (i >> 2) + 4 * hh, c = c0 + r;
-      if (c < Cin) rec[((size_t)o * Cin + c) * 3 + k] = acc[k][i];
+      if (c < Cin) rec[((size_t)o * Cin + c) * K + k] = acc[k][i];
     }
   ab += __shfl_xor(ab, 32, 64);
-  if (blockIdx.y == 0 && hh == 0) rec[(size_t)Cout * Cin * 3 + o0 + r] = ab;
+  if (blockIdx.y == 0 && hh == 0) rec[(size_t)Cout * Cin * K + o0 + r] = ab;
 }
 
 // ---- the same weight gradient on the bf16 matrix cores at fp32 grade: every fp32 operand is carried as three bf16 terms
@@ -223,32 +234,35 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
 // and 12 h frames (three reads: frames t-1 .. t+10) per 16-frame k-step, the three taps are register windows [k, k + 8) of
 // those 12 values.
 
-template <bool AUG, bool RAGGED = false>
+// K = 5 (layer 1 of the k = (5, 3, 3) variant): the five taps are the windows [k, k + 8) of the same 12 values, now frames
+// t - 2 .. t + 9, and the slab's window is all 68 frames of a row
+template <bool AUG, bool RAGGED = false, int K = 3>
 __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __restrict__ dz, const float* __restrict__ h,
                                                              int64_t hsb, int64_t hsc, int64_t hst,
                                                              float* __restrict__ partial, int B, int Cin, int Cout, int T,
                                                              int bchunk, AugCfg aug, const int* __restrict__ lens = nullptr) {
   constexpr int PITCH = 68;
   __shared__ __attribute__((aligned(16))) float dzs[32][PITCH];
-  __shared__ __attribute__((aligned(16))) float hs[32][PITCH];      // hs[c][i] = frame t0 - 1 + i, i < 66 (67 = zero)
+  __shared__ __attribute__((aligned(16))) float hs[32][PITCH];      // hs[c][i] = frame t0 - 1 + i, i < 66 (67 = zero); K = 5: frame t0 - 2 + i, i < 68
   const int lane = threadIdx.x, r = lane & 31, hh = lane >> 5;
   const int o0 = blockIdx.x * 32, c0 = blockIdx.y * 32, ch = blockIdx.z;
   const int b0 = ch * bchunk, b1 = min(B, b0 + bchunk);
-  f32x16_t acc[3];
+  f32x16_t acc[K];
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < K; ++k)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[k][i] = 0.f;
   float ab = 0.f;
   const int nslab_t = (T + W1D_TT - 1) / W1D_TT;
   const int nslab = (b1 - b0) * nslab_t;
   float rdz[32], rh[32], rh2 = 0.f;
+  [[maybe_unused]] float rh3 = 0.f;
   auto fetch = [&](int sl) {
     const int b = b0 + sl / nslab_t, t0 = (sl % nslab_t) * W1D_TT;
 #pragma unroll
     for (int oo = 0; oo < 32; ++oo)
       rdz[oo] = (t0 + lane < T) ? dz[((size_t)b * Cout + o0 + oo) * T + t0 + lane] : 0.f;
-    const int t = t0 - 1 + lane;
+    const int t = t0 - K / 2 + lane;
 #pragma unroll
     for (int cc = 0; cc < 32; ++cc) {
       const int ci = c0 + cc;
@@ -259,13 +273,20 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __rest
       else
         rh[cc] = (ci < Cin && t >= 0 && t < T) ? h[(int64_t)b * hsb + (int64_t)ci * hsc + (int64_t)t * hst] : 0.f;
     }
-    const int ci2 = c0 + (lane & 31), t2 = t0 + 63 + (lane >> 5);
+    const int ci2 = c0 + (lane & 31), t2 = t0 + 64 - K / 2 + (lane >> 5);
     if constexpr (AUG)
       rh2 = (ci2 < Cin && t2 < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)aug_src_t(aug, t2) * hst], b, t2, ci2) : 0.f;
     else if constexpr (RAGGED)
       rh2 = (ci2 < Cin && t2 < lens[b]) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
     else
       rh2 = (ci2 < Cin && t2 < T) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t2 * hst] : 0.f;
+    if constexpr (K == 5) {      // frames 66, 67 of the window (uniform batches only: never RAGGED)
+      const int t3 = t2 + 2;
+      if constexpr (AUG)
+        rh3 = (ci2 < Cin && t3 < T) ? aug_apply(aug, h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)aug_src_t(aug, t3) * hst], b, t3, ci2) : 0.f;
+      else
+        rh3 = (ci2 < Cin && t3 < T) ? h[(int64_t)b * hsb + (int64_t)ci2 * hsc + (int64_t)t3 * hst] : 0.f;
+    }
   };
   if (lane < 32) { hs[lane][66] = 0.f; hs[lane][67] = 0.f; }      // the tail of the 12-frame window of the last k-step
   if (nslab > 0) fetch(0);
@@ -276,6 +297,7 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __rest
 #pragma unroll
     for (int cc = 0; cc < 32; ++cc) hs[cc][lane] = rh[cc];
     hs[lane & 31][64 + (lane >> 5)] = rh2;
+    if constexpr (K == 5) hs[lane & 31][66 + (lane >> 5)] = rh3;
     __syncthreads();
     if (sl + 1 < nslab) fetch(sl + 1);
 #pragma unroll
@@ -291,7 +313,7 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __rest
       uint4 a[3];
       split8n<3>(dv, a);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
+      for (int k = 0; k < K; ++k) {
         const float win[8] = {hv[k], hv[k + 1], hv[k + 2], hv[k + 3], hv[k + 4], hv[k + 5], hv[k + 6], hv[k + 7]};
         uint4 bq[3];
         split8n<3>(win, bq);
@@ -304,16 +326,16 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_x3_kernel(const float* __rest
       }
     }
   }
-  float* rec = partial + (size_t)ch * ((size_t)Cout * Cin * 3 + Cout);
+  float* rec = partial + (size_t)ch * ((size_t)Cout * Cin * K + Cout);
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < K; ++k)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int o = o0 + (i & 3) + 8 * (i >> 2) + 4 * hh, c = c0 + r;
-      if (c < Cin) rec[((size_t)o * Cin + c) * 3 + k] = acc[k][i];
+      if (c < Cin) rec[((size_t)o * Cin + c) * K + k] = acc[k][i];
     }
   ab += __shfl_xor(ab, 32, 64);
-  if (blockIdx.y == 0 && hh == 0) rec[(size_t)Cout * Cin * 3 + o0 + r] = ab;
+  if (blockIdx.y == 0 && hh == 0) rec[(size_t)Cout * Cin * K + o0 + r] = ab;
 }
 
 // data-gradient weights of Conv1d: W'[c][o][k'] = W[o][c][2-k']  (a Conv1d with Cin' = Cout, Cout' = Cin)
@@ -390,13 +412,26 @@ hipError_t launch_cm_bn_bwd(int src, const float* z, const BnApply& bn, const fl
 // partial: conv1d_wgrad_chunks(B) * (Cout*Cin*3 + Cout) floats
 int conv1d_wgrad_chunks(int B) { return B < 256 ? B : 256; }
 hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int64_t hsc, int64_t hst, float* partial,
-                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug, int x3, const int* lens) {
+                               float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug, int x3, const int* lens,
+                               int taps) {
   const int nch = conv1d_wgrad_chunks(B), bchunk = (B + nch - 1) / nch;
   const bool aug_on = aug && aug->on;
   if (Cout % 32 != 0) return hipErrorInvalidValue;     // both kernels tile 32 output channels
   if (lens && aug_on) return hipErrorInvalidValue;     // a time roll has no per-utterance meaning
   // x3: the three-term bf16 matrix-core form (fp32-grade sums), else the fp32 matrix cores; lens: ragged layer 1, h = the padded x,
   // bounded per utterance in the loads
+  if (taps != 3 && (taps != 5 || lens)) return hipErrorInvalidValue;   // five taps: layer 1 of the variant, uniform batches
+  if (taps == 5) {
+    const auto k5 = x3 ? (aug_on ? conv1d_wgrad_x3_kernel<true, false, 5> : conv1d_wgrad_x3_kernel<false, false, 5>)
+                       : (aug_on ? conv1d_wgrad_mfma_kernel<true, false, 5> : conv1d_wgrad_mfma_kernel<false, false, 5>);
+    hipLaunchKernelGGL(k5, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk,
+                       aug_on ? *aug : AugCfg{}, nullptr);
+    hipError_t e5 = hipGetLastError();
+    if (e5 != hipSuccess) return e5;
+    const int n5 = Cout * Cin * 5;
+    hipLaunchKernelGGL(reduce_record2_kernel, dim3((n5 + Cout + 63) / 64), dim3(256), 0, s, partial, nch, n5 + Cout, n5, dw, Cout, db);
+    return hipGetLastError();
+  }
   const auto kern = x3 ? (lens ? conv1d_wgrad_x3_kernel<false, true> : aug_on ? conv1d_wgrad_x3_kernel<true> : conv1d_wgrad_x3_kernel<false>)
                        : (lens ? conv1d_wgrad_mfma_kernel<false, true> : aug_on ? conv1d_wgrad_mfma_kernel<true> : conv1d_wgrad_mfma_kernel<false>);
   hipLaunchKernelGGL(kern, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk,

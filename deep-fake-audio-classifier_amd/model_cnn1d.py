@@ -15,19 +15,63 @@ from . import _lib
 from ._params import BatchNormParams, ConvParams, LinearParams, Slots
 
 
+KERNEL_SETS = ((3, 3, 3), (5, 3, 3))     # the Conv1d kernel sizes the HIP path is built for
+
+
+def check_kernels(kernels) -> tuple:
+    """`kernels` as a tuple of three ints, or ValueError naming the two supported sets: (3, 3, 3) -- src/model_cnn1d.py -- and
+    (5, 3, 3), the reference's CNN1D_Variant (src/compare_kernels.py:38-67)."""
+    try:
+        k = tuple(int(v) for v in kernels)
+    except (TypeError, ValueError):
+        k = None
+    if k not in KERNEL_SETS:
+        raise ValueError(f"CNN1D kernels={kernels!r}: the HIP path is built for kernels=(3, 3, 3) and kernels=(5, 3, 3) only")
+    return k
+
+
+def parse_kernels(text: str) -> tuple:
+    """The CLIs' `--kernels 5,3,3`."""
+    try:
+        return check_kernels(int(v) for v in text.split(","))
+    except ValueError:
+        raise ValueError(f"--kernels {text}: the supported sets are 3,3,3 and 5,3,3") from None
+
+
+def resolve_kernels(flag, checkpoint_blob) -> tuple:
+    """The kernel sizes a scoring CLI builds its CNN1D with.  Pure, the rule of normalization.resolve_norm: an explicit `flag`
+    wins; else the checkpoint's "kernels" (the key src/compare_kernels.py:178-184 writes); else (3, 3, 3).  A flag that
+    contradicts the checkpoint warns on stderr."""
+    import sys
+    saved = checkpoint_blob.get("kernels") if isinstance(checkpoint_blob, dict) else None
+    if saved is not None:
+        saved = check_kernels(saved)
+    if flag is None:
+        return saved or (3, 3, 3)
+    flag = check_kernels(flag)
+    if flag != (saved or (3, 3, 3)):
+        print(f"warning: --kernels {','.join(map(str, flag))} but the checkpoint was trained with "
+              f"kernels={saved or (3, 3, 3)}", file=sys.stderr)
+    return flag
+
+
 class CNN1D(nn.Module):
     _CONV_IDX = (0, 4, 8)     # reference nn.Sequential indices that own parameters (src/model_cnn1d.py:15-32)
     _BN_IDX = (1, 5, 9)
 
-    def __init__(self, in_features=180, base_channels=32, num_classes=1, dropout=0.2):
+    def __init__(self, in_features=180, base_channels=32, num_classes=1, dropout=0.2, kernels=(3, 3, 3)):
+        """kernels: (3, 3, 3), or (5, 3, 3) -- the reference's CNN1D_Variant(kernels=(5, 3, 3)) of src/compare_kernels.py:38-67
+        (conv.0.weight [32, F, 5], padding 2; same state_dict keys).  That variant has the eval forward, uniform and ragged, and
+        the uniform training step; its ragged training step is refused by name."""
         super().__init__()
         if num_classes != 1:
             raise ValueError("dfa_amd.CNN1D implements the binary head (num_classes=1) the reference trains")
+        self.kernels = check_kernels(kernels)
         bc = base_channels
         chans = [(in_features, bc), (bc, 2 * bc), (2 * bc, 4 * bc)]
         slots = {}
-        for ci, bi, (cin, cout) in zip(self._CONV_IDX, self._BN_IDX, chans):
-            slots[ci] = ConvParams(cin, cout, (3,))
+        for ci, bi, (cin, cout), k in zip(self._CONV_IDX, self._BN_IDX, chans, self.kernels):
+            slots[ci] = ConvParams(cin, cout, (k,))
             slots[bi] = BatchNormParams(cout)
         self.conv = Slots(slots)
         self.classifier = LinearParams(4 * bc, num_classes)
@@ -43,7 +87,7 @@ class CNN1D(nn.Module):
 
     def _ensure_prepared(self, ctx):
         _lib.ensure_prepared(self, ctx, "cnn1d", "dfa_cnn1d_set_params", (self.in_features, self.base_channels),
-                             "dfa_cnn1d_prepare")
+                             "dfa_cnn1d_prepare", before=("dfa_cnn1d_set_kernels", self.kernels))
 
     def forward(self, x, lengths=None):
         """lengths: None (every utterance spans all T frames: the reference's call), or the per-utterance frame counts of a

@@ -13,12 +13,12 @@ import torch
 from .model import CNN2D
 
 
-def build_model(name: str, in_features: int = 180, dropout: float = 0.3, precision: str = "fp32"):
+def build_model(name: str, in_features: int = 180, dropout: float = 0.3, precision: str = "fp32", kernels=(3, 3, 3)):
     if name == "cnn2d":
         return CNN2D(in_features=in_features, dropout=dropout, precision=precision)
     if name == "cnn1d":
         from .model_cnn1d import CNN1D
-        return CNN1D(in_features=in_features, dropout=dropout)
+        return CNN1D(in_features=in_features, dropout=dropout, kernels=kernels)
     raise ValueError(f"unknown model {name!r} (choices: cnn2d, cnn1d)")
 
 
@@ -186,6 +186,9 @@ def parse_args(argv=None):
     p.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
     from .normalization import add_norm_argument
     add_norm_argument(p)          # not given: the checkpoint's "norm_mode", else raw (normalization.resolve_norm)
+    p.add_argument("--kernels", default=None, metavar="K1,K2,K3",
+                   help="--model cnn1d: Conv1d kernel sizes, 3,3,3 or 5,3,3 (src/compare_kernels.py's CNN1D_Variant); "
+                        "not given: the checkpoint's \"kernels\", else 3,3,3")
     sw = p.add_mutually_exclusive_group()
     sw.add_argument("--swap-tf", dest="swap_tf", action="store_true", help="swap time and feature dims (default)")
     sw.add_argument("--no-swap-tf", dest="swap_tf", action="store_false")
@@ -198,10 +201,22 @@ def _add_embedding_flag(p):
                    help="also write the block-3 embeddings [N, 128*F] (+ uttids, logits) to this .pt file (cnn2d only)")
 
 
+def check_kernels_arg(model: str, kernels_text):
+    """--kernels as a tuple (None when not given).  Pure -- called before a model or a file is touched: ValueError for a model
+    other than cnn1d or a set the HIP path is not built for."""
+    if kernels_text is None:
+        return None
+    if model != "cnn1d":
+        raise ValueError(f"--kernels is a --model cnn1d flag (got --model {model}): only the 1D CNN has the k = (5, 3, 3) variant")
+    from .model_cnn1d import parse_kernels
+    return parse_kernels(kernels_text)
+
+
 def main(argv=None):
     from . import distributed as _dist
     _dist.limit_cpu_threads()      # the job's CPU share, not the machine's CPU count (distributed.cpu_budget)
     args = parse_args(argv)
+    kernels_flag = check_kernels_arg(args.model, args.kernels)
     device = args.device or "cuda"
     apply_sigmoid = False if args.no_apply_sigmoid else args.apply_sigmoid
     features_df = pd.read_pickle(args.features)
@@ -210,9 +225,15 @@ def main(argv=None):
     ragged = len({tuple(f.shape) for f in features_df["features"]}) > 1      # utterances of unequal lengths
     if ragged:
         check_ragged_args(args.model, args.precision, args.swap_tf)
-    model = build_model(args.model, args.in_features, args.dropout, args.precision).to(device)
     from .normalization import explicit_norm, resolve_norm
-    blob = read_checkpoint(args.checkpoint, device)
+    if args.model == "cnn1d":          # its kernel sizes may come from the checkpoint: the file is read first
+        from .model_cnn1d import resolve_kernels
+        blob = read_checkpoint(args.checkpoint, device)
+        model = build_model(args.model, args.in_features, args.dropout, args.precision,
+                            kernels=resolve_kernels(kernels_flag, blob)).to(device)
+    else:                              # as before: a model the arguments do not allow is refused before the file is read
+        model = build_model(args.model, args.in_features, args.dropout, args.precision).to(device)
+        blob = read_checkpoint(args.checkpoint, device)
     load_weights(model, args.checkpoint, device, blob=blob)
     norm = resolve_norm(explicit_norm(args), blob)
     model.eval()

@@ -167,6 +167,9 @@ def parse_args(argv=None):
                    help="flat-buffer trainers: keep the whole training set in GPU memory (uploaded once; batches are device-side row "
                         "gathers) -- auto: when it needs at most half of the free memory")
     add_norm_argument(p)
+    p.add_argument("--kernels", default=None, metavar="K1,K2,K3",
+                   help="--model cnn1d: Conv1d kernel sizes, 3,3,3 (default) or 5,3,3 (src/compare_kernels.py's CNN1D_Variant; recorded "
+                        "in the checkpoint as \"kernels\"); uniform-length training files only")
     p.add_argument("--sync-bn", action="store_true",
                    help="data-parallel training: BatchNorm statistics over the global batch (N ranks x B train like one rank x N*B); "
                         "default: each rank's own statistics, as torch DistributedDataParallel")
@@ -184,6 +187,9 @@ def check_ragged_train_args(args, world: int = 1) -> None:
     head = "--train-features holds utterances of unequal lengths: "
     if args.model != "cnn1d":
         raise ValueError(head + f"variable-length training is --model cnn1d only in this version (got --model {args.model})")
+    if getattr(args, "kernels", None) not in (None, "3,3,3"):
+        raise ValueError(head + f"--kernels {args.kernels} trains on utterances of one length only (the variable-length step is "
+                         "built for kernels 3,3,3)")
     if not args.swap_tf:
         raise ValueError(head + "--no-swap-tf is not supported for such a file (the stored [F, T] layout is the only ragged layout)")
     aug = [f for f in ("spec_augment", "feature_mask", "time_shift", "channel_drop", "gaussian_jitter") if getattr(args, f, False)]
@@ -240,6 +246,8 @@ def main(argv=None):
     from . import distributed as _dist
     _dist.limit_cpu_threads()      # the job's CPU share, not the machine's CPU count (distributed.cpu_budget)
     args = parse_args(argv)
+    from .predict import check_kernels_arg
+    kernels = check_kernels_arg(args.model, args.kernels) or (3, 3, 3)      # refused here for any model but cnn1d: nothing exists yet
     set_seed(args.seed)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     device = torch.device("cuda", local_rank) if args.device.startswith("cuda") else torch.device(args.device)
@@ -255,7 +263,7 @@ def main(argv=None):
 
     if args.model == "cnn1d":
         from .model_cnn1d import CNN1D
-        model = CNN1D(in_features=args.in_features, dropout=args.dropout).to(device)
+        model = CNN1D(in_features=args.in_features, dropout=args.dropout, kernels=kernels).to(device)
     else:
         model = CNN2D(in_features=args.in_features, dropout=args.dropout, precision=args.precision).to(device)
     # dropout masks (and the jitter noise below) are Philox streams keyed by the run seed AND the rank: the ranks of one

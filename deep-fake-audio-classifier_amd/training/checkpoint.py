@@ -25,13 +25,17 @@ def build_config_dict(args) -> Dict[str, Any]:
 def checkpoint_blob(model, optimizer, epoch: int, args, scheduler: Optional[Any] = None, norm_mode: str = "raw") -> Dict[str, Any]:
     """The dict save_checkpoint writes.  norm_mode: the per-utterance normalisation the model was trained with; "cmn" / "cvmn" are
     recorded as blob["norm_mode"] (the key src/compare_kernels.py:178-184 writes; the reference's loader ignores it), "raw" adds
-    no key: a raw checkpoint is byte for byte what it was."""
+    no key: a raw checkpoint is byte for byte what it was.  By the same rule a model whose `kernels` are not (3, 3, 3) (the CNN1D
+    variant) is recorded as blob["kernels"], the other key of that script (model_cnn1d.resolve_kernels reads it back)."""
     blob = {"model_state": model.state_dict(), "optimizer_state": optimizer.state_dict(), "epoch": epoch,
             "config": build_config_dict(args)}
     if scheduler is not None:
         blob["scheduler_state"] = scheduler.state_dict()
     if norm_mode != "raw":
         blob["norm_mode"] = norm_mode
+    kernels = getattr(model, "kernels", None)
+    if kernels is not None and tuple(kernels) != (3, 3, 3):
+        blob["kernels"] = tuple(int(k) for k in kernels)
     return blob
 
 

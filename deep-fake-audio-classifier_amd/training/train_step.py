@@ -47,6 +47,8 @@ def _bind(model, ctx, kind):
     sig = (ctx.index, tuple(t.data_ptr() for t in ts))
     if ctx.owner_changed(kind, model) or getattr(model, "_bound", None) != sig:
         dims = (model.base_channels,) if kind == "cae" else (model.in_features, model.base_channels)
+        if kind == "cnn1d":     # the slot's kernel sizes are sticky: say whose model this is
+            _lib.check(ctx.handle, ctx.lib.dfa_cnn1d_set_kernels(ctx.handle, *model.kernels))
         _lib.check(ctx.handle, getattr(ctx.lib, f"dfa_{kind}_set_params")(ctx.handle, _lib.ptr_array([t.detach() for t in ts]),
                                                                             len(ts), *dims))
         model._bound = sig
@@ -80,6 +82,9 @@ def forward_train_raw(model, x, want=("recon", "latent"), lengths=None):
     dfa_cnn1d_forward_train_ragged (BatchNorm statistics over the valid frames only); `backward_raw` then runs its backward."""
     kind = KINDS[type(model).__name__]
     if lengths is not None:
+        if kind == "cnn1d" and tuple(model.kernels) != (3, 3, 3):
+            raise ValueError(f"CNN1D(kernels={tuple(model.kernels)}) trains on uniform batches only: the variable-length step "
+                             "(lengths=...) is built for kernels=(3, 3, 3)")
         lengths = _ragged_lengths(model, x, lengths)
     if x.device.type != "cuda":
         raise RuntimeError(f"dfa_amd.{type(model).__name__} runs on the GPU only: move the input with .to('cuda')")

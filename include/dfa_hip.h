@@ -210,6 +210,14 @@ int dfa_cnn1d_forward_ragged(dfa_ctx* ctx, const void* x, int x_dtype, int B, in
 int dfa_cnn1d_ragged_segments(int T, int F, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap);
 /* dynamic LDS bytes of the ragged CNN1D launch for a batch padded to T_max (<= 160 KiB) */
 size_t dfa_cnn1d_ragged_lds_bytes(int T_max, int F);
+/* The same two for a model whose first Conv1d has k1 taps (dfa_cnn1d_set_kernels).  k1 = 3: exactly the pair above.  k1 = 5:
+ * the windows of the k = (5, 3, 3) variant -- owned frames plus 4 frames to either side (3 + 1 for the wider layer 1), or up
+ * to the utterance's end; one window spans up to 384 frames at F = 180.  Any other k1: 0. */
+int dfa_cnn1d_ragged_segments_k(int T, int F, int k1, int* starts, int* lens, int* owned_lo, int* owned_hi, int cap);
+size_t dfa_cnn1d_ragged_lds_bytes_k(int T_max, int F, int k1);
+/* the largest T at which dfa_cnn1d_forward runs as ONE launch for the contiguous [B][F][T] storage with k1 taps in layer 1
+ * (349 at F = 180, k1 = 3; 384 at k1 = 5, whose layer-1 weights are streamed); 0 for an F or k1 the one-kernel form does not take */
+int dfa_cnn1d_fused_max_t(int F, int k1);
 
 /* ---- CNN2D training step (replaces, for src/train.py:71-76, torch autograd over src/model.py:13-39) ------------ */
 size_t dfa_cnn2d_train_workspace_bytes(const dfa_ctx* ctx, int B, int T, int F, int precision);
@@ -322,6 +330,21 @@ int dfa_adamw_step(dfa_ctx* ctx, float* param, const float* grad, float* exp_avg
 int dfa_cnn1d_set_params(dfa_ctx* ctx, const float* const* device_params, int n, int in_features,
                          int base_channels);
 int dfa_cnn1d_prepare(dfa_ctx* ctx);
+/* Kernel sizes of the three Conv1d layers that the NEXT dfa_cnn1d_set_params binds: (3, 3, 3) -- the default, src/model_cnn1d.py --
+ * or (5, 3, 3), the reference's CNN1D_Variant (src/compare_kernels.py:38-67: conv.0.weight is [32][in_features][5], padding 2).
+ * Sticky on the context.  Like dfa_cnn1d_set_params it ends a training batch in flight and clears what dfa_cnn1d_prepare built;
+ * a call that CHANGES k1 also unbinds the parameters (conv.0.weight has the other shape): call dfa_cnn1d_set_params again.
+ * Anything but the two sets returns DFA_E_UNSUPPORTED with a message and changes nothing.
+ * CAUTION: dfa_cnn1d_set_params cannot see the shape of the tensors it is given.  The caller must have set the kernels the bound
+ * conv.0.weight has -- binding a [32][F][3] weight on a context left at (5, 3, 3) makes dfa_cnn1d_prepare and the training step
+ * read past its end.  Call dfa_cnn1d_set_kernels in front of every dfa_cnn1d_set_params when one context serves both models.
+ * With (5, 3, 3): dfa_cnn1d_forward and dfa_cnn1d_forward_ragged work as documented (one launch for the layouts the three-tap
+ * model takes in one launch); dfa_cnn1d_forward_train / dfa_cnn1d_backward run the uniform step (layer 1: a five-tap
+ * convolution and a [32][F][5] weight gradient, on the matrix cores or the fp32 kernels as cnn1d_train_x3 says), and
+ * dfa_cnn1d_train_workspace_bytes / dfa_cnn1d_train_plan size `partial` for it; dfa_cnn1d_forward_train_ragged and
+ * dfa_cnn1d_train_plan(ragged) return DFA_E_UNSUPPORTED with a message before anything is launched, and
+ * dfa_cnn1d_train_ragged_workspace_bytes returns 0. */
+int dfa_cnn1d_set_kernels(dfa_ctx* ctx, int k1, int k2, int k3);
 /* eval-mode forward, fp32 arithmetic.  x as in dfa_cnn2d_forward (fp32 only); logits: device float[B]. */
 int dfa_cnn1d_forward(dfa_ctx* ctx, const void* x, int x_dtype, int B, int T, int F, int64_t stride_b,
                       int64_t stride_t, int64_t stride_f, float* logits, void* workspace,
