@@ -143,18 +143,13 @@ int cnn1d_forward_train_impl(dfa_ctx* ctx, const FeatView& v, const int32_t* len
   for (int l = 0; l < 3; ++l) {
     float* z = (float*)(ws + pl.z[l]);
     const LayerParams& q = layer[l];
-    if (l == 0 && m.k1 == 5) {
-      // five taps: the streamed matrix-core kernel where the three-tap one would run (its image is k-step-major), else the
-      // tap-templated fp32 kernel; the armed augmentation is folded into the loads of either
-      if (x3 && conv1d_x3_k5_supports(x, v.sb, v.sf, v.st, z, T, F, 32, terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3_k5(x, v.sb, tr.wx3[0], q.b, z, B, F, T, terms, s, aug));
+    if (l == 0) {
+      // m.k1 taps (five: uniform batches only, refused above otherwise): the matrix-core kernel, else the tap-templated fp32
+      // kernel; the armed augmentation or the ragged batch's bound is folded into the loads of either
+      if (x3 && conv1d_x3_supports(x, v.sb, v.sf, v.st, z, T, F, 32, terms, m.k1))
+        DFA_HIP_CHECK(ctx, launch_conv1d_x3(x, v.sb, tr.wx3[0], q.b, z, B, F, 32, T, terms, s, x3, aug, lens, m.k1));
       else
-        DFA_HIP_CHECK(ctx, launch_conv1d(x, v.sb, v.sf, v.st, q.w, q.b, z, B, F, 32, T, false, s, false, aug, nullptr, 5));
-    } else if (l == 0) {
-      if (x3 && conv1d_x3_supports(x, v.sb, v.sf, v.st, z, T, F, 32, terms))
-        DFA_HIP_CHECK(ctx, launch_conv1d_x3(x, v.sb, tr.wx3[0], q.b, z, B, F, 32, T, terms, s, x3, aug, lens));
-      else
-        DFA_HIP_CHECK(ctx, launch_conv1d(x, v.sb, v.sf, v.st, q.w, q.b, z, B, F, 32, T, false, s, false, aug, lens));
+        DFA_HIP_CHECK(ctx, launch_conv1d(x, v.sb, v.sf, v.st, q.w, q.b, z, B, F, 32, T, false, s, false, aug, lens, m.k1));
     } else {
       const float* hin = (const float*)(ws + pl.h[l - 1]);
       if (x3 && conv1d_x3_supports(hin, (int64_t)Cin[l] * T, T, 1, z, T, Cin[l], C[l], terms))

@@ -127,45 +127,24 @@ hipError_t launch_fold_conv1d(const LayerParams& lp, float* wf, float* bf, int c
 hipError_t launch_conv1d(const float* x, int64_t sb, int64_t sc, int64_t st, const float* w, const float* bias,
                          float* out, int B, int Cin, int Cout, int T, bool mean, hipStream_t s, bool relu, const AugCfg* aug, const int* lens,
                          int taps) {
-  if (taps == 5) {        // layer 1 of the k = (5, 3, 3) variant: eval (BatchNorm folded, ReLU) or train mode (raw, the augmentation folded)
-    if (lens || mean || (relu && aug && aug->on)) return hipErrorInvalidValue;
-    const dim3 grid((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B);
-    if (relu)
-      hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, true, false, false, 5>), grid, dim3(256), 0, s, x, sb, sc, st, w, bias, out, Cin, Cout,
-                         T, 0.f, AugCfg{}, nullptr);
-    else if (aug && aug->on)
-      hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, true, false, 5>), grid, dim3(256), 0, s, x, sb, sc, st, w, bias, out, Cin, Cout,
-                         T, 0.f, *aug, nullptr);
-    else
-      hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, false, false, 5>), grid, dim3(256), 0, s, x, sb, sc, st, w, bias, out, Cin, Cout,
-                         T, 0.f, AugCfg{}, nullptr);
-    return hipGetLastError();
-  }
-  if (taps != 3) return hipErrorInvalidValue;
-  if (lens) {             // train-mode layer 1 of a ragged batch
-    if (relu || mean || (aug && aug->on)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, false, true>), dim3((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256),
-                       0, s, x, sb, sc, st, w, bias, out, Cin, Cout, T, 0.f, AugCfg{}, lens);
-    return hipGetLastError();
-  }
-  if (aug && aug->on) {   // train-mode layer 1 with the augmentation folded into the x loads
-    if (relu || mean) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false, true>), dim3((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256),
-                       0, s, x, sb, sc, st, w, bias, out, Cin, Cout, T, 0.f, *aug);
-    return hipGetLastError();
-  }
-  if (!relu) {   // raw convolution (+ bias): train-mode forward and the data-gradient convolution
-    hipLaunchKernelGGL((conv1d_k3_bn_relu_kernel<false, false>), dim3((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256),
-                       0, s, x, sb, sc, st, w, bias, out, Cin, Cout, T, 0.f, AugCfg{});
-    return hipGetLastError();
-  }
-  if (mean) {
-    hipLaunchKernelGGL(conv1d_k3_bn_relu_kernel<true>, dim3(1, Cout / C1D_OT, B), dim3(256), 0, s, x, sb, sc, st, w,
-                       bias, out, Cin, Cout, T, 1.0f / (float)T, AugCfg{});
-  } else {
-    hipLaunchKernelGGL(conv1d_k3_bn_relu_kernel<false>, dim3((T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256), 0,
-                       s, x, sb, sc, st, w, bias, out, Cin, Cout, T, 0.f, AugCfg{});
-  }
+  const bool aug_on = aug && aug->on;
+  // five taps: layer 1 of the k = (5, 3, 3) variant, eval (BatchNorm folded, ReLU) or train mode (raw), uniform batches
+  if (taps != 3 && (taps != 5 || lens || mean)) return hipErrorInvalidValue;
+  // lens (train-mode layer 1 of a ragged batch) and the augmentation (folded into the x loads of train-mode layer 1) go with the
+  // raw convolution only, and not with each other
+  if ((lens || aug_on) && (relu || mean || (lens && aug_on))) return hipErrorInvalidValue;
+  // raw (+ bias, no ReLU): train-mode forward and the data-gradient convolution; the frame mean is the ReLU form's
+  const bool pooled = relu && mean;
+  const auto kern = taps == 5 ? (relu     ? conv1d_k3_bn_relu_kernel<false, true, false, false, 5>
+                                 : aug_on ? conv1d_k3_bn_relu_kernel<false, false, true, false, 5>
+                                          : conv1d_k3_bn_relu_kernel<false, false, false, false, 5>)
+                    : lens    ? conv1d_k3_bn_relu_kernel<false, false, false, true>
+                    : aug_on  ? conv1d_k3_bn_relu_kernel<false, false, true>
+                    : !relu   ? conv1d_k3_bn_relu_kernel<false, false>
+                    : pooled  ? conv1d_k3_bn_relu_kernel<true>
+                              : conv1d_k3_bn_relu_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(pooled ? 1 : (T + C1D_TT - 1) / C1D_TT, Cout / C1D_OT, B), dim3(256), 0, s, x, sb, sc, st, w, bias, out, Cin,
+                     Cout, T, pooled ? 1.0f / (float)T : 0.f, aug_on ? *aug : AugCfg{}, lens);
   return hipGetLastError();
 }
 

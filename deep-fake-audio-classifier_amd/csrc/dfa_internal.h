@@ -349,7 +349,6 @@ hipError_t launch_pack_cnn1d_fused(const float* wf, float* wp, int cin, int cout
 hipError_t launch_cnn1d_fused(const FeatView& v, const float* wp1, const float* b1, const float* wp2, const float* b2, const float* wp3,
                               const float* b3, const float* cw, const float* cb, float* logits, hipStream_t s, long long* stamps = nullptr);
 // cnn1d_fused_x3.hip: the same forward on the bf16 matrix cores with hi + lo bf16 operands (fp32-grade accuracy)
-int cnn1d_x3_nks(int cin);
 // k1 / taps: the taps of layer 1, 3 or 5 (the k = (5, 3, 3) variant: five-tap kernels, a k-step-major layer-1 image)
 size_t cnn1d_x3_pack_bytes(int cin, int cout, int taps = 3);
 hipError_t launch_pack_cnn1d_x3(const float* wf, void* wx, int cin, int cout, hipStream_t s, int taps = 3);
@@ -458,14 +457,12 @@ hipError_t launch_cm_bn_relu_drop(const float* z, const BnApply& bn, float* h, i
 hipError_t launch_cm_bn_relu_meant(const float* z, const BnApply& bn, float* pooled, int B, int C, int T, hipStream_t s, const int* lens = nullptr);
 hipError_t launch_cm_bn_bwd(int src, const float* z, const BnApply& bn, const float* up, float* partial, float* sums, float* dz, int B, int C,
                             int T, const DropCfg& dc, hipStream_t s, const BnSync* sync = nullptr, const int* lens = nullptr, double n_valid = 0.0);
-bool conv1d_x3_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms);
+// conv1d_x3.hip: the matrix-core layer kernel of the training step.  taps = 5: layer 1 of the k = (5, 3, 3) variant (Cout = 32, no
+// lens; weights streamed from the k-step-major image of launch_pack_conv1d_train_all, k1 = 5)
+bool conv1d_x3_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms, int taps = 3);
 hipError_t launch_conv1d_x3(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int Cout, int T,
-                            int terms, hipStream_t s, int mode = 1, const AugCfg* aug = nullptr, const int* lens = nullptr);
+                            int terms, hipStream_t s, int mode = 1, const AugCfg* aug = nullptr, const int* lens = nullptr, int taps = 3);
 size_t conv1d_terms_pack_bytes(int cin, int cout, int terms, int taps = 3);
-// layer 1 of the k = (5, 3, 3) variant's training step: five taps, weights streamed (image of launch_pack_conv1d_train_all, k1 = 5)
-bool conv1d_x3_k5_supports(const float* x, int64_t sb, int64_t sc, int64_t st, const float* z, int T, int Cin, int Cout, int terms);
-hipError_t launch_conv1d_x3_k5(const float* x, int64_t sb, const void* wx, const float* bias, float* z, int B, int Cin, int T, int terms,
-                               hipStream_t s, const AugCfg* aug);
 hipError_t launch_pack_conv1d_train_all(const float* w1, const float* w2, const float* w3, void* const* dst, int F, int terms, float* zero_bias,
                                         hipStream_t s, int k1 = 3);
 // taps = 5: layer 1 of the k = (5, 3, 3) variant (uniform batches; record [Cout][Cin][5] + [Cout])

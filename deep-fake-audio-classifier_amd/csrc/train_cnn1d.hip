@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64) void conv1d_wgrad_mfma_kernel(const float* __re
 
 // ---- the same weight gradient on the bf16 matrix cores at fp32 grade: every fp32 operand is carried as three bf16 terms
 // (split8n<3>; dfa_device.h has why three terms are the operand exactly) and every product is six v_mfma_f32_32x32x16_bf16 (all term pairs of order <= 2),
-// as the training convolutions of cnn1d_fused_x3.hip do.  The fp32 matrix pipe issues one 32x32x2 MFMA per ~80 cycles: 24 of them
+// as the training convolutions of conv1d_x3.hip do.  The fp32 matrix pipe issues one 32x32x2 MFMA per ~80 cycles: 24 of them
 // per 16 frames and tap triple = 1920 cycles; the same products cost 18 x 32 = 576 matrix-pipe cycles here plus the splits.
 // Same decomposition and slab pipeline as the kernel above; the LDS tiles are laid out for aligned 16-byte fragment reads (row
 // pitch 68 floats: the 16 lanes of a ds_read_b128 group fall on distinct banks): a lane reads its row's 8 dz frames (two reads)
@@ -409,7 +409,7 @@ hipError_t launch_cm_bn_bwd(int src, const float* z, const BnApply& bn, const fl
                      inv_n, dc, lens);
   return hipGetLastError();
 }
-// partial: conv1d_wgrad_chunks(B) * (Cout*Cin*3 + Cout) floats
+// partial: conv1d_wgrad_chunks(B) * (Cout*Cin*taps + Cout) floats
 int conv1d_wgrad_chunks(int B) { return B < 256 ? B : 256; }
 hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int64_t hsc, int64_t hst, float* partial,
                                float* dw, float* db, int B, int Cin, int Cout, int T, hipStream_t s, const AugCfg* aug, int x3, const int* lens,
@@ -421,24 +421,16 @@ hipError_t launch_conv1d_wgrad(const float* dz, const float* h, int64_t hsb, int
   // x3: the three-term bf16 matrix-core form (fp32-grade sums), else the fp32 matrix cores; lens: ragged layer 1, h = the padded x,
   // bounded per utterance in the loads
   if (taps != 3 && (taps != 5 || lens)) return hipErrorInvalidValue;   // five taps: layer 1 of the variant, uniform batches
-  if (taps == 5) {
-    const auto k5 = x3 ? (aug_on ? conv1d_wgrad_x3_kernel<true, false, 5> : conv1d_wgrad_x3_kernel<false, false, 5>)
-                       : (aug_on ? conv1d_wgrad_mfma_kernel<true, false, 5> : conv1d_wgrad_mfma_kernel<false, false, 5>);
-    hipLaunchKernelGGL(k5, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk,
-                       aug_on ? *aug : AugCfg{}, nullptr);
-    hipError_t e5 = hipGetLastError();
-    if (e5 != hipSuccess) return e5;
-    const int n5 = Cout * Cin * 5;
-    hipLaunchKernelGGL(reduce_record2_kernel, dim3((n5 + Cout + 63) / 64), dim3(256), 0, s, partial, nch, n5 + Cout, n5, dw, Cout, db);
-    return hipGetLastError();
-  }
-  const auto kern = x3 ? (lens ? conv1d_wgrad_x3_kernel<false, true> : aug_on ? conv1d_wgrad_x3_kernel<true> : conv1d_wgrad_x3_kernel<false>)
-                       : (lens ? conv1d_wgrad_mfma_kernel<false, true> : aug_on ? conv1d_wgrad_mfma_kernel<true> : conv1d_wgrad_mfma_kernel<false>);
+  const auto kern =
+      taps == 5 ? (x3 ? (aug_on ? conv1d_wgrad_x3_kernel<true, false, 5> : conv1d_wgrad_x3_kernel<false, false, 5>)
+                      : (aug_on ? conv1d_wgrad_mfma_kernel<true, false, 5> : conv1d_wgrad_mfma_kernel<false, false, 5>))
+      : x3      ? (lens ? conv1d_wgrad_x3_kernel<false, true> : aug_on ? conv1d_wgrad_x3_kernel<true> : conv1d_wgrad_x3_kernel<false>)
+                : (lens ? conv1d_wgrad_mfma_kernel<false, true> : aug_on ? conv1d_wgrad_mfma_kernel<true> : conv1d_wgrad_mfma_kernel<false>);
   hipLaunchKernelGGL(kern, dim3(Cout / 32, (Cin + 31) / 32, nch), dim3(64), 0, s, dz, h, hsb, hsc, hst, partial, B, Cin, Cout, T, bchunk,
                      aug_on ? *aug : AugCfg{}, lens);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int n = Cout * Cin * 3;
+  const int n = Cout * Cin * taps;
   hipLaunchKernelGGL(reduce_record2_kernel, dim3((n + Cout + 63) / 64), dim3(256), 0, s, partial, nch, n + Cout, n, dw, Cout, db);
   return hipGetLastError();
 }

@@ -131,8 +131,8 @@ int dfa_ctx_set_stream(dfa_ctx* ctx, void* hip_stream);
  *                   storage, the exact-fp32 matrix-core kernel for any other strides; 2 = always the exact-fp32 kernel; 0 = the
  *                   three-launch path
  *   "cnn1d_train_x3" 1 (default) = the five convolutions of a CNN1D training step (3 forward, 2 data gradients) on the matrix cores
- *                   (conv1d_x3_kernel) when the tensors are in the stored [B,F,T] layout, T <= 384, F % 4 == 0: every fp32 operand
- *                   as three bf16 terms (its 24-bit mantissa exactly), six MFMAs per product -- sums of fp32 grade; a folded
+ *                   (conv1d_x3_kernel, conv1d_x3.hip) when the tensors are in the stored [B,F,T] layout, T <= 384, F % 4 == 0:
+ *                   every fp32 operand as three bf16 terms (its 24-bit mantissa exactly), six MFMAs per product -- sums of fp32 grade; a folded
  *                   augmentation (dfa_cnn1d_set_train_augment) is applied as the input slabs are staged.  3 = two terms, three
  *                   MFMAs (bf16x3, ~1e-5 per product: gradients then carry ReLU-flip noise of ~3e-3 relative L2; opt-in);
  *                   0 = the fp32 vector-ALU kernels; 2 = diagnostic (as 1, one channel tile per workgroup)

@@ -8,7 +8,7 @@ channel-major [B, C, T] as the product stores them, and returns what ONE kernel 
 Everything the step stores is fp32; the arithmetic `dt` is a parameter (float64: the statement; float32: the CPU floor).
 
 Read off the kernels (csrc/cnn1d_train_api.hip names the ~30 launches):
-  Conv1d      conv1d_x3_kernel (cnn1d_fused_x3.hip; stored layout, 3 <= T <= 384, Cin % 4 == 0) or conv1d.hip (any strides,
+  Conv1d      conv1d_x3_kernel (conv1d_x3.hip; stored layout, 3 <= T <= 384, Cin % 4 == 0) or conv1d.hip (any strides,
               T < 3, T > 384): z = b + sum_{c,k} w[o][c][k] a[c][t + k - 1], a read as zero outside [0, lengths[b]).
   statistics  cm_stats_kernel + bn_finalize_kernel: sums over the sum-of-lengths frames of the batch, the variance biased, the
               running variance unbiased (n / (n - 1)), momentum as given.

@@ -138,7 +138,7 @@ def test_cnn1d_fused_is_one_launch_and_batch_independent(golden):
 @pytest.mark.parametrize("B,T,F", [(3, 321, 180), (2, 64, 180), (4, 100, 44), (2, 384, 180), (2, 5, 180), (3, 33, 8), (2, 3, 4)])
 def test_cnn1d_training_convolutions_on_matrix_cores_match_vector_twin(B, T, F):
     """Round 3: the five convolutions of a CNN1D training step (3 forward, 2 data gradients; src/train.py:71-76 through
-    src/model_cnn1d.py:17-34) run on `conv1d_x3_kernel` (csrc/cnn1d_fused_x3.hip) when the tensors are in the stored layout:
+    src/model_cnn1d.py:17-34) run on `conv1d_x3_kernel` (csrc/conv1d_x3.hip) when the tensors are in the stored layout:
     context option cnn1d_train_x3 = 1 -- every fp32 operand as three bf16 terms (its 24-bit mantissa exactly), six MFMAs per
     product -- must reproduce the fp32 VALU kernels (option 0) to fp32 rounding: logits 1e-6, gradients 1e-5 of their scale.
     Option 3 (two terms, bf16x3) is the opt-in fast form: logits within 1e-4, gradients limited by ReLU flips (a 1e-5

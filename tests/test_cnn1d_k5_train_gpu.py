@@ -1,6 +1,6 @@
 """GPU tests of the uniform training step of the k = (5, 3, 3) CNN1D variant (dfa_cnn1d_forward_train / dfa_cnn1d_backward with a
 five-tap layer 1), on both arithmetic options: cnn1d_train_x3 = 0 -- conv1d.hip<K = 5> forward, conv1d_wgrad_mfma_kernel<K = 5>
-weight gradient; 1 -- the streamed conv1d_x3_k5_kernel forward, conv1d_wgrad_x3_kernel<K = 5> weight gradient.
+weight gradient; 1 -- the streamed conv1d_x3_kernel<K = 5> forward (conv1d_x3.hip), conv1d_wgrad_x3_kernel<K = 5> weight gradient.
 
 Bounds are those of the three-tap cases of tests/test_train_shapes_gpu.py: logits atol 2e-4 / rtol 1e-5, loss rtol 1e-5, a
 gradient within 3e-2 of its scale in every element and 3e-3 in relative L2 (LOOSE, L2TOL: tolerant of single ReLU flips), a conv
@@ -101,7 +101,7 @@ def _oracle_case(B, T, F):
 
 
 @pytest.mark.parametrize("x3", [0, 1])
-@pytest.mark.parametrize("B,T,F", [(2, 3, 180), (3, 65, 8), (2, 321, 180)])
+@pytest.mark.parametrize("B,T,F", [(2, 3, 180), (3, 65, 8), (2, 321, 180), (2, 259, 20), (2, 33, 36)])
 def test_train_step_matches_float64_oracle(B, T, F, x3):
     sd, x, y, (logits_w, loss_w, grads_w) = _oracle_case(B, T, F)
     m, logits, loss = _step(sd, x, y, x3, F)
@@ -109,8 +109,8 @@ def test_train_step_matches_float64_oracle(B, T, F, x3):
 
 
 def test_two_term_option_stays_within_the_three_tap_logit_bound():
-    """option 3 (two bf16 terms per operand, conv1d_x3_k5_kernel<2>): logits within 1e-4 * max(1, |logit|) of the fp32 kernels',
-    the bound tests/test_cnn1d_gpu.py holds the three-tap two-term arm to"""
+    """option 3 (two bf16 terms per operand, conv1d_x3_kernel<1, 2, K = 5>): logits within 1e-4 * max(1, |logit|) of the fp32
+    kernels', the bound tests/test_cnn1d_gpu.py holds the three-tap two-term arm to"""
     sd, x, y, _ = _oracle_case(2, 321, 180)
     _, l0, _ = _step(sd, x, y, 0)
     _, l3, _ = _step(sd, x, y, 3)

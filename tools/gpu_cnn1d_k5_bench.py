@@ -5,13 +5,14 @@ child process (a process binds one build of the library), run in alternating rou
   k3          CNN1D() on this tree's library
   k3_as_parent  (with --parent-lib) this tree's library driven exactly as the parent's is -- named by file, symbol table filtered,
               dfa_cnn1d_set_kernels never called: separates what the library costs from what the leg's host path costs
+  k5_parent   (with --parent-lib) CNN1D(kernels=(5, 3, 3)) on the parent's library
   k5          CNN1D(kernels=(5, 3, 3)) on this tree's library
 A child walks `--buffers` distinct inputs in turn (8 x 59 MB: more than the 256 MB Infinity Cache, so every forward reads x from
 HBM), warms up, then times `--reps` groups of `--iters` forwards between device events and reports the median group.  Prints one
 JSON line: per leg the per-round medians, their median / min / max (the run-to-run spread the comparison has to be read
-against), k3 over k3_parent and k5 over k3 (MAC ratio per frame: 59,520 / 48,000 = 1.24).
+against), k3 over k3_parent, k5 over k5_parent and k5 over k3 (MAC ratio per frame: 59,520 / 48,000 = 1.24).
 --what train times the all-native training step instead (NativeTrainer.step on one resident batch, dropout 0.2, label smoothing
-0.05, lr 1e-6 so that every leg stays in one activation regime; 5 groups of 20 steps per child), the same three legs.
+0.05, lr 1e-6 so that every leg stays in one activation regime; 5 groups of 20 steps per child), the same legs.
 usage: timeout -k 10 600 python tools/gpu_cnn1d_k5_bench.py [--what forward|train] [--parent-lib libdfa_hip_parent.so] [--rounds 4]"""
 import argparse
 import json
@@ -35,7 +36,8 @@ def child(args):
         _lib.SYMBOLS[:] = [s for s in _lib.SYMBOLS if hasattr(probe, s[0])]   # an older build lacks the newer entry points
     from dfa_amd.model_cnn1d import CNN1D
     torch.manual_seed(0)
-    if args.leg == "k5":
+    k5 = args.leg.startswith("k5")       # (a parent that has the variant has dfa_cnn1d_set_kernels: its k5 leg is driven as this tree's)
+    if k5:
         model = CNN1D(kernels=(5, 3, 3))
     else:
         model = CNN1D()
@@ -46,7 +48,7 @@ def child(args):
     base = torch.randn(B, F, T, generator=g) * 3.2 - 0.07
     if args.what == "train":
         from dfa_amd.training import train_step
-        if args.lib:                   # the parent's library has no dfa_cnn1d_set_kernels: its _bind did not call it
+        if args.lib and not k5:        # the parent's library has no dfa_cnn1d_set_kernels: its _bind did not call it
             class _NoKernels:
                 def __init__(self, lib):
                     self._lib = lib
@@ -106,7 +108,8 @@ def main():
     args = ap.parse_args()
     if args.leg:
         return child(args)
-    legs = ([("k3_parent", args.parent_lib), ("k3_as_parent", "libdfa_hip.so")] if args.parent_lib else []) + [("k3", None), ("k5", None)]
+    legs = ([("k3_parent", args.parent_lib), ("k3_as_parent", "libdfa_hip.so")] if args.parent_lib else []) + [("k3", None)]
+    legs += ([("k5_parent", args.parent_lib)] if args.parent_lib else []) + [("k5", None)]
     res = {name: [] for name, _ in legs}
     sums = {}
     for _ in range(args.rounds):
@@ -128,6 +131,8 @@ def main():
         out["k3_over_k3_parent"] = out["k3"]["median"] / out["k3_parent"]["median"]
         out["k3_checksum_equals_parent"] = out["k3"]["checksum"] == out["k3_parent"]["checksum"]
         out["k3_as_parent_over_k3_parent"] = out["k3_as_parent"]["median"] / out["k3_parent"]["median"]
+        out["k5_over_k5_parent"] = out["k5"]["median"] / out["k5_parent"]["median"]
+        out["k5_checksum_equals_parent"] = out["k5"]["checksum"] == out["k5_parent"]["checksum"]
     out["k5_over_k3"] = out["k5"]["median"] / out["k3"]["median"]
     out["mac_ratio"] = 59520 / 48000
     print(json.dumps(out))
